@@ -20,10 +20,14 @@ counts[callset][SNP,INDEL,SV,ALL][TP,FP,FN][61 quality thresholds] (int64, compu
 device), are summed with one all-reduce (RCCL) at the end of every step.  `--scaling strong`
 deals one synthetic genome over the ranks instead (vcfdist_amd/shard.py), `--workload
 stress_synth | sv_synth` select BASELINE configs[4] (125 000 superclusters per GPU) and an
-emulation of configs[2].  The line also carries `roofline` (counter-based HBM fraction and VALU
-issue fraction of the dominant sweep kernel), `cpu_baseline` (the CPU port
-on the host cores, with its calibration against the reference's published timings),
-`step_parts_ms` and `setup_not_timed` (upload, one-shot rate).
+emulation of configs[2].  A plain run sets up, warms up, times the steps and prints the headline
+(`value`, `ms_per_step`, how the steps were run, `step_parts_ms`, `setup_not_timed`).  With `--full`
+the line also carries what takes work of its own: `roofline` (counter-based HBM fraction and VALU
+issue fraction of the dominant sweep kernel), per-kernel figures, the
+device-tally check and the PRECISION-RECALL SUMMARY, the `one_pass`, `one_at_a_time` and
+`secondary` legs, and `cpu_baseline` (the CPU port on the host cores, with its calibration against
+the reference's published timings).  `--dump-outputs DIR` writes the results of the last timed
+step as .npy files (float64, a fixed sample of the superclusters: dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -308,6 +312,45 @@ def secondary_leg(api, summary, workload, n_sc, seed, steps, device, cpu_target_
     return out
 
 
+DUMP_BYTES = 60_000_000     # data of one --dump-outputs directory (64 MB with the .npy headers to spare)
+
+
+def dump_outputs(out_dir, res, counts, batch):
+    """What a caller of the timed path receives from one step -- the downloaded results and the reduced counters
+    [callset][SNP,INDEL,SV,ALL][TP,FP,FN][quality] -- as DIR/<name>.npy in float64 (every int32 / uint32 / float32 value
+    exactly).  The results are those of a fixed sample of the superclusters: a seeded permutation of the batch taken up to
+    DUMP_BYTES, so the same batch gives the same sample on any build.  sc_index holds the sampled superclusters; the
+    per-alignment fields are [sc][4], the per-variant fields are the sampled superclusters' variants of hap 0 .. 3, each in
+    the order [swap 0, swap 1].  Every value written is finite: a float field (`credit` is NaN where the reference's
+    1 - query_ed / ref_ed is 1 - 0 / 0, and -inf where only ref_ed is 0) holds 0 where the result is not finite, and
+    <name>_nonfinite says what was there (0 finite, 1 NaN, 2 +inf, 3 -inf)."""
+    n, haps = batch.n_sc, len(batch.var_off)
+    nv = sum(np.diff(batch.var_off[h]) for h in range(haps))
+    floats = [name for name, dt in res.PER_VAR if np.dtype(dt).kind == "f"]
+    cost = 8 * (1 + 4 * 4 + 3 + 2 * (len(res.PER_VAR) + len(floats)) * nv)     # bytes a supercluster adds to the dump
+    perm = np.random.RandomState(0x5eed).permutation(n)
+    idx = np.sort(perm[:int(np.searchsorted(np.cumsum(cost[perm]), DUMP_BYTES, side="right"))])
+    aln = (4 * idx[:, None] + np.arange(4)).ravel()
+    var_idx = []
+    for h in range(haps):
+        beg, cnt = batch.var_off[h][idx], np.diff(batch.var_off[h])[idx]
+        var_idx.append(np.repeat(beg - np.cumsum(cnt) + cnt, cnt) + np.arange(int(cnt.sum())))
+    arrays = {"sc_index": idx, "counts": counts}
+    for name in ("aln_dist", "aln_end_plane", "aln_beg_plane", "aln_status"):
+        arrays[name] = getattr(res, name)[aln]
+    for name in ("sc_phase", "orig_phase_dist", "swap_phase_dist"):
+        arrays[name] = getattr(res, name)[idx]
+    for name, _ in res.PER_VAR:
+        arrays[name] = np.concatenate([getattr(res, name)[h][w][var_idx[h]] for h in range(haps) for w in range(2)])
+    for name in floats:
+        a = arrays[name]
+        arrays[name + "_nonfinite"] = np.select([np.isnan(a), np.isposinf(a), np.isneginf(a)], [1, 2, 3], 0)
+        arrays[name] = np.where(np.isfinite(a), a, 0)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a).astype(np.float64))
+
+
 class stdout_to_stderr:
     """file descriptor 1 -> 2 for the duration (RCCL prints a version banner to stdout when a communicator is created; the
     driver reads ONE JSON line from this script's stdout)"""
@@ -343,7 +386,7 @@ def main():
     ap.add_argument("--n-sc", type=int, default=1000000, help="superclusters per GPU")
     ap.add_argument("--workload", default="wgs_synth")
     ap.add_argument("--seed", type=int, default=0x5eed)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --n-sc superclusters per GPU (own seed, own contigs); strong: --n-sc-total superclusters of one "
                          "synthetic genome dealt over the ranks by estimated cells, phasing all-gathered every step")
@@ -353,19 +396,28 @@ def main():
                          "1 = strictly one step after the other.  Default: 3 for wgs_synth, 1 for the workloads of long alignments "
                          "(their replay scratches and ladder workspaces each want a large share of the free memory)")
     ap.add_argument("--one-pass-batches", type=int, default=None,
-                    help="batches of the one-pass leg (upload from the variant tables + execute + download each; 0 = skip; "
+                    help="batches of the one-pass leg of --full (upload from the variant tables + execute + download each; 0 = skip; "
                          "default 9 for wgs_synth, 0 for the other workloads)")
     ap.add_argument("--one-pass-in-flight", type=int, default=None,
                     help="batches in flight in the one-pass leg (default 3 for wgs_synth: a fresh batch keeps its host thread ~50 ms in "
                          "vpr_upload_variants and the device ~35 ms -- K0 + the step --, so a third thread fills the device: 103 M/s "
                          "against 87 with two; the headline keeps two)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the legs measured after the headline (N = 1, default workload only): two batches in flight, and the "
+                    help="skip the legs --full measures after the headline (N = 1, default workload only): two batches in flight, and the "
                          "sv_synth / stress_synth workloads (BASELINE configs[2] / configs[4]) on small batches")
     ap.add_argument("--plumbing-check", action="store_true",
                     help="launch path only (no GPU work): the ranks rendezvous over gloo, all-reduce their rank numbers and rank 0 "
                          "prints {n_gpus, rank_sum}; tests/test_distributed.py runs `bench.py --gpus 2 --plumbing-check` on CPU")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel statistics and roofline, the device-tally check, phasing and "
+                         "PRECISION-RECALL SUMMARY, the one_at_a_time, one_pass, two_in_flight and secondary legs, the CPU baseline "
+                         "(--no-cpu-baseline, --no-secondary and --one-pass-* select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's results of the last timed step and the reduced counters to "
+                         "DIR/<name>.npy (float64, finite; a fixed sample of the superclusters, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as a plain `python bench.py --gpus N`: become the launcher of N ranks (one process per GPU, RCCL); rank 0
@@ -642,7 +694,8 @@ def main():
                     r = step(i, slots[j])
                     if timed:
                         with lock:
-                            account(slots[j])
+                            if args.full:
+                                account(slots[j])
                             last[i] = (r, slots[j])
             except BaseException as e:      # (a failed step must not leave the other threads waiting for its turn)
                 with turn:
@@ -701,11 +754,13 @@ def main():
         sys.stderr.write("kernel ms: " + " ".join(f"{x:.1f}" for x in kern_ms) + "\n")
     (res, t), S_last = last[args.warmup + args.steps - 1]
     batch, pr = S_last.batch, S_last.pr
+    if args.dump_outputs and rank == 0:     # (before anything else runs on S_last: its next step rewrites `res` in place)
+        dump_outputs(args.dump_outputs, res, t.cpu().numpy(), batch)
     # two more steps of one batch ALONE (not timed, not in `value`): a kernel's launch duration without the neighbours that
     # stretch it while batches are in flight -- the figure a rocprofv3 trace of `--in-flight 1` shows
     alone_acc, alone_ms = {}, []
     one_at_a_time = None
-    if n_fl > 1:
+    if args.full and n_fl > 1:
         n_al = 6
         sync()
         t_al = time.perf_counter()
@@ -718,7 +773,7 @@ def main():
                          "ms_per_step": round(dt_al / n_al * 1e3, 3), "kernel_ms_per_step": round(float(np.mean(alone_ms)), 3),
                          "note": "rank 0's figure x ranks; the same steps strictly one after the other on one batch (the latency of a "
                                  "lone step: DESIGN.md section 6)"}
-    if rank == 0:       # the device tally must equal the one recomputed from the downloaded results
+    if args.full and rank == 0:       # the device tally must equal the one recomputed from the downloaded results
         assert np.array_equal(shard.tally_from_results(res, batch.var_off), pr.tally()), "device tally != host tally"
         # after the timed region: per-contig phasing (host Viterbi) and the PRECISION-RECALL SUMMARY of this rank
         pb, sw, fl = summary.phase(res.sc_phase, np.ones(batch.n_sc, np.int32))
@@ -744,7 +799,7 @@ def main():
     # flight overlap one batch's upload and planning with another's kernels.
     one_pass = None
     tm_main = pr.timing()
-    if world == 1 and not strong and args.one_pass_batches > 0:
+    if args.full and world == 1 and not strong and args.one_pass_batches > 0:
         nb = args.one_pass_batches
         op_parts = [0.0, 0.0, 0.0]
         n_op = args.one_pass_in_flight if args.one_pass_in_flight else (3 if args.workload == "wgs_synth" else n_fl)
@@ -811,7 +866,7 @@ def main():
     # ---- legs after the headline (rank 0 at N = 1 only; nothing here enters `value`)
     two_fl = None
     secondary = []
-    if world == 1 and not strong and not args.no_secondary and args.workload == "wgs_synth":
+    if args.full and world == 1 and not strong and not args.no_secondary and args.workload == "wgs_synth":
         # (a) two batches in flight behind two handles, when the headline ran one at a time (--in-flight 1 or the stall guard)
         try:
             if n_fl > 1:
@@ -869,7 +924,7 @@ def main():
             except Exception as e:
                 secondary.append({"workload": wl, "error": repr(e)})
 
-    if rank == 0:
+    if args.full and rank == 0:
         tm = tm_main
         # dominant K1/K2 kernel (the DP sweeps the byte model of SURVEY 8(d) is about): algorithmic bytes per launch
         # / average launch duration (HIP events on the stream the kernel is launched on)
@@ -976,6 +1031,7 @@ def main():
             "note": "largest accumulated launch time of any kernel over the timed steps (the throughput-dominant sweep kernel is `kernel` above)"}
         per_kernel = {k[1]: {"launches": v[0], "ms": round(v[1], 3), "other_launches": v[5], "other_ms": round(v[6], 3)}
                       for k, v in sorted(stats_acc.items())}
+    if rank == 0:
         out = {
             "metric": "supercluster-alignments/sec", "value": round(value, 1), "unit": "supercluster-alignments/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -987,8 +1043,6 @@ def main():
                                      "joint_synth": "lognormal(median 20, sigma 1.2) clip [4,10002], 0.75 % of the superclusters with one SV-sized indel (50..10000)"}.get(args.workload),
                        "sharding": (f"{args.n_sc_total} superclusters dealt over {world} ranks by estimated cells, phasing all-gathered"
                                     if strong else f"{world} ranks x independent superclusters")},
-            "dense_cells_per_s": round(tm.cells_dense * world * args.steps / elapsed, 1),
-            "kernel_ms_per_step": round(float(np.mean(kern_ms)), 3),
             # every timed step on this rank: its own duration (start of vpr_execute -> counters reduced; with batches in flight
             # the steps overlap, so this is a step's latency, not the time per step) and the spacing of the completions
             "step_ms": (lambda d: {"p50": round(float(np.percentile(d, 50)), 3), "p95": round(float(np.percentile(d, 95)), 3),
@@ -1001,13 +1055,6 @@ def main():
             "collective": collective, "comm_ranks": comm_ranks,
             "per_rank": dict(per_rank, note="each rank's own wall clock per step over the timed region, and the host time of its counters + "
                                              "collective call per step (with batches in flight it overlaps the other batch's kernels)"),
-            "bookkeeping_ms_per_step": round(acct_s[0] / max(args.steps, 1) * 1e3, 3),   # (reading the launch statistics: inside the timed region)
-            "host": {"n_device_allocs": int(host_acc["n_device_allocs"]), "n_device_frees": int(host_acc["n_device_frees"]),
-                     "n_host_allocs": int(host_acc["n_host_allocs"]), "ms_host_alloc": round(host_acc["ms_host_alloc"], 3),
-                     "ms_host_blocked": round(host_acc["ms_host_blocked"], 3),
-                     "execute_wall_ms_max": round(max(host_acc["execute_wall_ms"]), 3),
-                     "note": "allocator calls and blocking waits inside the timed vpr_execute calls of rank 0 (vpr_timing): 0 once a "
-                             "handle's workspaces have settled"},
             "step_parts_ms": {"vpr_execute": round(parts[0] / args.steps * 1e3, 3), "vpr_download": round(parts[1] / args.steps * 1e3, 3),
                               "counters_and_collective": round(parts[2] / args.steps * 1e3, 3)},
             "setup_not_timed": {"generate_s": round(t_b - t_a, 2), "host_marshalling_s": round(t_c - t_b, 2),
@@ -1017,60 +1064,72 @@ def main():
                                 "input_bytes": int(in_bytes),
                                 # one batch through upload + one step (vpr_create, a per-process cost, left out)
                                 "pcie_inclusive_value": round(4 * args.n_sc / ((t_d - t_c1) + elapsed / args.steps), 1)},
-            "kernel_only_value": round(4 * args.n_sc / (float(np.mean(kern_ms)) * 1e-3), 1),
-            "end_to_end_value": None if not one_pass else one_pass["value"],      # = one_pass.value: every batch from its variant tables
-            "lane_levels": {"zero_level_rejects_with_complete_wave_0": int(tm.n_lane1_seen), "finished_at_distance_1_lane_level": int(tm.n_lane1_finished),
-                            "waves_dropped": int(tm.n_lane1_waves_dropped), "retries_incl_in_place_round": int(tm.n_band_retries),
-                            "note": "pr_d1.hip: alignments the zero-distance lane kernel rejects with a complete wave 0 (at most VPR_D1_MAX_ROWS truth rows, "
-                                    "default 256) run the distance-1 lane kernel; the rest re-runs in place with the 16-cell kernels"},
-            "one_pass": one_pass,
-            "two_in_flight": two_fl,
-            "one_at_a_time": one_at_a_time,
             "stall_guard": stall_guard,
-            "secondary": secondary,
-            "kernels": per_kernel,
-            "counts_at_min_qual_TP_FP_FN": t.cpu().numpy()[:, 3, :, 0].tolist(),   # [callset][TP,FP,FN], type ALL, all ranks
-            "pr_summary_rank0": [{"type": summary.NAMES[r.vartype], "threshold": "BEST" if r.best else "NONE", "qual": r.qual,
-                                  "truth_tp": r.truth_tp, "query_tp": r.query_tp, "truth_fn": r.truth_fn, "query_fp": r.query_fp,
-                                  "precision": round(r.precision, 6), "recall": round(r.recall, 6), "f1": round(r.f1_score, 6)}
-                                 for r in rows if not r.best],
-            "phasing_rank0": {"switches": int(len(sw)), "flips": int(len(fl))},
-            "tie_replays": {"alignments_with_consulted_ties": int((res.aln_status & 1).sum()), "replays_per_step": int(tm.n_tie_replays),
-                            "replay_kernel_ms_per_step": round(tm.ms_tie, 3),
-                            "note": "reference keeps the last writer of swap_pred (dist.cpp:347,376): replayed on the device, results exact"},
-            "roofline": roof,
         }
-        if not args.no_cpu_baseline and world == 1:      # (rank 0 at N = 1 only: the other ranks would wait for it)
-            out["cpu_baseline"] = cpu_baseline(batch, target_s=8.0)
-            out["cpu_baseline"]["host"] = f"{os.cpu_count()} logical cores visible, {cpu_limit()} allowed (cgroup quota)"
-            if out["cpu_baseline"].get("calibrated_value"):
-                out["cpu_baseline"]["calibrated_single_thread_value"] = round(out["cpu_baseline"]["calibrated_value"] / out["cpu_baseline"]["cores"], 1)
-        # ---- the compact digest, LAST in the line (the driver keeps the line's tail): what the legs above measured
-        def _sec(x):
-            if "error" in x:
-                return {"workload": x.get("workload"), "error": x["error"][:80]}
-            r_ = x.get("roofline") or {}
-            c_ = x.get("cpu_baseline") or {}
-            return {"workload": x["workload"], "n_sc": x["superclusters"], "ms_per_step": x["ms_per_step"], "value": x["value"],
-                    "kernel": r_.get("kernel"), "frac": r_.get("frac"), "traffic": r_.get("traffic"),
-                    "cpu": c_.get("value"), "cpu_calibrated": c_.get("calibrated_value")}
-        cb = out.get("cpu_baseline") or {}
-        out["summary"] = {
-            "value": out["value"], "ms_per_step": out["ms_per_step"], "in_flight": n_fl, "n_gpus": world,
-            "comm_ranks": comm_ranks, "per_rank_ms_per_step": per_rank["ms_per_step"],
-            "one_pass": None if not one_pass else {"value": one_pass["value"], "ms_per_batch": one_pass["ms_per_batch"],
-                                                   "upload_variants_ms": one_pass["host_thread_ms_per_batch"]["upload_variants"]},
-            "one_at_a_time_ms_per_step": None if not one_at_a_time else one_at_a_time["ms_per_step"],
-            "roofline": {"kernel": roof["kernel"], "frac": roof["frac"], "traffic": roof["traffic"], "avg_launch_ms": roof["avg_launch_ms"],
-                         "alone_ms": None if not roof["alone"] else roof["alone"]["avg_launch_ms"],
-                         "alone_frac": None if not roof["alone"] else roof["alone"]["frac"], "valu_issue_frac": roof["valu_issue_frac"]},
-            "by_time": {k_: roof["by_time"][k_] for k_ in ("kernel", "ms_per_step", "traffic_main_launch", "frac_main_launch", "valu_issue_frac_main_launch")},
-            "tie_replays": {"per_step": int(tm.n_tie_replays), "kernel_ms_per_step": round(tm.ms_tie, 3)},
-            "secondary": [_sec(x) for x in secondary],
-            "cpu_baseline": {"value": cb.get("value"), "cores": cb.get("cores"), "single_thread": cb.get("single_thread_value"),
-                             "calibrated_value": cb.get("calibrated_value"), "within_15_percent": cb.get("calibration_within_15_percent"),
-                             "cpu_model": cb.get("cpu_model")},
-        }
+        if args.full:
+            out.update({
+                "dense_cells_per_s": round(tm.cells_dense * world * args.steps / elapsed, 1),
+                "kernel_ms_per_step": round(float(np.mean(kern_ms)), 3),
+                "bookkeeping_ms_per_step": round(acct_s[0] / max(args.steps, 1) * 1e3, 3),   # (reading the launch statistics: inside the timed region)
+                "host": {"n_device_allocs": int(host_acc["n_device_allocs"]), "n_device_frees": int(host_acc["n_device_frees"]),
+                         "n_host_allocs": int(host_acc["n_host_allocs"]), "ms_host_alloc": round(host_acc["ms_host_alloc"], 3),
+                         "ms_host_blocked": round(host_acc["ms_host_blocked"], 3),
+                         "execute_wall_ms_max": round(max(host_acc["execute_wall_ms"]), 3),
+                         "note": "allocator calls and blocking waits inside the timed vpr_execute calls of rank 0 (vpr_timing): 0 once a "
+                                 "handle's workspaces have settled"},
+                "kernel_only_value": round(4 * args.n_sc / (float(np.mean(kern_ms)) * 1e-3), 1),
+                "end_to_end_value": None if not one_pass else one_pass["value"],      # = one_pass.value: every batch from its variant tables
+                "lane_levels": {"zero_level_rejects_with_complete_wave_0": int(tm.n_lane1_seen), "finished_at_distance_1_lane_level": int(tm.n_lane1_finished),
+                                "waves_dropped": int(tm.n_lane1_waves_dropped), "retries_incl_in_place_round": int(tm.n_band_retries),
+                                "note": "pr_d1.hip: alignments the zero-distance lane kernel rejects with a complete wave 0 (at most VPR_D1_MAX_ROWS truth rows, "
+                                        "default 256) run the distance-1 lane kernel; the rest re-runs in place with the 16-cell kernels"},
+                "one_pass": one_pass,
+                "two_in_flight": two_fl,
+                "one_at_a_time": one_at_a_time,
+                "secondary": secondary,
+                "kernels": per_kernel,
+                "counts_at_min_qual_TP_FP_FN": t.cpu().numpy()[:, 3, :, 0].tolist(),   # [callset][TP,FP,FN], type ALL, all ranks
+                "pr_summary_rank0": [{"type": summary.NAMES[r.vartype], "threshold": "BEST" if r.best else "NONE", "qual": r.qual,
+                                      "truth_tp": r.truth_tp, "query_tp": r.query_tp, "truth_fn": r.truth_fn, "query_fp": r.query_fp,
+                                      "precision": round(r.precision, 6), "recall": round(r.recall, 6), "f1": round(r.f1_score, 6)}
+                                     for r in rows if not r.best],
+                "phasing_rank0": {"switches": int(len(sw)), "flips": int(len(fl))},
+                "tie_replays": {"alignments_with_consulted_ties": int((res.aln_status & 1).sum()), "replays_per_step": int(tm.n_tie_replays),
+                                "replay_kernel_ms_per_step": round(tm.ms_tie, 3),
+                                "note": "reference keeps the last writer of swap_pred (dist.cpp:347,376): replayed on the device, results exact"},
+                "roofline": roof,
+            })
+            if not args.no_cpu_baseline and world == 1:      # (rank 0 at N = 1 only: the other ranks would wait for it)
+                out["cpu_baseline"] = cpu_baseline(batch, target_s=8.0)
+                out["cpu_baseline"]["host"] = f"{os.cpu_count()} logical cores visible, {cpu_limit()} allowed (cgroup quota)"
+                if out["cpu_baseline"].get("calibrated_value"):
+                    out["cpu_baseline"]["calibrated_single_thread_value"] = round(out["cpu_baseline"]["calibrated_value"] / out["cpu_baseline"]["cores"], 1)
+            # ---- the compact digest, LAST in the line (the driver keeps the line's tail): what the legs above measured
+            def _sec(x):
+                if "error" in x:
+                    return {"workload": x.get("workload"), "error": x["error"][:80]}
+                r_ = x.get("roofline") or {}
+                c_ = x.get("cpu_baseline") or {}
+                return {"workload": x["workload"], "n_sc": x["superclusters"], "ms_per_step": x["ms_per_step"], "value": x["value"],
+                        "kernel": r_.get("kernel"), "frac": r_.get("frac"), "traffic": r_.get("traffic"),
+                        "cpu": c_.get("value"), "cpu_calibrated": c_.get("calibrated_value")}
+            cb = out.get("cpu_baseline") or {}
+            out["summary"] = {
+                "value": out["value"], "ms_per_step": out["ms_per_step"], "in_flight": n_fl, "n_gpus": world,
+                "comm_ranks": comm_ranks, "per_rank_ms_per_step": per_rank["ms_per_step"],
+                "one_pass": None if not one_pass else {"value": one_pass["value"], "ms_per_batch": one_pass["ms_per_batch"],
+                                                       "upload_variants_ms": one_pass["host_thread_ms_per_batch"]["upload_variants"]},
+                "one_at_a_time_ms_per_step": None if not one_at_a_time else one_at_a_time["ms_per_step"],
+                "roofline": {"kernel": roof["kernel"], "frac": roof["frac"], "traffic": roof["traffic"], "avg_launch_ms": roof["avg_launch_ms"],
+                             "alone_ms": None if not roof["alone"] else roof["alone"]["avg_launch_ms"],
+                             "alone_frac": None if not roof["alone"] else roof["alone"]["frac"], "valu_issue_frac": roof["valu_issue_frac"]},
+                "by_time": {k_: roof["by_time"][k_] for k_ in ("kernel", "ms_per_step", "traffic_main_launch", "frac_main_launch", "valu_issue_frac_main_launch")},
+                "tie_replays": {"per_step": int(tm.n_tie_replays), "kernel_ms_per_step": round(tm.ms_tie, 3)},
+                "secondary": [_sec(x) for x in secondary],
+                "cpu_baseline": {"value": cb.get("value"), "cores": cb.get("cores"), "single_thread": cb.get("single_thread_value"),
+                                 "calibrated_value": cb.get("calibrated_value"), "within_15_percent": cb.get("calibration_within_15_percent"),
+                                 "cpu_model": cb.get("cpu_model")},
+            }
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()

@@ -561,7 +561,7 @@ def test_bench_self_launch_two_ranks_on_one_gpu(scaling, workload):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["VCFDIST_BENCH_ONE_GPU"] = "1"
     extra = ["--scaling", "strong", "--n-sc-total", "30000"] if scaling == "strong" else []
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--n-sc", "20000", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--n-sc", "20000", "--steps", "2", "--warmup", "1",
                           "--no-cpu-baseline", "--workload", workload] + extra, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

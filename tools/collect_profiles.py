@@ -97,7 +97,7 @@ for k, c in kern.items():
             if name in c:
                 e[key] = round(c[name] / waves, 1)
     kept[k] = e
-json.dump({"command": "rocprofv3 --kernel-trace --pmc <one group per pass> -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline "
+json.dump({"command": "rocprofv3 --kernel-trace --pmc <one group per pass> -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline "
                       f"--workload {workload} --n-sc {n_sc}",
            "passes": ["FETCH_SIZE", "WRITE_SIZE", "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR",
                       "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS"],
