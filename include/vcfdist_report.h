@@ -11,6 +11,8 @@
  *   vrp_write_phasing_summary    phaseblockData::write_phasing_summary             src/phase.cpp:515-528
  *   vrp_ng50                     phaseblockData::calculate_ng50                    src/phase.cpp:534-626
  *   vrp_write_summary_vcf        phaseblockData::write_summary_vcf                 src/phase.cpp:8-222
+ *   vrp_write_distance           editData::write_distance                          src/edit.cpp:137-250
+ *   vrp_write_edits              editData::write_edits                             src/edit.cpp:256-270
  *                                ctgVariants::print_var_info / _empty / _sample    src/variant.cpp:229-286
  * Host code, like the reference's; the inputs are the columns of include/vcfdist_io.h, the tables of
  * include/vcfdist_cluster.h and the result arrays of include/vcfdist_pr.h (vpr_results, vpr_phase, vpr_pr_counts).
@@ -91,6 +93,29 @@ int vrp_write_variants(const char *path, const vrp_contig *ctgs, int32_t n_ctg, 
 /* cmd: the "##CL=" line; file_date: "YYYYMMDD" or NULL for today (local time); credit_threshold: g.credit_threshold */
 int vrp_write_summary_vcf(const char *path, const vrp_contig *ctgs, int32_t n_ctg, const char *cmd,
                           const char *file_date, float credit_threshold);
+
+/* ---- the distance mode (-d): the records of vpr_distance_download (include/vcfdist_distance.h), one set per contig in the
+   order the contigs were evaluated */
+typedef struct vrp_edits {
+    const char *ctg;             /* contig name */
+    int64_t n;                   /* records */
+    const int32_t *sc;
+    const uint8_t *hap;
+    const int32_t *pos;          /* 0-based contig position */
+    const uint8_t *type;         /* VPR_TYPE_SUB / INS / DEL */
+    const int32_t *len;
+    const int32_t *min_qual, *max_qual;
+} vrp_edits;
+/* <prefix>distance.tsv and <prefix>distance-summary.tsv (only when write_files != 0) and the ALIGNMENT DISTANCE SUMMARY text
+   (always) into summary.  The summary file and text hold the types the reference's verbosity filter keeps (edit.cpp:212-217:
+   0 ALL, 1 ALL / SNP / INDEL -- the command lines' setting --, 2 all five); distance.tsv is the same at every verbosity.  Into summary
+   (summary_cap bytes, NUL-terminated, may be NULL).  The per-quality counters come from difference arrays over the records'
+   [min_qual, max_qual) ranges.  Returns the summary's length (>= 0) or VRP_ERR_*. */
+int vrp_write_distance(const char *prefix, const vrp_edits *sets, int32_t n_sets, int32_t min_qual, int32_t max_qual,
+                       int32_t eval_sub, int32_t eval_open, int32_t eval_extend, int32_t verbosity, int32_t write_files,
+                       char *summary, int64_t summary_cap);
+/* edits.tsv: one line per record, in the order given */
+int vrp_write_edits(const char *path, const vrp_edits *sets, int32_t n_sets);
 
 const char *vrp_last_error(void);
 

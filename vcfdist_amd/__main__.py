@@ -4,8 +4,9 @@ The reference's command line for the precision/recall evaluation (vcfdist v2.6.4
 the MI355X path: VCF / BED / FASTA readers (include/vcfdist_io.h), biWFA or distance clustering and superclustering
 (include/vcfdist_cluster.h), the precision/recall alignment on the GPU (include/vcfdist_pr.h), phasing, counters and
 the PRECISION-RECALL SUMMARY and the output tables (include/vcfdist_report.h: precision-recall*.tsv, phase-blocks.tsv,
-superclusters.tsv, query.tsv, truth.tsv, summary.vcf under -p PREFIX; -n writes nothing).  Realignment and the --distance
-metrics are not part of it."""
+superclusters.tsv, query.tsv, truth.tsv, summary.vcf under -p PREFIX; -n writes nothing).  With -d the alignment-distance
+metrics run on the GPU behind each contig's path (include/vcfdist_distance.h): distance.tsv, distance-summary.tsv, edits.tsv and
+the ALIGNMENT DISTANCE SUMMARY (printed even with -n); one rank only.  Realignment is not part of it."""
 import argparse
 import sys
 
@@ -110,10 +111,10 @@ def prepare_contig(name, seq, slots, args, device=0):
                        [s["var_qual"] for s in slots], [h.ref_off for h in haps], [h.ref_len for h in haps],
                        [h.alt_off for h in haps], [h.alt_len for h in haps], [h.pool for h in haps])
         batch = api.batch_from_variants(v)
-    return dict(name=name, haps=haps, cl=cl, sc=sc, batch=batch, slots=slots)
+    return dict(name=name, haps=haps, cl=cl, sc=sc, batch=batch, slots=slots, variants=v if sc.n else None)
 
 
-def evaluate_contig(prep, args, device=0, part=None):
+def evaluate_contig(prep, args, device=0, part=None, dist_sets=None):
     """the precision/recall path on the GPU, phasing and counters for a prepared contig.  -> int64 counters [2][4][3][nq],
     n_sc, and what the writers need: (clusters after splitting, superclusters, results, phase sets, pb_phase, switches, flips).
     part = (rank, world, collective device): this rank evaluates its share of the contig's SUPERCLUSTERS -- dealt by the
@@ -139,6 +140,16 @@ def evaluate_contig(prep, args, device=0, part=None):
             r.sc_phase[bad] = A.PHASE_NONE
     if part is None:
         res = pr.run(prep["batch"])
+        if dist_sets is not None:      # -d: edits_wrapper behind the precision/recall path (main.cpp:223-238), from what it left on the device
+            d = pr.distance(prep["variants"], eval_sub=args.eval_sub, eval_open=args.eval_open, eval_extend=args.eval_extend,
+                            min_qual=args.min_qual, max_qual=args.max_qual)
+            info = d["info"]
+            if info.n_limit or info.n_error:
+                print(f"[WARN  vcfdist_amd] contig '{name}': {info.n_limit} distance alignment(s) beyond the device's memory plan and "
+                      f"{info.n_error} that failed: NOT EVALUATED -- left out of the distance metrics", file=sys.stderr)
+            print(f"[vcfdist_amd] {name}: {info.n_jobs} distance alignments, {info.n_edits} edits, edit distance {int(d['qual_dists'].min())}",
+                  file=sys.stderr)
+            dist_sets.append((name, d))
         mask_unevaluated(res)
         pb, sw, fl = S.phase(res.sc_phase, phase_sets)
         counts = S.pr_counts(pr, cls, pb, args.min_qual, args.max_qual)
@@ -214,6 +225,19 @@ def check_contigs(q, t, fasta, bed):
     return qc
 
 
+def eval_penalty(what):
+    """an evaluation penalty as globals.cpp:274-335 reads it: an integer, non-negative"""
+    def parse(v):
+        try:
+            x = int(v)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"Invalid {what} provided")
+        if x < 0:
+            raise argparse.ArgumentTypeError(f"Must provide non-negative {what}")
+        return x
+    return parse
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m vcfdist_amd", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("query"); ap.add_argument("truth"); ap.add_argument("fasta")
@@ -239,6 +263,10 @@ def main(argv=None):
                          "sources on one position, an alignment the dense kernels cannot place) instead of warning and leaving its "
                          "variants out of the counts and tables")
     ap.add_argument("--device", type=int, default=None, help="HIP device (default: LOCAL_RANK, else 0)")
+    ap.add_argument("-d", "--distance", action="store_true", help="alignment-distance metrics (distance.tsv, distance-summary.tsv, edits.tsv)")
+    ap.add_argument("-ex", "--eval-mismatch-penalty", type=eval_penalty("evaluation mismatch penalty"), default=3, dest="eval_sub")
+    ap.add_argument("-eo", "--eval-gap-open-penalty", type=eval_penalty("eval gap-opening penalty"), default=2, dest="eval_open")
+    ap.add_argument("-ee", "--eval-gap-extend-penalty", type=eval_penalty("eval gap-extension penalty"), default=1, dest="eval_extend")
     ap.add_argument("--shard", default="superclusters", choices=["superclusters", "contigs"],
                     help="several ranks (torch.distributed.run, one per GPU): deal every contig's superclusters over the ranks "
                          "(default; balanced whatever the contigs' sizes) or whole contigs")
@@ -254,6 +282,9 @@ def main(argv=None):
     # (RCCL), the result records are gathered, and rank 0 writes the files
     import os
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    if args.distance and world > 1:
+        raise SystemExit("ERROR: -d/--distance runs on one rank only (its edit records are not gathered over ranks): "
+                         "run it without torch.distributed.run")
     device = args.device if args.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
     one_gpu = bool(os.environ.get("VCFDIST_ONE_GPU"))      # plumbing check on a one-GPU box: every rank uses device 0, gloo
     if one_gpu and args.device is None:
@@ -306,10 +337,12 @@ def main(argv=None):
         except api.VprError as e:
             raise SystemExit(f"ERROR: contig '{ctg}': {e}")
     reports = {}
+    dist_sets = [] if args.distance else None
     for k in mine:
         ctg = contigs[k]
         try:
-            counts, n_sc, tables = evaluate_contig(prepared.pop(k), args, device=device, part=(rank, world, cdev) if by_sc else None)
+            counts, n_sc, tables = evaluate_contig(prepared.pop(k), args, device=device, part=(rank, world, cdev) if by_sc else None,
+                                                   dist_sets=dist_sets)
         except api.VprError as e:     # the library's explicit refusals end the run like the reference's ERROR()
             raise SystemExit(f"ERROR: contig '{ctg}': {e}")
         total += counts
@@ -328,6 +361,12 @@ def main(argv=None):
             dist.all_gather_object(gathered, reports)
             reports = {k: v for part in gathered for k, v in part.items()}
     rows = S.pr_summary(total, args.min_qual, args.max_qual)
+    if dist_sets is not None:       # write_distance (printed even with -n) and write_edits, edit.cpp:134-280
+        text = RP.write_distance(args.prefix, dist_sets, args.min_qual, args.max_qual, args.eval_sub, args.eval_open, args.eval_extend,
+                                 verbosity=1, write_files=not args.no_output_files)
+        if not args.no_output_files:
+            RP.write_edits(args.prefix + "edits.tsv", dist_sets)
+        print(text)
     if rank == 0:
         if not args.no_output_files:
             RP.write_precision_recall(args.prefix, total, args.min_qual, args.max_qual)

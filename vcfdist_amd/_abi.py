@@ -462,3 +462,25 @@ class Results:
                         out.append(f"{name}[hap {h}][swap {w}]: {len(bad)} mismatches, first at var {bad[0]}: "
                                    f"{getattr(self, name)[h][w][bad[0]]} vs {getattr(other, name)[h][w][bad[0]]}")
         return out
+
+
+# ---- include/vcfdist_distance.h
+DIST_ST_LIMIT = 1
+DIST_ST_ERROR = 2
+
+
+class VprDistConfig(C.Structure):
+    _fields_ = [("eval_sub", C.c_int32), ("eval_open", C.c_int32), ("eval_extend", C.c_int32), ("min_qual", C.c_int32),
+                ("max_qual", C.c_int32), ("flags", C.c_int32), ("round_bytes", C.c_int64)]
+
+
+class VprDistInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_jobs", "n_edits", "n_limit", "n_error", "n_rounds", "n_hist_rounds", "arena_bytes",
+                                         "plan_bytes", "input_bytes", "history_cells")] + \
+               [(n, C.c_double) for n in ("ms_upload", "ms_jobs", "ms_score", "ms_hist", "ms_back", "ms_wall")]
+
+
+class VprDistResults(C.Structure):
+    _fields_ = [("job_sc", P_i32), ("job_hap", P_u8), ("job_min_qual", P_i32), ("job_max_qual", P_i32), ("job_dist", P_i32),
+                ("job_status", P_u8), ("qual_dists", P_i64), ("edit_sc", P_i32), ("edit_hap", P_u8), ("edit_pos", P_i32),
+                ("edit_type", P_u8), ("edit_len", P_i32), ("edit_min_qual", P_i32), ("edit_max_qual", P_i32)]

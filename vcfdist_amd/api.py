@@ -79,6 +79,9 @@ def lib():
     L.vpr_synth_variants.restype = C.POINTER(A.VprVariants)
     L.vpr_synth_variants.argtypes = [H]
     L.vpr_synth_destroy.argtypes = [H]
+    L.vpr_distance.argtypes = [H, C.POINTER(A.VprVariants), C.POINTER(A.VprDistConfig)]
+    L.vpr_distance_info.argtypes = [H, C.POINTER(A.VprDistInfo)]
+    L.vpr_distance_download.argtypes = [H, C.POINTER(A.VprDistResults)]
     _LIB = L
     return L
 
@@ -91,6 +94,8 @@ EXPORTED = [
     "vpr_store_phase", "vpr_batch_from_variants", "vpr_owned_batch_view", "vpr_owned_batch_free",
     "vpr_synth_default_params", "vpr_synth_create", "vpr_synth_variants", "vpr_synth_destroy",
 ]
+# include/vcfdist_distance.h
+DIST_EXPORTED = ["vpr_distance", "vpr_distance_info", "vpr_distance_download"]
 
 
 def store_phase(s, thr=0.6):
@@ -250,6 +255,33 @@ class PrecisionRecall:
         self.upload(batch)
         self.execute()
         return self.download()
+
+    def distance(self, variants, eval_sub=3, eval_open=2, eval_extend=1, min_qual=0, max_qual=60, round_bytes=0):
+        """The distance metrics (include/vcfdist_distance.h) of the batch the last execute evaluated.  variants: the
+        A.Variants (or a VprVariants struct) the batch was made from.  -> dict of numpy arrays: job_* per (supercluster, hap,
+        threshold) job, qual_dists [max_qual + 2], edit_* per record; plus 'info' (VprDistInfo)."""
+        vs = variants.as_struct() if isinstance(variants, A.Variants) else variants
+        cfg = A.VprDistConfig(eval_sub=eval_sub, eval_open=eval_open, eval_extend=eval_extend, min_qual=min_qual, max_qual=max_qual,
+                              flags=0, round_bytes=round_bytes)
+        L = lib()
+        self._chk(L.vpr_distance(self._h, C.byref(vs), C.byref(cfg)), "vpr_distance")
+        info = A.VprDistInfo()
+        self._chk(L.vpr_distance_info(self._h, C.byref(info)), "vpr_distance_info")
+        nj, ne = int(info.n_jobs), int(info.n_edits)
+        out = dict(info=info, qual_dists=np.zeros(max_qual + 2, np.int64))
+        cols = dict(job_sc=(nj, np.int32), job_hap=(nj, np.uint8), job_min_qual=(nj, np.int32), job_max_qual=(nj, np.int32),
+                    job_dist=(nj, np.int32), job_status=(nj, np.uint8), edit_sc=(ne, np.int32), edit_hap=(ne, np.uint8),
+                    edit_pos=(ne, np.int32), edit_type=(ne, np.uint8), edit_len=(ne, np.int32), edit_min_qual=(ne, np.int32),
+                    edit_max_qual=(ne, np.int32))
+        r = A.VprDistResults()
+        for name, (n, dt) in cols.items():
+            out[name] = np.zeros(max(n, 1), dt)
+            setattr(r, name, A._ptr(out[name], C.c_int32 if dt == np.int32 else C.c_uint8))
+        r.qual_dists = A._ptr(out["qual_dists"], C.c_int64)
+        self._chk(L.vpr_distance_download(self._h, C.byref(r)), "vpr_distance_download")
+        for name, (n, _) in cols.items():
+            out[name] = out[name][:n]
+        return out
 
     def timing(self) -> A.VprTiming:
         t = A.VprTiming()

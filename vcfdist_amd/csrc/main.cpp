@@ -9,6 +9,9 @@
 //   vcfdist_gpu <query.vcf[.gz]> <truth.vcf[.gz]> <ref.fasta[.gz]> [-b regions.bed] [-p prefix] [-n] [-c biwfa | gap N | size N]
 //               [-l max variant size] [-s max supercluster size] [-mn / -mx qual] [-f filters] [-i iterations] [-x -o -e penalties]
 //               [-ct credit threshold] [-pt phasing threshold] [-sv threshold] [--reach-min-gap N] [--strict] [--device N]
+//               [-d] [-ex -eo -ee evaluation penalties]
+// With -d the distance metrics (edits_wrapper, dist.cpp:1908-2077) run on the GPU after each contig's precision/recall path
+// (include/vcfdist_distance.h), as the reference's main.cpp:223-238 runs them after precision_recall_threads_wrapper.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdint>
@@ -22,6 +25,7 @@
 #include <vector>
 
 #include "../../include/vcfdist_cluster.h"
+#include "../../include/vcfdist_distance.h"
 #include "../../include/vcfdist_io.h"
 #include "../../include/vcfdist_pr.h"
 #include "../../include/vcfdist_report.h"
@@ -32,6 +36,8 @@ struct Args {
     std::string query, truth, fasta, bed, filter, prefix = "./", cluster = "biwfa";
     int max_size = 5000, min_qual = 0, max_qual = 60, cluster_gap = 50, max_iterations = 4, max_supercluster_size = 10000;
     int sub = 5, open = 6, extend = 2, sv_threshold = 50, reach_min_gap = 10, device = 0;
+    int eval_sub = 3, eval_open = 2, eval_extend = 1;      // globals.h:52-55
+    bool distance = false;
     double credit_threshold = 0.7, phase_threshold = 0.6;
     bool no_output_files = false, strict = false;
 };
@@ -43,6 +49,13 @@ struct Args {
     va_end(ap);
     fputc('\n', stderr);
     exit(1);
+}
+// an evaluation penalty as globals.cpp:274-335 reads it: std::stoi, then non-negative
+int eval_penalty(const char *v, const char *what) {
+    int x = 0;
+    try { x = std::stoi(v); } catch (const std::exception &) { die("ERROR: Invalid %s provided", what); }
+    if (x < 0) die("ERROR: Must provide non-negative %s", what);
+    return x;
 }
 void warn(const std::string &m) { fprintf(stderr, "[WARN  vcfdist] %s\n", m.c_str()); }
 
@@ -75,6 +88,10 @@ Args parse(int argc, char **argv) {
         else if (o == "-n" || o == "--no-output-files") a.no_output_files = true;
         else if (o == "--strict") a.strict = true;
         else if (o == "--device") a.device = atoi(need(i));
+        else if (o == "-d" || o == "--distance") a.distance = true;
+        else if (o == "-ex" || o == "--eval-mismatch-penalty") a.eval_sub = eval_penalty(need(i), "evaluation mismatch penalty");
+        else if (o == "-eo" || o == "--eval-gap-open-penalty") a.eval_open = eval_penalty(need(i), "eval gap-opening penalty");
+        else if (o == "-ee" || o == "--eval-gap-extend-penalty") a.eval_extend = eval_penalty(need(i), "eval gap-extension penalty");
         else if (!o.empty() && o[0] == '-' && o.size() > 1) die("ERROR: unknown option '%s'", o.c_str());
         else pos.push_back(o);
     }
@@ -168,6 +185,9 @@ struct ContigOut {       // what the writers need of one contig, kept alive unti
     vpr_results res;
     void *res_block = nullptr;
     std::vector<int32_t> phase_sets, pb, sw, fl, phase_block;
+    // -d: the contig's edit records (vpr_distance_download)
+    std::vector<int32_t> e_sc, e_pos, e_len, e_minq, e_maxq;
+    std::vector<uint8_t> e_hap, e_type;
 };
 
 const vio_hap_vars EMPTY_HAP = {0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
@@ -273,6 +293,26 @@ int main(int argc, char **argv) {
             }
             if (vpr_upload_variants(h, &V) || vpr_execute(h)) die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
             if (vpr_results_alloc(h, &C->res, &C->res_block) || vpr_download(h, &C->res)) die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+            if (A.distance) {      // edits_wrapper for this contig's superclusters, behind the precision/recall path (main.cpp:223-238)
+                vpr_dist_config dc;
+                memset(&dc, 0, sizeof(dc));
+                dc.eval_sub = A.eval_sub; dc.eval_open = A.eval_open; dc.eval_extend = A.eval_extend; dc.min_qual = A.min_qual; dc.max_qual = A.max_qual;
+                vpr_dist_info di;
+                if (vpr_distance(h, &V, &dc) || vpr_distance_info(h, &di)) die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+                const size_t ne = size_t(di.n_edits);
+                C->e_sc.resize(ne); C->e_pos.resize(ne); C->e_len.resize(ne); C->e_minq.resize(ne); C->e_maxq.resize(ne); C->e_hap.resize(ne); C->e_type.resize(ne);
+                std::vector<int64_t> qd(size_t(A.max_qual) + 2);
+                vpr_dist_results dr;
+                memset(&dr, 0, sizeof(dr));
+                dr.qual_dists = qd.data(); dr.edit_sc = C->e_sc.data(); dr.edit_hap = C->e_hap.data(); dr.edit_pos = C->e_pos.data();
+                dr.edit_type = C->e_type.data(); dr.edit_len = C->e_len.data(); dr.edit_min_qual = C->e_minq.data(); dr.edit_max_qual = C->e_maxq.data();
+                if (vpr_distance_download(h, &dr)) die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+                if (di.n_limit || di.n_error)
+                    fprintf(stderr, "[WARN  vcfdist_amd] contig '%s': %lld distance alignment(s) beyond the device's memory plan and %lld that failed: "
+                                    "NOT EVALUATED -- left out of the distance metrics\n", ctg.c_str(), (long long)di.n_limit, (long long)di.n_error);
+                fprintf(stderr, "[vcfdist_amd] %s: %lld distance alignments, %lld edits, edit distance %lld\n", ctg.c_str(), (long long)di.n_jobs,
+                        (long long)di.n_edits, (long long)*std::min_element(qd.begin(), qd.end()));
+            }
             // a supercluster with an alignment the GPU path did not evaluate takes no side in the contig's phasing
             const uint32_t err_bits = VPR_ST_ERR_LIMIT | VPR_ST_ERR_NO_PTR | VPR_ST_ERR_UNFINISHED;
             for (int a = 0; a < 4 * n_sc; a++) if (C->res.aln_status[a] & err_bits) C->res.sc_phase[a >> 2] = VPR_PHASE_NONE;
@@ -332,6 +372,21 @@ int main(int argc, char **argv) {
         outs.push_back(C);
     }
 
+    if (A.distance) {      // write_distance (printed even with -n), write_edits (edit.cpp:134-280)
+        std::vector<vrp_edits> sets(outs.size());
+        for (size_t k = 0; k < outs.size(); k++) {
+            const ContigOut *C = outs[k];
+            sets[k] = vrp_edits{C->name.c_str(), int64_t(C->e_sc.size()), C->e_sc.data(), C->e_hap.data(), C->e_pos.data(), C->e_type.data(),
+                                C->e_len.data(), C->e_minq.data(), C->e_maxq.data()};
+        }
+        std::vector<char> text(size_t(1) << 16);
+        const int n = vrp_write_distance(A.prefix.c_str(), sets.data(), int32_t(sets.size()), A.min_qual, A.max_qual, A.eval_sub, A.eval_open,
+                                         A.eval_extend, 1, A.no_output_files ? 0 : 1, text.data(), int64_t(text.size()));
+        if (n < 0) die("ERROR: %s", vrp_last_error());
+        if (!A.no_output_files && vrp_write_edits((A.prefix + "edits.tsv").c_str(), sets.data(), int32_t(sets.size())))
+            die("ERROR: %s", vrp_last_error());
+        printf("%s\n", text.data());
+    }
     vpr_pr_row rows[2 * VPR_VARTYPES];
     if (vpr_pr_summary(total.data(), A.min_qual, A.max_qual, rows)) die("ERROR: vpr_pr_summary failed");
     if (!A.no_output_files) {
@@ -348,7 +403,8 @@ int main(int argc, char **argv) {
                        "sub = %d\nopen = %d\nextend = %d\neval_sub = %d\neval_open = %d\neval_extend = %d\ndistance = %s",
                     "vcfdist_amd", vpr_version(), A.prefix.c_str(), cmd.c_str(), A.fasta.c_str(), A.query.c_str(), A.truth.c_str(), A.bed.c_str(), "true",
                     A.filter.c_str(), A.min_qual, A.max_qual, A.max_size, A.sv_threshold, A.phase_threshold, A.credit_threshold, "false", "false",
-                    "false", A.cluster.c_str(), A.cluster_gap, A.reach_min_gap, A.max_iterations, 64, 64.0, A.sub, A.open, A.extend, 3, 2, 1, "false");
+                    "false", A.cluster.c_str(), A.cluster_gap, A.reach_min_gap, A.max_iterations, 64, 64.0, A.sub, A.open, A.extend, A.eval_sub, A.eval_open, A.eval_extend,
+                    A.distance ? "true" : "false");
             fclose(f);
         }
         std::vector<vrp_contig> ctgs(outs.size());

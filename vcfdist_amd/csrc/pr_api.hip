@@ -1160,6 +1160,7 @@ int vpr_create(const vpr_config *cfg, vpr_handle **out) {
 void vpr_destroy(vpr_handle *h) {
     if (!h) return;
     (void)hipSetDevice(h->cfg.device);
+    dist_free(h);
     free_batch(h);
     for (auto &b : h->dev_cache) (void)x_free(h, b.p, SITE);
     for (int k = 0; k < 4; k++)
@@ -3666,6 +3667,7 @@ extern "C" {
 int vpr_execute(vpr_handle *h) {
     if (!h) return VPR_ERR_ARG;
     if (!h->uploaded) return fail(h, VPR_ERR_STATE, "vpr_execute before vpr_upload");
+    dist_free(h);           // distance results of an earlier execute are no longer this execute's
     for (auto &b : h->exec_blks) b.used = false;
     for (auto &b : h->exec_pins) b.used = false;
     h->hs = vpr_handle::HostStat();

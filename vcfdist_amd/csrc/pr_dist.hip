@@ -1,0 +1,807 @@
+// pr_dist.hip -- the alignment-distance metrics (include/vcfdist_distance.h): edits_wrapper (dist.cpp:1908-2077) for an executed
+// batch, on the device end to end.
+//
+// A job is (supercluster, query hap, quality threshold).  Steps, all on the library's stream:
+//   k_dist_count   one thread per (supercluster, hap): the number of distinct thresholds {int(qual + 1)} u {max_qual + 2}
+//                  (0 for a supercluster with a VPR_ST_ERR_* alignment); a scan gives the job offsets
+//   k_dist_jobs    the jobs in ascending threshold order, their string lengths and pass-1 scratch sizes; the truth slot
+//                  follows the device-resident sc_phase
+//   k_dist_wave<false>  pass 1, one wavefront per job, lanes over diagonals: builds the reversed query / truth strings
+//                  (generate_ptrs_strs with the quality filter) and runs wf_swg_align with a ring of max(x, o+e)+1 rows,
+//                  for the score s and the exact size of the band-compacted history
+//   k_dist_wave<true>   pass 2: the same recurrence, every row kept in a slice of the round arena
+//   k_dist_back    one thread per job: wf_swg_backtrack over the history; the strings are reversed, so the backtrack emits
+//                  the forward CIGAR in order and count_dist and the add_edits state machine run on the fly.  Launched
+//                  twice: count (distance, record count, per-quality totals), then, after a scan, write.
+//
+// The band: a row's cells can be set only from rows s-x, s-(o+e), s-e one diagonal apart at most, so every row s has a
+// diagonal range [lo_s, hi_s] that the previous ranges bound (arithmetic, the same in both passes); a cell outside it is
+// provably never written (-2 / no pointer) and is not stored.  The reference loops over all q + t - 1 diagonals.
+//
+// Memory: the job tables live for the call; pass-1 scratch and pass-2 histories share one round arena.  Jobs run in
+// rounds (pass 1: at most 4 GiB, pass 2: up to the plan, both capped by vpr_dist_config.round_bytes); a job larger than its
+// round budget runs alone, a job larger than the memory plan (half the device's free memory) is marked VPR_DIST_ST_LIMIT.  Everything but what vpr_distance_download reads is
+// released when the call returns; the rest goes with the next upload or execute.
+#include "pr_host.h"
+#include "pr_plan.h"
+#include "../../include/vcfdist_distance.h"
+
+#include <climits>
+
+namespace {
+
+enum { DM_SUB = 0, DM_INS = 1, DM_DEL = 2 };
+enum : uint8_t { DP_INS = 1, DP_DEL = 2, DP_MAT = 4, DP_SUB = 8 };          // src/defs.h:110-114
+const uint32_t DIST_ERR_BITS = VPR_ST_ERR_LIMIT | VPR_ST_ERR_NO_PTR | VPR_ST_ERR_UNFINISHED;
+
+struct DTab {
+    const int64_t *ctg_off;
+    const uint8_t *ctg_seq;
+    const int32_t *sc_ctg, *sc_beg, *sc_end;
+    const int64_t *var_off[4];
+    const int32_t *var_pos[4];
+    const uint8_t *var_type[4];
+    const float *var_qual[4];
+    const int32_t *ref_len[4], *alt_len[4];
+    const int64_t *alt_off[4];
+    const uint8_t *pool[4];
+    const int32_t *sc_phase;
+    const uint32_t *aln_status;
+    int32_t n_sc, max_qual;
+};
+
+struct DJob { int32_t sc, hap, minq, maxq, q_len, t_len, tslot, pad; };
+struct DRow { int32_t lo, hi; int64_t base; };                 // diagonal range of a wavefront row, first cell of its slice
+struct DEdit { int32_t sc, pos, len, minq, maxq; uint8_t hap, type, pad[2]; };
+struct DPen { int x, o, e; };
+
+__host__ __device__ inline int64_t pad16(int64_t b) { return (b + 15) & ~int64_t(15); }
+
+// the threshold a variant adds to the set (dist.cpp:2014: float + 1 stored in a std::set<int>)
+__device__ inline int qual_key(float q) {
+    const float k = q + 1.0f;
+    return k >= 2147483520.0f ? INT_MAX - 1 : k > -2147483520.0f ? int(k) : INT_MIN + 1;   // (NaN and the extremes stay defined)
+}
+
+__device__ inline bool sc_bad(const DTab &T, int sc) {
+    uint32_t st = 0;
+    for (int k = 0; k < 4; k++) st |= T.aln_status[4 * sc + k];
+    return (st & DIST_ERR_BITS) != 0;
+}
+
+// generate_ptrs_strs' string (dist.cpp:145-242) of hap slot `slot` over the supercluster's region, variants with
+// qual >= minq only: emit(src, n) for every piece in order.  false: the walk went backwards (overlapping variants,
+// which the reference cannot process either).
+template <typename F>
+__device__ bool gen_walk(const DTab &T, int slot, int sc, float minq, F emit) {
+    const int ctg = T.sc_ctg[sc];
+    const uint8_t *fa = T.ctg_seq + T.ctg_off[ctg];
+    const int64_t ctg_len = T.ctg_off[ctg + 1] - T.ctg_off[ctg];
+    const int beg = T.sc_beg[sc];
+    const int end = int(min(int64_t(T.sc_end[sc]), ctg_len - 1));
+    int64_t v = T.var_off[slot][sc];
+    const int64_t ve = T.var_off[slot][sc + 1];
+    for (int pos = beg; pos <= end;) {
+        if (v < ve && pos == T.var_pos[slot][v]) {
+            if (T.var_qual[slot][v] >= minq) {
+                const int type = T.var_type[slot][v];
+                if (type == VPR_TYPE_INS) emit(T.pool[slot] + T.alt_off[slot][v], T.alt_len[slot][v]);
+                else if (type == VPR_TYPE_DEL) pos += T.ref_len[slot][v];
+                else { emit(T.pool[slot] + T.alt_off[slot][v], 1); pos++; }
+            }
+            v++;
+        } else {
+            const int stop = v < ve ? T.var_pos[slot][v] : end + 1;
+            if (stop < pos || stop > ctg_len) return false;
+            emit(fa + pos, stop - pos);
+            pos = stop;
+        }
+    }
+    return true;
+}
+
+__device__ int gen_len(const DTab &T, int slot, int sc, float minq, bool *ok) {
+    int n = 0;
+    *ok = gen_walk(T, slot, sc, minq, [&](const uint8_t *, int k) { n += k; });
+    return n;
+}
+
+// the thresholds of (supercluster, hap) in ascending order, {int(qual + 1)} u {max_qual + 2}: fn(prev_qual, qual) per job.
+// (k_dist_count and k_dist_jobs enumerate with this one loop, so the job counts and the jobs written agree whatever the qualities)
+template <typename F>
+__device__ void for_thresholds(const DTab &T, int hap, int sc, F fn) {
+    const int64_t b = T.var_off[hap][sc], e = T.var_off[hap][sc + 1];
+    const int top = T.max_qual + 2;
+    int prev = 0, cur = INT_MIN;
+    for (;;) {                  // the smallest key above the last one
+        int next = top > cur ? top : INT_MAX;
+        for (int64_t v = b; v < e; v++) {
+            const int k = qual_key(T.var_qual[hap][v]);
+            if (k > cur && k < next) next = k;
+        }
+        if (next == INT_MAX) break;
+        fn(prev, next);
+        prev = cur = next;
+    }
+}
+
+__global__ void k_dist_count(DTab T, int64_t *cnt) {
+    const int i = int(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= 2 * T.n_sc) return;
+    const int sc = i >> 1, hap = i & 1;
+    int64_t n = 0;
+    if (!sc_bad(T, sc)) for_thresholds(T, hap, sc, [&](int, int) { n++; });
+    cnt[i] = n;
+}
+
+// pass-1 scratch of a job: both strings, a ring of P row headers and P rows of three full-width matrices
+__device__ inline int64_t need1(int q, int t, int P) {
+    return pad16(pad16(q) + pad16(t) + 16 * int64_t(P) + 12 * int64_t(P) * max(q + t - 1, 1));
+}
+
+__global__ void k_dist_jobs(DTab T, const int64_t *job_off, DJob *jobs, int64_t *need, uint8_t *status, int P) {
+    const int i = int(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= 2 * T.n_sc) return;
+    const int sc = i >> 1, hap = i & 1;
+    if (sc_bad(T, sc)) return;
+    const int tslot = 2 + (T.sc_phase[sc] == VPR_PHASE_SWAP ? 1 - hap : hap);
+    bool tok;
+    const int t_len = gen_len(T, tslot, sc, 0.0f, &tok);
+    int64_t j = job_off[i];
+    for_thresholds(T, hap, sc, [&](int prev, int next) {
+        bool qok;
+        const int q_len = gen_len(T, hap, sc, float(prev), &qok);
+        DJob J;
+        J.sc = sc; J.hap = hap; J.minq = prev; J.maxq = next; J.q_len = q_len; J.t_len = t_len; J.tslot = tslot; J.pad = 0;
+        jobs[j] = J;
+        const bool ok = tok && qok && q_len > 0 && t_len > 0;
+        status[j] = ok ? 0 : VPR_DIST_ST_ERROR;
+        need[j] = ok ? need1(q_len, t_len, P) : 0;
+        j++;
+    });
+}
+
+// the job's strings, reversed (dist.cpp:2047-2048), lanes writing each piece side by side
+__device__ void load_reversed(const DTab &T, const DJob &J, uint8_t *qs, uint8_t *ts, int lane) {
+    int n = 0;
+    gen_walk(T, J.hap, J.sc, float(J.minq), [&](const uint8_t *src, int k) {
+        for (int c = lane; c < k; c += 64) qs[J.q_len - 1 - (n + c)] = src[c];
+        n += k;
+    });
+    n = 0;
+    gen_walk(T, J.tslot, J.sc, 0.0f, [&](const uint8_t *src, int k) {
+        for (int c = lane; c < k; c += 64) ts[J.t_len - 1 - (n + c)] = src[c];
+        n += k;
+    });
+}
+
+// wavefront rows of one job: a ring of P rows (pass 1) or every row, band-compacted (pass 2)
+template <bool HIST>
+struct Rows {
+    DRow *row;            // [P] or [s + 1]
+    int32_t *off;         // cells
+    uint8_t *ptr;         // pointer flags (HIST only)
+    int P;
+    __device__ DRow get(int s) const { return row[HIST ? s : s % P]; }
+    // offs[m][r][d] as the reference would read it: -2 outside the row's band or before score 0
+    __device__ int ld(int r, int m, int d) const {
+        if (r < 0) return -2;
+        const DRow R = get(r);
+        if (d < R.lo || d > R.hi) return -2;
+        return off[R.base + int64_t(m) * (R.hi - R.lo + 1) + (d - R.lo)];
+    }
+};
+
+// pass 1 (HIST = false) / pass 2 (HIST = true) of one job per wavefront.  Pass 1 writes the score and the bytes pass 2 will
+// need; pass 2 writes the history into the slice its caller sized from them.
+template <bool HIST>
+__global__ void __launch_bounds__(64) k_dist_wave(DTab T, const DJob *__restrict__ jobs, int64_t j0, int64_t n,
+                                                   const int64_t *__restrict__ slice, int64_t slice_base, uint8_t *arena,
+                                                   uint8_t *status, int32_t *score, int64_t *need2, int64_t *cells_out, DPen pen) {
+    const int64_t j = j0 + int64_t(blockIdx.x);
+    if (int64_t(blockIdx.x) >= n) return;
+    if (status[j]) return;
+    const int lane = threadIdx.x;
+    const DJob J = jobs[j];
+    const int q = J.q_len, t = J.t_len, mat_len = q + t - 1;
+    const int x = pen.x, o = pen.o, e = pen.e, oe = o + e;
+    const int P = max(x, oe) + 1;
+    uint8_t *base = arena + (slice[j] - slice_base);
+    uint8_t *qs = base, *ts = base + pad16(q);
+    Rows<HIST> R;
+    R.P = P;
+    R.row = reinterpret_cast<DRow *>(ts + pad16(t));
+    const int s_hist = HIST ? score[j] : 0;
+    const int64_t n_rows = HIST ? int64_t(s_hist) + 1 : P;
+    R.off = reinterpret_cast<int32_t *>(reinterpret_cast<uint8_t *>(R.row) + 16 * n_rows);
+    const int64_t cell_cap = HIST ? cells_out[j] : int64_t(3) * P * mat_len;
+    R.ptr = reinterpret_cast<uint8_t *>(R.off + cell_cap);
+    load_reversed(T, J, qs, ts, lane);
+    // a bound no alignment reaches: every base substituted plus every base gapped
+    const int64_t s_max = int64_t(x) * (q + t) + int64_t(oe) * (q + t) + 1;
+
+    int s = 0;
+    int64_t cells = 3;
+    if (lane == 0) {
+        R.row[0] = DRow{q - 1, q - 1, 0};
+        R.off[DM_SUB] = -1; R.off[DM_INS] = -2; R.off[DM_DEL] = -2;
+        if (HIST) { R.ptr[DM_SUB] = DP_MAT; R.ptr[DM_INS] = 0; R.ptr[DM_DEL] = 0; }
+    }
+    __syncthreads();
+    bool failed = false;
+    for (;;) {
+        const DRow C = R.get(s);
+        const int w = C.hi - C.lo + 1;
+        // close INS / DEL into SUB (INS first, then DEL), dist.cpp:1532-1546
+        for (int d = C.lo + lane; d <= C.hi; d += 64) {
+            const int64_t c = C.base + (d - C.lo);
+            const int diag = d + 1 - q;
+            for (int m = DM_INS; m <= DM_DEL; m++) {
+                const int off = R.off[c + int64_t(m) * w];
+                if (off >= 0 && off < q && diag + off >= 0 && diag + off < t && off >= R.off[c]) {
+                    R.off[c] = off;
+                    if (HIST) R.ptr[c] |= (m == DM_INS) ? DP_INS : DP_DEL;
+                }
+            }
+        }
+        // extend along the diagonals (SUB only); the reference stops at the first diagonal that finishes
+        bool done = false;
+        for (int d0 = C.lo; d0 <= C.hi && !done; d0 += 64) {
+            const int d = d0 + lane;
+            bool fin = false;
+            if (d <= C.hi) {
+                const int64_t c = C.base + (d - C.lo);
+                const int diag = d + 1 - q;
+                int off = R.off[c];
+                while (off != -2 && diag + off >= -1 && off < q - 1 && diag + off < t - 1 && qs[off + 1] == ts[diag + off + 1]) off++;
+                R.off[c] = off;
+                fin = off == q - 1 && off + diag == t - 1;
+            }
+            done = __any(fin);
+        }
+        if (done) break;
+        s++;
+        if (s > s_max) { failed = true; break; }
+        // the new row's band from the rows it reads
+        int lo = INT_MAX, hi = INT_MIN;
+        auto widen = [&](int r, int dl, int dh) {
+            if (r < 0) return;
+            const DRow S = R.get(r);
+            if (S.lo > S.hi) return;
+            lo = min(lo, S.lo + dl); hi = max(hi, S.hi + dh);
+        };
+        widen(s - x, 0, 0);
+        widen(s - oe, -1, 1);
+        widen(s - e, -1, 1);
+        lo = max(lo, 0); hi = min(hi, mat_len - 1);
+        if (lo > hi) { lo = 1; hi = 0; }
+        const int wn = hi - lo + 1;
+        const int64_t nb = HIST ? cells : int64_t(s % P) * 3 * mat_len;
+        if (HIST && (s > s_hist || cells + 3 * int64_t(wn) > cell_cap)) { failed = true; break; }
+        __syncthreads();                  // every lane is done reading the ring slot about to be replaced
+        if (lane == 0) R.row[HIST ? s : s % P] = DRow{lo, hi, nb};
+        __syncthreads();
+        cells += 3 * int64_t(wn);
+        for (int d = lo + lane; d <= hi; d += 64) {
+            const int diag = d + 1 - q;
+            int vs = -2, vd = -2, vi = -2;
+            uint8_t fs = 0, fd = 0, fi = 0;
+            int p;
+            if (s - x >= 0 && (p = R.ld(s - x, DM_SUB, d)) != -2 && p + 1 < q && diag + p + 1 < t && p + 1 >= vs) { vs = p + 1; fs |= DP_SUB; }
+            if (s - oe >= 0 && d > 0 && (p = R.ld(s - oe, DM_SUB, d - 1)) != -2 && diag + p < t && p >= vd) { vd = p; fd |= DP_SUB; }
+            if (s - oe >= 0 && d < mat_len - 1 && (p = R.ld(s - oe, DM_SUB, d + 1)) != -2 && p + 1 < q && diag + p + 1 < t &&
+                diag + p + 1 >= 0 && p + 1 >= vi) { vi = p + 1; fi |= DP_SUB; }
+            if (s - e >= 0 && d > 0 && (p = R.ld(s - e, DM_DEL, d - 1)) != -2 && diag + p < t && p >= vd) { vd = p; fd |= DP_DEL; }
+            if (s - e >= 0 && d < mat_len - 1 && (p = R.ld(s - e, DM_INS, d + 1)) != -2 && p + 1 < q && diag + p + 1 < t &&
+                diag + p + 1 >= 0 && p + 1 >= vi) { vi = p + 1; fi |= DP_INS; }
+            const int64_t c = nb + (d - lo);
+            R.off[c] = vs; R.off[c + wn] = vi; R.off[c + 2 * int64_t(wn)] = vd;
+            if (HIST) { R.ptr[c] = fs; R.ptr[c + wn] = fi; R.ptr[c + 2 * int64_t(wn)] = fd; }
+        }
+        __syncthreads();
+    }
+    if (lane != 0) return;
+    if (failed) { status[j] |= VPR_DIST_ST_ERROR; return; }
+    if (!HIST) {
+        score[j] = s;
+        cells_out[j] = cells;
+        need2[j] = pad16(pad16(q) + pad16(t) + 16 * (int64_t(s) + 1) + 4 * cells + pad16(cells));
+    }
+}
+
+// add_edits (edit.cpp:4-78) as a state machine over the CIGAR's steps (a MAT / SUB step is the reference's two CIGAR
+// entries, INS / DEL one): a run is recorded when the next run starts, a SUB run one record per base -- so the run still
+// open at the end is never recorded
+struct EditSM {
+    int last = DP_MAT, len = 0, pos;
+    template <typename R>
+    __device__ void step(int type, R rec) {
+        if (type != last) {
+            if (last == DP_SUB) rec(pos - 1, VPR_TYPE_SUB, 1);
+            else if (last == DP_INS) rec(pos, VPR_TYPE_INS, len);
+            else if (last == DP_DEL) rec(pos - len, VPR_TYPE_DEL, len);
+            last = type; len = 1;
+        } else {
+            if (type == DP_SUB) rec(pos - 1, VPR_TYPE_SUB, 1);
+            len++;
+        }
+        if (type != DP_INS) pos++;
+    }
+};
+
+// wf_swg_backtrack (dist.cpp:2625-2757) of one job per thread.  WRITE = false: distance, record count and the per-quality
+// totals (a difference array of max_qual + 3 words); WRITE = true: the records at the offsets the scan gave.
+template <bool WRITE>
+__global__ void k_dist_back(DTab T, const DJob *__restrict__ jobs, int64_t j0, int64_t n, const int64_t *__restrict__ slice,
+                            int64_t slice_base, const uint8_t *arena, uint8_t *status, const int32_t *score, const int64_t *cells_in,
+                            int32_t *dist_out, int64_t *n_rec, const int64_t *rec_off, int64_t rec_base, DEdit *rec_out,
+                            unsigned long long *qdiff, DPen pen) {
+    const int64_t k = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const int64_t j = j0 + k;
+    if (status[j]) { if (!WRITE) { dist_out[j] = 0; n_rec[k] = 0; } return; }
+    const DJob J = jobs[j];
+    const int q = J.q_len, t = J.t_len;
+    const uint8_t *base = arena + (slice[j] - slice_base);
+    const int s_fin = score[j];
+    Rows<true> R;
+    R.P = 0;
+    R.row = reinterpret_cast<DRow *>(const_cast<uint8_t *>(base) + pad16(q) + pad16(t));
+    R.off = reinterpret_cast<int32_t *>(reinterpret_cast<uint8_t *>(R.row) + 16 * (int64_t(s_fin) + 1));
+    R.ptr = reinterpret_cast<uint8_t *>(R.off + cells_in[j]);
+    auto flag = [&](int r, int m, int d) -> uint8_t {
+        if (r < 0) return 0;
+        const DRow W = R.get(r);
+        if (d < W.lo || d > W.hi) return 0;
+        return R.ptr[W.base + int64_t(m) * (W.hi - W.lo + 1) + (d - W.lo)];
+    };
+    const int x = pen.x, o = pen.o, e = pen.e;
+    int64_t nr = 0, out = WRITE ? rec_off[k] - rec_base : 0;
+    auto rec = [&](int pos, int type, int len) {
+        if (WRITE) {
+            DEdit E;
+            E.sc = J.sc; E.pos = pos; E.len = len; E.minq = J.minq; E.maxq = J.maxq; E.hap = uint8_t(J.hap); E.type = uint8_t(type);
+            E.pad[0] = E.pad[1] = 0;
+            rec_out[out + nr] = E;
+        }
+        nr++;
+    };
+    EditSM sm;
+    sm.pos = T.sc_beg[J.sc];
+    int dist = 0;
+    auto emit = [&](int type) { dist += type != DP_MAT; sm.step(type, rec); };
+    int qi = q - 1, ri = t - 1, mi = DM_SUB, s = s_fin;
+    bool bad = false;
+    while ((qi >= 0 || ri >= 0) && !bad) {
+        if (s < 0) { bad = true; break; }
+        const int d = q - 1 + ri - qi;
+        if (mi == DM_SUB) {
+            const uint8_t f = flag(s, DM_SUB, d);
+            if (f & (DP_INS | DP_DEL)) {              // a gap ends here: INS preferred
+                const int m = (f & DP_INS) ? DM_INS : DM_DEL;
+                const int prev = R.ld(s, m, d);
+                while (qi > prev && !bad) { emit(DP_MAT); qi--; ri--; bad = qi < 0 || ri < 0; }
+                mi = m;
+            } else if (f & DP_SUB) {
+                if (s - x < 0) { bad = true; break; }
+                const int prev = R.ld(s - x, DM_SUB, d);
+                while (qi > prev + 1 && !bad) { emit(DP_MAT); qi--; ri--; bad = qi < 0 || ri < 0; }
+                if (bad) break;
+                emit(DP_SUB); qi--; ri--;
+                s -= x;
+            } else if (f & DP_MAT) {
+                while (qi >= 0 && ri >= 0) { emit(DP_MAT); qi--; ri--; }
+                if (qi >= 0 || ri >= 0) bad = true;
+            } else {
+                bad = true;
+            }
+        } else {
+            const uint8_t f = flag(s, mi, d);
+            const uint8_t ext = mi == DM_INS ? DP_INS : DP_DEL;
+            if (!(f & (ext | DP_SUB))) { bad = true; break; }
+            emit(ext);
+            if (mi == DM_INS) qi--; else ri--;
+            if (f & ext) s -= e;
+            else { mi = DM_SUB; s -= o + e; }
+        }
+        if (!(qi == -1 && ri == -1) && (qi < 0 || ri < 0)) bad = true;
+    }
+    if (WRITE) return;
+    if (bad) { status[j] |= VPR_DIST_ST_ERROR; dist_out[j] = 0; n_rec[k] = 0; return; }
+    dist_out[j] = dist;
+    n_rec[k] = nr;
+    // all_qual_dists[q] += dist for q in [prev_qual, qual) (dist.cpp:2059-2063), as a difference array
+    const int top = T.max_qual + 2;
+    const int lo = max(J.minq, 0), hi = min(J.maxq, top);
+    if (dist && lo < hi) {
+        atomicAdd(&qdiff[lo], (unsigned long long)(int64_t)dist);
+        atomicAdd(&qdiff[hi], (unsigned long long)(-(int64_t)dist));
+    }
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------
+struct DistState {
+    uint8_t *in_blk = nullptr; size_t in_bytes = 0;         // the uploaded tables
+    DJob *jobs = nullptr; size_t job_cap = 0;               // job tables (grown on demand)
+    int64_t *need1 = nullptr, *need2 = nullptr, *cells = nullptr, *slice = nullptr, *nrec = nullptr, *recoff = nullptr;
+    int32_t *score = nullptr, *dist = nullptr;
+    uint8_t *status = nullptr;
+    int64_t *cnt = nullptr, *cnt_off = nullptr; size_t cnt_cap = 0, cnt_off_cap = 0;
+    void *scan_tmp = nullptr; size_t scan_tmp_bytes = 0;
+    unsigned long long *qdiff = nullptr; size_t qdiff_cap = 0;
+    uint8_t *arena = nullptr; int64_t arena_bytes = 0;
+    DEdit *edits = nullptr; int64_t edit_cap = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int32_t max_qual = 0;
+    bool valid = false;
+    vpr_dist_info info;
+};
+
+namespace {
+
+template <typename T>
+int dist_grow(vpr_handle *h, T **p, size_t *cap, size_t n, const char *site) {
+    if (*p && *cap >= n) return VPR_OK;
+    if (*p) (void)x_free(h, *p, site);
+    *p = nullptr;
+    const size_t want = std::max<size_t>(n, 1);
+    if (x_malloc(h, reinterpret_cast<void **>(p), want * sizeof(T), site) != hipSuccess) {
+        *p = nullptr; *cap = 0;
+        (void)hipGetLastError();
+        return fail(h, VPR_ERR_NOMEM, "vpr_distance: cannot allocate %zu bytes on the device (%s)", want * sizeof(T), site);
+    }
+    *cap = want;
+    return VPR_OK;
+}
+
+int scan_i64(vpr_handle *h, DistState *D, const int64_t *in, int64_t *out, size_t n) {
+    size_t need = 0;
+    if (vplan_exclusive_scan_i64(nullptr, &need, in, out, n, h->stream)) return fail(h, VPR_ERR_DEVICE, "vpr_distance: scan sizing failed");
+    if (int rc = dist_grow(h, reinterpret_cast<uint8_t **>(&D->scan_tmp), &D->scan_tmp_bytes, need, SITE)) return rc;
+    if (vplan_exclusive_scan_i64(D->scan_tmp, &need, in, out, n, h->stream)) return fail(h, VPR_ERR_DEVICE, "vpr_distance: scan failed");
+    return VPR_OK;
+}
+
+double ev_ms(DistState *D) {
+    float ms = 0;
+    (void)hipEventSynchronize(D->ev[1]);
+    (void)hipEventElapsedTime(&ms, D->ev[0], D->ev[1]);
+    return ms;
+}
+
+}  // namespace
+
+// the buffers only a vpr_distance call itself uses (tables, pass scratch, round arena): released when it returns, so that the
+// memory the next vpr_execute plans with is not held by the distance step.  What vpr_distance_download reads stays.
+void dist_release_work(vpr_handle *h) {
+    DistState *D = h->dist;
+    if (!D) return;
+    void **ps[] = {reinterpret_cast<void **>(&D->in_blk), reinterpret_cast<void **>(&D->need1), reinterpret_cast<void **>(&D->need2),
+                   reinterpret_cast<void **>(&D->cells), reinterpret_cast<void **>(&D->slice), reinterpret_cast<void **>(&D->nrec),
+                   reinterpret_cast<void **>(&D->recoff), reinterpret_cast<void **>(&D->score), reinterpret_cast<void **>(&D->cnt),
+                   reinterpret_cast<void **>(&D->cnt_off), reinterpret_cast<void **>(&D->scan_tmp), reinterpret_cast<void **>(&D->arena)};
+    for (void **p : ps) { if (*p) (void)x_free(h, *p, SITE); *p = nullptr; }
+    D->in_bytes = 0; D->cnt_cap = D->cnt_off_cap = 0; D->scan_tmp_bytes = 0; D->arena_bytes = 0;
+    D->job_cap = 0;         // (the per-job tables are allocated together: with their work columns gone the next call renews them all)
+}
+
+// everything of the distance step, results included: called by vpr_destroy, by every upload (free_batch) and at the start of
+// vpr_execute, so that vpr_distance_download / vpr_distance_info never return an earlier batch's or execute's results
+void dist_free(vpr_handle *h) {
+    DistState *D = h->dist;
+    if (!D) return;
+    void *ps[] = {D->in_blk, D->jobs, D->need1, D->need2, D->cells, D->slice, D->nrec, D->recoff, D->score, D->dist, D->status,
+                  D->cnt, D->cnt_off, D->scan_tmp, D->qdiff, D->arena, D->edits};
+    for (void *p : ps) if (p) (void)x_free(h, p, SITE);
+    for (int k = 0; k < 2; k++) if (D->ev[k]) (void)hipEventDestroy(D->ev[k]);
+    delete D;
+    h->dist = nullptr;
+}
+
+extern "C" int vpr_distance(vpr_handle *h, const vpr_variants *v, const vpr_dist_config *cfg) {
+    if (!h) return VPR_ERR_ARG;
+    if (!v || !cfg) return fail(h, VPR_ERR_ARG, "vpr_distance: null argument");
+    if (!h->executed) return fail(h, VPR_ERR_ARG, "vpr_distance: no batch has been executed");
+    if (v->n_sc != h->n_sc) return fail(h, VPR_ERR_ARG, "vpr_distance: %d superclusters given, the executed batch has %d", v->n_sc, h->n_sc);
+    if (cfg->eval_sub < 1 || cfg->eval_open < 0 || cfg->eval_extend < 1 || cfg->max_qual < 0 || cfg->max_qual > (1 << 24))
+        return fail(h, VPR_ERR_ARG, "vpr_distance: eval_sub and eval_extend must be at least 1, eval_open and max_qual non-negative");
+    if (v->n_sc > 0 && (!v->ctg_off || !v->ctg_seq || !v->sc_ctg || !v->sc_beg || !v->sc_end))
+        return fail(h, VPR_ERR_ARG, "vpr_distance: null table");
+    const double t_wall = wall_ms();
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!h->dist) {
+        h->dist = new DistState();
+        HIPCHK(h, hipEventCreate(&h->dist->ev[0]));
+        HIPCHK(h, hipEventCreate(&h->dist->ev[1]));
+    }
+    DistState *D = h->dist;
+    D->valid = false;
+    struct Release { vpr_handle *h; ~Release() { (void)hipStreamSynchronize(h->stream); dist_release_work(h); } } release{h};
+    memset(&D->info, 0, sizeof(D->info));
+    vpr_dist_info &I = D->info;
+    const int64_t n_sc = v->n_sc;
+    const DPen pen{cfg->eval_sub, cfg->eval_open, cfg->eval_extend};
+    const int P = std::max(pen.x, pen.o + pen.e) + 1;
+    D->max_qual = cfg->max_qual;
+    const int nqd = cfg->max_qual + 3;
+    if (int rc = dist_grow(h, &D->qdiff, &D->qdiff_cap, size_t(nqd), SITE)) return rc;
+    HIPCHK(h, hipMemsetAsync(D->qdiff, 0, sizeof(unsigned long long) * nqd, h->stream));
+    if (n_sc == 0) { D->valid = true; I.ms_wall = wall_ms() - t_wall; return VPR_OK; }
+
+    // ---- the tables the jobs read, one block (the resident Level A arrays hold the unfiltered strings only)
+    const double t_up = wall_ms();
+    struct Piece { const void *src; size_t bytes; size_t at; };
+    std::vector<Piece> pieces;
+    size_t total = 0;
+    auto add = [&](const void *src, size_t bytes) { pieces.push_back({src, bytes, total}); total += (bytes + 255) & ~size_t(255); return pieces.size() - 1; };
+    const size_t i_ctg_off = add(v->ctg_off, sizeof(int64_t) * (size_t(v->n_ctg) + 1));
+    const size_t i_ctg_seq = add(v->ctg_seq, size_t(v->ctg_off[v->n_ctg]));
+    const size_t i_sc_ctg = add(v->sc_ctg, 4 * size_t(n_sc)), i_beg = add(v->sc_beg, 4 * size_t(n_sc)), i_end = add(v->sc_end, 4 * size_t(n_sc));
+    size_t i_var[4][8];
+    for (int s = 0; s < 4; s++) {
+        if (!v->var_off[s]) return fail(h, VPR_ERR_ARG, "vpr_distance: null var_off");
+        const int64_t nv = v->var_off[s][n_sc];
+        int64_t pool = 1;
+        for (int64_t k = 0; k < nv; k++) pool = std::max(pool, v->var_alt_off[s][k] + v->var_alt_len[s][k]);
+        i_var[s][0] = add(v->var_off[s], 8 * (size_t(n_sc) + 1));
+        i_var[s][1] = add(v->var_pos[s], 4 * size_t(nv));
+        i_var[s][2] = add(v->var_type[s], size_t(nv));
+        i_var[s][3] = add(v->var_qual[s], 4 * size_t(nv));
+        i_var[s][4] = add(v->var_ref_len[s], 4 * size_t(nv));
+        i_var[s][5] = add(v->var_alt_len[s], 4 * size_t(nv));
+        i_var[s][6] = add(v->var_alt_off[s], 8 * size_t(nv));
+        i_var[s][7] = add(v->allele_pool[s], size_t(nv ? pool : 0));
+    }
+    if (int rc = dist_grow(h, &D->in_blk, &D->in_bytes, total, SITE)) return rc;
+    for (const Piece &p : pieces)
+        if (p.bytes && p.src) HIPCHK(h, hipMemcpyAsync(D->in_blk + p.at, p.src, p.bytes, hipMemcpyHostToDevice, h->stream));
+    I.input_bytes = int64_t(total);
+    auto at = [&](size_t i) { return D->in_blk + pieces[i].at; };
+    DTab T;
+    T.ctg_off = reinterpret_cast<const int64_t *>(at(i_ctg_off));
+    T.ctg_seq = at(i_ctg_seq);
+    T.sc_ctg = reinterpret_cast<const int32_t *>(at(i_sc_ctg));
+    T.sc_beg = reinterpret_cast<const int32_t *>(at(i_beg));
+    T.sc_end = reinterpret_cast<const int32_t *>(at(i_end));
+    for (int s = 0; s < 4; s++) {
+        T.var_off[s] = reinterpret_cast<const int64_t *>(at(i_var[s][0]));
+        T.var_pos[s] = reinterpret_cast<const int32_t *>(at(i_var[s][1]));
+        T.var_type[s] = at(i_var[s][2]);
+        T.var_qual[s] = reinterpret_cast<const float *>(at(i_var[s][3]));
+        T.ref_len[s] = reinterpret_cast<const int32_t *>(at(i_var[s][4]));
+        T.alt_len[s] = reinterpret_cast<const int32_t *>(at(i_var[s][5]));
+        T.alt_off[s] = reinterpret_cast<const int64_t *>(at(i_var[s][6]));
+        T.pool[s] = at(i_var[s][7]);
+    }
+    T.sc_phase = h->dR.sc_phase;
+    T.aln_status = h->dR.aln_status;
+    T.n_sc = int32_t(n_sc);
+    T.max_qual = cfg->max_qual;
+    I.ms_upload = wall_ms() - t_up;
+
+    // ---- the jobs
+    const size_t n_hs = size_t(2 * n_sc);
+    if (int rc = dist_grow(h, &D->cnt, &D->cnt_cap, n_hs + 1, SITE)) return rc;
+    if (int rc = dist_grow(h, &D->cnt_off, &D->cnt_off_cap, n_hs + 1, SITE)) return rc;
+    HIPCHK(h, hipEventRecord(D->ev[0], h->stream));
+    hipLaunchKernelGGL(k_dist_count, dim3(unsigned((n_hs + 255) / 256)), dim3(256), 0, h->stream, T, D->cnt);
+    HIPCHK(h, hipMemsetAsync(D->cnt + n_hs, 0, sizeof(int64_t), h->stream));
+    if (int rc = scan_i64(h, D, D->cnt, D->cnt_off, n_hs + 1)) return rc;
+    int64_t n_jobs = 0;
+    HIPCHK(h, hipMemcpyAsync(&n_jobs, D->cnt_off + n_hs, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, x_sync(h, h->stream, SITE));
+    I.n_jobs = n_jobs;
+    {
+        size_t c = D->job_cap;
+        const size_t nj = size_t(std::max<int64_t>(n_jobs, 1)) + 1;
+        if (c < nj) {
+            void **arr[] = {reinterpret_cast<void **>(&D->jobs), reinterpret_cast<void **>(&D->need1), reinterpret_cast<void **>(&D->need2),
+                            reinterpret_cast<void **>(&D->cells), reinterpret_cast<void **>(&D->slice), reinterpret_cast<void **>(&D->nrec),
+                            reinterpret_cast<void **>(&D->recoff), reinterpret_cast<void **>(&D->score), reinterpret_cast<void **>(&D->dist),
+                            reinterpret_cast<void **>(&D->status)};
+            const size_t sz[] = {sizeof(DJob), 8, 8, 8, 8, 8, 8, 4, 4, 1};
+            for (int k = 0; k < 10; k++) {
+                if (*arr[k]) (void)x_free(h, *arr[k], SITE);
+                *arr[k] = nullptr;
+            }
+            D->job_cap = 0;
+            for (int k = 0; k < 10; k++)
+                if (x_malloc(h, arr[k], std::max<size_t>(nj * sz[k], 256), SITE) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return fail(h, VPR_ERR_NOMEM, "vpr_distance: cannot allocate the tables of %lld jobs", (long long)n_jobs);
+                }
+            D->job_cap = nj;
+        }
+    }
+    if (n_jobs > 0)
+        hipLaunchKernelGGL(k_dist_jobs, dim3(unsigned((n_hs + 255) / 256)), dim3(256), 0, h->stream, T, D->cnt_off, D->jobs, D->need1,
+                           D->status, P);
+    HIPCHK(h, hipEventRecord(D->ev[1], h->stream));
+    HIPCHK(h, hipGetLastError());
+    I.ms_jobs = ev_ms(D);
+    std::vector<int64_t> n1(static_cast<size_t>(n_jobs)), n2;
+    std::vector<uint8_t> st(static_cast<size_t>(n_jobs));
+    if (n_jobs) {
+        HIPCHK(h, hipMemcpyAsync(n1.data(), D->need1, 8 * size_t(n_jobs), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(st.data(), D->status, size_t(n_jobs), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, x_sync(h, h->stream, SITE));
+    }
+
+    // ---- memory plan: half of what the device has free (by the process's books) for one job; the round budget is that or the
+    // caller's cap
+    size_t fr = 0, tt = 0;
+    HIPCHK(h, hipMemGetInfo(&fr, &tt));
+    const int64_t plan = std::max<int64_t>(books_free(int64_t(fr), int64_t(tt)) / 2, int64_t(1) << 20);
+    // Pass-1 rounds of at most 4 GiB (a whole-genome batch's full-width rings came to 17 GB at once; in four rounds the call took
+    // 183 -> 220-240 ms).  Pass-2 rounds take up to the plan: a history round is as long as its longest job, and with 4 GiB the SV-sized jobs
+    // of joint_synth ran in 31 rounds instead of 2 (7 s -> 62 s).  round_bytes caps both.
+    const int64_t round_cap1 = std::min<int64_t>(cfg->round_bytes > 0 ? cfg->round_bytes : int64_t(4) << 30, plan);
+    const int64_t round_cap2 = cfg->round_bytes > 0 ? std::min<int64_t>(cfg->round_bytes, plan) : plan;
+    I.plan_bytes = plan;
+    auto ensure_arena = [&](int64_t bytes) -> int {
+        I.arena_bytes = std::max(I.arena_bytes, bytes);          // peak bytes a round occupies
+        if (bytes <= D->arena_bytes) return VPR_OK;
+        if (D->arena) (void)x_free(h, D->arena, SITE);
+        D->arena = nullptr; D->arena_bytes = 0;
+        if (x_malloc(h, reinterpret_cast<void **>(&D->arena), size_t(bytes), SITE) != hipSuccess) {
+            (void)hipGetLastError();
+            D->arena = nullptr;
+            return fail(h, VPR_ERR_NOMEM, "vpr_distance: cannot allocate a round arena of %lld bytes", (long long)bytes);
+        }
+        D->arena_bytes = bytes;
+        return VPR_OK;
+    };
+    // greedy rounds over [a, b): sum of `need` within the round budget, a larger job alone, a job beyond the plan marked
+    auto next_round = [&](const std::vector<int64_t> &need, int64_t a, int64_t b, int64_t off0, std::vector<int64_t> &slice, int64_t round_cap) {
+        int64_t sum = 0, k = a;
+        for (; k < b; k++) {
+            const int64_t nb = need[size_t(k - off0)];
+            if (st[size_t(k)]) { slice[size_t(k - off0)] = sum; continue; }
+            if (nb > plan) { st[size_t(k)] = VPR_DIST_ST_LIMIT; slice[size_t(k - off0)] = sum; continue; }
+            if (sum > 0 && sum + nb > round_cap) break;
+            slice[size_t(k - off0)] = sum;
+            sum += nb;
+        }
+        return std::make_pair(k, sum);
+    };
+    int64_t n_edits = 0;
+    double ms_score = 0, ms_hist = 0, ms_back = 0;
+    std::vector<int64_t> sl1(static_cast<size_t>(n_jobs)), sl2;
+    for (int64_t a = 0; a < n_jobs;) {
+        const auto r1 = next_round(n1, a, n_jobs, 0, sl1, round_cap1);
+        const int64_t b = r1.first;
+        I.n_rounds++;
+        if (int rc = ensure_arena(std::max<int64_t>(r1.second, 16))) return rc;
+        const int64_t nr = b - a;
+        HIPCHK(h, hipMemcpyAsync(D->slice + a, sl1.data() + a, 8 * size_t(nr), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(D->status + a, st.data() + a, size_t(nr), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipEventRecord(D->ev[0], h->stream));
+        hipLaunchKernelGGL(k_dist_wave<false>, dim3(unsigned(nr)), dim3(64), 0, h->stream, T, D->jobs, a, nr, D->slice, int64_t(0), D->arena,
+                           D->status, D->score, D->need2, D->cells, pen);
+        HIPCHK(h, hipEventRecord(D->ev[1], h->stream));
+        HIPCHK(h, hipGetLastError());
+        n2.assign(size_t(nr), 0);
+        HIPCHK(h, hipMemcpyAsync(n2.data(), D->need2 + a, 8 * size_t(nr), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(st.data() + a, D->status + a, size_t(nr), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, x_sync(h, h->stream, SITE));
+        ms_score += ev_ms(D);
+        sl2.assign(size_t(nr), 0);
+        for (int64_t c = a; c < b;) {
+            const auto r2 = next_round(n2, c, b, a, sl2, round_cap2);
+            const int64_t dd = r2.first, m = dd - c;
+            I.n_hist_rounds++;
+            if (int rc = ensure_arena(std::max<int64_t>(r2.second, 16))) return rc;
+            HIPCHK(h, hipMemcpyAsync(D->slice + c, sl2.data() + (c - a), 8 * size_t(m), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(D->status + c, st.data() + c, size_t(m), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipEventRecord(D->ev[0], h->stream));
+            hipLaunchKernelGGL(k_dist_wave<true>, dim3(unsigned(m)), dim3(64), 0, h->stream, T, D->jobs, c, m, D->slice, int64_t(0), D->arena,
+                               D->status, D->score, D->need2, D->cells, pen);
+            HIPCHK(h, hipEventRecord(D->ev[1], h->stream));
+            ms_hist += ev_ms(D);
+            HIPCHK(h, hipEventRecord(D->ev[0], h->stream));
+            const unsigned gb = unsigned((m + 63) / 64);
+            hipLaunchKernelGGL(k_dist_back<false>, dim3(gb), dim3(64), 0, h->stream, T, D->jobs, c, m, D->slice, int64_t(0), D->arena,
+                               D->status, D->score, D->cells, D->dist, D->nrec, D->recoff, int64_t(0), D->edits, D->qdiff, pen);
+            HIPCHK(h, hipMemsetAsync(D->nrec + m, 0, sizeof(int64_t), h->stream));
+            if (int rc = scan_i64(h, D, D->nrec, D->recoff, size_t(m) + 1)) return rc;
+            int64_t got = 0;
+            HIPCHK(h, hipMemcpyAsync(&got, D->recoff + m, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, x_sync(h, h->stream, SITE));
+            if (n_edits + got > D->edit_cap) {              // grow the record buffer, keeping what it holds
+                int64_t cap = std::max<int64_t>(D->edit_cap * 2, std::max<int64_t>(n_edits + got, 1024));
+                DEdit *nb = nullptr;
+                if (x_malloc(h, reinterpret_cast<void **>(&nb), size_t(cap) * sizeof(DEdit), SITE) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return fail(h, VPR_ERR_NOMEM, "vpr_distance: cannot allocate %lld edit records", (long long)cap);
+                }
+                if (n_edits) HIPCHK(h, hipMemcpyAsync(nb, D->edits, size_t(n_edits) * sizeof(DEdit), hipMemcpyDeviceToDevice, h->stream));
+                HIPCHK(h, x_sync(h, h->stream, SITE));
+                if (D->edits) (void)x_free(h, D->edits, SITE);
+                D->edits = nb; D->edit_cap = cap;
+            }
+            if (got)
+                hipLaunchKernelGGL(k_dist_back<true>, dim3(gb), dim3(64), 0, h->stream, T, D->jobs, c, m, D->slice, int64_t(0), D->arena,
+                                   D->status, D->score, D->cells, D->dist, D->nrec, D->recoff, -n_edits, D->edits, D->qdiff, pen);
+            HIPCHK(h, hipEventRecord(D->ev[1], h->stream));
+            HIPCHK(h, hipGetLastError());
+            ms_back += ev_ms(D);
+            n_edits += got;
+            c = dd;
+        }
+        HIPCHK(h, hipMemcpyAsync(st.data() + a, D->status + a, size_t(nr), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, x_sync(h, h->stream, SITE));
+        a = b;
+    }
+    // cells of the histories, for the statistics
+    if (n_jobs) {
+        std::vector<int64_t> cl(static_cast<size_t>(n_jobs));
+        HIPCHK(h, hipMemcpyAsync(cl.data(), D->cells, 8 * size_t(n_jobs), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, x_sync(h, h->stream, SITE));
+        for (int64_t k = 0; k < n_jobs; k++) if (!st[size_t(k)]) I.history_cells += cl[size_t(k)];
+        for (uint8_t s : st) { I.n_limit += (s & VPR_DIST_ST_LIMIT) != 0; I.n_error += (s & VPR_DIST_ST_ERROR) != 0; }
+        // jobs that never ran keep no distance
+        HIPCHK(h, hipMemcpyAsync(D->status, st.data(), size_t(n_jobs), hipMemcpyHostToDevice, h->stream));
+    }
+    I.n_edits = n_edits;
+    I.ms_score = ms_score; I.ms_hist = ms_hist; I.ms_back = ms_back;
+    HIPCHK(h, x_sync(h, h->stream, SITE));
+    I.ms_wall = wall_ms() - t_wall;
+    D->valid = true;
+    return VPR_OK;
+}
+
+extern "C" int vpr_distance_info(const vpr_handle *h, vpr_dist_info *out) {
+    if (!h || !out || !h->dist || !h->dist->valid) return VPR_ERR_ARG;
+    *out = h->dist->info;
+    return VPR_OK;
+}
+
+extern "C" int vpr_distance_download(vpr_handle *h, vpr_dist_results *r) {
+    if (!h) return VPR_ERR_ARG;
+    if (!r || !h->dist || !h->dist->valid) return fail(h, VPR_ERR_ARG, "vpr_distance_download: no vpr_distance results");
+    DistState *D = h->dist;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int64_t nj = D->info.n_jobs, ne = D->info.n_edits;
+    const int nq = D->max_qual + 2;
+    std::vector<DJob> jobs(static_cast<size_t>(nj));
+    std::vector<int32_t> dist(static_cast<size_t>(nj));
+    std::vector<uint8_t> st(static_cast<size_t>(nj));
+    std::vector<DEdit> ed(static_cast<size_t>(ne));
+    std::vector<unsigned long long> qd(size_t(nq) + 1);
+    if (nj) {
+        HIPCHK(h, hipMemcpyAsync(jobs.data(), D->jobs, sizeof(DJob) * size_t(nj), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(dist.data(), D->dist, 4 * size_t(nj), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(st.data(), D->status, size_t(nj), hipMemcpyDeviceToHost, h->stream));
+    }
+    if (ne) HIPCHK(h, hipMemcpyAsync(ed.data(), D->edits, sizeof(DEdit) * size_t(ne), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(qd.data(), D->qdiff, sizeof(unsigned long long) * (size_t(nq) + 1), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, x_sync(h, h->stream, SITE));
+    for (int64_t k = 0; k < nj; k++) {
+        const DJob &J = jobs[size_t(k)];
+        if (r->job_sc) r->job_sc[k] = J.sc;
+        if (r->job_hap) r->job_hap[k] = uint8_t(J.hap);
+        if (r->job_min_qual) r->job_min_qual[k] = J.minq;
+        if (r->job_max_qual) r->job_max_qual[k] = J.maxq;
+        if (r->job_dist) r->job_dist[k] = st[size_t(k)] ? 0 : dist[size_t(k)];
+        if (r->job_status) r->job_status[k] = st[size_t(k)];
+    }
+    if (r->qual_dists) {
+        int64_t run = 0;
+        for (int q = 0; q < nq; q++) { run += int64_t(qd[size_t(q)]); r->qual_dists[q] = run; }
+    }
+    for (int64_t k = 0; k < ne; k++) {
+        const DEdit &E = ed[size_t(k)];
+        if (r->edit_sc) r->edit_sc[k] = E.sc;
+        if (r->edit_hap) r->edit_hap[k] = E.hap;
+        if (r->edit_pos) r->edit_pos[k] = E.pos;
+        if (r->edit_type) r->edit_type[k] = E.type;
+        if (r->edit_len) r->edit_len[k] = E.len;
+        if (r->edit_min_qual) r->edit_min_qual[k] = E.minq;
+        if (r->edit_max_qual) r->edit_max_qual[k] = E.maxq;
+    }
+    return VPR_OK;
+}

@@ -260,6 +260,8 @@ const int TIE_DEC_SLOTS = 64;     // early-replay launches per execute that can 
 }  // namespace vprh
 using namespace vprh;
 
+struct DistState;                        // the distance step's tables and arena (pr_dist.hip)
+
 struct vpr_handle {
     vpr_config cfg;
     std::string err;
@@ -405,6 +407,7 @@ struct vpr_handle {
     int zl_lds_bytes = 0;                // (diagnostic, VPR_ZL_LDS_KB) LDS the zero level's waves ask for and never touch: caps how many of them a compute unit holds
     int lane_prio_rows = 256;            // waves of the lane levels with at least this many rows issue ahead of the others (k_zero_lane; a quarter for k_one_lane)
     DevResults dR;                       // final results, produced on the device
+    DistState *dist = nullptr;           // vpr_distance (pr_dist.hip), created by its first call
     vpr_timing timing;
     bool uploaded = false, executed = false;
 };
@@ -440,6 +443,8 @@ int dev_alloc_bytes(vpr_handle *h, void **p, size_t bytes);          // 256-byte
 int exec_alloc(vpr_handle *h, void **out, size_t bytes);
 int exec_pin(vpr_handle *h, void **out, size_t bytes);
 void free_batch(vpr_handle *h);
+void dist_free(vpr_handle *h);                                       // pr_dist.hip: all of the distance step's device memory
+void dist_release_work(vpr_handle *h);                               // pr_dist.hip: all but what vpr_distance_download reads
 template <typename T>
 int dev_alloc(vpr_handle *h, T **p, size_t n) {
     void *q = nullptr;

@@ -19,3 +19,8 @@ int vplan_sort_pairs_desc(void *tmp, size_t *tmp_bytes, const uint16_t *keys, ui
 int vplan_exclusive_scan_u32(void *tmp, size_t *tmp_bytes, const uint32_t *in, uint32_t *out, size_t n, hipStream_t st) {
     return int(rocprim::exclusive_scan(tmp, *tmp_bytes, in, out, uint32_t(0), n, rocprim::plus<uint32_t>(), st));
 }
+
+// exclusive prefix sums of int64 values (the distance step's job offsets, slice sizes and record counts, pr_dist.hip)
+int vplan_exclusive_scan_i64(void *tmp, size_t *tmp_bytes, const int64_t *in, int64_t *out, size_t n, hipStream_t st) {
+    return int(rocprim::exclusive_scan(tmp, *tmp_bytes, in, out, int64_t(0), n, rocprim::plus<int64_t>(), st));
+}

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <ctime>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -500,5 +501,127 @@ extern "C" int vrp_write_summary_vcf(const char *path, const vrp_contig *ctgs, i
         }
     }
     if (!out.finish()) return fail(VRP_ERR_OPEN, std::string("write error on ") + path);
+    return VRP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The distance files (editData::write_distance / write_edits, src/edit.cpp:134-280).  The reference rescans every edit for every
+// quality and type (get_ed / get_de / get_score, edit.cpp:105-132); the counters here come from difference arrays over the
+// records' [min_qual, max_qual) ranges, one pass over the records: the same integers.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+const char *const TYPE_STR2[] = {"ALL", "SNP", "INS", "DEL", "INDEL"};
+
+bool in_category(int type, int cat) { return cat == 0 || type == cat || (cat == 4 && (type == VPR_TYPE_INS || type == VPR_TYPE_DEL)); }
+float dist_qscore(double p) { return float(std::min(100.0, std::max(0.0, -10 * std::log10(p)))); }
+
+struct DistCounters {
+    int32_t q0 = 0, n = 0;                    // qualities q0 .. q0 + n - 1
+    std::vector<int64_t> ed[5], de[5], score;
+    int32_t ED(int q, int c) const { return int32_t(ed[c][size_t(q - q0)]); }
+    int32_t DE(int q, int c) const { return int32_t(de[c][size_t(q - q0)]); }
+    int32_t SC(int q) const { return int32_t(score[size_t(q - q0)]); }
+};
+
+bool dist_counters(const vrp_edits *sets, int32_t n_sets, int32_t min_qual, int32_t max_qual, int32_t sub, int32_t open, int32_t extend,
+                   DistCounters &C) {
+    C.q0 = std::min(min_qual, 0);
+    const int32_t q1 = max_qual + 2;          // queries run over [min_qual, max_qual + 1]
+    C.n = q1 - C.q0;
+    for (int c = 0; c < 5; c++) { C.ed[c].assign(size_t(C.n) + 1, 0); C.de[c].assign(size_t(C.n) + 1, 0); }
+    C.score.assign(size_t(C.n) + 1, 0);
+    for (int32_t k = 0; k < n_sets; k++) {
+        const vrp_edits &E = sets[k];
+        if (E.n > 0 && (!E.type || !E.len || !E.min_qual || !E.max_qual)) return false;
+        for (int64_t i = 0; i < E.n; i++) {
+            const int lo = std::max(E.min_qual[i], C.q0), hi = std::min(E.max_qual[i], q1);
+            if (lo >= hi) continue;
+            const size_t a = size_t(lo - C.q0), b = size_t(hi - C.q0);
+            const int type = E.type[i];
+            for (int c = 0; c < 5; c++)
+                if (in_category(type, c)) { C.ed[c][a] += E.len[i]; C.ed[c][b] -= E.len[i]; C.de[c][a]++; C.de[c][b]--; }
+            const int64_t w = type == VPR_TYPE_SUB ? sub : (type == VPR_TYPE_INS || type == VPR_TYPE_DEL) ? int64_t(open) + int64_t(extend) * E.len[i] : 0;
+            C.score[a] += w; C.score[b] -= w;
+        }
+    }
+    auto run = [&](std::vector<int64_t> &v) { for (size_t i = 1; i < v.size(); i++) v[i] += v[i - 1]; };
+    for (int c = 0; c < 5; c++) { run(C.ed[c]); run(C.de[c]); }
+    run(C.score);
+    return true;
+}
+
+}  // namespace
+
+extern "C" int vrp_write_distance(const char *prefix, const vrp_edits *sets, int32_t n_sets, int32_t min_qual, int32_t max_qual,
+                                  int32_t eval_sub, int32_t eval_open, int32_t eval_extend, int32_t verbosity, int32_t write_files,
+                                  char *summary, int64_t summary_cap) {
+    if ((n_sets && !sets) || n_sets < 0 || max_qual + 1 < min_qual || (write_files && !prefix)) return fail(VRP_ERR_ARG, "vrp_write_distance: bad arguments");
+    DistCounters C;
+    if (!dist_counters(sets, n_sets, min_qual, max_qual, eval_sub, eval_open, eval_extend, C)) return fail(VRP_ERR_ARG, "vrp_write_distance: null column");
+    const std::string pre = prefix ? prefix : "";
+    const int top = max_qual + 1;
+    const int orig = C.SC(top);
+    int orig_ed[5], orig_de[5], best_q[5];
+    double best[5];
+    for (int c = 0; c < 5; c++) { orig_ed[c] = C.ED(top, c); orig_de[c] = C.DE(top, c); best[c] = std::numeric_limits<double>::max(); best_q[c] = 0; }
+    {
+        File f(write_files ? (pre + "distance.tsv").c_str() : nullptr);
+        if (write_files && !f) return fail(VRP_ERR_OPEN, "cannot create " + pre + "distance.tsv");
+        if (f) fprintf(f, "MIN_QUAL\tSUB_DE\tINS_DE\tDEL_DE\tSUB_ED\tINS_ED\tDEL_ED\tDISTINCT_EDITS\tEDIT_DIST\tALN_SCORE\tALN_QSCORE\n");
+        for (int q = min_qual; q <= top; q++) {
+            for (int c = 0; c < 5; c++) {
+                const double v = double(C.ED(q, c)) * C.DE(q, c);
+                if (v < best[c]) { best[c] = v; best_q[c] = q; }
+            }
+            if (f) fprintf(f, "%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%f\n", q, C.DE(q, 1), C.DE(q, 2), C.DE(q, 3), C.ED(q, 1), C.ED(q, 2),
+                           C.ED(q, 3), C.DE(q, 0), C.ED(q, 0), C.SC(q), dist_qscore(double(C.SC(q)) / orig));
+        }
+        if (f && !f.finish()) return fail(VRP_ERR_OPEN, "write to " + pre + "distance.tsv failed");
+    }
+    std::string txt = "ALIGNMENT DISTANCE SUMMARY\n";
+    {
+        File g(write_files ? (pre + "distance-summary.tsv").c_str() : nullptr);
+        if (write_files && !g) return fail(VRP_ERR_OPEN, "cannot create " + pre + "distance-summary.tsv");
+        if (g) fprintf(g, "VAR_TYPE\tTHRESHOLD\tMIN_QUAL\tEDIT_DIST\tDISTINCT_EDITS\tED_QSCORE\tDE_QSCORE\tALN_QSCORE\n");
+        char line[512];
+        for (int c = 0; c < 5; c++) {
+            // the reference's verbosity filter (edit.cpp:212-217) skips a type before anything is written: stdout and file alike
+            if ((verbosity == 0 && c != 0) || (verbosity == 1 && (c == VPR_TYPE_INS || c == VPR_TYPE_DEL))) continue;
+            txt += c == 0 ? "\nTYPE\tTHRESHOLD\tEDIT_DIST\tDISTINCT_EDITS\tED_QSCORE\tDE_QSCORE\tALN_QSCORE\n"
+                          : "\nTYPE\tTHRESHOLD\tEDIT_DIST\tDISTINCT_EDITS\tED_QSCORE\tDE_QSCORE\n";
+            const int qs[3] = {min_qual, best_q[c], top};
+            const char *const names[3] = {"NONE", "BEST", "REF "};
+            for (int i = 0; i < 3; i++) {
+                const int q = qs[i];
+                const float eq = dist_qscore(double(C.ED(q, c)) / orig_ed[c]), dq = dist_qscore(double(C.DE(q, c)) / orig_de[c]);
+                const float aq = c == 0 ? dist_qscore(double(C.SC(q)) / orig) : 0;
+                if (g) fprintf(g, "%s\t%s\t%d\t%d\t%d\t%f\t%f\t%f\n", TYPE_STR2[c], names[i], q, C.ED(q, c), C.DE(q, c), eq, dq, aq);
+                if (c == 0) snprintf(line, sizeof(line), "%s\t%s Q >= %d\t%-16d%-16d%f\t%f\t%f\n", TYPE_STR2[c], names[i], q, C.ED(q, c), C.DE(q, c), eq, dq, aq);
+                else snprintf(line, sizeof(line), "%s\t%s Q >= %d\t%-16d%-16d%f\t%f\n", TYPE_STR2[c], names[i], q, C.ED(q, c), C.DE(q, c), eq, dq);
+                txt += line;
+            }
+        }
+        if (g && !g.finish()) return fail(VRP_ERR_OPEN, "write to " + pre + "distance-summary.tsv failed");
+    }
+    if (summary && summary_cap > 0) snprintf(summary, size_t(summary_cap), "%s", txt.c_str());
+    return int(txt.size());
+}
+
+extern "C" int vrp_write_edits(const char *path, const vrp_edits *sets, int32_t n_sets) {
+    if (!path || (n_sets && !sets) || n_sets < 0) return fail(VRP_ERR_ARG, "vrp_write_edits: bad arguments");
+    File f(path);
+    if (!f) return fail(VRP_ERR_OPEN, std::string("cannot create ") + path);
+    fprintf(f, "CONTIG\tSTART\tHAP\tTYPE\tSIZE\tSUPERCLUSTER\tMIN_QUAL\tMAX_QUAL\n");
+    for (int32_t k = 0; k < n_sets; k++) {
+        const vrp_edits &E = sets[k];
+        for (int64_t i = 0; i < E.n; i++) {
+            const int type = E.type[i];
+            if (type < 0 || type > 4) return fail(VRP_ERR_ARG, "vrp_write_edits: bad edit type");
+            fprintf(f, "%s\t%d\t%d\t%s\t%d\t%d\t%d\t%d\n", E.ctg, E.pos[i], int(E.hap[i]), TYPE_STR[type], E.len[i], E.sc[i], E.min_qual[i],
+                    E.max_qual[i]);
+        }
+    }
+    if (!f.finish()) return fail(VRP_ERR_OPEN, std::string("write to ") + path + " failed");
     return VRP_OK;
 }

@@ -27,7 +27,7 @@ class VrpContig(C.Structure):
 
 EXPORTED = ["vrp_phase_blocks", "vrp_write_precision_recall", "vrp_write_phase_blocks", "vrp_write_superclusters",
             "vrp_write_switchflips", "vrp_write_phasing_summary", "vrp_ng50",
-            "vrp_write_variants", "vrp_write_summary_vcf", "vrp_last_error"]
+            "vrp_write_variants", "vrp_write_summary_vcf", "vrp_write_distance", "vrp_write_edits", "vrp_last_error"]
 
 
 class ReportError(RuntimeError):
@@ -150,10 +150,58 @@ def write_results(prefix, contigs, cmd="", file_date=None, credit_threshold=0.7)
                                    file_date.encode() if file_date else None, credit_threshold), "vrp_write_summary_vcf")
 
 
+class VrpEdits(C.Structure):
+    _fields_ = [("ctg", C.c_char_p), ("n", C.c_int64), ("sc", A.P_i32), ("hap", A.P_u8), ("pos", A.P_i32), ("type", A.P_u8),
+                ("len", A.P_i32), ("min_qual", A.P_i32), ("max_qual", A.P_i32)]
+
+
+def _edit_sets(sets):
+    """[(contig name, dict of edit_* columns as PrecisionRecall.distance returns them)] -> (ctypes array, arrays kept alive)"""
+    keep, arr = [], (VrpEdits * max(len(sets), 1))()
+    for k, (name, d) in enumerate(sets):
+        e = arr[k]
+        nm = name.encode()
+        keep.append(nm)
+        e.ctg, e.n = nm, len(d["edit_sc"])
+        for f, col, ct, dt in (("sc", "edit_sc", C.c_int32, np.int32), ("hap", "edit_hap", C.c_uint8, np.uint8),
+                               ("pos", "edit_pos", C.c_int32, np.int32), ("type", "edit_type", C.c_uint8, np.uint8),
+                               ("len", "edit_len", C.c_int32, np.int32), ("min_qual", "edit_min_qual", C.c_int32, np.int32),
+                               ("max_qual", "edit_max_qual", C.c_int32, np.int32)):
+            a = np.ascontiguousarray(d[col], dt)
+            if len(a) == 0:
+                a = np.zeros(1, dt)
+            keep.append(a)
+            setattr(e, f, A._ptr(a, ct))
+    return arr, keep
+
+
+def write_distance(prefix, sets, min_qual, max_qual, eval_sub, eval_open, eval_extend, verbosity=1, write_files=True):
+    """distance.tsv and distance-summary.tsv under prefix (write_files) and the ALIGNMENT DISTANCE SUMMARY text, which is returned
+    (editData::write_distance, edit.cpp:137-250; vrp_write_distance)"""
+    arr, keep = _edit_sets(sets)
+    L = api.lib()
+    L.vrp_write_distance.argtypes = [C.c_char_p, C.POINTER(VrpEdits), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_int32, C.c_char_p, C.c_int64]
+    buf = C.create_string_buffer(1 << 16)
+    n = L.vrp_write_distance((prefix or "").encode(), arr, len(sets), min_qual, max_qual, eval_sub, eval_open, eval_extend, verbosity,
+                             1 if write_files else 0, buf, len(buf))
+    if n < 0:
+        _check(n, "vrp_write_distance")
+    return buf.value.decode()
+
+
+def write_edits(path, sets):
+    """edits.tsv (editData::write_edits, edit.cpp:256-270; vrp_write_edits)"""
+    arr, keep = _edit_sets(sets)
+    L = api.lib()
+    L.vrp_write_edits.argtypes = [C.c_char_p, C.POINTER(VrpEdits), C.c_int32]
+    _check(L.vrp_write_edits(path.encode(), arr, len(sets)), "vrp_write_edits")
+
+
 def write_parameters(prefix, args, cmd):
     """parameters.txt (write_params, print.cpp:30-56): the run's settings, one `key = value` per line, in the reference's order and
     formats (strings quoted, booleans true / false, the two thresholds and max_ram with %f).  Keys of stages this implementation
-    does not have keep the reference's defaults (realignment off, eval penalties 3 / 2 / 1, distance false, globals.h:41-59)."""
+    does not have keep the reference's defaults (realignment off, globals.h:41-59); eval penalties and distance are the run's."""
     b2s = lambda b: "true" if b else "false"
     L = api.lib()
     L.vpr_version.restype = C.c_char_p
@@ -168,6 +216,7 @@ def write_parameters(prefix, args, cmd):
             "vcfdist_amd", L.vpr_version().decode(), prefix, cmd, args.fasta, args.query, args.truth, args.bed or "",
             b2s(not args.no_output_files), args.filter, args.min_qual, args.max_qual, args.max_size, args.sv_threshold,
             args.phase_threshold, args.credit_threshold, b2s(False), b2s(False), b2s(False), args.cluster, args.cluster_gap,
-            args.reach_min_gap, args.max_iterations, 64, 64.0, args.sub, args.open, args.extend, 3, 2, 1, b2s(False)))
+            args.reach_min_gap, args.max_iterations, 64, 64.0, args.sub, args.open, args.extend,
+            getattr(args, "eval_sub", 3), getattr(args, "eval_open", 2), getattr(args, "eval_extend", 1), b2s(getattr(args, "distance", False))))
     with open(prefix + "parameters.txt", "w") as f:
         f.write(text)
