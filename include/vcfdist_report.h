@@ -13,6 +13,7 @@
  *   vrp_write_summary_vcf        phaseblockData::write_summary_vcf                 src/phase.cpp:8-222
  *   vrp_write_distance           editData::write_distance                          src/edit.cpp:137-250
  *   vrp_write_edits              editData::write_edits                             src/edit.cpp:256-270
+ *   vrp_write_vcf                variantData::write_vcf / print_variant            src/variant.cpp:132-222, 292-315
  *                                ctgVariants::print_var_info / _empty / _sample    src/variant.cpp:229-286
  * Host code, like the reference's; the inputs are the columns of include/vcfdist_io.h, the tables of
  * include/vcfdist_cluster.h and the result arrays of include/vcfdist_pr.h (vpr_results, vpr_phase, vpr_pr_counts).
@@ -116,6 +117,21 @@ int vrp_write_distance(const char *prefix, const vrp_edits *sets, int32_t n_sets
                        char *summary, int64_t summary_cap);
 /* edits.tsv: one line per record, in the order given */
 int vrp_write_edits(const char *path, const vrp_edits *sets, int32_t n_sets);
+
+/* ---- a callset as a VCF (orig-query.vcf / query.vcf ... of the realignment modes -rq / -rt / -ro): the header with ##fileDate
+   (file_date "YYYYMMDD", or NULL for today in local time), one ##contig line per contig (length, ploidy) and the sample; the two
+   haps merged by position (an INS / DEL at its position minus one, with the anchor base in front of REF and ALT); a pair on one
+   position with equal alleles is 1|1, otherwise two records 1|0 and 0|1; a record on one hap alone is 1|0 / 0|1, or 1 on a ploidy-1
+   contig; QUAL %f of var_qual.  Of each vrp_hap only n_var, pos, type, var_qual and the allele columns are read. */
+typedef struct vrp_vcf_contig {
+    const char *name;
+    int32_t length;              /* ##contig length */
+    int32_t ploidy;
+    const uint8_t *seq;          /* reference sequence of the contig (anchor bases; may be NULL when no INS / DEL needs one) */
+    int64_t seq_len;
+    vrp_hap hap[2];
+} vrp_vcf_contig;
+int vrp_write_vcf(const char *path, const vrp_vcf_contig *ctgs, int32_t n_ctg, const char *sample, const char *file_date);
 
 const char *vrp_last_error(void);
 

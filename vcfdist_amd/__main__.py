@@ -6,7 +6,9 @@ the MI355X path: VCF / BED / FASTA readers (include/vcfdist_io.h), biWFA or dist
 the PRECISION-RECALL SUMMARY and the output tables (include/vcfdist_report.h: precision-recall*.tsv, phase-blocks.tsv,
 superclusters.tsv, query.tsv, truth.tsv, summary.vcf under -p PREFIX; -n writes nothing).  With -d the alignment-distance
 metrics run on the GPU behind each contig's path (include/vcfdist_distance.h): distance.tsv, distance-summary.tsv, edits.tsv and
-the ALIGNMENT DISTANCE SUMMARY (printed even with -n); one rank only.  Realignment is not part of it."""
+the ALIGNMENT DISTANCE SUMMARY (printed even with -n); one rank only.  With -rq / -rt a callset is clustered and realigned on the
+GPU before the evaluation (include/vcfdist_realign.h): orig-query.vcf / orig-truth.vcf as read, query.vcf / truth.vcf realigned;
+-ro stops after the realignment; one rank only."""
 import argparse
 import sys
 
@@ -225,6 +227,43 @@ def check_contigs(q, t, fasta, bed):
     return qc
 
 
+def realign_callset(which, cs, fasta, args, device=0):
+    """wf_swg_realign + left_shift of a whole callset (main.cpp:74-100): per contig and hap, cluster as the run clusters (biWFA on
+    the GPU, or gap / size), then vrl_realign.  -> the callset with its hap columns replaced by the realigned ones"""
+    out, n_cl, n_in, n_out, kept = [], 0, 0, 0, dict(edge=0, limit=0, error=0)
+    for k, ctg in enumerate(cs["contigs"]):
+        if ctg not in fasta:
+            raise SystemExit(f"ERROR: Contig '{ctg}' not in reference FASTA (realignment of the {which} VCF)")
+        seq = fasta[ctg]
+        per = []
+        for s in cs["vars"][k]:
+            h = K.HapSeq.__new__(K.HapSeq)
+            K.Hap.__init__(h, s["pos"], s["rlen"], s["type"], s["ref_len"], s["alt_len"])
+            h.ref_off, h.alt_off, h.pool = s["ref_off"], s["alt_off"], s["pool"]
+            if args.cluster == "biwfa":
+                cl = K.wfa_cluster(h, bytes(seq), sub=args.sub, open=args.open, extend=args.extend, max_cluster_itrs=args.max_iterations,
+                                   reach_min_gap=args.reach_min_gap, device=device)[0]
+            else:
+                cl = K.simple_cluster(h, 1 if args.cluster == "size" else 0, args.cluster_gap, args.reach_min_gap)
+            try:
+                cols, _, info = api.realign(s, cl, seq, sub=args.sub, open=args.open, extend=args.extend, max_qual=args.max_qual, device=device)
+            except api.VprError as e:
+                raise SystemExit(f"ERROR: contig '{ctg}': realigning the {which} VCF failed: {e}")
+            per.append(cols)
+            n_cl += info.n_clusters; n_in += len(s["pos"]); n_out += len(cols["pos"])
+            kept["edge"] += info.n_edge; kept["limit"] += info.n_limit; kept["error"] += info.n_error
+        out.append(per)
+    print(f"[vcfdist_amd] realigned {which} VCF: {n_cl} clusters, {n_in} -> {n_out} hap-variants", file=sys.stderr)
+    n_kept = sum(kept.values())
+    if n_kept:
+        print(f"[WARN  vcfdist_amd] {which} VCF: {n_kept} cluster(s) NOT REALIGNED, their variants kept as read: {kept['edge']} starting at "
+              f"the contig's first base, {kept['limit']} beyond the memory limit of one alignment, {kept['error']} with inconsistent variants",
+              file=sys.stderr)
+        if args.strict:
+            raise SystemExit(f"ERROR: {which} VCF: {n_kept} cluster(s) not realigned (--strict)")
+    return dict(cs, vars=out)
+
+
 def eval_penalty(what):
     """an evaluation penalty as globals.cpp:274-335 reads it: an integer, non-negative"""
     def parse(v):
@@ -267,6 +306,9 @@ def main(argv=None):
     ap.add_argument("-ex", "--eval-mismatch-penalty", type=eval_penalty("evaluation mismatch penalty"), default=3, dest="eval_sub")
     ap.add_argument("-eo", "--eval-gap-open-penalty", type=eval_penalty("eval gap-opening penalty"), default=2, dest="eval_open")
     ap.add_argument("-ee", "--eval-gap-extend-penalty", type=eval_penalty("eval gap-extension penalty"), default=1, dest="eval_extend")
+    ap.add_argument("-rq", "--realign-query", action="store_true", help="realign the query variants before the evaluation")
+    ap.add_argument("-rt", "--realign-truth", action="store_true", help="realign the truth variants before the evaluation")
+    ap.add_argument("-ro", "--realign-only", action="store_true", help="stop after the realignment (query.vcf / truth.vcf)")
     ap.add_argument("--shard", default="superclusters", choices=["superclusters", "contigs"],
                     help="several ranks (torch.distributed.run, one per GPU): deal every contig's superclusters over the ranks "
                          "(default; balanced whatever the contigs' sizes) or whole contigs")
@@ -277,6 +319,9 @@ def main(argv=None):
     args.cluster = args.cluster[0]
     if args.max_size + 2 > args.max_supercluster_size:          # globals.cpp:478-481
         raise SystemExit("ERROR: Max supercluster size (-s) must be at least two larger than max variant size (-l).")
+    realigning = args.realign_query or args.realign_truth
+    if realigning and (args.sub < 1 or args.extend < 1):
+        raise SystemExit("ERROR: realignment needs a mismatch penalty (-x) and a gap-extension penalty (-e) of at least 1")
     # one process per GPU under torch.distributed.run: every contig's superclusters are dealt over the ranks (--shard; the
     # per-supercluster phasing is all-gathered, a contig's phasing needs all of it), the counters are summed with one all-reduce
     # (RCCL), the result records are gathered, and rank 0 writes the files
@@ -284,6 +329,9 @@ def main(argv=None):
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     if args.distance and world > 1:
         raise SystemExit("ERROR: -d/--distance runs on one rank only (its edit records are not gathered over ranks): "
+                         "run it without torch.distributed.run")
+    if realigning and world > 1:
+        raise SystemExit("ERROR: -rq/-rt realignment runs on one rank only (the realigned callsets are not sharded): "
                          "run it without torch.distributed.run")
     device = args.device if args.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
     one_gpu = bool(os.environ.get("VCFDIST_ONE_GPU"))      # plumbing check on a one-GPU box: every rank uses device 0, gloo
@@ -308,7 +356,26 @@ def main(argv=None):
     q = IO.read_vcf(args.query, bed, **kw)
     t = IO.read_vcf(args.truth, bed, **kw)
     fasta = IO.read_fasta(args.fasta)
+    write = not args.no_output_files
+    # realignment (main.cpp:50-180): the callsets as read, then each realigned in place of its columns; -ro stops there
+    if write and args.realign_query:
+        RP.write_vcf(args.prefix + "orig-query.vcf", q, fasta)
+    if write and args.realign_truth:
+        RP.write_vcf(args.prefix + "orig-truth.vcf", t, fasta)
     contigs = check_contigs(q, t, fasta, bed)
+    cmd = " ".join(["vcfdist"] + list(sys.argv[1:] if argv is None else argv))
+    if args.realign_query:
+        q = realign_callset("query", q, fasta, args, device=device)
+        if args.realign_only and write:
+            RP.write_vcf(args.prefix + "query.vcf", q, fasta)
+    if args.realign_truth:
+        t = realign_callset("truth", t, fasta, args, device=device)
+    if args.realign_only:       # the parameters (written first by the reference, main.cpp:35) and stop
+        if args.realign_truth and write:
+            RP.write_vcf(args.prefix + "truth.vcf", t, fasta)
+        if write:
+            RP.write_parameters(args.prefix, args, cmd)
+        return []
     nq = args.max_qual - args.min_qual + 1
     total = np.zeros((2, 4, 3, nq), np.int64)
     empty = dict(pos=np.zeros(0, np.int32), rlen=np.zeros(0, np.int32), type=np.zeros(0, np.uint8), var_qual=np.zeros(0, np.float32),
@@ -370,10 +437,13 @@ def main(argv=None):
     if rank == 0:
         if not args.no_output_files:
             RP.write_precision_recall(args.prefix, total, args.min_qual, args.max_qual)
-            cmd = " ".join(["vcfdist"] + list(sys.argv[1:] if argv is None else argv))
             RP.write_parameters(args.prefix, args, cmd)
             ctgs = [RP.Contig(c, ln, pl, fasta[c], sl, *tb) for c, ln, pl, sl, tb in (reports[k] for k in sorted(reports))]
             RP.write_results(args.prefix, ctgs, cmd=cmd, credit_threshold=args.credit_threshold)
+            if args.realign_query:
+                RP.write_vcf(args.prefix + "query.vcf", q, fasta)
+            if args.realign_truth:
+                RP.write_vcf(args.prefix + "truth.vcf", t, fasta)
         print("PRECISION-RECALL SUMMARY\n")
         print("TYPE\tTHRESHOLD\tTRUTH_TP\tQUERY_TP\tTRUTH_FN\tQUERY_FP\tPREC\t\tRECALL\t\tF1_SCORE\tF1_QSCORE")
         for r in rows:

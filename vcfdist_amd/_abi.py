@@ -484,3 +484,27 @@ class VprDistResults(C.Structure):
     _fields_ = [("job_sc", P_i32), ("job_hap", P_u8), ("job_min_qual", P_i32), ("job_max_qual", P_i32), ("job_dist", P_i32),
                 ("job_status", P_u8), ("qual_dists", P_i64), ("edit_sc", P_i32), ("edit_hap", P_u8), ("edit_pos", P_i32),
                 ("edit_type", P_u8), ("edit_len", P_i32), ("edit_min_qual", P_i32), ("edit_max_qual", P_i32)]
+
+
+# ---- include/vcfdist_realign.h
+RL_ST_EDGE = 1
+RL_ST_LIMIT = 2
+RL_ST_ERROR = 4
+RL_GT_REF_REF = 2
+
+
+class VrlConfig(C.Structure):
+    _fields_ = [("sub", C.c_int32), ("open", C.c_int32), ("extend", C.c_int32), ("max_qual", C.c_int32), ("round_bytes", C.c_int64),
+                ("job_bytes_limit", C.c_int64)]
+
+
+class VrlInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_clusters", "n_realigned", "n_records", "n_kept", "n_edge", "n_limit", "n_error", "n_rounds",
+                                         "n_hist_rounds", "arena_bytes", "plan_bytes")] + \
+               [(n, C.c_double) for n in ("ms_upload", "ms_jobs", "ms_score", "ms_hist", "ms_back", "ms_host", "ms_wall")]
+
+
+class VrlResult(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pos", P_i32), ("rlen", P_i32), ("type", P_u8), ("ref_len", P_i32), ("alt_len", P_i32),
+                ("ref_off", P_i64), ("alt_off", P_i64), ("pool", P_u8), ("pool_len", C.c_int64), ("var_qual", P_f32), ("gt_qual", P_f32),
+                ("phase_set", P_i32), ("orig_gt", P_u8), ("n_clusters", C.c_int32), ("cluster_status", P_u8), ("info", VrlInfo)]

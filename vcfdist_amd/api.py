@@ -82,6 +82,10 @@ def lib():
     L.vpr_distance.argtypes = [H, C.POINTER(A.VprVariants), C.POINTER(A.VprDistConfig)]
     L.vpr_distance_info.argtypes = [H, C.POINTER(A.VprDistInfo)]
     L.vpr_distance_download.argtypes = [H, C.POINTER(A.VprDistResults)]
+    from .cluster import VclHapSeq, VclClusters
+    L.vrl_realign.argtypes = [C.POINTER(VclHapSeq), A.P_f32, A.P_f32, A.P_i32, A.P_u8, C.POINTER(VclClusters), A.P_u8, C.c_int32,
+                              C.POINTER(A.VrlConfig), C.c_int32, C.POINTER(C.POINTER(A.VrlResult))]
+    L.vrl_result_free.argtypes = [C.POINTER(A.VrlResult)]
     _LIB = L
     return L
 
@@ -96,6 +100,55 @@ EXPORTED = [
 ]
 # include/vcfdist_distance.h
 DIST_EXPORTED = ["vpr_distance", "vpr_distance_info", "vpr_distance_download"]
+# include/vcfdist_realign.h
+RL_EXPORTED = ["vrl_realign", "vrl_result_free"]
+
+RL_COLS = (("pos", np.int32), ("rlen", np.int32), ("type", np.uint8), ("ref_len", np.int32), ("alt_len", np.int32), ("ref_off", np.int64),
+           ("alt_off", np.int64), ("var_qual", np.float32), ("gt_qual", np.float32), ("phase_set", np.int32), ("orig_gt", np.uint8))
+
+
+def realign(hap, clusters, seq, sub=5, open=6, extend=2, max_qual=60, round_bytes=0, job_bytes_limit=0, device=0):
+    """vrl_realign (include/vcfdist_realign.h) of one (contig, hap).  hap: a dict of the reader's columns (vcfdist_amd.io: pos, rlen,
+    type, ref_len, alt_len, ref_off, alt_off, pool, var_qual, phase_set and optionally gt_qual, orig_gt); clusters: a
+    cluster.Clusters of it; seq: the contig's sequence.  -> (dict of the realigned, left-shifted columns in the same layout,
+    cluster_status uint8[n_clusters], VrlInfo).  A refusal raises VprError with the return code."""
+    from . import cluster as K
+    L = lib()
+    keep = []
+
+    def arr(a, dt):
+        a = np.ascontiguousarray(a, dt)
+        if a.size == 0:
+            a = np.zeros(1, dt)
+        keep.append(a)
+        return A._ptr(a, np.ctypeslib.as_ctypes_type(dt))
+    n = len(hap["pos"])
+    hs = K.VclHapSeq()
+    hs.cols.n_var = n
+    for f in ("pos", "rlen", "ref_len", "alt_len"):
+        setattr(hs.cols, f, arr(hap[f], np.int32))
+    hs.cols.type = arr(hap["type"], np.uint8)
+    hs.ref_off, hs.alt_off = arr(hap["ref_off"], np.int64), arr(hap["alt_off"], np.int64)
+    hs.pool = arr(hap["pool"], np.uint8)
+    cs = clusters.as_struct()
+    seq = np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else np.asarray(seq, np.uint8)
+    cfg = A.VrlConfig(sub=sub, open=open, extend=extend, max_qual=max_qual, round_bytes=round_bytes, job_bytes_limit=job_bytes_limit)
+    out = C.POINTER(A.VrlResult)()
+    gq = arr(hap["gt_qual"], np.float32) if "gt_qual" in hap else None
+    og = arr(hap["orig_gt"], np.uint8) if "orig_gt" in hap else None
+    rc = L.vrl_realign(C.byref(hs), arr(hap["var_qual"], np.float32), gq, arr(hap["phase_set"], np.int32), og, C.byref(cs),
+                       arr(seq, np.uint8), len(seq), C.byref(cfg), device, C.byref(out))
+    if rc:
+        raise VprError(f"vrl_realign failed ({rc})")
+    try:
+        r = out.contents
+        cols = {f: A._from_ptr(getattr(r, f), r.n, dt).copy() if r.n else np.zeros(0, dt) for f, dt in RL_COLS}
+        cols["pool"] = A._from_ptr(r.pool, int(r.pool_len), np.uint8).copy() if r.pool_len else np.zeros(1, np.uint8)
+        status = A._from_ptr(r.cluster_status, r.n_clusters, np.uint8).copy() if r.n_clusters else np.zeros(0, np.uint8)
+        info = A.VrlInfo.from_buffer_copy(r.info)
+    finally:
+        L.vrl_result_free(out)
+    return cols, status, info
 
 
 def store_phase(s, thr=0.6):

@@ -9,9 +9,11 @@
 //   vcfdist_gpu <query.vcf[.gz]> <truth.vcf[.gz]> <ref.fasta[.gz]> [-b regions.bed] [-p prefix] [-n] [-c biwfa | gap N | size N]
 //               [-l max variant size] [-s max supercluster size] [-mn / -mx qual] [-f filters] [-i iterations] [-x -o -e penalties]
 //               [-ct credit threshold] [-pt phasing threshold] [-sv threshold] [--reach-min-gap N] [--strict] [--device N]
-//               [-d] [-ex -eo -ee evaluation penalties]
+//               [-d] [-ex -eo -ee evaluation penalties] [-rq] [-rt] [-ro]
 // With -d the distance metrics (edits_wrapper, dist.cpp:1908-2077) run on the GPU after each contig's precision/recall path
 // (include/vcfdist_distance.h), as the reference's main.cpp:223-238 runs them after precision_recall_threads_wrapper.
+// With -rq / -rt a callset is clustered and realigned on the GPU (include/vcfdist_realign.h) before the evaluation, in the order of
+// the reference's main.cpp:50-180 (orig-*.vcf, realign query, realign truth; -ro stops there and writes query.vcf / truth.vcf).
 #include <algorithm>
 #include <cstdarg>
 #include <cstdint>
@@ -28,6 +30,7 @@
 #include "../../include/vcfdist_distance.h"
 #include "../../include/vcfdist_io.h"
 #include "../../include/vcfdist_pr.h"
+#include "../../include/vcfdist_realign.h"
 #include "../../include/vcfdist_report.h"
 
 namespace {
@@ -38,6 +41,7 @@ struct Args {
     int sub = 5, open = 6, extend = 2, sv_threshold = 50, reach_min_gap = 10, device = 0;
     int eval_sub = 3, eval_open = 2, eval_extend = 1;      // globals.h:52-55
     bool distance = false;
+    bool realign_query = false, realign_truth = false, realign_only = false;
     double credit_threshold = 0.7, phase_threshold = 0.6;
     bool no_output_files = false, strict = false;
 };
@@ -89,6 +93,9 @@ Args parse(int argc, char **argv) {
         else if (o == "--strict") a.strict = true;
         else if (o == "--device") a.device = atoi(need(i));
         else if (o == "-d" || o == "--distance") a.distance = true;
+        else if (o == "-rq" || o == "--realign-query") a.realign_query = true;
+        else if (o == "-rt" || o == "--realign-truth") a.realign_truth = true;
+        else if (o == "-ro" || o == "--realign-only") a.realign_only = true;
         else if (o == "-ex" || o == "--eval-mismatch-penalty") a.eval_sub = eval_penalty(need(i), "evaluation mismatch penalty");
         else if (o == "-eo" || o == "--eval-gap-open-penalty") a.eval_open = eval_penalty(need(i), "eval gap-opening penalty");
         else if (o == "-ee" || o == "--eval-gap-extend-penalty") a.eval_extend = eval_penalty(need(i), "eval gap-extension penalty");
@@ -99,6 +106,8 @@ Args parse(int argc, char **argv) {
     a.query = pos[0]; a.truth = pos[1]; a.fasta = pos[2];
     if (a.max_size + 2 > a.max_supercluster_size)          // globals.cpp:478-481
         die("ERROR: Max supercluster size (-s) must be at least two larger than max variant size (-l).");
+    if ((a.realign_query || a.realign_truth) && (a.sub < 1 || a.extend < 1))
+        die("ERROR: realignment needs a mismatch penalty (-x) and a gap-extension penalty (-e) of at least 1");
     return a;
 }
 
@@ -192,6 +201,89 @@ struct ContigOut {       // what the writers need of one contig, kept alive unti
 
 const vio_hap_vars EMPTY_HAP = {0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
 
+// parameters.txt, write_params (print.cpp:30-56)
+void write_params(const Args &A, const std::string &cmd) {
+    FILE *f = fopen((A.prefix + "parameters.txt").c_str(), "w");
+    if (!f) die("ERROR: cannot write %sparameters.txt", A.prefix.c_str());
+    auto b2s = [](bool b) { return b ? "true" : "false"; };
+    fprintf(f, "program = '%s'\nversion = '%s'\nout_prefix = '%s'\ncommand = '%s'\nreference_fasta = '%s'\n"
+               "query_vcf = '%s'\ntruth_vcf = '%s'\nbed_file = '%s'\nwrite_outputs = %s\nfilters = '%s'\n"
+               "min_var_qual = %d\nmax_var_qual = %d\nmax_var_size = %d\nsv_threshold = %d\n"
+               "phase_threshold = %f\ncredit_threshold = %f\nrealign_truth = %s\nrealign_query = %s\n"
+               "realign_only = %s\ncluster_method = '%s'\ncluster_min_gap = %d\n"
+               "reach_min_gap = %d\nmax_cluster_itrs = %d\nmax_threads = %d\nmax_ram = %f\n"
+               "sub = %d\nopen = %d\nextend = %d\neval_sub = %d\neval_open = %d\neval_extend = %d\ndistance = %s",
+            "vcfdist_amd", vpr_version(), A.prefix.c_str(), cmd.c_str(), A.fasta.c_str(), A.query.c_str(), A.truth.c_str(), A.bed.c_str(), "true",
+            A.filter.c_str(), A.min_qual, A.max_qual, A.max_size, A.sv_threshold, A.phase_threshold, A.credit_threshold, b2s(A.realign_truth),
+            b2s(A.realign_query), b2s(A.realign_only), A.cluster.c_str(), A.cluster_gap, A.reach_min_gap, A.max_iterations, 64, 64.0, A.sub, A.open,
+            A.extend, A.eval_sub, A.eval_open, A.eval_extend, b2s(A.distance));
+    fclose(f);
+}
+
+// a callset's ##contig lines and both haps per contig, for vrp_write_vcf (variantData::write_vcf)
+void write_callset_vcf(const std::string &path, const vio_callset *cs, const vio_fasta *fa, const std::vector<std::string> &fn) {
+    std::vector<vrp_vcf_contig> ctgs(size_t(cs->n_ctg));
+    static const uint8_t no_pool[1] = {0};
+    for (int k = 0; k < cs->n_ctg; k++) {
+        vrp_vcf_contig &c = ctgs[size_t(k)];
+        memset(&c, 0, sizeof(c));
+        c.name = cs->ctg_name[k]; c.length = int32_t(cs->ctg_len[k]); c.ploidy = cs->ploidy[k];
+        const int fi = find(fn, cs->ctg_name[k]);
+        if (fi >= 0) { c.seq = fa->seq + fa->ctg_off[fi]; c.seq_len = fa->ctg_off[fi + 1] - fa->ctg_off[fi]; }
+        for (int h = 0; h < 2; h++) {
+            const vio_hap_vars &v = cs->vars[2 * k + h];
+            vrp_hap &hp = c.hap[h];
+            hp.n_var = v.n; hp.pos = v.pos; hp.type = v.type; hp.var_qual = v.var_qual; hp.ref_len = v.ref_len; hp.alt_len = v.alt_len;
+            hp.ref_off = v.ref_off; hp.alt_off = v.alt_off; hp.pool = v.pool ? v.pool : no_pool;
+        }
+    }
+    if (vrp_write_vcf(path.c_str(), ctgs.data(), cs->n_ctg, cs->sample, nullptr)) die("ERROR: %s", vrp_last_error());
+}
+
+// wf_swg_realign + left_shift of a whole callset (main.cpp:74-100): per contig and hap, cluster as the run clusters (biWFA on the
+// GPU, or gap / size), then vrl_realign.  The callset's hap columns are pointed at the results, which `keep` owns.
+void realign_callset(const char *which, vio_callset *cs, const vio_fasta *fa, const std::vector<std::string> &fn, const Args &A,
+                     std::vector<vrl_result *> &keep, std::vector<vio_hap_vars> &cols) {
+    cols.assign(size_t(2) * size_t(cs->n_ctg), EMPTY_HAP);
+    int64_t n_cl = 0, n_in = 0, n_out = 0, n_edge = 0, n_limit = 0, n_error = 0;
+    for (int k = 0; k < cs->n_ctg; k++) {
+        const int fi = find(fn, cs->ctg_name[k]);
+        if (fi < 0) die("ERROR: Contig '%s' not in reference FASTA (realignment of the %s VCF)", cs->ctg_name[k], which);
+        const uint8_t *seq = fa->seq + fa->ctg_off[fi];
+        const int64_t seq_len = fa->ctg_off[fi + 1] - fa->ctg_off[fi];
+        for (int h = 0; h < 2; h++) {
+            const vio_hap_vars *s = &cs->vars[2 * k + h];
+            const vcl_hap hp = {s->n, s->pos, s->rlen, s->type, s->ref_len, s->alt_len};
+            static const uint8_t no_pool[1] = {0};
+            const vcl_hap_seq hs = {hp, s->ref_off, s->alt_off, s->pool ? s->pool : no_pool};
+            vcl_clusters *cl = nullptr;
+            int rc = A.cluster == "biwfa"
+                         ? vcl_wfa_cluster(&hs, seq, int32_t(seq_len), A.sub, A.open, A.extend, A.max_iterations, A.reach_min_gap, A.device, &cl, nullptr)
+                         : vcl_simple_cluster(&hp, A.cluster == "size" ? 1 : 0, A.cluster_gap, A.reach_min_gap, &cl);
+            if (rc) die("ERROR: contig '%s': clustering the %s VCF failed (%d)", cs->ctg_name[k], which, rc);
+            vrl_config rc_cfg = {A.sub, A.open, A.extend, A.max_qual, 0, 0};
+            vrl_result *r = nullptr;
+            rc = vrl_realign(&hs, s->var_qual, s->gt_qual, s->phase_set, s->orig_gt, cl, seq, int32_t(seq_len), &rc_cfg, A.device, &r);
+            vcl_clusters_free(cl);
+            if (rc) die("ERROR: contig '%s': realigning the %s VCF failed (%d)", cs->ctg_name[k], which, rc);
+            keep.push_back(r);
+            cols[size_t(2 * k + h)] = vio_hap_vars{r->n, r->pos, r->rlen, r->type, r->orig_gt, r->var_qual, r->gt_qual, r->phase_set,
+                                                   r->ref_len, r->alt_len, r->ref_off, r->alt_off, r->pool, r->pool_len};
+            n_cl += r->info.n_clusters; n_in += s->n; n_out += r->n;
+            n_edge += r->info.n_edge; n_limit += r->info.n_limit; n_error += r->info.n_error;
+        }
+    }
+    fprintf(stderr, "[vcfdist_amd] realigned %s VCF: %lld clusters, %lld -> %lld hap-variants\n", which, (long long)n_cl, (long long)n_in,
+            (long long)n_out);
+    if (n_edge + n_limit + n_error) {
+        fprintf(stderr, "[WARN  vcfdist_amd] %s VCF: %lld cluster(s) NOT REALIGNED, their variants kept as read: %lld starting at the contig's "
+                        "first base, %lld beyond the memory limit of one alignment, %lld with inconsistent variants\n",
+                which, (long long)(n_edge + n_limit + n_error), (long long)n_edge, (long long)n_limit, (long long)n_error);
+        if (A.strict) die("ERROR: %s VCF: %lld cluster(s) not realigned (--strict)", which, (long long)(n_edge + n_limit + n_error));
+    }
+    cs->vars = cols.data();
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -221,7 +313,32 @@ int main(int argc, char **argv) {
     for (int k = 0; k < q->n_ctg; k++) qn.push_back(q->ctg_name[k]);
     for (int k = 0; k < t->n_ctg; k++) tn.push_back(t->ctg_name[k]);
     for (int k = 0; k < fa->n_ctg; k++) fn.push_back(fa->ctg_name[k]);
+    const bool write = !A.no_output_files;
+    // realignment (main.cpp:50-180): the callsets as read, then each realigned in place of its columns
+    if (write && A.realign_query) write_callset_vcf(A.prefix + "orig-query.vcf", q, fa, fn);
+    if (write && A.realign_truth) write_callset_vcf(A.prefix + "orig-truth.vcf", t, fa, fn);
     const std::vector<std::string> contigs = check_contigs(qn, tn, fn, bed ? &bedc : nullptr);
+    vio_hap_vars *q_read = q->vars, *t_read = t->vars;
+    std::vector<vrl_result *> realigned;
+    std::vector<vio_hap_vars> q_cols, t_cols;
+    if (A.realign_query) {
+        realign_callset("query", q, fa, fn, A, realigned, q_cols);
+        if (A.realign_only && write) write_callset_vcf(A.prefix + "query.vcf", q, fa, fn);
+    }
+    if (A.realign_truth) realign_callset("truth", t, fa, fn, A, realigned, t_cols);
+    auto release_realigned = [&]() {
+        q->vars = q_read; t->vars = t_read;
+        for (vrl_result *r : realigned) vrl_result_free(r);
+        realigned.clear();
+    };
+    if (A.realign_only) {          // realign only: the parameters (written first by the reference, main.cpp:35) and stop
+        if (A.realign_truth && write) write_callset_vcf(A.prefix + "truth.vcf", t, fa, fn);
+        if (write) write_params(A, cmd);
+        release_realigned();
+        vio_callset_free(q); vio_callset_free(t); vio_fasta_free(fa);
+        if (bed) vio_bed_free(bed);
+        return 0;
+    }
 
     const int nq = A.max_qual - A.min_qual + 1;
     std::vector<int64_t> total(size_t(2) * VPR_VARTYPES * 3 * size_t(nq), 0);
@@ -391,22 +508,7 @@ int main(int argc, char **argv) {
     if (vpr_pr_summary(total.data(), A.min_qual, A.max_qual, rows)) die("ERROR: vpr_pr_summary failed");
     if (!A.no_output_files) {
         if (vrp_write_precision_recall(A.prefix.c_str(), total.data(), A.min_qual, A.max_qual)) die("ERROR: %s", vrp_last_error());
-        {   // parameters.txt, write_params (print.cpp:30-56)
-            FILE *f = fopen((A.prefix + "parameters.txt").c_str(), "w");
-            if (!f) die("ERROR: cannot write %sparameters.txt", A.prefix.c_str());
-            fprintf(f, "program = '%s'\nversion = '%s'\nout_prefix = '%s'\ncommand = '%s'\nreference_fasta = '%s'\n"
-                       "query_vcf = '%s'\ntruth_vcf = '%s'\nbed_file = '%s'\nwrite_outputs = %s\nfilters = '%s'\n"
-                       "min_var_qual = %d\nmax_var_qual = %d\nmax_var_size = %d\nsv_threshold = %d\n"
-                       "phase_threshold = %f\ncredit_threshold = %f\nrealign_truth = %s\nrealign_query = %s\n"
-                       "realign_only = %s\ncluster_method = '%s'\ncluster_min_gap = %d\n"
-                       "reach_min_gap = %d\nmax_cluster_itrs = %d\nmax_threads = %d\nmax_ram = %f\n"
-                       "sub = %d\nopen = %d\nextend = %d\neval_sub = %d\neval_open = %d\neval_extend = %d\ndistance = %s",
-                    "vcfdist_amd", vpr_version(), A.prefix.c_str(), cmd.c_str(), A.fasta.c_str(), A.query.c_str(), A.truth.c_str(), A.bed.c_str(), "true",
-                    A.filter.c_str(), A.min_qual, A.max_qual, A.max_size, A.sv_threshold, A.phase_threshold, A.credit_threshold, "false", "false",
-                    "false", A.cluster.c_str(), A.cluster_gap, A.reach_min_gap, A.max_iterations, 64, 64.0, A.sub, A.open, A.extend, A.eval_sub, A.eval_open, A.eval_extend,
-                    A.distance ? "true" : "false");
-            fclose(f);
-        }
+        write_params(A, cmd);
         std::vector<vrp_contig> ctgs(outs.size());
         for (size_t k = 0; k < outs.size(); k++) {
             ContigOut *C = outs[k];
@@ -441,6 +543,8 @@ int main(int argc, char **argv) {
             vrp_write_variants(path("query.tsv").c_str(), ctgs.data(), n, 0) || vrp_write_variants(path("truth.tsv").c_str(), ctgs.data(), n, 1) ||
             vrp_write_summary_vcf(path("summary.vcf").c_str(), ctgs.data(), n, cmd.c_str(), nullptr, float(A.credit_threshold)))
             die("ERROR: %s", vrp_last_error());
+        if (A.realign_query) write_callset_vcf(A.prefix + "query.vcf", q, fa, fn);
+        if (A.realign_truth) write_callset_vcf(A.prefix + "truth.vcf", t, fa, fn);
     }
     printf("PRECISION-RECALL SUMMARY\n\n");
     printf("TYPE\tTHRESHOLD\tTRUTH_TP\tQUERY_TP\tTRUTH_FN\tQUERY_FP\tPREC\t\tRECALL\t\tF1_SCORE\tF1_QSCORE\n");
@@ -456,6 +560,7 @@ int main(int argc, char **argv) {
         delete C;
     }
     vpr_destroy(h);
+    release_realigned();
     vio_callset_free(q); vio_callset_free(t); vio_fasta_free(fa);
     if (bed) vio_bed_free(bed);
     return 0;

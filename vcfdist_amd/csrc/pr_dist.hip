@@ -10,13 +10,11 @@
 //                  (generate_ptrs_strs with the quality filter) and runs wf_swg_align with a ring of max(x, o+e)+1 rows,
 //                  for the score s and the exact size of the band-compacted history
 //   k_dist_wave<true>   pass 2: the same recurrence, every row kept in a slice of the round arena
-//   k_dist_back    one thread per job: wf_swg_backtrack over the history; the strings are reversed, so the backtrack emits
+//   k_dist_back    one thread per job: wf_swg_backtrack over the history (swg_walk); the strings are reversed, so the backtrack emits
 //                  the forward CIGAR in order and count_dist and the add_edits state machine run on the fly.  Launched
 //                  twice: count (distance, record count, per-quality totals), then, after a scan, write.
 //
-// The band: a row's cells can be set only from rows s-x, s-(o+e), s-e one diagonal apart at most, so every row s has a
-// diagonal range [lo_s, hi_s] that the previous ranges bound (arithmetic, the same in both passes); a cell outside it is
-// provably never written (-2 / no pointer) and is not stored.  The reference loops over all q + t - 1 diagonals.
+// The recurrence, its band and the backtrack walk are shared with the realignment (pr_swg.h).
 //
 // Memory: the job tables live for the call; pass-1 scratch and pass-2 histories share one round arena.  Jobs run in
 // rounds (pass 1: at most 4 GiB, pass 2: up to the plan, both capped by vpr_dist_config.round_bytes); a job larger than its
@@ -24,14 +22,14 @@
 // released when the call returns; the rest goes with the next upload or execute.
 #include "pr_host.h"
 #include "pr_plan.h"
+#include "pr_swg.h"
 #include "../../include/vcfdist_distance.h"
 
 #include <climits>
 
 namespace {
 
-enum { DM_SUB = 0, DM_INS = 1, DM_DEL = 2 };
-enum : uint8_t { DP_INS = 1, DP_DEL = 2, DP_MAT = 4, DP_SUB = 8 };          // src/defs.h:110-114
+using namespace swg;
 const uint32_t DIST_ERR_BITS = VPR_ST_ERR_LIMIT | VPR_ST_ERR_NO_PTR | VPR_ST_ERR_UNFINISHED;
 
 struct DTab {
@@ -51,11 +49,7 @@ struct DTab {
 };
 
 struct DJob { int32_t sc, hap, minq, maxq, q_len, t_len, tslot, pad; };
-struct DRow { int32_t lo, hi; int64_t base; };                 // diagonal range of a wavefront row, first cell of its slice
 struct DEdit { int32_t sc, pos, len, minq, maxq; uint8_t hap, type, pad[2]; };
-struct DPen { int x, o, e; };
-
-__host__ __device__ inline int64_t pad16(int64_t b) { return (b + 15) & ~int64_t(15); }
 
 // the threshold a variant adds to the set (dist.cpp:2014: float + 1 stored in a std::set<int>)
 __device__ inline int qual_key(float q) {
@@ -134,11 +128,6 @@ __global__ void k_dist_count(DTab T, int64_t *cnt) {
     cnt[i] = n;
 }
 
-// pass-1 scratch of a job: both strings, a ring of P row headers and P rows of three full-width matrices
-__device__ inline int64_t need1(int q, int t, int P) {
-    return pad16(pad16(q) + pad16(t) + 16 * int64_t(P) + 12 * int64_t(P) * max(q + t - 1, 1));
-}
-
 __global__ void k_dist_jobs(DTab T, const int64_t *job_off, DJob *jobs, int64_t *need, uint8_t *status, int P) {
     const int i = int(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= 2 * T.n_sc) return;
@@ -175,137 +164,24 @@ __device__ void load_reversed(const DTab &T, const DJob &J, uint8_t *qs, uint8_t
     });
 }
 
-// wavefront rows of one job: a ring of P rows (pass 1) or every row, band-compacted (pass 2)
-template <bool HIST>
-struct Rows {
-    DRow *row;            // [P] or [s + 1]
-    int32_t *off;         // cells
-    uint8_t *ptr;         // pointer flags (HIST only)
-    int P;
-    __device__ DRow get(int s) const { return row[HIST ? s : s % P]; }
-    // offs[m][r][d] as the reference would read it: -2 outside the row's band or before score 0
-    __device__ int ld(int r, int m, int d) const {
-        if (r < 0) return -2;
-        const DRow R = get(r);
-        if (d < R.lo || d > R.hi) return -2;
-        return off[R.base + int64_t(m) * (R.hi - R.lo + 1) + (d - R.lo)];
-    }
-};
-
-// pass 1 (HIST = false) / pass 2 (HIST = true) of one job per wavefront.  Pass 1 writes the score and the bytes pass 2 will
-// need; pass 2 writes the history into the slice its caller sized from them.
+// pass 1 (HIST = false) / pass 2 (HIST = true) of one job per wavefront (swg_wave, pr_swg.h).  Pass 1 writes the score and the bytes
+// pass 2 will need; pass 2 writes the history into the slice its caller sized from them.
 template <bool HIST>
 __global__ void __launch_bounds__(64) k_dist_wave(DTab T, const DJob *__restrict__ jobs, int64_t j0, int64_t n,
                                                    const int64_t *__restrict__ slice, int64_t slice_base, uint8_t *arena,
-                                                   uint8_t *status, int32_t *score, int64_t *need2, int64_t *cells_out, DPen pen) {
+                                                   uint8_t *status, int32_t *score, int64_t *need2_out, int64_t *cells_out, DPen pen) {
     const int64_t j = j0 + int64_t(blockIdx.x);
     if (int64_t(blockIdx.x) >= n) return;
     if (status[j]) return;
-    const int lane = threadIdx.x;
     const DJob J = jobs[j];
-    const int q = J.q_len, t = J.t_len, mat_len = q + t - 1;
-    const int x = pen.x, o = pen.o, e = pen.e, oe = o + e;
-    const int P = max(x, oe) + 1;
-    uint8_t *base = arena + (slice[j] - slice_base);
-    uint8_t *qs = base, *ts = base + pad16(q);
-    Rows<HIST> R;
-    R.P = P;
-    R.row = reinterpret_cast<DRow *>(ts + pad16(t));
-    const int s_hist = HIST ? score[j] : 0;
-    const int64_t n_rows = HIST ? int64_t(s_hist) + 1 : P;
-    R.off = reinterpret_cast<int32_t *>(reinterpret_cast<uint8_t *>(R.row) + 16 * n_rows);
-    const int64_t cell_cap = HIST ? cells_out[j] : int64_t(3) * P * mat_len;
-    R.ptr = reinterpret_cast<uint8_t *>(R.off + cell_cap);
-    load_reversed(T, J, qs, ts, lane);
-    // a bound no alignment reaches: every base substituted plus every base gapped
-    const int64_t s_max = int64_t(x) * (q + t) + int64_t(oe) * (q + t) + 1;
-
-    int s = 0;
-    int64_t cells = 3;
-    if (lane == 0) {
-        R.row[0] = DRow{q - 1, q - 1, 0};
-        R.off[DM_SUB] = -1; R.off[DM_INS] = -2; R.off[DM_DEL] = -2;
-        if (HIST) { R.ptr[DM_SUB] = DP_MAT; R.ptr[DM_INS] = 0; R.ptr[DM_DEL] = 0; }
-    }
-    __syncthreads();
-    bool failed = false;
-    for (;;) {
-        const DRow C = R.get(s);
-        const int w = C.hi - C.lo + 1;
-        // close INS / DEL into SUB (INS first, then DEL), dist.cpp:1532-1546
-        for (int d = C.lo + lane; d <= C.hi; d += 64) {
-            const int64_t c = C.base + (d - C.lo);
-            const int diag = d + 1 - q;
-            for (int m = DM_INS; m <= DM_DEL; m++) {
-                const int off = R.off[c + int64_t(m) * w];
-                if (off >= 0 && off < q && diag + off >= 0 && diag + off < t && off >= R.off[c]) {
-                    R.off[c] = off;
-                    if (HIST) R.ptr[c] |= (m == DM_INS) ? DP_INS : DP_DEL;
-                }
-            }
-        }
-        // extend along the diagonals (SUB only); the reference stops at the first diagonal that finishes
-        bool done = false;
-        for (int d0 = C.lo; d0 <= C.hi && !done; d0 += 64) {
-            const int d = d0 + lane;
-            bool fin = false;
-            if (d <= C.hi) {
-                const int64_t c = C.base + (d - C.lo);
-                const int diag = d + 1 - q;
-                int off = R.off[c];
-                while (off != -2 && diag + off >= -1 && off < q - 1 && diag + off < t - 1 && qs[off + 1] == ts[diag + off + 1]) off++;
-                R.off[c] = off;
-                fin = off == q - 1 && off + diag == t - 1;
-            }
-            done = __any(fin);
-        }
-        if (done) break;
-        s++;
-        if (s > s_max) { failed = true; break; }
-        // the new row's band from the rows it reads
-        int lo = INT_MAX, hi = INT_MIN;
-        auto widen = [&](int r, int dl, int dh) {
-            if (r < 0) return;
-            const DRow S = R.get(r);
-            if (S.lo > S.hi) return;
-            lo = min(lo, S.lo + dl); hi = max(hi, S.hi + dh);
-        };
-        widen(s - x, 0, 0);
-        widen(s - oe, -1, 1);
-        widen(s - e, -1, 1);
-        lo = max(lo, 0); hi = min(hi, mat_len - 1);
-        if (lo > hi) { lo = 1; hi = 0; }
-        const int wn = hi - lo + 1;
-        const int64_t nb = HIST ? cells : int64_t(s % P) * 3 * mat_len;
-        if (HIST && (s > s_hist || cells + 3 * int64_t(wn) > cell_cap)) { failed = true; break; }
-        __syncthreads();                  // every lane is done reading the ring slot about to be replaced
-        if (lane == 0) R.row[HIST ? s : s % P] = DRow{lo, hi, nb};
-        __syncthreads();
-        cells += 3 * int64_t(wn);
-        for (int d = lo + lane; d <= hi; d += 64) {
-            const int diag = d + 1 - q;
-            int vs = -2, vd = -2, vi = -2;
-            uint8_t fs = 0, fd = 0, fi = 0;
-            int p;
-            if (s - x >= 0 && (p = R.ld(s - x, DM_SUB, d)) != -2 && p + 1 < q && diag + p + 1 < t && p + 1 >= vs) { vs = p + 1; fs |= DP_SUB; }
-            if (s - oe >= 0 && d > 0 && (p = R.ld(s - oe, DM_SUB, d - 1)) != -2 && diag + p < t && p >= vd) { vd = p; fd |= DP_SUB; }
-            if (s - oe >= 0 && d < mat_len - 1 && (p = R.ld(s - oe, DM_SUB, d + 1)) != -2 && p + 1 < q && diag + p + 1 < t &&
-                diag + p + 1 >= 0 && p + 1 >= vi) { vi = p + 1; fi |= DP_SUB; }
-            if (s - e >= 0 && d > 0 && (p = R.ld(s - e, DM_DEL, d - 1)) != -2 && diag + p < t && p >= vd) { vd = p; fd |= DP_DEL; }
-            if (s - e >= 0 && d < mat_len - 1 && (p = R.ld(s - e, DM_INS, d + 1)) != -2 && p + 1 < q && diag + p + 1 < t &&
-                diag + p + 1 >= 0 && p + 1 >= vi) { vi = p + 1; fi |= DP_INS; }
-            const int64_t c = nb + (d - lo);
-            R.off[c] = vs; R.off[c + wn] = vi; R.off[c + 2 * int64_t(wn)] = vd;
-            if (HIST) { R.ptr[c] = fs; R.ptr[c + wn] = fi; R.ptr[c + 2 * int64_t(wn)] = fd; }
-        }
-        __syncthreads();
-    }
-    if (lane != 0) return;
-    if (failed) { status[j] |= VPR_DIST_ST_ERROR; return; }
+    const WaveOut W = swg_wave<HIST>(J.q_len, J.t_len, pen, arena + (slice[j] - slice_base), HIST ? score[j] : 0,
+                                     HIST ? cells_out[j] : 0, [&](uint8_t *qs, uint8_t *ts, int lane) { load_reversed(T, J, qs, ts, lane); });
+    if (threadIdx.x != 0) return;
+    if (W.failed) { status[j] |= VPR_DIST_ST_ERROR; return; }
     if (!HIST) {
-        score[j] = s;
-        cells_out[j] = cells;
-        need2[j] = pad16(pad16(q) + pad16(t) + 16 * (int64_t(s) + 1) + 4 * cells + pad16(cells));
+        score[j] = W.s;
+        cells_out[j] = W.cells;
+        need2_out[j] = need2(J.q_len, J.t_len, W.s, W.cells);
     }
 }
 
@@ -343,19 +219,6 @@ __global__ void k_dist_back(DTab T, const DJob *__restrict__ jobs, int64_t j0, i
     const DJob J = jobs[j];
     const int q = J.q_len, t = J.t_len;
     const uint8_t *base = arena + (slice[j] - slice_base);
-    const int s_fin = score[j];
-    Rows<true> R;
-    R.P = 0;
-    R.row = reinterpret_cast<DRow *>(const_cast<uint8_t *>(base) + pad16(q) + pad16(t));
-    R.off = reinterpret_cast<int32_t *>(reinterpret_cast<uint8_t *>(R.row) + 16 * (int64_t(s_fin) + 1));
-    R.ptr = reinterpret_cast<uint8_t *>(R.off + cells_in[j]);
-    auto flag = [&](int r, int m, int d) -> uint8_t {
-        if (r < 0) return 0;
-        const DRow W = R.get(r);
-        if (d < W.lo || d > W.hi) return 0;
-        return R.ptr[W.base + int64_t(m) * (W.hi - W.lo + 1) + (d - W.lo)];
-    };
-    const int x = pen.x, o = pen.o, e = pen.e;
     int64_t nr = 0, out = WRITE ? rec_off[k] - rec_base : 0;
     auto rec = [&](int pos, int type, int len) {
         if (WRITE) {
@@ -369,43 +232,7 @@ __global__ void k_dist_back(DTab T, const DJob *__restrict__ jobs, int64_t j0, i
     EditSM sm;
     sm.pos = T.sc_beg[J.sc];
     int dist = 0;
-    auto emit = [&](int type) { dist += type != DP_MAT; sm.step(type, rec); };
-    int qi = q - 1, ri = t - 1, mi = DM_SUB, s = s_fin;
-    bool bad = false;
-    while ((qi >= 0 || ri >= 0) && !bad) {
-        if (s < 0) { bad = true; break; }
-        const int d = q - 1 + ri - qi;
-        if (mi == DM_SUB) {
-            const uint8_t f = flag(s, DM_SUB, d);
-            if (f & (DP_INS | DP_DEL)) {              // a gap ends here: INS preferred
-                const int m = (f & DP_INS) ? DM_INS : DM_DEL;
-                const int prev = R.ld(s, m, d);
-                while (qi > prev && !bad) { emit(DP_MAT); qi--; ri--; bad = qi < 0 || ri < 0; }
-                mi = m;
-            } else if (f & DP_SUB) {
-                if (s - x < 0) { bad = true; break; }
-                const int prev = R.ld(s - x, DM_SUB, d);
-                while (qi > prev + 1 && !bad) { emit(DP_MAT); qi--; ri--; bad = qi < 0 || ri < 0; }
-                if (bad) break;
-                emit(DP_SUB); qi--; ri--;
-                s -= x;
-            } else if (f & DP_MAT) {
-                while (qi >= 0 && ri >= 0) { emit(DP_MAT); qi--; ri--; }
-                if (qi >= 0 || ri >= 0) bad = true;
-            } else {
-                bad = true;
-            }
-        } else {
-            const uint8_t f = flag(s, mi, d);
-            const uint8_t ext = mi == DM_INS ? DP_INS : DP_DEL;
-            if (!(f & (ext | DP_SUB))) { bad = true; break; }
-            emit(ext);
-            if (mi == DM_INS) qi--; else ri--;
-            if (f & ext) s -= e;
-            else { mi = DM_SUB; s -= o + e; }
-        }
-        if (!(qi == -1 && ri == -1) && (qi < 0 || ri < 0)) bad = true;
-    }
+    const bool bad = !swg_walk(base, q, t, score[j], cells_in[j], pen, [&](int type, int, int) { dist += type != DP_MAT; sm.step(type, rec); });
     if (WRITE) return;
     if (bad) { status[j] |= VPR_DIST_ST_ERROR; dist_out[j] = 0; n_rec[k] = 0; return; }
     dist_out[j] = dist;

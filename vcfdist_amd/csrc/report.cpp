@@ -625,3 +625,76 @@ extern "C" int vrp_write_edits(const char *path, const vrp_edits *sets, int32_t 
     if (!f.finish()) return fail(VRP_ERR_OPEN, std::string("write to ") + path + " failed");
     return VRP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// A callset as a VCF (variantData::write_vcf + print_variant, src/variant.cpp:132-222, 292-315): orig-query.vcf, query.vcf ... of
+// the realignment modes.
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int vrp_write_vcf(const char *path, const vrp_vcf_contig *ctgs, int32_t n_ctg, const char *sample, const char *file_date) {
+    if (!path || n_ctg < 0 || (n_ctg && !ctgs)) return fail(VRP_ERR_ARG, "vrp_write_vcf: bad argument");
+    for (int32_t ci = 0; ci < n_ctg; ci++)
+        for (int h = 0; h < 2; h++) {
+            const vrp_hap &H = ctgs[ci].hap[h];
+            if (H.n_var < 0 || (H.n_var && (!H.pos || !H.type || !H.var_qual || !H.ref_len || !H.alt_len || !H.ref_off || !H.alt_off || !H.pool)))
+                return fail(VRP_ERR_ARG, "vrp_write_vcf: incomplete variant columns");
+        }
+    File out(path);
+    if (!out) return fail(VRP_ERR_OPEN, std::string("cannot create ") + path);
+    fprintf(out, "##fileformat=VCFv4.2\n");
+    if (file_date) {
+        fprintf(out, "##fileDate=%s\n", file_date);
+    } else {
+        const time_t tt = time(nullptr);
+        const tm lt = *localtime(&tt);
+        fprintf(out, "##fileDate=%04d%02d%02d\n", lt.tm_year + 1900, lt.tm_mon + 1, lt.tm_mday);
+    }
+    for (int32_t ci = 0; ci < n_ctg; ci++)
+        fprintf(out, "##contig=<ID=%s,length=%d,ploidy=%d>\n", ctgs[ci].name, ctgs[ci].length, ctgs[ci].ploidy);
+    fprintf(out, "##FILTER=<ID=PASS,Description=\"All filters passed\">\n");
+    fprintf(out, "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n");
+    fprintf(out, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n", sample ? sample : "");
+    std::string ref, alt;
+    for (int32_t ci = 0; ci < n_ctg; ci++) {
+        const vrp_vcf_contig &c = ctgs[ci];
+        // print_variant: an INS / DEL at pos (already one left) gets the anchor base in front of both alleles
+        auto print = [&](const vrp_hap &H, int32_t i, int pos, const char *gt) {
+            const int type = H.type[i];
+            ref.assign(reinterpret_cast<const char *>(H.pool + H.ref_off[i]), size_t(H.ref_len[i]));
+            alt.assign(reinterpret_cast<const char *>(H.pool + H.alt_off[i]), size_t(H.alt_len[i]));
+            if (type == VPR_TYPE_INS || type == VPR_TYPE_DEL) {
+                if (!c.seq || pos < 0 || pos >= c.seq_len) return false;
+                const char base = char(c.seq[pos]);
+                ref.insert(ref.begin(), base);
+                alt.insert(alt.begin(), base);
+            } else if (type != VPR_TYPE_SUB) {
+                return false;
+            }
+            fprintf(out, "%s\t%d\t.\t%s\t%s\t%f\tPASS\t.\tGT\t%s\n", c.name, pos + 1, ref.c_str(), alt.c_str(), H.var_qual[i], gt);
+            return true;
+        };
+        const vrp_hap &A = c.hap[0], &B = c.hap[1];
+        int32_t pa = 0, pb = 0;
+        while (pa < A.n_var || pb < B.n_var) {
+            auto at = [](const vrp_hap &H, int32_t p) {
+                if (p >= H.n_var) return INT32_MAX;
+                return H.type[p] == VPR_TYPE_INS || H.type[p] == VPR_TYPE_DEL ? H.pos[p] - 1 : H.pos[p];
+            };
+            const int p1 = at(A, pa), p2 = at(B, pb), pos = std::min(p1, p2);
+            const bool h1 = p1 == pos, h2 = p2 == pos;
+            bool ok = true;
+            if (h1 && h2) {
+                if (same_allele(A, pa, B, pb)) ok = print(A, pa, pos, "1|1");
+                else ok = print(A, pa, pos, "1|0") && print(B, pb, pos, "0|1");
+            } else if (h1) {
+                ok = print(A, pa, pos, c.ploidy == 1 ? "1" : "1|0");
+            } else {
+                ok = print(B, pb, pos, c.ploidy == 1 ? "1" : "0|1");
+            }
+            if (!ok) return fail(VRP_ERR_ARG, std::string("vrp_write_vcf: variant type / anchor base unavailable on ") + c.name);
+            if (h1) pa++;
+            if (h2) pb++;
+        }
+    }
+    if (!out.finish()) return fail(VRP_ERR_OPEN, std::string("write error on ") + path);
+    return VRP_OK;
+}

@@ -27,7 +27,7 @@ class VrpContig(C.Structure):
 
 EXPORTED = ["vrp_phase_blocks", "vrp_write_precision_recall", "vrp_write_phase_blocks", "vrp_write_superclusters",
             "vrp_write_switchflips", "vrp_write_phasing_summary", "vrp_ng50",
-            "vrp_write_variants", "vrp_write_summary_vcf", "vrp_write_distance", "vrp_write_edits", "vrp_last_error"]
+            "vrp_write_variants", "vrp_write_summary_vcf", "vrp_write_distance", "vrp_write_edits", "vrp_write_vcf", "vrp_last_error"]
 
 
 class ReportError(RuntimeError):
@@ -201,7 +201,7 @@ def write_edits(path, sets):
 def write_parameters(prefix, args, cmd):
     """parameters.txt (write_params, print.cpp:30-56): the run's settings, one `key = value` per line, in the reference's order and
     formats (strings quoted, booleans true / false, the two thresholds and max_ram with %f).  Keys of stages this implementation
-    does not have keep the reference's defaults (realignment off, globals.h:41-59); eval penalties and distance are the run's."""
+    does not have keep the reference's defaults (globals.h:41-59); realignment, eval penalties and distance are the run's."""
     b2s = lambda b: "true" if b else "false"
     L = api.lib()
     L.vpr_version.restype = C.c_char_p
@@ -215,8 +215,48 @@ def write_parameters(prefix, args, cmd):
         "sub = %d\nopen = %d\nextend = %d\neval_sub = %d\neval_open = %d\neval_extend = %d\ndistance = %s" % (
             "vcfdist_amd", L.vpr_version().decode(), prefix, cmd, args.fasta, args.query, args.truth, args.bed or "",
             b2s(not args.no_output_files), args.filter, args.min_qual, args.max_qual, args.max_size, args.sv_threshold,
-            args.phase_threshold, args.credit_threshold, b2s(False), b2s(False), b2s(False), args.cluster, args.cluster_gap,
+            args.phase_threshold, args.credit_threshold, b2s(getattr(args, "realign_truth", False)), b2s(getattr(args, "realign_query", False)),
+            b2s(getattr(args, "realign_only", False)), args.cluster, args.cluster_gap,
             args.reach_min_gap, args.max_iterations, 64, 64.0, args.sub, args.open, args.extend,
             getattr(args, "eval_sub", 3), getattr(args, "eval_open", 2), getattr(args, "eval_extend", 1), b2s(getattr(args, "distance", False))))
     with open(prefix + "parameters.txt", "w") as f:
         f.write(text)
+
+
+class VrpVcfContig(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("length", C.c_int32), ("ploidy", C.c_int32), ("seq", A.P_u8), ("seq_len", C.c_int64),
+                ("hap", VrpHap * 2)]
+
+
+def write_vcf(path, callset, fasta=None, vars=None, file_date=None):
+    """a callset as a VCF (variantData::write_vcf, variant.cpp:132-222; vrp_write_vcf).  callset: what vcfdist_amd.io.read_vcf returns
+    (contigs, lengths, ploidy, sample, vars); vars: per-contig [hap 1, hap 2] column dicts in place of callset["vars"] (a realigned
+    callset); fasta: {name: sequence} for the anchor bases of INS / DEL records"""
+    vars = callset["vars"] if vars is None else vars
+    keep = []
+
+    def own(a, dt):
+        a = np.ascontiguousarray(a, dt)
+        if a.size == 0:
+            a = np.zeros(1, dt)
+        keep.append(a)
+        return A._ptr(a, np.ctypeslib.as_ctypes_type(dt))
+    n = len(callset["contigs"])
+    arr = (VrpVcfContig * max(n, 1))()
+    for k, name in enumerate(callset["contigs"]):
+        c = arr[k]
+        nm = name.encode()
+        keep.append(nm)
+        c.name, c.length, c.ploidy = nm, int(callset["lengths"][k]), int(callset["ploidy"][k])
+        if fasta is not None and name in fasta:
+            sq = np.asarray(fasta[name], np.uint8)
+            c.seq, c.seq_len = own(sq, np.uint8), len(sq)
+        for h in range(2):
+            s, H = vars[k][h], c.hap[h]
+            H.n_var = len(s["pos"])
+            H.pos, H.type, H.var_qual = own(s["pos"], np.int32), own(s["type"], np.uint8), own(s["var_qual"], np.float32)
+            H.ref_len, H.alt_len = own(s["ref_len"], np.int32), own(s["alt_len"], np.int32)
+            H.ref_off, H.alt_off, H.pool = own(s["ref_off"], np.int64), own(s["alt_off"], np.int64), own(s["pool"], np.uint8)
+    L = api.lib()
+    L.vrp_write_vcf.argtypes = [C.c_char_p, C.POINTER(VrpVcfContig), C.c_int32, C.c_char_p, C.c_char_p]
+    _check(L.vrp_write_vcf(path.encode(), arr, n, callset["sample"].encode(), file_date.encode() if file_date else None), "vrp_write_vcf")
