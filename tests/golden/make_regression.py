@@ -1,6 +1,6 @@
 """Regenerates tests/golden/regression_seed7.npz and regression_joint61.npz: inputs (generator parameters) and the ORACLE's outputs for a
 small seeded batch.  These are regression vectors of the CPU restatement (oracle/pr_oracle.cpp), NOT outputs of
-the reference: the reference cannot be built in this image.  Run from the repo root:
+the reference (those are under tests/golden/ref/, see make_ref_goldens.py).  Run from the repo root:
     python tests/golden/make_regression.py"""
 import os
 import sys
