@@ -37,6 +37,14 @@ void vio_bed_free(vio_bed *b);
 /* start / stop: 0-based half-open span of the record's original REF allele; type: VPR_TYPE_* of the parsed variant.
    bed == NULL: always INSIDE (g.bed_exists false). */
 int vio_bed_contains(const vio_bed *bed, const char *contig, int32_t start, int32_t stop, int32_t type);
+/* The regions of one contig as vio_read_bed checked them (sorted, non-overlapping, non-empty): *n of them, *starts / *stops
+   point into the vio_bed and live as long as it does.  A contig the BED does not list: *n = 0 and null pointers.  With
+   it a vpr_strata (include/vcfdist_strata.h) is assembled from BEDs read by vio_read_bed. */
+/* vio_bed_contains of n variants of one contig, one after the other on the calling thread: start = pos[i], stop = pos[i] +
+   ref_len[i]; loc[i] = VIO_BED_*.  The host's answer to what vpr_strata_masks computes on the device. */
+int vio_bed_contains_many(const vio_bed *bed, const char *contig, int64_t n, const int32_t *pos, const int32_t *ref_len,
+                          const uint8_t *type, uint8_t *loc);
+int vio_bed_intervals(const vio_bed *bed, const char *contig, int64_t *n, const int32_t **starts, const int32_t **stops);
 
 typedef struct vio_params {
     int32_t min_qual;         /* g.min_qual (0): records with QUAL below it are dropped */

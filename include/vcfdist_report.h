@@ -4,6 +4,7 @@
  * Reference interfaces replaced (TimD1/vcfdist v2.6.4):
  *   vrp_phase_blocks             phaseblockData::phaseblockData (phase-set runs)   src/phase.cpp:229-262
  *   vrp_write_precision_recall   write_precision_recall (the two TSV files)        src/print.cpp:441-566
+ *   vrp_write_stratified         (none: the same tables per stratum, include/vcfdist_strata.h)
  *   vrp_write_phase_blocks       write_results, phase-blocks.tsv                   src/print.cpp:585-609
  *   vrp_write_superclusters      write_results, superclusters.tsv                  src/print.cpp:611-671
  *   vrp_write_variants           write_results, query.tsv / truth.tsv              src/print.cpp:673-876
@@ -80,6 +81,12 @@ int32_t vrp_phase_blocks(const int32_t *sc_phase_set, int32_t n_sc, int32_t *pha
 /* <prefix>precision-recall.tsv and <prefix>precision-recall-summary.tsv from the counters of vpr_pr_counts
    (summed over contigs by the caller). */
 int vrp_write_precision_recall(const char *prefix, const int64_t *counts, int32_t min_qual, int32_t max_qual);
+/* <prefix>stratified-precision-recall.tsv and <prefix>stratified-precision-recall-summary.tsv from the counters of
+   vpr_pr_counts_strata (include/vcfdist_strata.h; counts[n_strata][2][VPR_VARTYPES][3][nq], summed over contigs by the
+   caller): the two tables above once per stratum, in list order, behind a leading STRATUM column that holds names[k].
+   A stratum's rows without that column are byte for byte what vrp_write_precision_recall writes for its counts. */
+int vrp_write_stratified(const char *prefix, const char *const *names, int32_t n_strata, const int64_t *counts,
+                         int32_t min_qual, int32_t max_qual);
 
 int vrp_write_phase_blocks(const char *path, const vrp_contig *ctgs, int32_t n_ctg);
 /* switchflips.tsv: where every switch / flip error may have happened; phasing-summary.tsv: block and error totals with

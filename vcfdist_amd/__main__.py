@@ -8,7 +8,9 @@ superclusters.tsv, query.tsv, truth.tsv, summary.vcf under -p PREFIX; -n writes 
 metrics run on the GPU behind each contig's path (include/vcfdist_distance.h): distance.tsv, distance-summary.tsv, edits.tsv and
 the ALIGNMENT DISTANCE SUMMARY (printed even with -n); one rank only.  With -rq / -rt a callset is clustered and realigned on the
 GPU before the evaluation (include/vcfdist_realign.h): orig-query.vcf / orig-truth.vcf as read, query.vcf / truth.vcf realigned;
--ro stops after the realignment; one rank only."""
+-ro stops after the realignment; one rank only.  With --stratify FILE (the GIAB list format: one name<TAB>path of a BED per line) the
+counters of the one evaluation are also cut by region on the GPU (include/vcfdist_strata.h): stratified-precision-recall.tsv and
+stratified-precision-recall-summary.tsv; works under several ranks in both --shard modes."""
 import argparse
 import sys
 
@@ -116,7 +118,25 @@ def prepare_contig(name, seq, slots, args, device=0):
     return dict(name=name, haps=haps, cl=cl, sc=sc, batch=batch, slots=slots, variants=v if sc.n else None)
 
 
-def evaluate_contig(prep, args, device=0, part=None, dist_sets=None):
+def stratify_contig(pr, prep, strat, args, pb, part_idx=None):
+    """--stratify: the contig's membership words on the device (every hap-variant against every stratum), then the counters of the
+    executed batch cut by them, added to strat['counts'].  part_idx: this rank holds the superclusters part_idx of the contig -- the
+    words are computed for the whole contig and the rank keeps its share's."""
+    from . import shard
+    name, whole = prep["name"], prep["batch"]
+    n_strata = len(strat["beds"])
+    pr.strata_masks(prep["variants"], IO.contig_strata(strat["beds"], [name]))
+    words = pr.download_strata_masks()
+    if part_idx is not None:
+        words = [np.stack([shard.subset_per_variant(w, whole.var_off[s], part_idx) for w in words[s]]) for s in range(4)]
+        pr.upload_strata_masks(n_strata, words)
+    strat["counts"] += S.pr_counts_strata(pr, None, pb, args.min_qual, args.max_qual)     # (the classes are resident: pr_counts)
+    for w in words:
+        strat["vars"] += w.shape[1]
+        strat["none"] += int((np.bitwise_or.reduce(w, axis=0) == 0).sum())
+
+
+def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None):
     """the precision/recall path on the GPU, phasing and counters for a prepared contig.  -> int64 counters [2][4][3][nq],
     n_sc, and what the writers need: (clusters after splitting, superclusters, results, phase sets, pb_phase, switches, flips).
     part = (rank, world, collective device): this rank evaluates its share of the contig's SUPERCLUSTERS -- dealt by the
@@ -155,6 +175,8 @@ def evaluate_contig(prep, args, device=0, part=None, dist_sets=None):
         mask_unevaluated(res)
         pb, sw, fl = S.phase(res.sc_phase, phase_sets)
         counts = S.pr_counts(pr, cls, pb, args.min_qual, args.max_qual)
+        if strat is not None:
+            stratify_contig(pr, prep, strat, args, pb)
     else:
         from . import shard
         rank, world, cdev = part
@@ -176,6 +198,8 @@ def evaluate_contig(prep, args, device=0, part=None, dist_sets=None):
         if len(idx):
             cls_mine = [shard.subset_per_variant(cls[s], whole.var_off[s], idx) for s in range(4)]
             counts = S.pr_counts(pr, cls_mine, pb[idx], args.min_qual, args.max_qual)
+            if strat is not None:
+                stratify_contig(pr, prep, strat, args, pb[idx], part_idx=idx)
         else:
             counts = np.zeros((2, 4, 3, nq), np.int64)
         res = shard.gather_results(local, idx, whole.var_off, device=cdev)
@@ -309,6 +333,9 @@ def main(argv=None):
     ap.add_argument("-rq", "--realign-query", action="store_true", help="realign the query variants before the evaluation")
     ap.add_argument("-rt", "--realign-truth", action="store_true", help="realign the truth variants before the evaluation")
     ap.add_argument("-ro", "--realign-only", action="store_true", help="stop after the realignment (query.vcf / truth.vcf)")
+    ap.add_argument("--stratify", metavar="FILE",
+                    help="strata list (one name<TAB>path of a BED per line, paths relative to the list): the counters of the one "
+                         "evaluation are also cut by region (stratified-precision-recall.tsv, stratified-precision-recall-summary.tsv)")
     ap.add_argument("--shard", default="superclusters", choices=["superclusters", "contigs"],
                     help="several ranks (torch.distributed.run, one per GPU): deal every contig's superclusters over the ranks "
                          "(default; balanced whatever the contigs' sizes) or whole contigs")
@@ -350,6 +377,13 @@ def main(argv=None):
         if backend == "nccl":
             torch.cuda.set_device(device)
         dist.init_process_group(backend=backend)
+    strat = None
+    if args.stratify:       # the strata list and every BED it names are read and checked before anything is evaluated
+        try:
+            names, beds = IO.read_strata(args.stratify)
+        except IOError as e:
+            raise SystemExit(f"ERROR: {e}")
+        strat = dict(names=names, beds=beds, counts=None, vars=0, none=0)
     filters = tuple(f for f in args.filter.split(",") if f)
     bed = IO.Bed(args.bed) if args.bed else None
     kw = dict(min_qual=args.min_qual, max_qual=args.max_qual, max_size=args.max_size, cluster_min_gap=args.cluster_gap, filters=filters)
@@ -378,6 +412,8 @@ def main(argv=None):
         return []
     nq = args.max_qual - args.min_qual + 1
     total = np.zeros((2, 4, 3, nq), np.int64)
+    if strat is not None:
+        strat["counts"] = np.zeros((len(strat["names"]), 2, 4, 3, nq), np.int64)
     empty = dict(pos=np.zeros(0, np.int32), rlen=np.zeros(0, np.int32), type=np.zeros(0, np.uint8), var_qual=np.zeros(0, np.float32),
                  phase_set=np.zeros(0, np.int32), ref_len=np.zeros(0, np.int32), alt_len=np.zeros(0, np.int32),
                  ref_off=np.zeros(0, np.int64), alt_off=np.zeros(0, np.int64), pool=np.zeros(1, np.uint8))
@@ -409,7 +445,7 @@ def main(argv=None):
         ctg = contigs[k]
         try:
             counts, n_sc, tables = evaluate_contig(prepared.pop(k), args, device=device, part=(rank, world, cdev) if by_sc else None,
-                                                   dist_sets=dist_sets)
+                                                   dist_sets=dist_sets, strat=strat)
         except api.VprError as e:     # the library's explicit refusals end the run like the reference's ERROR()
             raise SystemExit(f"ERROR: contig '{ctg}': {e}")
         total += counts
@@ -422,7 +458,13 @@ def main(argv=None):
                 length, ploidy = len(fasta[ctg]), 0
             reports[k] = (ctg, length, ploidy, slots_of(ctg), tables)
     if dist is not None:
-        total = shard.allreduce_tally(total, device=cdev)       # the one all-reduce: counts[2][4][3][nq] summed over the ranks
+        # the one all-reduce: counts[2][4][3][nq] summed over the ranks, with --stratify the stratified ones behind them
+        tail = [] if strat is None else [strat["counts"].ravel(), np.asarray([strat["vars"], strat["none"]], np.int64)]
+        summed = shard.allreduce_tally(np.concatenate([total.ravel()] + tail), device=cdev)
+        total = summed[:total.size].reshape(total.shape)
+        if strat is not None:
+            strat["counts"] = summed[total.size:-2].reshape(strat["counts"].shape)
+            strat["vars"], strat["none"] = int(summed[-2]), int(summed[-1])
         if not by_sc:       # (by superclusters every rank already holds every contig's gathered tables)
             gathered = [None] * world
             dist.all_gather_object(gathered, reports)
@@ -438,12 +480,17 @@ def main(argv=None):
         if not args.no_output_files:
             RP.write_precision_recall(args.prefix, total, args.min_qual, args.max_qual)
             RP.write_parameters(args.prefix, args, cmd)
+            if strat is not None:
+                RP.write_stratified(args.prefix, strat["names"], strat["counts"], args.min_qual, args.max_qual)
             ctgs = [RP.Contig(c, ln, pl, fasta[c], sl, *tb) for c, ln, pl, sl, tb in (reports[k] for k in sorted(reports))]
             RP.write_results(args.prefix, ctgs, cmd=cmd, credit_threshold=args.credit_threshold)
             if args.realign_query:
                 RP.write_vcf(args.prefix + "query.vcf", q, fasta)
             if args.realign_truth:
                 RP.write_vcf(args.prefix + "truth.vcf", t, fasta)
+        if strat is not None:
+            print(f"[vcfdist_amd] stratified: {len(strat['names'])} strata, {strat['none']} of {strat['vars']} hap-variants in none of them",
+                  file=sys.stderr)
         print("PRECISION-RECALL SUMMARY\n")
         print("TYPE\tTHRESHOLD\tTRUTH_TP\tQUERY_TP\tTRUTH_FN\tQUERY_FP\tPREC\t\tRECALL\t\tF1_SCORE\tF1_QSCORE")
         for r in rows:

@@ -486,6 +486,35 @@ class VprDistResults(C.Structure):
                 ("edit_type", P_u8), ("edit_len", P_i32), ("edit_min_qual", P_i32), ("edit_max_qual", P_i32)]
 
 
+# ---- include/vcfdist_strata.h
+class VprStrata(C.Structure):
+    _fields_ = [("n_strata", C.c_int32), ("n_ctg", C.c_int32), ("iv_off", P_i64), ("iv_start", P_i32), ("iv_stop", P_i32)]
+
+
+class Strata:
+    """vpr_strata: per (stratum, contig) a sorted list of non-overlapping 0-based half-open intervals.  rows: one entry per
+    stratum, each a list (one entry per contig, in the numbering of the Variants it is used with) of (starts, stops)."""
+
+    def __init__(self, rows, n_ctg):
+        self.n_strata, self.n_ctg = len(rows), int(n_ctg)
+        off, st, sp = [0], [], []
+        for per_ctg in rows:
+            if len(per_ctg) != self.n_ctg:
+                raise ValueError(f"a stratum lists {len(per_ctg)} contigs, expected {self.n_ctg}")
+            for a, b in per_ctg:
+                st.append(np.asarray(a, np.int32)); sp.append(np.asarray(b, np.int32))
+                off.append(off[-1] + len(st[-1]))
+        self.iv_off = np.asarray(off, np.int64)
+        self.iv_start = _arr(np.concatenate(st) if st else [], np.int32)
+        self.iv_stop = _arr(np.concatenate(sp) if sp else [], np.int32)
+
+    def as_struct(self):
+        z = np.zeros(1, np.int32)
+        self._keep = (self.iv_start if len(self.iv_start) else z, self.iv_stop if len(self.iv_stop) else z)
+        return VprStrata(self.n_strata, self.n_ctg, _ptr(self.iv_off, C.c_int64), _ptr(self._keep[0], C.c_int32),
+                         _ptr(self._keep[1], C.c_int32))
+
+
 # ---- include/vcfdist_realign.h
 RL_ST_EDGE = 1
 RL_ST_LIMIT = 2

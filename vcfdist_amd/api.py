@@ -82,6 +82,13 @@ def lib():
     L.vpr_distance.argtypes = [H, C.POINTER(A.VprVariants), C.POINTER(A.VprDistConfig)]
     L.vpr_distance_info.argtypes = [H, C.POINTER(A.VprDistInfo)]
     L.vpr_distance_download.argtypes = [H, C.POINTER(A.VprDistResults)]
+    P_u64 = C.POINTER(C.c_uint64)
+    L.vpr_strata_masks.argtypes = [H, C.POINTER(A.VprVariants), C.POINTER(A.VprStrata)]
+    L.vpr_strata_download_masks.argtypes = [H, P_u64 * A.HAPS]
+    L.vpr_strata_upload_masks.argtypes = [H, C.c_int32, A.P_i64, P_u64 * A.HAPS]
+    L.vpr_pr_counts_strata.argtypes = [H, C.c_void_p, A.P_i32, C.c_int32, C.c_int32, A.P_i64]
+    L.vpr_allreduce_counts_strata.argtypes = [H, C.c_void_p, C.c_void_p, A.P_i32, C.c_int32, C.c_int32, A.P_i64]
+    L.vpr_strata_timing.argtypes = [H, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     from .cluster import VclHapSeq, VclClusters
     L.vrl_realign.argtypes = [C.POINTER(VclHapSeq), A.P_f32, A.P_f32, A.P_i32, A.P_u8, C.POINTER(VclClusters), A.P_u8, C.c_int32,
                               C.POINTER(A.VrlConfig), C.c_int32, C.POINTER(C.POINTER(A.VrlResult))]
@@ -100,6 +107,9 @@ EXPORTED = [
 ]
 # include/vcfdist_distance.h
 DIST_EXPORTED = ["vpr_distance", "vpr_distance_info", "vpr_distance_download"]
+# include/vcfdist_strata.h
+STRATA_EXPORTED = ["vpr_strata_masks", "vpr_strata_download_masks", "vpr_strata_upload_masks", "vpr_pr_counts_strata",
+                   "vpr_allreduce_counts_strata", "vpr_strata_timing"]
 # include/vcfdist_realign.h
 RL_EXPORTED = ["vrl_realign", "vrl_result_free"]
 
@@ -282,6 +292,7 @@ class PrecisionRecall:
 
     def upload(self, batch: A.Batch):
         self._batch = batch
+        self._strata = None       # (the library releases the membership words with the batch)
         s = batch.as_struct()
         self._chk(lib().vpr_upload(self._h, C.byref(s)), "vpr_upload")
 
@@ -336,6 +347,42 @@ class PrecisionRecall:
             out[name] = out[name][:n]
         return out
 
+    def strata_masks(self, variants, strata: A.Strata):
+        """Membership words of the variants' four hap slots for every stratum (include/vcfdist_strata.h), computed and kept on the
+        device until the next upload.  variants: an A.Variants (or a VprVariants struct); it need not be the executed batch."""
+        vs = variants.as_struct() if isinstance(variants, A.Variants) else variants
+        n_sc = int(vs.n_sc)
+        ss = strata.as_struct()
+        self._chk(lib().vpr_strata_masks(self._h, C.byref(vs), C.byref(ss)), "vpr_strata_masks")
+        self._strata = (strata.n_strata, [int(vs.var_off[h][n_sc]) for h in range(A.HAPS)])
+
+    def download_strata_masks(self):
+        """the resident words: per hap slot a uint64 array [n_words, n_var]; bit k & 63 of word k >> 6 is stratum k"""
+        n_strata, nv = getattr(self, "_strata", None) or (1, [0] * A.HAPS)     # (without words the call refuses: VPR_ERR_STATE)
+        nw = (n_strata + 63) // 64
+        out = [np.zeros((nw, n), np.uint64) for n in nv]
+        keep = [o if o.size else np.zeros(1, np.uint64) for o in out]
+        arr = (C.POINTER(C.c_uint64) * A.HAPS)(*[A._ptr(k, C.c_uint64) for k in keep])
+        self._chk(lib().vpr_strata_download_masks(self._h, arr), "vpr_strata_download_masks")
+        return out
+
+    def upload_strata_masks(self, n_strata, masks):
+        """make caller-supplied words resident (a rank's share of download_strata_masks(), or words made elsewhere):
+        masks[slot] is uint64 [n_words, n_var]"""
+        nw = (int(n_strata) + 63) // 64
+        ms = [np.ascontiguousarray(m, np.uint64).reshape(nw, -1) for m in masks]
+        nv = np.asarray([m.shape[1] for m in ms], np.int64)
+        keep = [m if m.size else np.zeros(1, np.uint64) for m in ms]
+        arr = (C.POINTER(C.c_uint64) * A.HAPS)(*[A._ptr(k, C.c_uint64) for k in keep])
+        self._chk(lib().vpr_strata_upload_masks(self._h, int(n_strata), A._ptr(nv, C.c_int64), arr), "vpr_strata_upload_masks")
+        self._strata = (int(n_strata), [int(n) for n in nv])
+
+    def strata_timing(self):
+        """(ms of the last strata_masks' kernels, ms of the last stratified histogram's) from HIP events on the handle's stream"""
+        a, b = C.c_double(), C.c_double()
+        self._chk(lib().vpr_strata_timing(self._h, C.byref(a), C.byref(b)), "vpr_strata_timing")
+        return a.value, b.value
+
     def timing(self) -> A.VprTiming:
         t = A.VprTiming()
         self._chk(lib().vpr_get_timing(self._h, C.byref(t)), "vpr_get_timing")
@@ -359,6 +406,7 @@ class PrecisionRecall:
         haplotype strings and pointer arrays (generate_ptrs_strs, pr_gen.hip).  `batch_for_results` only sizes the result
         buffers: anything with n_sc and n_vars(h) (a Batch, a Variants)."""
         self._batch = batch_for_results
+        self._strata = None
         self._chk(lib().vpr_upload_variants(self._h, C.byref(variants_struct)), "vpr_upload_variants")
 
     def download_level_a(self, like: A.Batch) -> A.Batch:

@@ -9,11 +9,13 @@
 //   vcfdist_gpu <query.vcf[.gz]> <truth.vcf[.gz]> <ref.fasta[.gz]> [-b regions.bed] [-p prefix] [-n] [-c biwfa | gap N | size N]
 //               [-l max variant size] [-s max supercluster size] [-mn / -mx qual] [-f filters] [-i iterations] [-x -o -e penalties]
 //               [-ct credit threshold] [-pt phasing threshold] [-sv threshold] [--reach-min-gap N] [--strict] [--device N]
-//               [-d] [-ex -eo -ee evaluation penalties] [-rq] [-rt] [-ro]
+//               [-d] [-ex -eo -ee evaluation penalties] [-rq] [-rt] [-ro] [--stratify strata.tsv]
 // With -d the distance metrics (edits_wrapper, dist.cpp:1908-2077) run on the GPU after each contig's precision/recall path
 // (include/vcfdist_distance.h), as the reference's main.cpp:223-238 runs them after precision_recall_threads_wrapper.
 // With -rq / -rt a callset is clustered and realigned on the GPU (include/vcfdist_realign.h) before the evaluation, in the order of
 // the reference's main.cpp:50-180 (orig-*.vcf, realign query, realign truth; -ro stops there and writes query.vcf / truth.vcf).
+// With --stratify FILE (the GIAB list format: one name<TAB>path of a BED per line) the counters of the one evaluation are also cut
+// by region on the GPU (include/vcfdist_strata.h): stratified-precision-recall.tsv and stratified-precision-recall-summary.tsv.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdint>
@@ -32,11 +34,12 @@
 #include "../../include/vcfdist_pr.h"
 #include "../../include/vcfdist_realign.h"
 #include "../../include/vcfdist_report.h"
+#include "../../include/vcfdist_strata.h"
 
 namespace {
 
 struct Args {
-    std::string query, truth, fasta, bed, filter, prefix = "./", cluster = "biwfa";
+    std::string query, truth, fasta, bed, filter, prefix = "./", cluster = "biwfa", stratify;
     int max_size = 5000, min_qual = 0, max_qual = 60, cluster_gap = 50, max_iterations = 4, max_supercluster_size = 10000;
     int sub = 5, open = 6, extend = 2, sv_threshold = 50, reach_min_gap = 10, device = 0;
     int eval_sub = 3, eval_open = 2, eval_extend = 1;      // globals.h:52-55
@@ -93,6 +96,7 @@ Args parse(int argc, char **argv) {
         else if (o == "--strict") a.strict = true;
         else if (o == "--device") a.device = atoi(need(i));
         else if (o == "-d" || o == "--distance") a.distance = true;
+        else if (o == "--stratify") a.stratify = need(i);
         else if (o == "-rq" || o == "--realign-query") a.realign_query = true;
         else if (o == "-rt" || o == "--realign-truth") a.realign_truth = true;
         else if (o == "-ro" || o == "--realign-only") a.realign_only = true;
@@ -122,6 +126,38 @@ std::vector<std::string> bed_contigs(const std::string &path) {
         if (ss >> c && std::find(out.begin(), out.end(), c) == out.end()) out.push_back(c);
     }
     return out;
+}
+
+// --stratify: the strata list (GIAB format: name<TAB>path per line, blank and '#' lines skipped, a relative path is taken from
+// the list's own directory) and its BEDs, each read and checked by vio_read_bed; any fault ends the run before anything is evaluated
+struct Strata { std::vector<std::string> names; std::vector<vio_bed *> beds; };
+Strata read_strata(const std::string &list) {
+    Strata S;
+    std::ifstream f(list);
+    if (!f) die("ERROR: cannot open the strata list '%s'", list.c_str());
+    const size_t sl = list.rfind('/');
+    const std::string dir = sl == std::string::npos ? "" : list.substr(0, sl + 1);
+    std::string line;
+    int ln = 0;
+    while (std::getline(f, line)) {
+        ln++;
+        while (!line.empty() && (line.back() == '\r' || line.back() == '\n')) line.pop_back();
+        if (line.find_first_not_of(" \t") == std::string::npos || line[0] == '#') continue;
+        const size_t tab = line.find('\t');
+        if (tab == std::string::npos || tab == 0 || tab + 1 >= line.size())
+            die("ERROR: strata list '%s' line %d: expected name<TAB>path", list.c_str(), ln);
+        const std::string name = line.substr(0, tab);
+        std::string path = line.substr(tab + 1);
+        if (path.find('\t') != std::string::npos) path = path.substr(0, path.find('\t'));
+        if (std::find(S.names.begin(), S.names.end(), name) != S.names.end())
+            die("ERROR: strata list '%s' line %d: duplicate stratum name '%s'", list.c_str(), ln, name.c_str());
+        if (path[0] != '/') path = dir + path;
+        vio_bed *b = nullptr;
+        if (vio_read_bed(path.c_str(), &b)) die("ERROR: stratum '%s': %s", name.c_str(), vio_last_error());
+        S.names.push_back(name); S.beds.push_back(b);
+    }
+    if (S.names.empty()) die("ERROR: strata list '%s' names no stratum", list.c_str());
+    return S;
 }
 
 int find(const std::vector<std::string> &v, const std::string &s) {
@@ -299,6 +335,9 @@ int main(int argc, char **argv) {
         if (vio_read_bed(A.bed.c_str(), &bed)) die("ERROR: %s", vio_last_error());
         bedc = bed_contigs(A.bed);
     }
+    Strata strata;
+    if (!A.stratify.empty()) strata = read_strata(A.stratify);
+    const int n_strata = int(strata.names.size());
     std::vector<std::string> filters;
     { std::istringstream ss(A.filter); std::string f; while (std::getline(ss, f, ',')) if (!f.empty()) filters.push_back(f); }
     std::vector<const char *> fptr;
@@ -337,11 +376,14 @@ int main(int argc, char **argv) {
         release_realigned();
         vio_callset_free(q); vio_callset_free(t); vio_fasta_free(fa);
         if (bed) vio_bed_free(bed);
+        for (vio_bed *b : strata.beds) vio_bed_free(b);
         return 0;
     }
 
     const int nq = A.max_qual - A.min_qual + 1;
     std::vector<int64_t> total(size_t(2) * VPR_VARTYPES * 3 * size_t(nq), 0);
+    std::vector<int64_t> strat_total(total.size() * size_t(n_strata), 0);      // --stratify: counts[n_strata][2][4][3][nq]
+    int64_t strat_vars = 0, strat_none = 0;                                     // hap-variants seen / in no stratum
     vpr_config cfg;
     memset(&cfg, 0, sizeof(cfg));
     cfg.device = A.device; cfg.max_qual = float(A.max_qual); cfg.credit_threshold = A.credit_threshold; cfg.phase_threshold = A.phase_threshold;
@@ -450,6 +492,36 @@ int main(int argc, char **argv) {
             std::vector<int64_t> counts(total.size(), 0);
             if (vpr_pr_counts(h, clsp, C->pb.data(), A.min_qual, A.max_qual, counts.data())) die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
             for (size_t k = 0; k < total.size(); k++) total[k] += counts[k];
+            if (n_strata) {        // the same evaluation, cut by region: membership words, then the histogram per stratum
+                std::vector<int64_t> iv_off(size_t(n_strata) + 1, 0);
+                std::vector<int32_t> iv_start, iv_stop;
+                for (int k = 0; k < n_strata; k++) {
+                    int64_t n = 0;
+                    const int32_t *st = nullptr, *sp = nullptr;
+                    if (vio_bed_intervals(strata.beds[size_t(k)], ctg.c_str(), &n, &st, &sp)) die("ERROR: %s", vio_last_error());
+                    iv_start.insert(iv_start.end(), st, st + n); iv_stop.insert(iv_stop.end(), sp, sp + n);
+                    iv_off[size_t(k) + 1] = int64_t(iv_start.size());
+                }
+                const vpr_strata ST = {n_strata, 1, iv_off.data(), iv_start.data(), iv_stop.data()};
+                std::vector<int64_t> sc_counts(strat_total.size(), 0);
+                if (vpr_strata_masks(h, &V, &ST) || vpr_pr_counts_strata(h, nullptr, C->pb.data(), A.min_qual, A.max_qual, sc_counts.data()))
+                    die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+                for (size_t k = 0; k < strat_total.size(); k++) strat_total[k] += sc_counts[k];
+                const size_t n_words = (size_t(n_strata) + 63) / 64;
+                std::vector<uint64_t> words[4];
+                uint64_t *wp[4];
+                for (int i = 0; i < 4; i++) { words[i].assign(std::max<size_t>(n_words * size_t(C->slot[i]->n), 1), 0); wp[i] = words[i].data(); }
+                if (vpr_strata_download_masks(h, wp)) die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+                for (int i = 0; i < 4; i++) {
+                    const size_t nv = size_t(C->slot[i]->n);
+                    for (size_t v = 0; v < nv; v++) {
+                        uint64_t any = 0;
+                        for (size_t w = 0; w < n_words; w++) any |= words[i][w * nv + v];
+                        strat_none += any == 0;
+                    }
+                    strat_vars += int64_t(nv);
+                }
+            }
             // the reference's WARN lines (dist.cpp:1203-1223) and -- loudly -- what this implementation did not evaluate
             static const struct { uint32_t bit; const char *text; } W[] = {
                 {VPR_ST_WARN_REF_ED, "Nonzero reference edit distance with no truth variants at ctg %s supercluster %d"},
@@ -509,6 +581,11 @@ int main(int argc, char **argv) {
     if (!A.no_output_files) {
         if (vrp_write_precision_recall(A.prefix.c_str(), total.data(), A.min_qual, A.max_qual)) die("ERROR: %s", vrp_last_error());
         write_params(A, cmd);
+        if (n_strata) {
+            std::vector<const char *> names;
+            for (const auto &n : strata.names) names.push_back(n.c_str());
+            if (vrp_write_stratified(A.prefix.c_str(), names.data(), n_strata, strat_total.data(), A.min_qual, A.max_qual)) die("ERROR: %s", vrp_last_error());
+        }
         std::vector<vrp_contig> ctgs(outs.size());
         for (size_t k = 0; k < outs.size(); k++) {
             ContigOut *C = outs[k];
@@ -546,6 +623,9 @@ int main(int argc, char **argv) {
         if (A.realign_query) write_callset_vcf(A.prefix + "query.vcf", q, fa, fn);
         if (A.realign_truth) write_callset_vcf(A.prefix + "truth.vcf", t, fa, fn);
     }
+    if (n_strata)
+        fprintf(stderr, "[vcfdist_amd] stratified: %d strata, %lld of %lld hap-variants in none of them\n", n_strata, (long long)strat_none,
+                (long long)strat_vars);
     printf("PRECISION-RECALL SUMMARY\n\n");
     printf("TYPE\tTHRESHOLD\tTRUTH_TP\tQUERY_TP\tTRUTH_FN\tQUERY_FP\tPREC\t\tRECALL\t\tF1_SCORE\tF1_QSCORE\n");
     static const char *NAMES[] = {"SNP", "INDEL", "SV", "ALL"};
@@ -563,5 +643,6 @@ int main(int argc, char **argv) {
     release_realigned();
     vio_callset_free(q); vio_callset_free(t); vio_fasta_free(fa);
     if (bed) vio_bed_free(bed);
+    for (vio_bed *b : strata.beds) vio_bed_free(b);
     return 0;
 }

@@ -128,45 +128,35 @@ extern "C" {
 int vpr_rccl_available(void) { return Rccl::get().all_reduce && Rccl::get().all_gather ? 1 : 0; }
 const char *vpr_rccl_library(void) { return Rccl::get().path.c_str(); }
 
-static int pr_counts_impl(vpr_handle *h, void *comm, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase,
-                          int32_t min_qual, int32_t max_qual, int64_t *counts) {
-    if (!h || !counts || max_qual < min_qual) return VPR_ERR_ARG;
-    if (comm && !Rccl::get().all_reduce) return fail(h, VPR_ERR_STATE, "no RCCL in this process (librccl.so.1 not found)");
-    if (!h->executed) return fail(h, VPR_ERR_STATE, "vpr_pr_counts before vpr_execute");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int nq = max_qual - min_qual + 1;
-    const size_t nh = size_t(2) * 3 * 3 * size_t(nq + 1);
+}   // extern "C"
+
+// ---- what the stratified counters (pr_strata.hip) share with vpr_pr_counts
+bool rccl_has_allreduce() { return Rccl::get().all_reduce != nullptr; }
+
+// the one collective of the path: histogram words summed over the ranks, in place on the device
+int rccl_allreduce_u64(vpr_handle *h, unsigned long long *d_buf, size_t n, void *comm) {
+    const int e = Rccl::get().all_reduce(d_buf, d_buf, n, RCCL_UINT64, RCCL_SUM, comm, h->stream);
+    if (e) return fail(h, VPR_ERR_DEVICE, "ncclAllReduce failed: %s", Rccl::get().err_str ? Rccl::get().err_str(e) : "?");
+    return VPR_OK;
+}
+
+// the caller's phase-block phasing and variant classes on the device (*d_pb stays null without pb_phase)
+int pr_counts_inputs(vpr_handle *h, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase, int32_t **d_pb) {
     int rc;
-    if (nh > h->hist_cap) {
-        if ((rc = dev_alloc(h, &h->d_hist, nh))) return rc;
-        h->hist_cap = nh;
-    }
-    unsigned long long *d_hist = h->d_hist;
-    int32_t *d_pb = nullptr;
-    HIPCHK(h, hipMemsetAsync(d_hist, 0, nh * 8, h->stream));
+    *d_pb = nullptr;
     if (pb_phase && h->n_sc) {
         if (!h->d_pb && (rc = dev_alloc(h, &h->d_pb, size_t(h->n_sc)))) return rc;
-        d_pb = h->d_pb;
-        HIPCHK(h, hipMemcpyAsync(d_pb, pb_phase, size_t(h->n_sc) * 4, hipMemcpyHostToDevice, h->stream));
+        *d_pb = h->d_pb;
+        HIPCHK(h, hipMemcpyAsync(*d_pb, pb_phase, size_t(h->n_sc) * 4, hipMemcpyHostToDevice, h->stream));
     }
-    if (var_class) { int rc = vpr_upload_var_class(h, var_class); if (rc) return rc; }
-    for (int s = 0; s < VPR_HAPS; s++) {
-        const int64_t nv = h->n_var[s];
-        if (!nv) continue;
-        if (!h->d_cls[s]) return fail(h, VPR_ERR_STATE, "vpr_pr_counts: no variant classes (pass var_class or call vpr_upload_var_class)");
-        hipLaunchKernelGGL(k_pr_hist, dim3(unsigned((nv + 255) / 256)), dim3(256), size_t(9) * (nq + 1) * 4, h->stream,
-                           h->dB.var_off[s], h->n_sc, nv, h->d_cls[s], h->dR.sc_phase, d_pb, h->dR.v[s][0], h->dR.v[s][1],
-                           s >> 1, min_qual, max_qual, d_hist);
-    }
-    if (comm) {     // the one collective of the path: the histogram words summed over the ranks, in place on the device
-        const int e = Rccl::get().all_reduce(d_hist, d_hist, nh, RCCL_UINT64, RCCL_SUM, comm, h->stream);
-        if (e) return fail(h, VPR_ERR_DEVICE, "ncclAllReduce failed: %s", Rccl::get().err_str ? Rccl::get().err_str(e) : "?");
-    }
-    std::vector<unsigned long long> hist(nh);
-    HIPCHK(h, hipMemcpyAsync(hist.data(), d_hist, nh * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, x_sync(h, h->stream, SITE));
-    // counts at threshold k: variants whose last threshold index is >= k (print.cpp:378-381, 425-428); a truth variant
-    // additionally counts as FN at every threshold above its own (print.cpp:429-432)
+    if (var_class && (rc = vpr_upload_var_class(h, var_class))) return rc;
+    return VPR_OK;
+}
+
+// histogram [2][3 classes][3][nq + 1] -> counts [2][VPR_VARTYPES][3][nq].  Counts at threshold k: variants whose last
+// threshold index is >= k (print.cpp:378-381, 425-428); a truth variant additionally counts as FN at every threshold above
+// its own (print.cpp:429-432)
+void pr_fold_counts(const unsigned long long *hist, int nq, int64_t *counts) {
     std::fill(counts, counts + size_t(2) * VPR_VARTYPES * 3 * size_t(nq), 0);
     auto C = [&](int cs, int t, int e, int k) -> int64_t & { return counts[((size_t(cs) * VPR_VARTYPES + t) * 3 + e) * nq + k]; };
     for (int cs = 0; cs < 2; cs++)
@@ -189,6 +179,40 @@ static int pr_counts_impl(vpr_handle *h, void *comm, const uint8_t *const var_cl
                 }
             }
         }
+}
+
+extern "C" {
+
+static int pr_counts_impl(vpr_handle *h, void *comm, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase,
+                          int32_t min_qual, int32_t max_qual, int64_t *counts) {
+    if (!h || !counts || max_qual < min_qual) return VPR_ERR_ARG;
+    if (comm && !rccl_has_allreduce()) return fail(h, VPR_ERR_STATE, "no RCCL in this process (librccl.so.1 not found)");
+    if (!h->executed) return fail(h, VPR_ERR_STATE, "vpr_pr_counts before vpr_execute");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int nq = max_qual - min_qual + 1;
+    const size_t nh = size_t(2) * 3 * 3 * size_t(nq + 1);
+    int rc;
+    if (nh > h->hist_cap) {
+        if ((rc = dev_alloc(h, &h->d_hist, nh))) return rc;
+        h->hist_cap = nh;
+    }
+    unsigned long long *d_hist = h->d_hist;
+    int32_t *d_pb = nullptr;
+    HIPCHK(h, hipMemsetAsync(d_hist, 0, nh * 8, h->stream));
+    if ((rc = pr_counts_inputs(h, var_class, pb_phase, &d_pb))) return rc;
+    for (int s = 0; s < VPR_HAPS; s++) {
+        const int64_t nv = h->n_var[s];
+        if (!nv) continue;
+        if (!h->d_cls[s]) return fail(h, VPR_ERR_STATE, "vpr_pr_counts: no variant classes (pass var_class or call vpr_upload_var_class)");
+        hipLaunchKernelGGL(k_pr_hist, dim3(unsigned((nv + 255) / 256)), dim3(256), size_t(9) * (nq + 1) * 4, h->stream,
+                           h->dB.var_off[s], h->n_sc, nv, h->d_cls[s], h->dR.sc_phase, d_pb, h->dR.v[s][0], h->dR.v[s][1],
+                           s >> 1, min_qual, max_qual, d_hist);
+    }
+    if (comm && (rc = rccl_allreduce_u64(h, d_hist, nh, comm))) return rc;
+    std::vector<unsigned long long> hist(nh);
+    HIPCHK(h, hipMemcpyAsync(hist.data(), d_hist, nh * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, x_sync(h, h->stream, SITE));
+    pr_fold_counts(hist.data(), nq, counts);
     return VPR_OK;
 }
 

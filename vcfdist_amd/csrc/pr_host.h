@@ -4,6 +4,7 @@
 //   pr_mem.hip      allocator wrappers, the process-wide books of device memory, block caches (dev_alloc, pin_alloc, exec_alloc)
 //   pr_results.hip  vpr_download, vpr_results_alloc, tallies, timing and launch statistics
 //   pr_collect.hip  the counters histogram, vpr_pr_counts, and the RCCL collectives (vpr_allreduce_counts, vpr_allgather_phase)
+//   pr_strata.hip   the region-stratified counters (include/vcfdist_strata.h): membership words, the stratified histogram
 #ifndef PR_HOST_H_
 #define PR_HOST_H_
 #include <hip/hip_runtime.h>
@@ -261,6 +262,7 @@ const int TIE_DEC_SLOTS = 64;     // early-replay launches per execute that can 
 using namespace vprh;
 
 struct DistState;                        // the distance step's tables and arena (pr_dist.hip)
+struct StrataState;                      // the membership words and the stratified histogram (pr_strata.hip)
 
 struct vpr_handle {
     vpr_config cfg;
@@ -408,6 +410,7 @@ struct vpr_handle {
     int lane_prio_rows = 256;            // waves of the lane levels with at least this many rows issue ahead of the others (k_zero_lane; a quarter for k_one_lane)
     DevResults dR;                       // final results, produced on the device
     DistState *dist = nullptr;           // vpr_distance (pr_dist.hip), created by its first call
+    StrataState *strata = nullptr;       // vpr_strata_masks / vpr_strata_upload_masks (pr_strata.hip), released with the batch
     vpr_timing timing;
     bool uploaded = false, executed = false;
 };
@@ -445,6 +448,12 @@ int exec_pin(vpr_handle *h, void **out, size_t bytes);
 void free_batch(vpr_handle *h);
 void dist_free(vpr_handle *h);                                       // pr_dist.hip: all of the distance step's device memory
 void dist_release_work(vpr_handle *h);                               // pr_dist.hip: all but what vpr_distance_download reads
+void strata_free(vpr_handle *h);                                     // pr_strata.hip: the membership words and the stratified histogram
+// pr_collect.hip, shared with pr_strata.hip: the inputs of a counters call, the host fold of one histogram, the all-reduce
+int pr_counts_inputs(vpr_handle *h, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase, int32_t **d_pb);
+void pr_fold_counts(const unsigned long long *hist, int nq, int64_t *counts);
+bool rccl_has_allreduce();
+int rccl_allreduce_u64(vpr_handle *h, unsigned long long *d_buf, size_t n, void *comm);
 template <typename T>
 int dev_alloc(vpr_handle *h, T **p, size_t n) {
     void *q = nullptr;

@@ -87,15 +87,11 @@ extern "C" int32_t vrp_phase_blocks(const int32_t *sc_phase_set, int32_t n_sc, i
     return n_pb;
 }
 
-extern "C" int vrp_write_precision_recall(const char *prefix, const int64_t *counts, int32_t min_qual, int32_t max_qual) {
-    if (!prefix || !counts || max_qual < min_qual) return fail(VRP_ERR_ARG, "vrp_write_precision_recall: bad argument");
+namespace {
+// the rows of precision-recall.tsv (all) and precision-recall-summary.tsv (sum) for one set of counters, every line behind
+// `lead` ("" for the unstratified files, "<stratum>\t" for the stratified ones)
+void pr_rows(FILE *all, FILE *sum, const char *lead, const int64_t *counts, int min_qual, int max_qual) {
     const int nq = max_qual - min_qual + 1;
-    const std::string fn_all = std::string(prefix) + "precision-recall.tsv", fn_sum = std::string(prefix) + "precision-recall-summary.tsv";
-    File all(fn_all.c_str());
-    if (!all) return fail(VRP_ERR_OPEN, "cannot create " + fn_all);
-    File sum(fn_sum.c_str());
-    if (!sum) return fail(VRP_ERR_OPEN, "cannot create " + fn_sum);
-    fprintf(all, "VAR_TYPE\tMIN_QUAL\tPREC\tRECALL\tF1_SCORE\tF1_QSCORE\tTRUTH_TOTAL\tTRUTH_TP\tTRUTH_FN\tQUERY_TOTAL\tQUERY_TP\tQUERY_FP\n");
     int best_qual[VPR_VARTYPES];
     for (int type = 0; type < VPR_VARTYPES; type++) {
         float best = 0;
@@ -103,22 +99,55 @@ extern "C" int vrp_write_precision_recall(const char *prefix, const int64_t *cou
         for (int qual = min_qual; qual <= max_qual; qual++) {
             const Metrics m = metrics(counts, nq, type, qual - min_qual);
             if (m.f1 > best) { best = m.f1; best_qual[type] = qual; }   // first maximum wins (print.cpp:470)
-            fprintf(all, "%s\t%d\t%f\t%f\t%f\t%f\t%d\t%d\t%d\t%d\t%d\t%d\n", VARTYPE_STR[type], qual, m.precision, m.recall,
+            fprintf(all, "%s%s\t%d\t%f\t%f\t%f\t%f\t%d\t%d\t%d\t%d\t%d\t%d\n", lead, VARTYPE_STR[type], qual, m.precision, m.recall,
                     m.f1, m.f1_q, m.truth_tp + m.truth_fn, m.truth_tp, m.truth_fn, m.query_tp + m.query_fp, m.query_tp, m.query_fp);
         }
         // (an all-zero F1 column leaves quality 0 in the reference, which it then indexes; keep the index in range)
         if (best_qual[type] < min_qual || best_qual[type] > max_qual) best_qual[type] = min_qual;
     }
-    fprintf(sum, "VAR_TYPE\tTHRESHOLD\tMIN_QUAL\tTRUTH_TP\tQUERY_TP\tTRUTH_FN\tQUERY_FP\tPREC\tRECALL\tF1_SCORE\tF1_QSCORE\n");
     for (int type = 0; type < VPR_VARTYPES; type++) {
         const int quals[2] = {min_qual, best_qual[type]};
         const char *const thresh[2] = {"NONE", "BEST"};
         for (int i = 0; i < 2; i++) {
             const Metrics m = metrics(counts, nq, type, quals[i] - min_qual);
-            fprintf(sum, "%s\t%s\t%d\t%d\t%d\t%d\t%d\t%f\t%f\t%f\t%f\n", VARTYPE_STR[type], thresh[i], quals[i], m.truth_tp,
+            fprintf(sum, "%s%s\t%s\t%d\t%d\t%d\t%d\t%d\t%f\t%f\t%f\t%f\n", lead, VARTYPE_STR[type], thresh[i], quals[i], m.truth_tp,
                     m.query_tp, m.truth_fn, m.query_fp, m.precision, m.recall, m.f1, m.f1_q);
         }
     }
+}
+const char *const PR_ALL_HEADER = "VAR_TYPE\tMIN_QUAL\tPREC\tRECALL\tF1_SCORE\tF1_QSCORE\tTRUTH_TOTAL\tTRUTH_TP\tTRUTH_FN\tQUERY_TOTAL\tQUERY_TP\tQUERY_FP\n";
+const char *const PR_SUM_HEADER = "VAR_TYPE\tTHRESHOLD\tMIN_QUAL\tTRUTH_TP\tQUERY_TP\tTRUTH_FN\tQUERY_FP\tPREC\tRECALL\tF1_SCORE\tF1_QSCORE\n";
+}  // namespace
+
+extern "C" int vrp_write_precision_recall(const char *prefix, const int64_t *counts, int32_t min_qual, int32_t max_qual) {
+    if (!prefix || !counts || max_qual < min_qual) return fail(VRP_ERR_ARG, "vrp_write_precision_recall: bad argument");
+    const std::string fn_all = std::string(prefix) + "precision-recall.tsv", fn_sum = std::string(prefix) + "precision-recall-summary.tsv";
+    File all(fn_all.c_str());
+    if (!all) return fail(VRP_ERR_OPEN, "cannot create " + fn_all);
+    File sum(fn_sum.c_str());
+    if (!sum) return fail(VRP_ERR_OPEN, "cannot create " + fn_sum);
+    fputs(PR_ALL_HEADER, all);
+    fputs(PR_SUM_HEADER, sum);
+    pr_rows(all, sum, "", counts, min_qual, max_qual);
+    if (!all.finish() || !sum.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn_all + " / " + fn_sum);
+    return VRP_OK;
+}
+
+extern "C" int vrp_write_stratified(const char *prefix, const char *const *names, int32_t n_strata, const int64_t *counts,
+                                    int32_t min_qual, int32_t max_qual) {
+    if (!prefix || !names || n_strata < 0 || (n_strata && !counts) || max_qual < min_qual) return fail(VRP_ERR_ARG, "vrp_write_stratified: bad argument");
+    for (int32_t k = 0; k < n_strata; k++) if (!names[k]) return fail(VRP_ERR_ARG, "vrp_write_stratified: null stratum name");
+    const size_t nc1 = size_t(2) * VPR_VARTYPES * 3 * size_t(max_qual - min_qual + 1);
+    const std::string fn_all = std::string(prefix) + "stratified-precision-recall.tsv",
+                      fn_sum = std::string(prefix) + "stratified-precision-recall-summary.tsv";
+    File all(fn_all.c_str());
+    if (!all) return fail(VRP_ERR_OPEN, "cannot create " + fn_all);
+    File sum(fn_sum.c_str());
+    if (!sum) return fail(VRP_ERR_OPEN, "cannot create " + fn_sum);
+    fprintf(all, "STRATUM\t%s", PR_ALL_HEADER);
+    fprintf(sum, "STRATUM\t%s", PR_SUM_HEADER);
+    for (int32_t k = 0; k < n_strata; k++)
+        pr_rows(all, sum, (std::string(names[k]) + "\t").c_str(), counts + size_t(k) * nc1, min_qual, max_qual);
     if (!all.finish() || !sum.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn_all + " / " + fn_sum);
     return VRP_OK;
 }

@@ -161,6 +161,23 @@ int vio_bed_contains(const vio_bed *bed, const char *contig, int32_t start, int3
     return VIO_BED_BORDER;
 }
 
+int vio_bed_contains_many(const vio_bed *bed, const char *contig, int64_t n, const int32_t *pos, const int32_t *ref_len,
+                          const uint8_t *type, uint8_t *loc) {
+    if (!contig || n < 0 || (n && (!pos || !ref_len || !type || !loc))) return VIO_ERR_ARG;
+    for (int64_t i = 0; i < n; i++) loc[i] = uint8_t(vio_bed_contains(bed, contig, pos[i], pos[i] + ref_len[i], type[i]));
+    return VIO_OK;
+}
+
+int vio_bed_intervals(const vio_bed *bed, const char *contig, int64_t *n, const int32_t **starts, const int32_t **stops) {
+    if (!bed || !contig || !n || !starts || !stops) return VIO_ERR_ARG;
+    *n = 0; *starts = nullptr; *stops = nullptr;
+    const auto it = bed->regions.find(contig);
+    if (it == bed->regions.end()) return VIO_OK;
+    *n = int64_t(it->second.first.size());
+    *starts = it->second.first.data(); *stops = it->second.second.data();
+    return VIO_OK;
+}
+
 int vio_read_vcf(const char *path, const vio_bed *bed, const vio_params *prm, const char *const *filters,
                  int32_t n_filters, vio_callset **out) {
     if (!path || !prm || !out) return VIO_ERR_ARG;

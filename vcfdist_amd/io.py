@@ -33,7 +33,7 @@ class VioFasta(C.Structure):
     _fields_ = [("n_ctg", C.c_int32), ("ctg_name", C.POINTER(C.c_char_p)), ("ctg_off", A.P_i64), ("seq", A.P_u8)]
 
 
-EXPORTED = ["vio_read_bed", "vio_bed_free", "vio_bed_contains", "vio_read_vcf", "vio_callset_free", "vio_read_fasta",
+EXPORTED = ["vio_read_bed", "vio_bed_free", "vio_bed_contains", "vio_bed_contains_many", "vio_bed_intervals", "vio_read_vcf", "vio_callset_free", "vio_read_fasta",
             "vio_fasta_free", "vio_last_error"]
 
 
@@ -65,6 +65,27 @@ class Bed:
         L.vio_bed_contains.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32]
         return L.vio_bed_contains(self._h, ctg.encode(), start, stop, typ)
 
+    def contains_many(self, ctg, pos, ref_len, typ):
+        """contains(ctg, pos[i], pos[i] + ref_len[i], typ[i]) of many variants of one contig in one host loop -> uint8 VIO_BED_*"""
+        L = api.lib()
+        pos, ref_len, typ = A._arr(pos, np.int32), A._arr(ref_len, np.int32), A._arr(typ, np.uint8)
+        out = np.zeros(len(pos), np.uint8)
+        L.vio_bed_contains_many.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, A.P_i32, A.P_i32, A.P_u8, A.P_u8]
+        if len(pos) and L.vio_bed_contains_many(self._h, ctg.encode(), len(pos), A._ptr(pos, C.c_int32), A._ptr(ref_len, C.c_int32),
+                                                A._ptr(typ, C.c_uint8), A._ptr(out, C.c_uint8)):
+            raise IOError("vio_bed_contains_many failed")
+        return out
+
+    def intervals(self, ctg):
+        """(starts, stops) of one contig as the reader checked them: sorted, non-overlapping, non-empty (int32 copies)"""
+        L = api.lib()
+        L.vio_bed_intervals.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(A.P_i32), C.POINTER(A.P_i32)]
+        n, st, sp = C.c_int64(), A.P_i32(), A.P_i32()
+        rc = L.vio_bed_intervals(self._h, ctg.encode(), C.byref(n), C.byref(st), C.byref(sp))
+        if rc:
+            raise IOError(f"vio_bed_intervals failed ({rc})")
+        return A._from_ptr(st, n.value, np.int32).copy(), A._from_ptr(sp, n.value, np.int32).copy()
+
     def __del__(self):
         try:
             L = api.lib()
@@ -74,6 +95,42 @@ class Bed:
                 self._h = None
         except Exception:
             pass
+
+
+def read_strata(path):
+    """A strata list in the GIAB format: one name<TAB>path of a BED per line, blank and '#' lines skipped, a relative path
+    taken from the list's own directory.  -> (names, [Bed]) in list order.  A malformed line, a duplicate name, a missing or
+    malformed BED, or one with unsorted, overlapping or empty regions raises IOError."""
+    import os
+    names, beds = [], []
+    base = os.path.dirname(os.path.abspath(path))
+    try:
+        fh = open(path)
+    except OSError as e:
+        raise IOError(f"cannot open the strata list '{path}': {e.strerror}")
+    with fh:
+        for ln, line in enumerate(fh, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip() or line.startswith("#"):
+                continue
+            f = line.split("\t")
+            if len(f) < 2 or not f[0] or not f[1]:
+                raise IOError(f"strata list '{path}' line {ln}: expected name<TAB>path")
+            if f[0] in names:
+                raise IOError(f"strata list '{path}' line {ln}: duplicate stratum name '{f[0]}'")
+            try:
+                beds.append(Bed(f[1] if os.path.isabs(f[1]) else os.path.join(base, f[1])))
+            except IOError as e:
+                raise IOError(f"stratum '{f[0]}': {e}")
+            names.append(f[0])
+    if not names:
+        raise IOError(f"strata list '{path}' names no stratum")
+    return names, beds
+
+
+def contig_strata(beds, contigs):
+    """the A.Strata of `beds` (read_strata) for the contig names `contigs`, in that numbering"""
+    return A.Strata([[b.intervals(c) for c in contigs] for b in beds], len(contigs))
 
 
 def read_vcf(path, bed=None, min_qual=0, max_qual=60, max_size=5000, cluster_min_gap=50, filters=()):

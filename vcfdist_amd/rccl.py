@@ -146,6 +146,11 @@ def allreduce_counts(pr, comm: Comm, var_class_per_slot=None, pb_phase=None, min
     return out
 
 
+def allreduce_counts_strata(pr, comm: Comm, var_class_per_slot=None, pb_phase=None, min_qual=0, max_qual=60):
+    """summary.pr_counts_strata summed over the ranks of `comm`: one all-reduce of the whole stratified device histogram"""
+    return summary.pr_counts_strata(pr, var_class_per_slot, pb_phase, min_qual, max_qual, comm=comm._c)
+
+
 def allgather_phase(pr, comm: Comm, idx_local, n_total: int):
     """(sc_phase, orig_phase_dist, swap_phase_dist) of all n_total superclusters on every rank; idx_local[k] = global index of
     this rank's k-th supercluster"""

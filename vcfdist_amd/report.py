@@ -25,7 +25,7 @@ class VrpContig(C.Structure):
                 ("n_flips", C.c_int32), ("switches", A.P_i32), ("flips", A.P_i32)]
 
 
-EXPORTED = ["vrp_phase_blocks", "vrp_write_precision_recall", "vrp_write_phase_blocks", "vrp_write_superclusters",
+EXPORTED = ["vrp_phase_blocks", "vrp_write_precision_recall", "vrp_write_stratified", "vrp_write_phase_blocks", "vrp_write_superclusters",
             "vrp_write_switchflips", "vrp_write_phasing_summary", "vrp_ng50",
             "vrp_write_variants", "vrp_write_summary_vcf", "vrp_write_distance", "vrp_write_edits", "vrp_write_vcf", "vrp_last_error"]
 
@@ -126,6 +126,17 @@ def write_precision_recall(prefix, counts, min_qual, max_qual):
     L = api.lib()
     L.vrp_write_precision_recall.argtypes = [C.c_char_p, A.P_i64, C.c_int32, C.c_int32]
     _check(L.vrp_write_precision_recall(prefix.encode(), A._ptr(cnt, C.c_int64), min_qual, max_qual), "vrp_write_precision_recall")
+
+
+def write_stratified(prefix, names, counts, min_qual, max_qual):
+    """stratified-precision-recall.tsv / -summary.tsv: counts int64 [n_strata][2][4][3][nq] (summary.pr_counts_strata)"""
+    cnt = np.ascontiguousarray(counts, np.int64)
+    if cnt.shape[0] != len(names):
+        raise ReportError(f"{len(names)} stratum names for counts of {cnt.shape[0]} strata")
+    L = api.lib()
+    arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+    L.vrp_write_stratified.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, A.P_i64, C.c_int32, C.c_int32]
+    _check(L.vrp_write_stratified(prefix.encode(), arr, len(names), A._ptr(cnt, C.c_int64), min_qual, max_qual), "vrp_write_stratified")
 
 
 def write_results(prefix, contigs, cmd="", file_date=None, credit_threshold=0.7):

@@ -74,6 +74,26 @@ def pr_counts(pr, var_class_per_slot, pb_phase=None, min_qual=0, max_qual=60):
     return out
 
 
+def pr_counts_strata(pr, var_class_per_slot, pb_phase=None, min_qual=0, max_qual=60, comm=None):
+    """pr_counts cut by region: the counters of the last execute repeated into every stratum of the handle's resident
+    membership words (pr.strata_masks / pr.upload_strata_masks) -> int64 [n_strata][2][4][3][nq].  comm: an ncclComm_t (as an
+    integer) for vpr_allreduce_counts_strata."""
+    L = api.lib()
+    st = getattr(pr, "_strata", None)
+    nq = max_qual - min_qual + 1
+    out = np.zeros((st[0] if st else 1, 2, VARTYPES, 3, nq), np.int64)
+    pb = None if pb_phase is None else np.ascontiguousarray(pb_phase, dtype=np.int32)
+    arr = None
+    if var_class_per_slot is not None:      # None: classes already resident (upload_var_class, an earlier pr_counts)
+        cls = [np.ascontiguousarray(c, dtype=np.uint8) for c in var_class_per_slot]
+        arr = (A.P_u8 * 4)(*[A._ptr(c, C.c_uint8) for c in cls])
+    args = (arr, None if pb is None else A._ptr(pb, C.c_int32), min_qual, max_qual, A._ptr(out, C.c_int64))
+    rc = L.vpr_pr_counts_strata(pr._h, *args) if comm is None else L.vpr_allreduce_counts_strata(pr._h, comm if isinstance(comm, C.c_void_p) else C.c_void_p(comm), *args)
+    if rc:
+        raise api.VprError(f"vpr_pr_counts_strata failed ({rc}): {L.vpr_last_error(pr._h).decode()}")
+    return out
+
+
 def upload_var_class(pr, var_class_per_slot):
     L = api.lib()
     cls = [np.ascontiguousarray(c, dtype=np.uint8) for c in var_class_per_slot]
