@@ -10,7 +10,11 @@ the ALIGNMENT DISTANCE SUMMARY (printed even with -n); one rank only.  With -rq 
 GPU before the evaluation (include/vcfdist_realign.h): orig-query.vcf / orig-truth.vcf as read, query.vcf / truth.vcf realigned;
 -ro stops after the realignment; one rank only.  With --stratify FILE (the GIAB list format: one name<TAB>path of a BED per line) the
 counters of the one evaluation are also cut by region on the GPU (include/vcfdist_strata.h): stratified-precision-recall.tsv and
-stratified-precision-recall-summary.tsv; works under several ranks in both --shard modes."""
+stratified-precision-recall-summary.tsv; works under several ranks in both --shard modes.  With --bootstrap N the counters are
+resampled N times on the GPU (include/vcfdist_bootstrap.h: a Poisson bootstrap over superclusters, conditional on the phasing, the
+BEST threshold kept at the point estimate's): bootstrap-precision-recall-summary.tsv with 95 % percentile intervals for precision,
+recall and F1, bootstrap-replicates.tsv, and with --stratify stratified-bootstrap-precision-recall-summary.tsv; --bootstrap-seed S
+(default 1); works under several ranks in both --shard modes."""
 import argparse
 import sys
 
@@ -136,7 +140,19 @@ def stratify_contig(pr, prep, strat, args, pb, part_idx=None):
         strat["none"] += int((np.bitwise_or.reduce(w, axis=0) == 0).sum())
 
 
-def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None):
+def bootstrap_contig(pr, boot, strat, args, pb, keys):
+    """--bootstrap: the replicate counters of the executed batch, added to boot['counts']; with --stratify one pass per stratum
+    of the resident membership words, added to boot['strat']"""
+    kw = dict(n_rep=boot["n"], seed=boot["seed"], min_qual=args.min_qual, max_qual=args.max_qual)
+    boot["counts"] += pr.pr_counts_boot(None, pb, keys, **kw)        # (the classes are resident: pr_counts)
+    boot["ms"] += pr.boot_info()[1]
+    if strat is not None:
+        for k in range(len(strat["beds"])):
+            boot["strat"][k] += pr.pr_counts_boot(None, pb, keys, stratum=k, **kw)
+            boot["ms"] += pr.boot_info()[1]
+
+
+def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None, boot=None, ordinal=0):
     """the precision/recall path on the GPU, phasing and counters for a prepared contig.  -> int64 counters [2][4][3][nq],
     n_sc, and what the writers need: (clusters after splitting, superclusters, results, phase sets, pb_phase, switches, flips).
     part = (rank, world, collective device): this rank evaluates its share of the contig's SUPERCLUSTERS -- dealt by the
@@ -177,6 +193,8 @@ def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None)
         counts = S.pr_counts(pr, cls, pb, args.min_qual, args.max_qual)
         if strat is not None:
             stratify_contig(pr, prep, strat, args, pb)
+        if boot is not None:
+            bootstrap_contig(pr, boot, strat, args, pb, A.boot_keys(ordinal, np.arange(sc.n)))
     else:
         from . import shard
         rank, world, cdev = part
@@ -200,6 +218,8 @@ def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None)
             counts = S.pr_counts(pr, cls_mine, pb[idx], args.min_qual, args.max_qual)
             if strat is not None:
                 stratify_contig(pr, prep, strat, args, pb[idx], part_idx=idx)
+            if boot is not None:
+                bootstrap_contig(pr, boot, strat, args, pb[idx], A.boot_keys(ordinal, idx))
         else:
             counts = np.zeros((2, 4, 3, nq), np.int64)
         res = shard.gather_results(local, idx, whole.var_off, device=cdev)
@@ -301,6 +321,26 @@ def eval_penalty(what):
     return parse
 
 
+def bootstrap_replicates(v):
+    try:
+        n = int(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"Invalid number of bootstrap replicates '{v}'")
+    if not 1 <= n <= A.BOOT_MAX_REPLICATES:
+        raise argparse.ArgumentTypeError(f"Must provide 1 to {A.BOOT_MAX_REPLICATES} bootstrap replicates")
+    return n
+
+
+def bootstrap_seed(v):
+    try:
+        s = int(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"Invalid bootstrap seed '{v}'")
+    if not 0 <= s < 2 ** 64:
+        raise argparse.ArgumentTypeError("Must provide a bootstrap seed of 0 to 2^64 - 1")
+    return s
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m vcfdist_amd", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("query"); ap.add_argument("truth"); ap.add_argument("fasta")
@@ -336,6 +376,10 @@ def main(argv=None):
     ap.add_argument("--stratify", metavar="FILE",
                     help="strata list (one name<TAB>path of a BED per line, paths relative to the list): the counters of the one "
                          "evaluation are also cut by region (stratified-precision-recall.tsv, stratified-precision-recall-summary.tsv)")
+    ap.add_argument("--bootstrap", metavar="N", type=bootstrap_replicates, default=0,
+                    help="resample the counters N times (1 to 100000) over superclusters on the GPU: 95 %% percentile intervals for "
+                         "precision, recall and F1 (bootstrap-precision-recall-summary.tsv, bootstrap-replicates.tsv)")
+    ap.add_argument("--bootstrap-seed", metavar="S", type=bootstrap_seed, default=1, help="seed of the bootstrap weights (default 1)")
     ap.add_argument("--shard", default="superclusters", choices=["superclusters", "contigs"],
                     help="several ranks (torch.distributed.run, one per GPU): deal every contig's superclusters over the ranks "
                          "(default; balanced whatever the contigs' sizes) or whole contigs")
@@ -414,6 +458,10 @@ def main(argv=None):
     total = np.zeros((2, 4, 3, nq), np.int64)
     if strat is not None:
         strat["counts"] = np.zeros((len(strat["names"]), 2, 4, 3, nq), np.int64)
+    boot = None
+    if args.bootstrap:
+        boot = dict(n=args.bootstrap, seed=args.bootstrap_seed, ms=0.0, counts=np.zeros((args.bootstrap, 2, 4, 3, nq), np.int64),
+                    strat=None if strat is None else np.zeros((len(strat["names"]), args.bootstrap, 2, 4, 3, nq), np.int64))
     empty = dict(pos=np.zeros(0, np.int32), rlen=np.zeros(0, np.int32), type=np.zeros(0, np.uint8), var_qual=np.zeros(0, np.float32),
                  phase_set=np.zeros(0, np.int32), ref_len=np.zeros(0, np.int32), alt_len=np.zeros(0, np.int32),
                  ref_off=np.zeros(0, np.int64), alt_off=np.zeros(0, np.int64), pool=np.zeros(1, np.uint8))
@@ -445,7 +493,7 @@ def main(argv=None):
         ctg = contigs[k]
         try:
             counts, n_sc, tables = evaluate_contig(prepared.pop(k), args, device=device, part=(rank, world, cdev) if by_sc else None,
-                                                   dist_sets=dist_sets, strat=strat)
+                                                   dist_sets=dist_sets, strat=strat, boot=boot, ordinal=k)
         except api.VprError as e:     # the library's explicit refusals end the run like the reference's ERROR()
             raise SystemExit(f"ERROR: contig '{ctg}': {e}")
         total += counts
@@ -459,12 +507,23 @@ def main(argv=None):
             reports[k] = (ctg, length, ploidy, slots_of(ctg), tables)
     if dist is not None:
         # the one all-reduce: counts[2][4][3][nq] summed over the ranks, with --stratify the stratified ones behind them
+        # and with --bootstrap the replicate ones behind those
         tail = [] if strat is None else [strat["counts"].ravel(), np.asarray([strat["vars"], strat["none"]], np.int64)]
+        if boot is not None:
+            tail += [boot["counts"].ravel()] + ([] if strat is None else [boot["strat"].ravel()])
         summed = shard.allreduce_tally(np.concatenate([total.ravel()] + tail), device=cdev)
         total = summed[:total.size].reshape(total.shape)
+        at = total.size
         if strat is not None:
-            strat["counts"] = summed[total.size:-2].reshape(strat["counts"].shape)
-            strat["vars"], strat["none"] = int(summed[-2]), int(summed[-1])
+            strat["counts"] = summed[at:at + strat["counts"].size].reshape(strat["counts"].shape)
+            at += strat["counts"].size
+            strat["vars"], strat["none"] = int(summed[at]), int(summed[at + 1])
+            at += 2
+        if boot is not None:
+            boot["counts"] = summed[at:at + boot["counts"].size].reshape(boot["counts"].shape)
+            at += boot["counts"].size
+            if strat is not None:
+                boot["strat"] = summed[at:at + boot["strat"].size].reshape(boot["strat"].shape)
         if not by_sc:       # (by superclusters every rank already holds every contig's gathered tables)
             gathered = [None] * world
             dist.all_gather_object(gathered, reports)
@@ -482,6 +541,11 @@ def main(argv=None):
             RP.write_parameters(args.prefix, args, cmd)
             if strat is not None:
                 RP.write_stratified(args.prefix, strat["names"], strat["counts"], args.min_qual, args.max_qual)
+            if boot is not None:
+                RP.write_bootstrap(args.prefix, total, boot["counts"], boot["seed"], args.min_qual, args.max_qual)
+                if strat is not None:
+                    RP.write_bootstrap_stratified(args.prefix, strat["names"], strat["counts"], boot["strat"], boot["seed"], args.min_qual,
+                                                  args.max_qual)
             ctgs = [RP.Contig(c, ln, pl, fasta[c], sl, *tb) for c, ln, pl, sl, tb in (reports[k] for k in sorted(reports))]
             RP.write_results(args.prefix, ctgs, cmd=cmd, credit_threshold=args.credit_threshold)
             if args.realign_query:
@@ -491,6 +555,8 @@ def main(argv=None):
         if strat is not None:
             print(f"[vcfdist_amd] stratified: {len(strat['names'])} strata, {strat['none']} of {strat['vars']} hap-variants in none of them",
                   file=sys.stderr)
+        if boot is not None:
+            print(f"[vcfdist_amd] bootstrap: {boot['n']} replicates, seed {boot['seed']}, {boot['ms']:.3f} ms on the device", file=sys.stderr)
         print("PRECISION-RECALL SUMMARY\n")
         print("TYPE\tTHRESHOLD\tTRUTH_TP\tQUERY_TP\tTRUTH_FN\tQUERY_FP\tPREC\t\tRECALL\t\tF1_SCORE\tF1_QSCORE")
         for r in rows:

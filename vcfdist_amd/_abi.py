@@ -537,3 +537,15 @@ class VrlResult(C.Structure):
     _fields_ = [("n", C.c_int32), ("pos", P_i32), ("rlen", P_i32), ("type", P_u8), ("ref_len", P_i32), ("alt_len", P_i32),
                 ("ref_off", P_i64), ("alt_off", P_i64), ("pool", P_u8), ("pool_len", C.c_int64), ("var_qual", P_f32), ("gt_qual", P_f32),
                 ("phase_set", P_i32), ("orig_gt", P_u8), ("n_clusters", C.c_int32), ("cluster_status", P_u8), ("info", VrlInfo)]
+
+
+# ---- include/vcfdist_bootstrap.h
+BOOT_MAX_WEIGHT = 12
+BOOT_MAX_REPLICATES = 100000
+BOOT_T = (1580030168, 3160060337, 3950075421, 4213413783, 4279248373, 4292415291,
+          4294609777, 4294923276, 4294962463, 4294966817, 4294967252, 4294967292)      # VPR_BOOT_T: the Poisson(1) CDF x 2^32
+
+
+def boot_keys(contig_ordinal, sc_index):
+    """the command lines' supercluster keys: (ordinal of the contig in the run's contig list << 32) | index within the contig"""
+    return (np.uint64(contig_ordinal) << np.uint64(32)) | np.asarray(sc_index, np.uint64)

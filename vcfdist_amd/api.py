@@ -89,6 +89,10 @@ def lib():
     L.vpr_pr_counts_strata.argtypes = [H, C.c_void_p, A.P_i32, C.c_int32, C.c_int32, A.P_i64]
     L.vpr_allreduce_counts_strata.argtypes = [H, C.c_void_p, C.c_void_p, A.P_i32, C.c_int32, C.c_int32, A.P_i64]
     L.vpr_strata_timing.argtypes = [H, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    boot = [C.c_void_p, A.P_i32, C.c_int32, C.c_int32, P_u64, C.c_uint64, C.c_int32, C.c_int32, A.P_i64]
+    L.vpr_pr_counts_boot.argtypes = [H] + boot
+    L.vpr_allreduce_counts_boot.argtypes = [H, C.c_void_p] + boot
+    L.vpr_boot_info.argtypes = [H, C.POINTER(C.c_int32 * 3), C.POINTER(C.c_double)]
     from .cluster import VclHapSeq, VclClusters
     L.vrl_realign.argtypes = [C.POINTER(VclHapSeq), A.P_f32, A.P_f32, A.P_i32, A.P_u8, C.POINTER(VclClusters), A.P_u8, C.c_int32,
                               C.POINTER(A.VrlConfig), C.c_int32, C.POINTER(C.POINTER(A.VrlResult))]
@@ -110,6 +114,8 @@ DIST_EXPORTED = ["vpr_distance", "vpr_distance_info", "vpr_distance_download"]
 # include/vcfdist_strata.h
 STRATA_EXPORTED = ["vpr_strata_masks", "vpr_strata_download_masks", "vpr_strata_upload_masks", "vpr_pr_counts_strata",
                    "vpr_allreduce_counts_strata", "vpr_strata_timing"]
+# include/vcfdist_bootstrap.h
+BOOT_EXPORTED = ["vpr_pr_counts_boot", "vpr_allreduce_counts_boot", "vpr_boot_info", "vrp_write_bootstrap", "vrp_write_bootstrap_stratified"]
 # include/vcfdist_realign.h
 RL_EXPORTED = ["vrl_realign", "vrl_result_free"]
 
@@ -382,6 +388,19 @@ class PrecisionRecall:
         a, b = C.c_double(), C.c_double()
         self._chk(lib().vpr_strata_timing(self._h, C.byref(a), C.byref(b)), "vpr_strata_timing")
         return a.value, b.value
+
+    def pr_counts_boot(self, var_class_per_slot, pb_phase, sc_key, n_rep, seed=1, min_qual=0, max_qual=60, stratum=-1, comm=None):
+        """The bootstrap replicates of the counters of the last execute (include/vcfdist_bootstrap.h): replicate r counts every
+        variant w(seed, r, sc_key[its supercluster]) times -> int64 [n_rep][2][4][3][nq].  stratum >= 0: only the variants of
+        that stratum of the resident membership words; comm: an ncclComm_t (as an integer) for vpr_allreduce_counts_boot."""
+        from . import summary
+        return summary.pr_counts_boot(self, var_class_per_slot, pb_phase, sc_key, n_rep, seed, min_qual, max_qual, stratum, comm)
+
+    def boot_info(self):
+        """((spans, replicate groups, quality slices), device ms) of the last pr_counts_boot"""
+        g, ms = (C.c_int32 * 3)(), C.c_double()
+        self._chk(lib().vpr_boot_info(self._h, C.byref(g), C.byref(ms)), "vpr_boot_info")
+        return tuple(int(x) for x in g), ms.value
 
     def timing(self) -> A.VprTiming:
         t = A.VprTiming()

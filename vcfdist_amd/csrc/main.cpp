@@ -10,13 +10,18 @@
 //               [-l max variant size] [-s max supercluster size] [-mn / -mx qual] [-f filters] [-i iterations] [-x -o -e penalties]
 //               [-ct credit threshold] [-pt phasing threshold] [-sv threshold] [--reach-min-gap N] [--strict] [--device N]
 //               [-d] [-ex -eo -ee evaluation penalties] [-rq] [-rt] [-ro] [--stratify strata.tsv]
+//               [--bootstrap N] [--bootstrap-seed S]
 // With -d the distance metrics (edits_wrapper, dist.cpp:1908-2077) run on the GPU after each contig's precision/recall path
 // (include/vcfdist_distance.h), as the reference's main.cpp:223-238 runs them after precision_recall_threads_wrapper.
 // With -rq / -rt a callset is clustered and realigned on the GPU (include/vcfdist_realign.h) before the evaluation, in the order of
 // the reference's main.cpp:50-180 (orig-*.vcf, realign query, realign truth; -ro stops there and writes query.vcf / truth.vcf).
 // With --stratify FILE (the GIAB list format: one name<TAB>path of a BED per line) the counters of the one evaluation are also cut
 // by region on the GPU (include/vcfdist_strata.h): stratified-precision-recall.tsv and stratified-precision-recall-summary.tsv.
+// With --bootstrap N the counters are resampled N times on the GPU (include/vcfdist_bootstrap.h: a Poisson bootstrap over
+// superclusters, conditional on the phasing): bootstrap-precision-recall-summary.tsv with 95 % percentile intervals,
+// bootstrap-replicates.tsv, and with --stratify stratified-bootstrap-precision-recall-summary.tsv.
 #include <algorithm>
+#include <cerrno>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -28,6 +33,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/vcfdist_bootstrap.h"
 #include "../../include/vcfdist_cluster.h"
 #include "../../include/vcfdist_distance.h"
 #include "../../include/vcfdist_io.h"
@@ -47,6 +53,8 @@ struct Args {
     bool realign_query = false, realign_truth = false, realign_only = false;
     double credit_threshold = 0.7, phase_threshold = 0.6;
     bool no_output_files = false, strict = false;
+    int bootstrap = 0;                 // --bootstrap: replicates (0: none)
+    uint64_t bootstrap_seed = 1;
 };
 
 [[noreturn]] void die(const char *fmt, ...) {
@@ -63,6 +71,22 @@ int eval_penalty(const char *v, const char *what) {
     try { x = std::stoi(v); } catch (const std::exception &) { die("ERROR: Invalid %s provided", what); }
     if (x < 0) die("ERROR: Must provide non-negative %s", what);
     return x;
+}
+// --bootstrap N: 1 to VPR_BOOT_MAX_REPLICATES; --bootstrap-seed S: an unsigned 64-bit integer
+int bootstrap_replicates(const char *v) {
+    char *end = nullptr;
+    errno = 0;
+    const long long n = strtoll(v, &end, 10);
+    if (end == v || *end || errno) die("ERROR: Invalid number of bootstrap replicates '%s'", v);
+    if (n < 1 || n > VPR_BOOT_MAX_REPLICATES) die("ERROR: Must provide 1 to %d bootstrap replicates", VPR_BOOT_MAX_REPLICATES);
+    return int(n);
+}
+uint64_t bootstrap_seed(const char *v) {
+    char *end = nullptr;
+    errno = 0;
+    const unsigned long long s = strtoull(v, &end, 10);
+    if (end == v || *end || errno || v[0] == '-') die("ERROR: Invalid bootstrap seed '%s'", v);
+    return s;
 }
 void warn(const std::string &m) { fprintf(stderr, "[WARN  vcfdist] %s\n", m.c_str()); }
 
@@ -97,6 +121,8 @@ Args parse(int argc, char **argv) {
         else if (o == "--device") a.device = atoi(need(i));
         else if (o == "-d" || o == "--distance") a.distance = true;
         else if (o == "--stratify") a.stratify = need(i);
+        else if (o == "--bootstrap") a.bootstrap = bootstrap_replicates(need(i));
+        else if (o == "--bootstrap-seed") a.bootstrap_seed = bootstrap_seed(need(i));
         else if (o == "-rq" || o == "--realign-query") a.realign_query = true;
         else if (o == "-rt" || o == "--realign-truth") a.realign_truth = true;
         else if (o == "-ro" || o == "--realign-only") a.realign_only = true;
@@ -384,6 +410,9 @@ int main(int argc, char **argv) {
     std::vector<int64_t> total(size_t(2) * VPR_VARTYPES * 3 * size_t(nq), 0);
     std::vector<int64_t> strat_total(total.size() * size_t(n_strata), 0);      // --stratify: counts[n_strata][2][4][3][nq]
     int64_t strat_vars = 0, strat_none = 0;                                     // hap-variants seen / in no stratum
+    // --bootstrap: counts[n_rep][2][4][3][nq], with --stratify also [n_strata][n_rep][2][4][3][nq]; device ms of the launches
+    std::vector<int64_t> boot_total(total.size() * size_t(A.bootstrap), 0), boot_strat(boot_total.size() * size_t(n_strata), 0);
+    double boot_ms = 0;
     vpr_config cfg;
     memset(&cfg, 0, sizeof(cfg));
     cfg.device = A.device; cfg.max_qual = float(A.max_qual); cfg.credit_threshold = A.credit_threshold; cfg.phase_threshold = A.phase_threshold;
@@ -522,6 +551,22 @@ int main(int argc, char **argv) {
                     strat_vars += int64_t(nv);
                 }
             }
+            if (A.bootstrap) {     // the same evaluation, resampled over superclusters (after the masks: a pass per stratum cuts by them)
+                const size_t ordinal = size_t(&ctg - contigs.data());
+                std::vector<uint64_t> keys(static_cast<size_t>(n_sc), 0);
+                for (int k = 0; k < n_sc; k++) keys[size_t(k)] = (uint64_t(ordinal) << 32) | uint64_t(k);
+                std::vector<int64_t> rep(boot_total.size(), 0);
+                for (int k = -1; k < n_strata; k++) {
+                    int32_t grid[3];
+                    double ms = 0;
+                    if (vpr_pr_counts_boot(h, nullptr, C->pb.data(), A.min_qual, A.max_qual, keys.data(), A.bootstrap_seed, A.bootstrap, k, rep.data()) ||
+                        vpr_boot_info(h, grid, &ms))
+                        die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+                    int64_t *into = k < 0 ? boot_total.data() : boot_strat.data() + size_t(k) * rep.size();
+                    for (size_t j = 0; j < rep.size(); j++) into[j] += rep[j];
+                    boot_ms += ms;
+                }
+            }
             // the reference's WARN lines (dist.cpp:1203-1223) and -- loudly -- what this implementation did not evaluate
             static const struct { uint32_t bit; const char *text; } W[] = {
                 {VPR_ST_WARN_REF_ED, "Nonzero reference edit distance with no truth variants at ctg %s supercluster %d"},
@@ -585,7 +630,12 @@ int main(int argc, char **argv) {
             std::vector<const char *> names;
             for (const auto &n : strata.names) names.push_back(n.c_str());
             if (vrp_write_stratified(A.prefix.c_str(), names.data(), n_strata, strat_total.data(), A.min_qual, A.max_qual)) die("ERROR: %s", vrp_last_error());
+            if (A.bootstrap && vrp_write_bootstrap_stratified(A.prefix.c_str(), names.data(), n_strata, strat_total.data(), boot_strat.data(), A.bootstrap,
+                                                              A.bootstrap_seed, A.min_qual, A.max_qual))
+                die("ERROR: %s", vrp_last_error());
         }
+        if (A.bootstrap && vrp_write_bootstrap(A.prefix.c_str(), total.data(), boot_total.data(), A.bootstrap, A.bootstrap_seed, A.min_qual, A.max_qual))
+            die("ERROR: %s", vrp_last_error());
         std::vector<vrp_contig> ctgs(outs.size());
         for (size_t k = 0; k < outs.size(); k++) {
             ContigOut *C = outs[k];
@@ -626,6 +676,8 @@ int main(int argc, char **argv) {
     if (n_strata)
         fprintf(stderr, "[vcfdist_amd] stratified: %d strata, %lld of %lld hap-variants in none of them\n", n_strata, (long long)strat_none,
                 (long long)strat_vars);
+    if (A.bootstrap)
+        fprintf(stderr, "[vcfdist_amd] bootstrap: %d replicates, seed %llu, %.3f ms on the device\n", A.bootstrap, (unsigned long long)A.bootstrap_seed, boot_ms);
     printf("PRECISION-RECALL SUMMARY\n\n");
     printf("TYPE\tTHRESHOLD\tTRUTH_TP\tQUERY_TP\tTRUTH_FN\tQUERY_FP\tPREC\t\tRECALL\t\tF1_SCORE\tF1_QSCORE\n");
     static const char *NAMES[] = {"SNP", "INDEL", "SV", "ALL"};

@@ -5,6 +5,7 @@
 //   pr_results.hip  vpr_download, vpr_results_alloc, tallies, timing and launch statistics
 //   pr_collect.hip  the counters histogram, vpr_pr_counts, and the RCCL collectives (vpr_allreduce_counts, vpr_allgather_phase)
 //   pr_strata.hip   the region-stratified counters (include/vcfdist_strata.h): membership words, the stratified histogram
+//   pr_boot.hip     the bootstrap replicates of the counters (include/vcfdist_bootstrap.h): the replicate histogram
 #ifndef PR_HOST_H_
 #define PR_HOST_H_
 #include <hip/hip_runtime.h>
@@ -263,6 +264,7 @@ using namespace vprh;
 
 struct DistState;                        // the distance step's tables and arena (pr_dist.hip)
 struct StrataState;                      // the membership words and the stratified histogram (pr_strata.hip)
+struct BootState;                        // the replicate histogram and the supercluster keys (pr_boot.hip)
 
 struct vpr_handle {
     vpr_config cfg;
@@ -411,6 +413,7 @@ struct vpr_handle {
     DevResults dR;                       // final results, produced on the device
     DistState *dist = nullptr;           // vpr_distance (pr_dist.hip), created by its first call
     StrataState *strata = nullptr;       // vpr_strata_masks / vpr_strata_upload_masks (pr_strata.hip), released with the batch
+    BootState *boot = nullptr;           // vpr_pr_counts_boot (pr_boot.hip), created by its first call, released with the batch
     vpr_timing timing;
     bool uploaded = false, executed = false;
 };
@@ -449,6 +452,9 @@ void free_batch(vpr_handle *h);
 void dist_free(vpr_handle *h);                                       // pr_dist.hip: all of the distance step's device memory
 void dist_release_work(vpr_handle *h);                               // pr_dist.hip: all but what vpr_distance_download reads
 void strata_free(vpr_handle *h);                                     // pr_strata.hip: the membership words and the stratified histogram
+// pr_strata.hip: the resident membership words (word-major per slot) for pr_boot.hip's stratum cut; false without valid words
+bool strata_view(const vpr_handle *h, int32_t *n_strata, int64_t n_var[VPR_HAPS], const uint64_t *words[VPR_HAPS]);
+void boot_free(vpr_handle *h);                                       // pr_boot.hip: the replicate histogram and the keys
 // pr_collect.hip, shared with pr_strata.hip: the inputs of a counters call, the host fold of one histogram, the all-reduce
 int pr_counts_inputs(vpr_handle *h, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase, int32_t **d_pb);
 void pr_fold_counts(const unsigned long long *hist, int nq, int64_t *counts);

@@ -224,6 +224,14 @@ void strata_free(vpr_handle *h) {
     h->strata = nullptr;
 }
 
+bool strata_view(const vpr_handle *h, int32_t *n_strata, int64_t n_var[VPR_HAPS], const uint64_t *words[VPR_HAPS]) {
+    const StrataState *S = h->strata;
+    if (!S || !S->valid) return false;
+    *n_strata = S->n_strata;
+    for (int s = 0; s < VPR_HAPS; s++) { n_var[s] = S->n_var[s]; words[s] = S->words[s]; }
+    return true;
+}
+
 extern "C" {
 
 int vpr_strata_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *s) {

@@ -14,6 +14,7 @@
 
 #include "../../include/vcfdist_pr.h"
 #include "../../include/vcfdist_report.h"
+#include "../../include/vcfdist_bootstrap.h"
 
 namespace {
 
@@ -88,22 +89,31 @@ extern "C" int32_t vrp_phase_blocks(const int32_t *sc_phase_set, int32_t n_sc, i
 }
 
 namespace {
+// the BEST threshold of one type: the first quality of the largest F1 (print.cpp:470), as pr_rows settles it
+int best_qual_of(const int64_t *counts, int type, int min_qual, int max_qual) {
+    const int nq = max_qual - min_qual + 1;
+    float best = 0;
+    int best_qual = 0;
+    for (int qual = min_qual; qual <= max_qual; qual++) {
+        const Metrics m = metrics(counts, nq, type, qual - min_qual);
+        if (m.f1 > best) { best = m.f1; best_qual = qual; }
+    }
+    // (an all-zero F1 column leaves quality 0 in the reference, which it then indexes; keep the index in range)
+    return best_qual < min_qual || best_qual > max_qual ? min_qual : best_qual;
+}
+
 // the rows of precision-recall.tsv (all) and precision-recall-summary.tsv (sum) for one set of counters, every line behind
 // `lead` ("" for the unstratified files, "<stratum>\t" for the stratified ones)
 void pr_rows(FILE *all, FILE *sum, const char *lead, const int64_t *counts, int min_qual, int max_qual) {
     const int nq = max_qual - min_qual + 1;
     int best_qual[VPR_VARTYPES];
     for (int type = 0; type < VPR_VARTYPES; type++) {
-        float best = 0;
-        best_qual[type] = 0;
         for (int qual = min_qual; qual <= max_qual; qual++) {
             const Metrics m = metrics(counts, nq, type, qual - min_qual);
-            if (m.f1 > best) { best = m.f1; best_qual[type] = qual; }   // first maximum wins (print.cpp:470)
             fprintf(all, "%s%s\t%d\t%f\t%f\t%f\t%f\t%d\t%d\t%d\t%d\t%d\t%d\n", lead, VARTYPE_STR[type], qual, m.precision, m.recall,
                     m.f1, m.f1_q, m.truth_tp + m.truth_fn, m.truth_tp, m.truth_fn, m.query_tp + m.query_fp, m.query_tp, m.query_fp);
         }
-        // (an all-zero F1 column leaves quality 0 in the reference, which it then indexes; keep the index in range)
-        if (best_qual[type] < min_qual || best_qual[type] > max_qual) best_qual[type] = min_qual;
+        best_qual[type] = best_qual_of(counts, type, min_qual, max_qual);
     }
     for (int type = 0; type < VPR_VARTYPES; type++) {
         const int quals[2] = {min_qual, best_qual[type]};
@@ -115,6 +125,42 @@ void pr_rows(FILE *all, FILE *sum, const char *lead, const int64_t *counts, int 
         }
     }
 }
+// the rows of bootstrap-precision-recall-summary.tsv (sum) and, where wanted, bootstrap-replicates.tsv (rep) for one set of
+// point counters and its n_rep replicate counters (include/vcfdist_bootstrap.h: percentile interval, BEST fixed at the point
+// estimate's quality), every summary line behind `lead`
+void boot_rows(FILE *sum, FILE *rep, const char *lead, const int64_t *counts, const int64_t *counts_boot, int n_rep,
+               unsigned long long seed, int min_qual, int max_qual) {
+    const int nq = max_qual - min_qual + 1;
+    const size_t nc1 = size_t(2) * VPR_VARTYPES * 3 * size_t(nq);
+    const char *const thresh[2] = {"NONE", "BEST"};
+    int quals[VPR_VARTYPES][2];
+    for (int type = 0; type < VPR_VARTYPES; type++) { quals[type][0] = min_qual; quals[type][1] = best_qual_of(counts, type, min_qual, max_qual); }
+    // x[floor(0.025 n)] and x[ceil(0.975 n) - 1] in integers: n / 40 and ceil(39 n / 40) - 1
+    const size_t lo = size_t(n_rep) / 40, hi = (size_t(39) * size_t(n_rep) + 39) / 40 - 1;
+    std::vector<float> x[3];
+    for (int type = 0; type < VPR_VARTYPES; type++)
+        for (int i = 0; i < 2; i++) {
+            const Metrics m = metrics(counts, nq, type, quals[type][i] - min_qual);
+            for (auto &v : x) v.resize(size_t(n_rep));
+            for (int r = 0; r < n_rep; r++) {
+                const Metrics b = metrics(counts_boot + size_t(r) * nc1, nq, type, quals[type][i] - min_qual);
+                x[0][size_t(r)] = b.precision; x[1][size_t(r)] = b.recall; x[2][size_t(r)] = b.f1;
+            }
+            for (auto &v : x) std::sort(v.begin(), v.end());
+            fprintf(sum, "%s%s\t%s\t%d\t%d\t%llu\t%f\t%f\t%f\t%f\t%f\t%f\t%f\t%f\t%f\n", lead, VARTYPE_STR[type], thresh[i], quals[type][i],
+                    n_rep, seed, m.precision, x[0][lo], x[0][hi], m.recall, x[1][lo], x[1][hi], m.f1, x[2][lo], x[2][hi]);
+        }
+    if (!rep) return;
+    for (int r = 0; r < n_rep; r++)
+        for (int type = 0; type < VPR_VARTYPES; type++)
+            for (int i = 0; i < 2; i++) {
+                const Metrics b = metrics(counts_boot + size_t(r) * nc1, nq, type, quals[type][i] - min_qual);
+                fprintf(rep, "%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t%f\t%f\t%f\n", r, VARTYPE_STR[type], thresh[i], quals[type][i], b.truth_tp,
+                        b.query_tp, b.truth_fn, b.query_fp, b.precision, b.recall, b.f1);
+            }
+}
+const char *const BOOT_SUM_HEADER = "VAR_TYPE\tTHRESHOLD\tMIN_QUAL\tREPLICATES\tSEED\tPREC\tPREC_LO\tPREC_HI\tRECALL\tRECALL_LO\tRECALL_HI\tF1_SCORE\tF1_LO\tF1_HI\n";
+const char *const BOOT_REP_HEADER = "REPLICATE\tVAR_TYPE\tTHRESHOLD\tMIN_QUAL\tTRUTH_TP\tQUERY_TP\tTRUTH_FN\tQUERY_FP\tPREC\tRECALL\tF1_SCORE\n";
 const char *const PR_ALL_HEADER = "VAR_TYPE\tMIN_QUAL\tPREC\tRECALL\tF1_SCORE\tF1_QSCORE\tTRUTH_TOTAL\tTRUTH_TP\tTRUTH_FN\tQUERY_TOTAL\tQUERY_TP\tQUERY_FP\n";
 const char *const PR_SUM_HEADER = "VAR_TYPE\tTHRESHOLD\tMIN_QUAL\tTRUTH_TP\tQUERY_TP\tTRUTH_FN\tQUERY_FP\tPREC\tRECALL\tF1_SCORE\tF1_QSCORE\n";
 }  // namespace
@@ -149,6 +195,38 @@ extern "C" int vrp_write_stratified(const char *prefix, const char *const *names
     for (int32_t k = 0; k < n_strata; k++)
         pr_rows(all, sum, (std::string(names[k]) + "\t").c_str(), counts + size_t(k) * nc1, min_qual, max_qual);
     if (!all.finish() || !sum.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn_all + " / " + fn_sum);
+    return VRP_OK;
+}
+
+extern "C" int vrp_write_bootstrap(const char *prefix, const int64_t *counts, const int64_t *counts_boot, int32_t n_rep, uint64_t seed,
+                                   int32_t min_qual, int32_t max_qual) {
+    if (!prefix || !counts || !counts_boot || n_rep < 1 || max_qual < min_qual) return fail(VRP_ERR_ARG, "vrp_write_bootstrap: bad argument");
+    const std::string fn_sum = std::string(prefix) + "bootstrap-precision-recall-summary.tsv", fn_rep = std::string(prefix) + "bootstrap-replicates.tsv";
+    File sum(fn_sum.c_str());
+    if (!sum) return fail(VRP_ERR_OPEN, "cannot create " + fn_sum);
+    File rep(fn_rep.c_str());
+    if (!rep) return fail(VRP_ERR_OPEN, "cannot create " + fn_rep);
+    fputs(BOOT_SUM_HEADER, sum);
+    fputs(BOOT_REP_HEADER, rep);
+    boot_rows(sum, rep, "", counts, counts_boot, n_rep, seed, min_qual, max_qual);
+    if (!sum.finish() || !rep.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn_sum + " / " + fn_rep);
+    return VRP_OK;
+}
+
+extern "C" int vrp_write_bootstrap_stratified(const char *prefix, const char *const *names, int32_t n_strata, const int64_t *counts,
+                                              const int64_t *counts_boot, int32_t n_rep, uint64_t seed, int32_t min_qual, int32_t max_qual) {
+    if (!prefix || !names || n_strata < 0 || (n_strata && (!counts || !counts_boot)) || n_rep < 1 || max_qual < min_qual)
+        return fail(VRP_ERR_ARG, "vrp_write_bootstrap_stratified: bad argument");
+    for (int32_t k = 0; k < n_strata; k++) if (!names[k]) return fail(VRP_ERR_ARG, "vrp_write_bootstrap_stratified: null stratum name");
+    const size_t nc1 = size_t(2) * VPR_VARTYPES * 3 * size_t(max_qual - min_qual + 1);
+    const std::string fn_sum = std::string(prefix) + "stratified-bootstrap-precision-recall-summary.tsv";
+    File sum(fn_sum.c_str());
+    if (!sum) return fail(VRP_ERR_OPEN, "cannot create " + fn_sum);
+    fprintf(sum, "STRATUM\t%s", BOOT_SUM_HEADER);
+    for (int32_t k = 0; k < n_strata; k++)
+        boot_rows(sum, nullptr, (std::string(names[k]) + "\t").c_str(), counts + size_t(k) * nc1, counts_boot + size_t(k) * size_t(n_rep) * nc1,
+                  n_rep, seed, min_qual, max_qual);
+    if (!sum.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn_sum);
     return VRP_OK;
 }
 

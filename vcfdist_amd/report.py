@@ -25,7 +25,7 @@ class VrpContig(C.Structure):
                 ("n_flips", C.c_int32), ("switches", A.P_i32), ("flips", A.P_i32)]
 
 
-EXPORTED = ["vrp_phase_blocks", "vrp_write_precision_recall", "vrp_write_stratified", "vrp_write_phase_blocks", "vrp_write_superclusters",
+EXPORTED = ["vrp_phase_blocks", "vrp_write_precision_recall", "vrp_write_stratified", "vrp_write_bootstrap", "vrp_write_bootstrap_stratified", "vrp_write_phase_blocks", "vrp_write_superclusters",
             "vrp_write_switchflips", "vrp_write_phasing_summary", "vrp_ng50",
             "vrp_write_variants", "vrp_write_summary_vcf", "vrp_write_distance", "vrp_write_edits", "vrp_write_vcf", "vrp_last_error"]
 
@@ -137,6 +137,32 @@ def write_stratified(prefix, names, counts, min_qual, max_qual):
     arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
     L.vrp_write_stratified.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, A.P_i64, C.c_int32, C.c_int32]
     _check(L.vrp_write_stratified(prefix.encode(), arr, len(names), A._ptr(cnt, C.c_int64), min_qual, max_qual), "vrp_write_stratified")
+
+
+def write_bootstrap(prefix, counts, counts_boot, seed, min_qual, max_qual):
+    """bootstrap-precision-recall-summary.tsv and bootstrap-replicates.tsv (include/vcfdist_bootstrap.h): counts int64
+    [2][4][3][nq] (summary.pr_counts), counts_boot int64 [n_rep][2][4][3][nq] (summary.pr_counts_boot)"""
+    cnt, boot = np.ascontiguousarray(counts, np.int64), np.ascontiguousarray(counts_boot, np.int64)
+    if boot.ndim != 5 or boot.shape[1:] != cnt.shape:
+        raise ReportError(f"replicate counts of shape {boot.shape} for point counts of shape {cnt.shape}")
+    L = api.lib()
+    L.vrp_write_bootstrap.argtypes = [C.c_char_p, A.P_i64, A.P_i64, C.c_int32, C.c_uint64, C.c_int32, C.c_int32]
+    _check(L.vrp_write_bootstrap(prefix.encode(), A._ptr(cnt, C.c_int64), A._ptr(boot, C.c_int64), boot.shape[0], int(seed), min_qual, max_qual),
+           "vrp_write_bootstrap")
+
+
+def write_bootstrap_stratified(prefix, names, counts, counts_boot, seed, min_qual, max_qual):
+    """stratified-bootstrap-precision-recall-summary.tsv: counts int64 [n_strata][2][4][3][nq], counts_boot int64
+    [n_strata][n_rep][2][4][3][nq]"""
+    cnt, boot = np.ascontiguousarray(counts, np.int64), np.ascontiguousarray(counts_boot, np.int64)
+    if cnt.shape[0] != len(names) or boot.ndim != 6 or boot.shape[0] != len(names) or boot.shape[2:] != cnt.shape[1:]:
+        raise ReportError(f"{len(names)} stratum names for point counts of shape {cnt.shape} and replicate counts of shape {boot.shape}")
+    L = api.lib()
+    arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+    L.vrp_write_bootstrap_stratified.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, A.P_i64, A.P_i64, C.c_int32, C.c_uint64,
+                                                 C.c_int32, C.c_int32]
+    _check(L.vrp_write_bootstrap_stratified(prefix.encode(), arr, len(names), A._ptr(cnt, C.c_int64), A._ptr(boot, C.c_int64), boot.shape[1],
+                                            int(seed), min_qual, max_qual), "vrp_write_bootstrap_stratified")
 
 
 def write_results(prefix, contigs, cmd="", file_date=None, credit_threshold=0.7):

@@ -94,6 +94,30 @@ def pr_counts_strata(pr, var_class_per_slot, pb_phase=None, min_qual=0, max_qual
     return out
 
 
+def pr_counts_boot(pr, var_class_per_slot, pb_phase, sc_key, n_rep, seed=1, min_qual=0, max_qual=60, stratum=-1, comm=None):
+    """pr_counts resampled: the Poisson bootstrap over superclusters of include/vcfdist_bootstrap.h on the device ->
+    int64 [n_rep][2][4][3][nq].  sc_key: uint64 per supercluster of the executed batch; stratum >= 0: only that stratum of
+    the resident membership words; comm: an ncclComm_t (as an integer) for vpr_allreduce_counts_boot."""
+    L = api.lib()
+    nq = max_qual - min_qual + 1
+    n_rep = int(n_rep)
+    out = np.zeros((n_rep if 1 <= n_rep <= A.BOOT_MAX_REPLICATES else 1, 2, VARTYPES, 3, max(nq, 1)), np.int64)      # (out of range: the call refuses)
+    pb = None if pb_phase is None else np.ascontiguousarray(pb_phase, dtype=np.int32)
+    key = None if sc_key is None else np.ascontiguousarray(sc_key, dtype=np.uint64)
+    if key is not None and key.size == 0:
+        key = np.zeros(1, np.uint64)
+    arr = None
+    if var_class_per_slot is not None:      # None: classes already resident (upload_var_class, an earlier pr_counts)
+        cls = [np.ascontiguousarray(c, dtype=np.uint8) for c in var_class_per_slot]
+        arr = (A.P_u8 * 4)(*[A._ptr(c, C.c_uint8) for c in cls])
+    args = (arr, None if pb is None else A._ptr(pb, C.c_int32), min_qual, max_qual, None if key is None else A._ptr(key, C.c_uint64),
+            int(seed) & (2 ** 64 - 1), n_rep, int(stratum), A._ptr(out, C.c_int64))
+    rc = L.vpr_pr_counts_boot(pr._h, *args) if comm is None else L.vpr_allreduce_counts_boot(pr._h, comm if isinstance(comm, C.c_void_p) else C.c_void_p(comm), *args)
+    if rc:
+        raise api.VprError(f"vpr_pr_counts_boot failed ({rc}): {L.vpr_last_error(pr._h).decode()}")
+    return out
+
+
 def upload_var_class(pr, var_class_per_slot):
     L = api.lib()
     cls = [np.ascontiguousarray(c, dtype=np.uint8) for c in var_class_per_slot]
