@@ -5,6 +5,7 @@
  *   vrp_phase_blocks             phaseblockData::phaseblockData (phase-set runs)   src/phase.cpp:229-262
  *   vrp_write_precision_recall   write_precision_recall (the two TSV files)        src/print.cpp:441-566
  *   vrp_write_stratified         (none: the same tables per stratum, include/vcfdist_strata.h)
+ *   vrp_write_context_bed        (none: the intervals of the sequence-context strata, include/vcfdist_context.h)
  *   vrp_write_phase_blocks       write_results, phase-blocks.tsv                   src/print.cpp:585-609
  *   vrp_write_superclusters      write_results, superclusters.tsv                  src/print.cpp:611-671
  *   vrp_write_variants           write_results, query.tsv / truth.tsv              src/print.cpp:673-876
@@ -87,6 +88,12 @@ int vrp_write_precision_recall(const char *prefix, const int64_t *counts, int32_
    A stratum's rows without that column are byte for byte what vrp_write_precision_recall writes for its counts. */
 int vrp_write_stratified(const char *prefix, const char *const *names, int32_t n_strata, const int64_t *counts,
                          int32_t min_qual, int32_t max_qual);
+
+/* <prefix>context-strata.bed: the intervals of the sequence-context strata (include/vcfdist_context.h) as contig, start, stop,
+   name -- by contig in the given (evaluation) order, then by stratum in table order, then by start.  iv_off[n_ctg * n_strata + 1],
+   row = contig * n_strata + stratum, into start / stop (0-based half-open). */
+int vrp_write_context_bed(const char *prefix, const char *const *contigs, int32_t n_ctg, const char *const *names, int32_t n_strata,
+                          const int64_t *iv_off, const int32_t *start, const int32_t *stop);
 
 int vrp_write_phase_blocks(const char *path, const vrp_contig *ctgs, int32_t n_ctg);
 /* switchflips.tsv: where every switch / flip error may have happened; phasing-summary.tsv: block and error totals with

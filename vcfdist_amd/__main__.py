@@ -10,7 +10,9 @@ the ALIGNMENT DISTANCE SUMMARY (printed even with -n); one rank only.  With -rq 
 GPU before the evaluation (include/vcfdist_realign.h): orig-query.vcf / orig-truth.vcf as read, query.vcf / truth.vcf realigned;
 -ro stops after the realignment; one rank only.  With --stratify FILE (the GIAB list format: one name<TAB>path of a BED per line) the
 counters of the one evaluation are also cut by region on the GPU (include/vcfdist_strata.h): stratified-precision-recall.tsv and
-stratified-precision-recall-summary.tsv; works under several ranks in both --shard modes.  With --bootstrap N the counters are
+stratified-precision-recall-summary.tsv; works under several ranks in both --shard modes.  With --stratify-context the default
+sequence-context strata (include/vcfdist_context.h: intervals built on the GPU from the FASTA) follow the list's strata, or stand
+alone, and context-strata.bed holds their intervals.  With --bootstrap N the counters are
 resampled N times on the GPU (include/vcfdist_bootstrap.h: a Poisson bootstrap over superclusters, conditional on the phasing, the
 BEST threshold kept at the point estimate's): bootstrap-precision-recall-summary.tsv with 95 % percentile intervals for precision,
 recall and F1, bootstrap-replicates.tsv, and with --stratify stratified-bootstrap-precision-recall-summary.tsv; --bootstrap-seed S
@@ -128,8 +130,12 @@ def stratify_contig(pr, prep, strat, args, pb, part_idx=None):
     words are computed for the whole contig and the rank keeps its share's."""
     from . import shard
     name, whole = prep["name"], prep["batch"]
-    n_strata = len(strat["beds"])
-    pr.strata_masks(prep["variants"], IO.contig_strata(strat["beds"], [name]))
+    n_strata = len(strat["names"])
+    if strat["ctx"]:        # --stratify-context: the context intervals are built on the device and go to the same mask kernel
+        pr.context_masks(prep["variants"], strat["ctx"], IO.contig_strata(strat["beds"], [name]) if strat["beds"] else None)
+        keep_context_intervals(pr, strat, name)
+    else:
+        pr.strata_masks(prep["variants"], IO.contig_strata(strat["beds"], [name]))
     words = pr.download_strata_masks()
     if part_idx is not None:
         words = [np.stack([shard.subset_per_variant(w, whole.var_off[s], part_idx) for w in words[s]]) for s in range(4)]
@@ -140,6 +146,26 @@ def stratify_contig(pr, prep, strat, args, pb, part_idx=None):
         strat["none"] += int((np.bitwise_or.reduce(w, axis=0) == 0).sum())
 
 
+def keep_context_intervals(pr, strat, name):
+    """the context intervals of the contig the last context_masks saw, for context-strata.bed and the stderr line"""
+    strat["intervals"][name] = [row[0] for row in pr.download_context_intervals()]
+    strat["ctx_ms"][name] = pr.context_timing()[0]
+
+
+def context_only(name, seq, strat, args, device=0):
+    """--stratify-context for a contig (or a rank's share of one) without a supercluster: the intervals alone, for no variant"""
+    cfg = A.default_config(device=device)
+    cfg.max_qual = float(args.max_qual)
+    pr = api.PrecisionRecall(cfg)
+    z32, z64, z8 = np.zeros(0, np.int32), np.zeros(1, np.int64), np.zeros(0, np.uint8)
+    seq = np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else np.asarray(seq, np.uint8)
+    v = A.Variants(np.array([0, len(seq)], np.int64), seq, z32, z32, z32, [z64] * 4, [z32] * 4, [z8] * 4, [np.zeros(0, np.float32)] * 4,
+                   [np.zeros(0, np.int64)] * 4, [z32] * 4, [np.zeros(0, np.int64)] * 4, [z32] * 4, [z8] * 4)
+    pr.context_masks(v, strat["ctx"])
+    keep_context_intervals(pr, strat, name)
+    pr.close()
+
+
 def bootstrap_contig(pr, boot, strat, args, pb, keys):
     """--bootstrap: the replicate counters of the executed batch, added to boot['counts']; with --stratify one pass per stratum
     of the resident membership words, added to boot['strat']"""
@@ -147,7 +173,7 @@ def bootstrap_contig(pr, boot, strat, args, pb, keys):
     boot["counts"] += pr.pr_counts_boot(None, pb, keys, **kw)        # (the classes are resident: pr_counts)
     boot["ms"] += pr.boot_info()[1]
     if strat is not None:
-        for k in range(len(strat["beds"])):
+        for k in range(len(strat["names"])):
             boot["strat"][k] += pr.pr_counts_boot(None, pb, keys, stratum=k, **kw)
             boot["ms"] += pr.boot_info()[1]
 
@@ -376,6 +402,9 @@ def main(argv=None):
     ap.add_argument("--stratify", metavar="FILE",
                     help="strata list (one name<TAB>path of a BED per line, paths relative to the list): the counters of the one "
                          "evaluation are also cut by region (stratified-precision-recall.tsv, stratified-precision-recall-summary.tsv)")
+    ap.add_argument("--stratify-context", action="store_true",
+                    help="the default sequence-context strata (homopolymers, short tandem repeats, GC bands), built on the GPU from the "
+                         "FASTA, behind those of --stratify or alone; their intervals are written to context-strata.bed")
     ap.add_argument("--bootstrap", metavar="N", type=bootstrap_replicates, default=0,
                     help="resample the counters N times (1 to 100000) over superclusters on the GPU: 95 %% percentile intervals for "
                          "precision, recall and F1 (bootstrap-precision-recall-summary.tsv, bootstrap-replicates.tsv)")
@@ -422,12 +451,21 @@ def main(argv=None):
             torch.cuda.set_device(device)
         dist.init_process_group(backend=backend)
     strat = None
-    if args.stratify:       # the strata list and every BED it names are read and checked before anything is evaluated
-        try:
-            names, beds = IO.read_strata(args.stratify)
-        except IOError as e:
-            raise SystemExit(f"ERROR: {e}")
-        strat = dict(names=names, beds=beds, counts=None, vars=0, none=0)
+    if args.stratify or args.stratify_context:       # the strata list and every BED it names are read and checked before anything is evaluated
+        names, beds = [], []
+        if args.stratify:
+            try:
+                names, beds = IO.read_strata(args.stratify)
+            except IOError as e:
+                raise SystemExit(f"ERROR: {e}")
+        strat = dict(names=list(names), beds=beds, counts=None, vars=0, none=0, ctx=None, ctx_names=[], intervals={}, ctx_ms={})
+        if args.stratify_context:       # the default sequence-context strata (include/vcfdist_context.h) behind the list's
+            strat["ctx_names"], strat["ctx"] = api.context_default()
+            for n in strat["ctx_names"]:
+                if n in names:
+                    raise SystemExit(f"ERROR: strata list '{args.stratify}': duplicate stratum name '{n}' (a sequence-context stratum of "
+                                     "--stratify-context)")
+            strat["names"] += strat["ctx_names"]
     filters = tuple(f for f in args.filter.split(",") if f)
     bed = IO.Bed(args.bed) if args.bed else None
     kw = dict(min_qual=args.min_qual, max_qual=args.max_qual, max_size=args.max_size, cluster_min_gap=args.cluster_gap, filters=filters)
@@ -497,6 +535,11 @@ def main(argv=None):
         except api.VprError as e:     # the library's explicit refusals end the run like the reference's ERROR()
             raise SystemExit(f"ERROR: contig '{ctg}': {e}")
         total += counts
+        if strat is not None and strat["ctx"] and ctg not in strat["intervals"] and (rank == 0 or not by_sc):
+            try:
+                context_only(ctg, fasta[ctg], strat, args, device=device)
+            except api.VprError as e:
+                raise SystemExit(f"ERROR: contig '{ctg}': {e}")
         if not args.no_output_files:
             src = q if ctg in q["contigs"] else t     # superclusterData ctor, cluster.cpp:134-157: query's header wins
             if ctg in src["contigs"]:
@@ -528,6 +571,10 @@ def main(argv=None):
             gathered = [None] * world
             dist.all_gather_object(gathered, reports)
             reports = {k: v for part in gathered for k, v in part.items()}
+            if strat is not None and strat["ctx"]:
+                dist.all_gather_object(gathered, (strat["intervals"], strat["ctx_ms"]))
+                strat["intervals"] = {k: v for part in gathered for k, v in part[0].items()}
+                strat["ctx_ms"] = {k: v for part in gathered for k, v in part[1].items()}
     rows = S.pr_summary(total, args.min_qual, args.max_qual)
     if dist_sets is not None:       # write_distance (printed even with -n) and write_edits, edit.cpp:134-280
         text = RP.write_distance(args.prefix, dist_sets, args.min_qual, args.max_qual, args.eval_sub, args.eval_open, args.eval_extend,
@@ -541,6 +588,8 @@ def main(argv=None):
             RP.write_parameters(args.prefix, args, cmd)
             if strat is not None:
                 RP.write_stratified(args.prefix, strat["names"], strat["counts"], args.min_qual, args.max_qual)
+                if strat["ctx"]:
+                    RP.write_context_bed(args.prefix, contigs, strat["ctx_names"], strat["intervals"])
             if boot is not None:
                 RP.write_bootstrap(args.prefix, total, boot["counts"], boot["seed"], args.min_qual, args.max_qual)
                 if strat is not None:
@@ -555,6 +604,10 @@ def main(argv=None):
         if strat is not None:
             print(f"[vcfdist_amd] stratified: {len(strat['names'])} strata, {strat['none']} of {strat['vars']} hap-variants in none of them",
                   file=sys.stderr)
+            if strat["ctx"]:
+                n_iv = sum(len(a) for rows in strat["intervals"].values() for a, _ in rows)
+                print(f"[vcfdist_amd] context strata: {n_iv} intervals of {len(strat['ctx'])} strata, {sum(strat['ctx_ms'].values()):.3f} ms "
+                      "on the device", file=sys.stderr)
         if boot is not None:
             print(f"[vcfdist_amd] bootstrap: {boot['n']} replicates, seed {boot['seed']}, {boot['ms']:.3f} ms on the device", file=sys.stderr)
         print("PRECISION-RECALL SUMMARY\n")

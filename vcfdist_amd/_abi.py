@@ -515,6 +515,30 @@ class Strata:
                          _ptr(self._keep[1], C.c_int32))
 
 
+# ---- include/vcfdist_context.h
+CTX_PERIOD, CTX_GC = 0, 1
+CTX_MAX_SPEC = 64
+
+
+class VprContextStratum(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("kind", "period", "min_len", "max_len", "gc_lo", "gc_hi", "window", "slop")]
+
+    def __repr__(self):
+        if self.kind == CTX_PERIOD:
+            return f"period(p={self.period}, {self.min_len}..{self.max_len or ''}, slop={self.slop})"
+        return f"gc({self.gc_lo}..{self.gc_hi}, W={self.window}, slop={self.slop})"
+
+
+def ctx_period(period, min_len, max_len=0, slop=0):
+    """a period stratum: tracts of period `period` and length min_len..max_len (0: unbounded), padded by slop"""
+    return VprContextStratum(CTX_PERIOD, period, min_len, max_len, 0, 0, 0, slop)
+
+
+def ctx_gc(lo, hi, window, slop=0):
+    """a GC stratum: bases whose window of `window` called bases has lo <= GC percent < hi, padded by slop"""
+    return VprContextStratum(CTX_GC, 0, 0, 0, lo, hi, window, slop)
+
+
 # ---- include/vcfdist_realign.h
 RL_ST_EDGE = 1
 RL_ST_LIMIT = 2

@@ -89,6 +89,12 @@ def lib():
     L.vpr_pr_counts_strata.argtypes = [H, C.c_void_p, A.P_i32, C.c_int32, C.c_int32, A.P_i64]
     L.vpr_allreduce_counts_strata.argtypes = [H, C.c_void_p, C.c_void_p, A.P_i32, C.c_int32, C.c_int32, A.P_i64]
     L.vpr_strata_timing.argtypes = [H, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.vpr_context_default.argtypes = [C.POINTER(C.POINTER(A.VprContextStratum)), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.c_int32)]
+    L.vpr_context_masks.argtypes = [H, C.POINTER(A.VprVariants), C.POINTER(A.VprStrata), C.POINTER(A.VprContextStratum), C.c_int32]
+    L.vpr_context_interval_counts.argtypes = [H, A.P_i64]
+    L.vpr_context_download_intervals.argtypes = [H, A.P_i32, A.P_i32]
+    L.vpr_context_info.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.vpr_context_timing.argtypes = [H, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     boot = [C.c_void_p, A.P_i32, C.c_int32, C.c_int32, P_u64, C.c_uint64, C.c_int32, C.c_int32, A.P_i64]
     L.vpr_pr_counts_boot.argtypes = [H] + boot
     L.vpr_allreduce_counts_boot.argtypes = [H, C.c_void_p] + boot
@@ -114,6 +120,9 @@ DIST_EXPORTED = ["vpr_distance", "vpr_distance_info", "vpr_distance_download"]
 # include/vcfdist_strata.h
 STRATA_EXPORTED = ["vpr_strata_masks", "vpr_strata_download_masks", "vpr_strata_upload_masks", "vpr_pr_counts_strata",
                    "vpr_allreduce_counts_strata", "vpr_strata_timing"]
+# include/vcfdist_context.h
+CONTEXT_EXPORTED = ["vpr_context_default", "vpr_context_masks", "vpr_context_interval_counts", "vpr_context_download_intervals",
+                    "vpr_context_info", "vpr_context_timing"]
 # include/vcfdist_bootstrap.h
 BOOT_EXPORTED = ["vpr_pr_counts_boot", "vpr_allreduce_counts_boot", "vpr_boot_info", "vrp_write_bootstrap", "vrp_write_bootstrap_stratified"]
 # include/vcfdist_realign.h
@@ -165,6 +174,24 @@ def realign(hap, clusters, seq, sub=5, open=6, extend=2, max_qual=60, round_byte
     finally:
         L.vrl_result_free(out)
     return cols, status, info
+
+
+def context_default():
+    """the command lines' default context strata (vpr_context_default): (names, [A.VprContextStratum])"""
+    spec, names, n = C.POINTER(A.VprContextStratum)(), C.POINTER(C.c_char_p)(), C.c_int32()
+    rc = lib().vpr_context_default(C.byref(spec), C.byref(names), C.byref(n))
+    if rc:
+        raise VprError(f"vpr_context_default failed ({rc})")
+    return [names[k].decode() for k in range(n.value)], [A.VprContextStratum.from_buffer_copy(spec[k]) for k in range(n.value)]
+
+
+def context_info():
+    """(bases per workgroup, bases per lane) of the interval kernels (vpr_context_info; a property of the build)"""
+    a, b = C.c_int32(), C.c_int32()
+    rc = lib().vpr_context_info(None, C.byref(a), C.byref(b))
+    if rc:
+        raise VprError(f"vpr_context_info failed ({rc})")
+    return a.value, b.value
 
 
 def store_phase(s, thr=0.6):
@@ -387,6 +414,39 @@ class PrecisionRecall:
         """(ms of the last strata_masks' kernels, ms of the last stratified histogram's) from HIP events on the handle's stream"""
         a, b = C.c_double(), C.c_double()
         self._chk(lib().vpr_strata_timing(self._h, C.byref(a), C.byref(b)), "vpr_strata_timing")
+        return a.value, b.value
+
+    def context_masks(self, variants, spec, bed: A.Strata = None):
+        """The sequence-context strata (include/vcfdist_context.h): the intervals of every entry of `spec` (A.ctx_period /
+        A.ctx_gc) are built on the device from the variants' contig sequences, and the membership words of the variants become
+        resident as after strata_masks: the strata of `bed` first (if given), the context strata behind them in spec order."""
+        vs = variants.as_struct() if isinstance(variants, A.Variants) else variants
+        n_sc = int(vs.n_sc)
+        arr = (A.VprContextStratum * max(len(spec), 1))(*spec)
+        ss = bed.as_struct() if bed is not None else None
+        self._context = None
+        self._chk(lib().vpr_context_masks(self._h, C.byref(vs), C.byref(ss) if ss is not None else None, arr, len(spec)), "vpr_context_masks")
+        self._context = (len(spec), int(vs.n_ctg))
+        self._strata = ((bed.n_strata if bed is not None else 0) + len(spec), [int(vs.var_off[h][n_sc]) for h in range(A.HAPS)])
+
+    def download_context_intervals(self):
+        """the intervals of the last context_masks: rows[spec][contig] = (starts, stops), int32 arrays, 0-based half-open"""
+        n_spec, n_ctg = getattr(self, "_context", None) or (0, 1)      # (before a call the library refuses: VPR_ERR_STATE)
+        off = np.zeros(n_spec * n_ctg + 1, np.int64)
+        self._chk(lib().vpr_context_interval_counts(self._h, A._ptr(off, C.c_int64)), "vpr_context_interval_counts")
+        st, sp = np.zeros(max(int(off[-1]), 1), np.int32), np.zeros(max(int(off[-1]), 1), np.int32)
+        self._chk(lib().vpr_context_download_intervals(self._h, A._ptr(st, C.c_int32), A._ptr(sp, C.c_int32)), "vpr_context_download_intervals")
+        return [[(st[off[k * n_ctg + c]:off[k * n_ctg + c + 1]], sp[off[k * n_ctg + c]:off[k * n_ctg + c + 1]]) for c in range(n_ctg)]
+                for k in range(n_spec)]
+
+    def context_info(self):
+        """(bases per workgroup, bases per lane) of the interval kernels"""
+        return context_info()
+
+    def context_timing(self):
+        """(ms of the last context_masks' interval kernels, ms of its membership kernel) from HIP events on the handle's stream"""
+        a, b = C.c_double(), C.c_double()
+        self._chk(lib().vpr_context_timing(self._h, C.byref(a), C.byref(b)), "vpr_context_timing")
         return a.value, b.value
 
     def pr_counts_boot(self, var_class_per_slot, pb_phase, sc_key, n_rep, seed=1, min_qual=0, max_qual=60, stratum=-1, comm=None):

@@ -9,7 +9,7 @@
 //   vcfdist_gpu <query.vcf[.gz]> <truth.vcf[.gz]> <ref.fasta[.gz]> [-b regions.bed] [-p prefix] [-n] [-c biwfa | gap N | size N]
 //               [-l max variant size] [-s max supercluster size] [-mn / -mx qual] [-f filters] [-i iterations] [-x -o -e penalties]
 //               [-ct credit threshold] [-pt phasing threshold] [-sv threshold] [--reach-min-gap N] [--strict] [--device N]
-//               [-d] [-ex -eo -ee evaluation penalties] [-rq] [-rt] [-ro] [--stratify strata.tsv]
+//               [-d] [-ex -eo -ee evaluation penalties] [-rq] [-rt] [-ro] [--stratify strata.tsv] [--stratify-context]
 //               [--bootstrap N] [--bootstrap-seed S]
 // With -d the distance metrics (edits_wrapper, dist.cpp:1908-2077) run on the GPU after each contig's precision/recall path
 // (include/vcfdist_distance.h), as the reference's main.cpp:223-238 runs them after precision_recall_threads_wrapper.
@@ -17,6 +17,8 @@
 // the reference's main.cpp:50-180 (orig-*.vcf, realign query, realign truth; -ro stops there and writes query.vcf / truth.vcf).
 // With --stratify FILE (the GIAB list format: one name<TAB>path of a BED per line) the counters of the one evaluation are also cut
 // by region on the GPU (include/vcfdist_strata.h): stratified-precision-recall.tsv and stratified-precision-recall-summary.tsv.
+// With --stratify-context the default sequence-context strata (homopolymers, short tandem repeats, GC bands: intervals built on
+// the GPU from the FASTA, include/vcfdist_context.h) follow the list's strata, or stand alone; context-strata.bed holds them.
 // With --bootstrap N the counters are resampled N times on the GPU (include/vcfdist_bootstrap.h: a Poisson bootstrap over
 // superclusters, conditional on the phasing): bootstrap-precision-recall-summary.tsv with 95 % percentile intervals,
 // bootstrap-replicates.tsv, and with --stratify stratified-bootstrap-precision-recall-summary.tsv.
@@ -40,12 +42,14 @@
 #include "../../include/vcfdist_pr.h"
 #include "../../include/vcfdist_realign.h"
 #include "../../include/vcfdist_report.h"
+#include "../../include/vcfdist_context.h"
 #include "../../include/vcfdist_strata.h"
 
 namespace {
 
 struct Args {
     std::string query, truth, fasta, bed, filter, prefix = "./", cluster = "biwfa", stratify;
+    bool stratify_context = false;
     int max_size = 5000, min_qual = 0, max_qual = 60, cluster_gap = 50, max_iterations = 4, max_supercluster_size = 10000;
     int sub = 5, open = 6, extend = 2, sv_threshold = 50, reach_min_gap = 10, device = 0;
     int eval_sub = 3, eval_open = 2, eval_extend = 1;      // globals.h:52-55
@@ -121,6 +125,7 @@ Args parse(int argc, char **argv) {
         else if (o == "--device") a.device = atoi(need(i));
         else if (o == "-d" || o == "--distance") a.distance = true;
         else if (o == "--stratify") a.stratify = need(i);
+        else if (o == "--stratify-context") a.stratify_context = true;
         else if (o == "--bootstrap") a.bootstrap = bootstrap_replicates(need(i));
         else if (o == "--bootstrap-seed") a.bootstrap_seed = bootstrap_seed(need(i));
         else if (o == "-rq" || o == "--realign-query") a.realign_query = true;
@@ -363,7 +368,38 @@ int main(int argc, char **argv) {
     }
     Strata strata;
     if (!A.stratify.empty()) strata = read_strata(A.stratify);
+    // --stratify-context: the default sequence-context strata (include/vcfdist_context.h) behind the list's
+    const int n_bed = int(strata.names.size());
+    const vpr_context_stratum *ctx_spec = nullptr;
+    const char *const *ctx_names = nullptr;
+    int32_t n_ctx = 0;
+    if (A.stratify_context) {
+        if (vpr_context_default(&ctx_spec, &ctx_names, &n_ctx)) die("ERROR: vpr_context_default failed");
+        for (int k = 0; k < n_ctx; k++) {
+            if (find(strata.names, ctx_names[k]) >= 0)
+                die("ERROR: strata list '%s': duplicate stratum name '%s' (a sequence-context stratum of --stratify-context)", A.stratify.c_str(), ctx_names[k]);
+            strata.names.push_back(ctx_names[k]);
+        }
+    }
     const int n_strata = int(strata.names.size());
+    std::vector<std::string> ctx_contigs;                                       // context-strata.bed: contigs, rows contig-major
+    std::vector<int64_t> ctx_off(1, 0);
+    std::vector<int32_t> ctx_start, ctx_stop;
+    double ctx_ms = 0;
+    // the context intervals of the contig the last vpr_context_masks saw, appended to the table of context-strata.bed
+    auto keep_context_intervals = [&](vpr_handle *h, const std::string &ctg) {
+        std::vector<int64_t> off(size_t(n_ctx) + 1, 0);
+        if (vpr_context_interval_counts(h, off.data())) die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+        const size_t at = ctx_start.size(), n = size_t(off[size_t(n_ctx)]);
+        ctx_start.resize(at + n + 1); ctx_stop.resize(at + n + 1);
+        if (vpr_context_download_intervals(h, ctx_start.data() + at, ctx_stop.data() + at)) die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+        ctx_start.resize(at + n); ctx_stop.resize(at + n);
+        for (int k = 1; k <= n_ctx; k++) ctx_off.push_back(int64_t(at) + off[size_t(k)]);
+        ctx_contigs.push_back(ctg);
+        double ms = 0, ms_mask = 0;
+        (void)vpr_context_timing(h, &ms, &ms_mask);
+        ctx_ms += ms;
+    };
     std::vector<std::string> filters;
     { std::istringstream ss(A.filter); std::string f; while (std::getline(ss, f, ',')) if (!f.empty()) filters.push_back(f); }
     std::vector<const char *> fptr;
@@ -522,18 +558,19 @@ int main(int argc, char **argv) {
             if (vpr_pr_counts(h, clsp, C->pb.data(), A.min_qual, A.max_qual, counts.data())) die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
             for (size_t k = 0; k < total.size(); k++) total[k] += counts[k];
             if (n_strata) {        // the same evaluation, cut by region: membership words, then the histogram per stratum
-                std::vector<int64_t> iv_off(size_t(n_strata) + 1, 0);
+                std::vector<int64_t> iv_off(size_t(n_bed) + 1, 0);
                 std::vector<int32_t> iv_start, iv_stop;
-                for (int k = 0; k < n_strata; k++) {
+                for (int k = 0; k < n_bed; k++) {
                     int64_t n = 0;
                     const int32_t *st = nullptr, *sp = nullptr;
                     if (vio_bed_intervals(strata.beds[size_t(k)], ctg.c_str(), &n, &st, &sp)) die("ERROR: %s", vio_last_error());
                     iv_start.insert(iv_start.end(), st, st + n); iv_stop.insert(iv_stop.end(), sp, sp + n);
                     iv_off[size_t(k) + 1] = int64_t(iv_start.size());
                 }
-                const vpr_strata ST = {n_strata, 1, iv_off.data(), iv_start.data(), iv_stop.data()};
+                const vpr_strata ST = {n_bed, 1, iv_off.data(), iv_start.data(), iv_stop.data()};
                 std::vector<int64_t> sc_counts(strat_total.size(), 0);
-                if (vpr_strata_masks(h, &V, &ST) || vpr_pr_counts_strata(h, nullptr, C->pb.data(), A.min_qual, A.max_qual, sc_counts.data()))
+                // (with --stratify-context the context intervals are built on the device and go to the same mask kernel)
+                if ((n_ctx ? vpr_context_masks(h, &V, n_bed ? &ST : nullptr, ctx_spec, n_ctx) : vpr_strata_masks(h, &V, &ST)) || vpr_pr_counts_strata(h, nullptr, C->pb.data(), A.min_qual, A.max_qual, sc_counts.data()))
                     die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
                 for (size_t k = 0; k < strat_total.size(); k++) strat_total[k] += sc_counts[k];
                 const size_t n_words = (size_t(n_strata) + 63) / 64;
@@ -541,6 +578,7 @@ int main(int argc, char **argv) {
                 uint64_t *wp[4];
                 for (int i = 0; i < 4; i++) { words[i].assign(std::max<size_t>(n_words * size_t(C->slot[i]->n), 1), 0); wp[i] = words[i].data(); }
                 if (vpr_strata_download_masks(h, wp)) die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+                if (n_ctx) keep_context_intervals(h, ctg);
                 for (int i = 0; i < 4; i++) {
                     const size_t nv = size_t(C->slot[i]->n);
                     for (size_t v = 0; v < nv; v++) {
@@ -596,6 +634,15 @@ int main(int argc, char **argv) {
                     C->res.ref_ed[i][w] = zero32; C->res.query_ed[i][w] = zero32; C->res.callq[i][w] = zerof;
                 }
             C->res.sc_phase = zero32; C->res.orig_phase_dist = zero32; C->res.swap_phase_dist = zero32;
+            if (n_ctx) {           // context-strata.bed lists every evaluated contig: the intervals alone, for no variant
+                const int64_t ctg_off[2] = {0, seq_len}, none[1] = {0};
+                vpr_variants V;
+                memset(&V, 0, sizeof(V));
+                V.n_ctg = 1; V.ctg_off = ctg_off; V.ctg_seq = seq;
+                for (int i = 0; i < 4; i++) V.var_off[i] = none;
+                if (vpr_context_masks(h, &V, nullptr, ctx_spec, n_ctx)) die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+                keep_context_intervals(h, ctg);
+            }
         }
         fprintf(stderr, "[vcfdist_amd] %s: %lld hap-variants, %d clusters, %d superclusters, %zu switch / %zu flip errors\n", ctg.c_str(),
                 (long long)n_hapvars, n_clusters, n_sc, C->sw.size(), C->fl.size());
@@ -633,6 +680,12 @@ int main(int argc, char **argv) {
             if (A.bootstrap && vrp_write_bootstrap_stratified(A.prefix.c_str(), names.data(), n_strata, strat_total.data(), boot_strat.data(), A.bootstrap,
                                                               A.bootstrap_seed, A.min_qual, A.max_qual))
                 die("ERROR: %s", vrp_last_error());
+            if (n_ctx) {
+                std::vector<const char *> cn;
+                for (const auto &c : ctx_contigs) cn.push_back(c.c_str());
+                if (vrp_write_context_bed(A.prefix.c_str(), cn.data(), int32_t(cn.size()), ctx_names, n_ctx, ctx_off.data(), ctx_start.data(), ctx_stop.data()))
+                    die("ERROR: %s", vrp_last_error());
+            }
         }
         if (A.bootstrap && vrp_write_bootstrap(A.prefix.c_str(), total.data(), boot_total.data(), A.bootstrap, A.bootstrap_seed, A.min_qual, A.max_qual))
             die("ERROR: %s", vrp_last_error());
@@ -676,6 +729,8 @@ int main(int argc, char **argv) {
     if (n_strata)
         fprintf(stderr, "[vcfdist_amd] stratified: %d strata, %lld of %lld hap-variants in none of them\n", n_strata, (long long)strat_none,
                 (long long)strat_vars);
+    if (n_ctx)
+        fprintf(stderr, "[vcfdist_amd] context strata: %lld intervals of %d strata, %.3f ms on the device\n", (long long)ctx_start.size(), n_ctx, ctx_ms);
     if (A.bootstrap)
         fprintf(stderr, "[vcfdist_amd] bootstrap: %d replicates, seed %llu, %.3f ms on the device\n", A.bootstrap, (unsigned long long)A.bootstrap_seed, boot_ms);
     printf("PRECISION-RECALL SUMMARY\n\n");

@@ -5,6 +5,7 @@
 //   pr_results.hip  vpr_download, vpr_results_alloc, tallies, timing and launch statistics
 //   pr_collect.hip  the counters histogram, vpr_pr_counts, and the RCCL collectives (vpr_allreduce_counts, vpr_allgather_phase)
 //   pr_strata.hip   the region-stratified counters (include/vcfdist_strata.h): membership words, the stratified histogram
+//   pr_context.hip  the sequence-context strata (include/vcfdist_context.h): interval lists built from the contig sequences
 //   pr_boot.hip     the bootstrap replicates of the counters (include/vcfdist_bootstrap.h): the replicate histogram
 #ifndef PR_HOST_H_
 #define PR_HOST_H_
@@ -264,6 +265,7 @@ using namespace vprh;
 
 struct DistState;                        // the distance step's tables and arena (pr_dist.hip)
 struct StrataState;                      // the membership words and the stratified histogram (pr_strata.hip)
+struct ContextState;                     // the sequence-context intervals (pr_context.hip)
 struct BootState;                        // the replicate histogram and the supercluster keys (pr_boot.hip)
 
 struct vpr_handle {
@@ -413,6 +415,7 @@ struct vpr_handle {
     DevResults dR;                       // final results, produced on the device
     DistState *dist = nullptr;           // vpr_distance (pr_dist.hip), created by its first call
     StrataState *strata = nullptr;       // vpr_strata_masks / vpr_strata_upload_masks (pr_strata.hip), released with the batch
+    ContextState *context = nullptr;     // vpr_context_masks (pr_context.hip), released by the next one or vpr_destroy
     BootState *boot = nullptr;           // vpr_pr_counts_boot (pr_boot.hip), created by its first call, released with the batch
     vpr_timing timing;
     bool uploaded = false, executed = false;
@@ -454,6 +457,12 @@ void dist_release_work(vpr_handle *h);                               // pr_dist.
 void strata_free(vpr_handle *h);                                     // pr_strata.hip: the membership words and the stratified histogram
 // pr_strata.hip: the resident membership words (word-major per slot) for pr_boot.hip's stratum cut; false without valid words
 bool strata_view(const vpr_handle *h, int32_t *n_strata, int64_t n_var[VPR_HAPS], const uint64_t *words[VPR_HAPS]);
+// pr_strata.hip, shared with pr_context.hip: the argument checks of vpr_strata_masks (s null: the variant tables alone) and the
+// membership words of the checked variants against interval tables that are already on the device
+int strata_check(vpr_handle *h, const vpr_variants *v, const struct vpr_strata *s);
+int strata_masks_device(vpr_handle *h, const vpr_variants *v, int32_t n_strata, const int64_t *d_iv_off, const int32_t *d_iv_start,
+                        const int32_t *d_iv_stop);
+void context_free(vpr_handle *h);                                    // pr_context.hip: the resident context intervals
 void boot_free(vpr_handle *h);                                       // pr_boot.hip: the replicate histogram and the keys
 // pr_collect.hip, shared with pr_strata.hip: the inputs of a counters call, the host fold of one histogram, the all-reduce
 int pr_counts_inputs(vpr_handle *h, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase, int32_t **d_pb);

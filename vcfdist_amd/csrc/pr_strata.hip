@@ -224,62 +224,60 @@ void strata_free(vpr_handle *h) {
     h->strata = nullptr;
 }
 
-bool strata_view(const vpr_handle *h, int32_t *n_strata, int64_t n_var[VPR_HAPS], const uint64_t *words[VPR_HAPS]) {
-    const StrataState *S = h->strata;
-    if (!S || !S->valid) return false;
-    *n_strata = S->n_strata;
-    for (int s = 0; s < VPR_HAPS; s++) { n_var[s] = S->n_var[s]; words[s] = S->words[s]; }
-    return true;
-}
-
-extern "C" {
-
-int vpr_strata_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *s) {
-    if (!h) return VPR_ERR_ARG;
-    if (!v || !s) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: null argument");
-    if (s->n_strata < 1) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: n_strata must be at least 1");
-    if (s->n_ctg < 1 || s->n_ctg != v->n_ctg)
-        return fail(h, VPR_ERR_ARG, "vpr_strata_masks: the strata number %d contigs, the variants %d", s->n_ctg, v->n_ctg);
-    if (!s->iv_off || v->n_sc < 0 || (v->n_sc > 0 && !v->sc_ctg)) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: null table");
-    const size_t n_rows = size_t(s->n_strata) * size_t(s->n_ctg);
-    if (s->iv_off[0] != 0) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: iv_off[0] is not 0");
-    for (size_t r = 0; r < n_rows; r++) {
-        const int64_t a = s->iv_off[r], b = s->iv_off[r + 1];
-        if (b < a) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: iv_off decreases at row %zu", r);
-        if (b > a && (!s->iv_start || !s->iv_stop)) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: null interval table");
-        if (b - a > INT32_MAX) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: more than 2^31 - 1 intervals in one row");
-        const int k = int(r / size_t(s->n_ctg)), c = int(r % size_t(s->n_ctg));
-        for (int64_t j = a; j < b; j++) {
-            if (s->iv_stop[j] <= s->iv_start[j])
-                return fail(h, VPR_ERR_ARG, "vpr_strata_masks: stratum %d contig %d: region %d-%d has stop <= start", k, c, s->iv_start[j], s->iv_stop[j]);
-            if (j > a && s->iv_start[j] < s->iv_start[j - 1])
-                return fail(h, VPR_ERR_ARG, "vpr_strata_masks: stratum %d contig %d is unsorted: region %d-%d precedes %d-%d", k, c,
-                            s->iv_start[j - 1], s->iv_stop[j - 1], s->iv_start[j], s->iv_stop[j]);
-            if (j > a && s->iv_start[j] < s->iv_stop[j - 1])
-                return fail(h, VPR_ERR_ARG, "vpr_strata_masks: stratum %d contig %d: regions %d-%d and %d-%d overlap", k, c,
-                            s->iv_start[j - 1], s->iv_stop[j - 1], s->iv_start[j], s->iv_stop[j]);
+// the argument checks of vpr_strata_masks: the interval tables (sorted, non-overlapping, non-empty per row) and the variant
+// tables the mask kernel reads (s null: the variant tables alone)
+int strata_check(vpr_handle *h, const vpr_variants *v, const vpr_strata *s) {
+    if (s) {
+        if (s->n_strata < 1) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: n_strata must be at least 1");
+        if (s->n_ctg < 1 || s->n_ctg != v->n_ctg)
+            return fail(h, VPR_ERR_ARG, "vpr_strata_masks: the strata number %d contigs, the variants %d", s->n_ctg, v->n_ctg);
+    }
+    if ((s && !s->iv_off) || v->n_sc < 0 || (v->n_sc > 0 && !v->sc_ctg)) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: null table");
+    if (s) {
+        const size_t n_rows = size_t(s->n_strata) * size_t(s->n_ctg);
+        if (s->iv_off[0] != 0) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: iv_off[0] is not 0");
+        for (size_t r = 0; r < n_rows; r++) {
+            const int64_t a = s->iv_off[r], b = s->iv_off[r + 1];
+            if (b < a) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: iv_off decreases at row %zu", r);
+            if (b > a && (!s->iv_start || !s->iv_stop)) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: null interval table");
+            if (b - a > INT32_MAX) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: more than 2^31 - 1 intervals in one row");
+            const int k = int(r / size_t(s->n_ctg)), c = int(r % size_t(s->n_ctg));
+            for (int64_t j = a; j < b; j++) {
+                if (s->iv_stop[j] <= s->iv_start[j])
+                    return fail(h, VPR_ERR_ARG, "vpr_strata_masks: stratum %d contig %d: region %d-%d has stop <= start", k, c, s->iv_start[j], s->iv_stop[j]);
+                if (j > a && s->iv_start[j] < s->iv_start[j - 1])
+                    return fail(h, VPR_ERR_ARG, "vpr_strata_masks: stratum %d contig %d is unsorted: region %d-%d precedes %d-%d", k, c,
+                                s->iv_start[j - 1], s->iv_stop[j - 1], s->iv_start[j], s->iv_stop[j]);
+                if (j > a && s->iv_start[j] < s->iv_stop[j - 1])
+                    return fail(h, VPR_ERR_ARG, "vpr_strata_masks: stratum %d contig %d: regions %d-%d and %d-%d overlap", k, c,
+                                s->iv_start[j - 1], s->iv_stop[j - 1], s->iv_start[j], s->iv_stop[j]);
+            }
         }
     }
     const int64_t n_sc = v->n_sc;
-    int64_t n_var[VPR_HAPS];
     for (int i = 0; i < VPR_HAPS; i++) {
         if (!v->var_off[i]) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: null var_off");
-        n_var[i] = v->var_off[i][n_sc];
-        if (n_var[i] && (!v->var_pos[i] || !v->var_ref_len[i] || !v->var_type[i])) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: null variant column");
+        if (v->var_off[i][n_sc] && (!v->var_pos[i] || !v->var_ref_len[i] || !v->var_type[i])) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: null variant column");
     }
     for (int64_t k = 0; k < n_sc; k++)
         if (v->sc_ctg[k] < 0 || v->sc_ctg[k] >= v->n_ctg) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: supercluster %lld names contig %d", (long long)k, v->sc_ctg[k]);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (int rc = strata_prepare(h, s->n_strata, n_var)) return rc;
-    StrataState *S = h->strata;
+    return VPR_OK;
+}
 
-    // ---- the columns the kernel reads and the interval tables, one block that lives as long as the call
+// The membership words of the (checked) variants of `v` against interval tables that are on the device already, in the
+// handle's stream order behind whatever filled them: the columns the kernel reads go up in one block that lives as long as
+// the call, k_strata_mask runs once per hap slot, and the words are resident when the call returns.
+int strata_masks_device(vpr_handle *h, const vpr_variants *v, int32_t n_strata, const int64_t *d_iv_off, const int32_t *d_iv_start,
+                        const int32_t *d_iv_stop) {
+    const int64_t n_sc = v->n_sc;
+    int64_t n_var[VPR_HAPS];
+    for (int i = 0; i < VPR_HAPS; i++) n_var[i] = v->var_off[i][n_sc];
+    if (int rc = strata_prepare(h, n_strata, n_var)) return rc;
+    StrataState *S = h->strata;
     struct Piece { const void *src; size_t bytes; size_t at; };
     std::vector<Piece> pieces;
     size_t total = 0;
     auto add = [&](const void *src, size_t bytes) { pieces.push_back({src, bytes, total}); total += (bytes + 255) & ~size_t(255); return pieces.size() - 1; };
-    const size_t n_iv = size_t(s->iv_off[n_rows]);
-    const size_t i_off = add(s->iv_off, 8 * (n_rows + 1)), i_st = add(s->iv_start, 4 * n_iv), i_sp = add(s->iv_stop, 4 * n_iv);
     const size_t i_ctg = add(v->sc_ctg, 4 * size_t(n_sc));
     size_t i_var[VPR_HAPS][4];
     for (int i = 0; i < VPR_HAPS; i++) {
@@ -304,8 +302,7 @@ int vpr_strata_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *s) 
         hipLaunchKernelGGL(k_strata_mask, dim3(unsigned((n_var[i] + 255) / 256), unsigned(S->n_words)), dim3(256), 0, h->stream,
                            reinterpret_cast<const int64_t *>(at(i_var[i][0])), int(n_sc), n_var[i], reinterpret_cast<const int32_t *>(at(i_ctg)),
                            reinterpret_cast<const int32_t *>(at(i_var[i][1])), reinterpret_cast<const int32_t *>(at(i_var[i][2])), at(i_var[i][3]),
-                           reinterpret_cast<const int64_t *>(at(i_off)), reinterpret_cast<const int32_t *>(at(i_st)),
-                           reinterpret_cast<const int32_t *>(at(i_sp)), s->n_strata, s->n_ctg, S->words[i]);
+                           d_iv_off, d_iv_start, d_iv_stop, n_strata, v->n_ctg, S->words[i]);
         HIPCHK(h, hipGetLastError());
     }
     HIPCHK(h, hipEventRecord(S->ev[1], h->stream));
@@ -313,6 +310,40 @@ int vpr_strata_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *s) 
     S->ms_mask = ev_ms(S);
     S->valid = true;
     return VPR_OK;
+}
+
+bool strata_view(const vpr_handle *h, int32_t *n_strata, int64_t n_var[VPR_HAPS], const uint64_t *words[VPR_HAPS]) {
+    const StrataState *S = h->strata;
+    if (!S || !S->valid) return false;
+    *n_strata = S->n_strata;
+    for (int s = 0; s < VPR_HAPS; s++) { n_var[s] = S->n_var[s]; words[s] = S->words[s]; }
+    return true;
+}
+
+extern "C" {
+
+int vpr_strata_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *s) {
+    if (!h) return VPR_ERR_ARG;
+    if (!v || !s) return fail(h, VPR_ERR_ARG, "vpr_strata_masks: null argument");
+    if (int rc = strata_check(h, v, s)) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    // ---- the interval tables: one block that lives as long as the call
+    const size_t n_rows = size_t(s->n_strata) * size_t(s->n_ctg), n_iv = size_t(s->iv_off[n_rows]);
+    const size_t at_st = (8 * (n_rows + 1) + 255) & ~size_t(255), at_sp = at_st + ((4 * n_iv + 255) & ~size_t(255));
+    const size_t total = at_sp + ((4 * n_iv + 255) & ~size_t(255));
+    uint8_t *blk = nullptr;
+    if (x_malloc(h, reinterpret_cast<void **>(&blk), std::max<size_t>(total, 256), SITE) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, VPR_ERR_NOMEM, "vpr_strata_masks: cannot allocate %zu bytes on the device", total);
+    }
+    struct Release { vpr_handle *h; uint8_t *p; ~Release() { (void)hipStreamSynchronize(h->stream); (void)x_free(h, p, SITE); } } release{h, blk};
+    HIPCHK(h, hipMemcpyAsync(blk, s->iv_off, 8 * (n_rows + 1), hipMemcpyHostToDevice, h->stream));
+    if (n_iv) {
+        HIPCHK(h, hipMemcpyAsync(blk + at_st, s->iv_start, 4 * n_iv, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(blk + at_sp, s->iv_stop, 4 * n_iv, hipMemcpyHostToDevice, h->stream));
+    }
+    return strata_masks_device(h, v, s->n_strata, reinterpret_cast<const int64_t *>(blk), reinterpret_cast<const int32_t *>(blk + at_st),
+                               reinterpret_cast<const int32_t *>(blk + at_sp));
 }
 
 int vpr_strata_timing(const vpr_handle *h, double *ms_mask, double *ms_hist) {

@@ -198,6 +198,23 @@ extern "C" int vrp_write_stratified(const char *prefix, const char *const *names
     return VRP_OK;
 }
 
+extern "C" int vrp_write_context_bed(const char *prefix, const char *const *contigs, int32_t n_ctg, const char *const *names, int32_t n_strata,
+                                     const int64_t *iv_off, const int32_t *start, const int32_t *stop) {
+    if (!prefix || !contigs || !names || n_ctg < 0 || n_strata < 0 || !iv_off) return fail(VRP_ERR_ARG, "vrp_write_context_bed: bad argument");
+    const size_t n_rows = size_t(n_ctg) * size_t(n_strata);
+    if (iv_off[n_rows] > iv_off[0] && (!start || !stop)) return fail(VRP_ERR_ARG, "vrp_write_context_bed: null interval table");
+    for (int32_t c = 0; c < n_ctg; c++) if (!contigs[c]) return fail(VRP_ERR_ARG, "vrp_write_context_bed: null contig name");
+    for (int32_t k = 0; k < n_strata; k++) if (!names[k]) return fail(VRP_ERR_ARG, "vrp_write_context_bed: null stratum name");
+    const std::string fn = std::string(prefix) + "context-strata.bed";
+    File bed(fn.c_str());
+    if (!bed) return fail(VRP_ERR_OPEN, "cannot create " + fn);
+    for (size_t r = 0; r < n_rows; r++)
+        for (int64_t j = iv_off[r]; j < iv_off[r + 1]; j++)
+            fprintf(bed, "%s\t%d\t%d\t%s\n", contigs[r / size_t(n_strata)], start[j], stop[j], names[r % size_t(n_strata)]);
+    if (!bed.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn);
+    return VRP_OK;
+}
+
 extern "C" int vrp_write_bootstrap(const char *prefix, const int64_t *counts, const int64_t *counts_boot, int32_t n_rep, uint64_t seed,
                                    int32_t min_qual, int32_t max_qual) {
     if (!prefix || !counts || !counts_boot || n_rep < 1 || max_qual < min_qual) return fail(VRP_ERR_ARG, "vrp_write_bootstrap: bad argument");

@@ -25,7 +25,7 @@ class VrpContig(C.Structure):
                 ("n_flips", C.c_int32), ("switches", A.P_i32), ("flips", A.P_i32)]
 
 
-EXPORTED = ["vrp_phase_blocks", "vrp_write_precision_recall", "vrp_write_stratified", "vrp_write_bootstrap", "vrp_write_bootstrap_stratified", "vrp_write_phase_blocks", "vrp_write_superclusters",
+EXPORTED = ["vrp_phase_blocks", "vrp_write_precision_recall", "vrp_write_stratified", "vrp_write_context_bed", "vrp_write_bootstrap", "vrp_write_bootstrap_stratified", "vrp_write_phase_blocks", "vrp_write_superclusters",
             "vrp_write_switchflips", "vrp_write_phasing_summary", "vrp_ng50",
             "vrp_write_variants", "vrp_write_summary_vcf", "vrp_write_distance", "vrp_write_edits", "vrp_write_vcf", "vrp_last_error"]
 
@@ -137,6 +137,28 @@ def write_stratified(prefix, names, counts, min_qual, max_qual):
     arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
     L.vrp_write_stratified.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, A.P_i64, C.c_int32, C.c_int32]
     _check(L.vrp_write_stratified(prefix.encode(), arr, len(names), A._ptr(cnt, C.c_int64), min_qual, max_qual), "vrp_write_stratified")
+
+
+def write_context_bed(prefix, contigs, names, intervals):
+    """context-strata.bed (include/vcfdist_context.h): contigs in evaluation order, names of the context strata in table order,
+    intervals[contig] = [(starts, stops) per stratum]"""
+    off, st, sp = [0], [], []
+    for c in contigs:
+        rows = intervals[c]
+        if len(rows) != len(names):
+            raise ReportError(f"contig '{c}': intervals of {len(rows)} strata for {len(names)} names")
+        for a, b in rows:
+            st.append(np.asarray(a, np.int32)); sp.append(np.asarray(b, np.int32))
+            off.append(off[-1] + len(st[-1]))
+    off = np.asarray(off, np.int64)
+    st = np.ascontiguousarray(np.concatenate(st + [np.zeros(1, np.int32)]), np.int32)     # (never empty: a pointer is wanted)
+    sp = np.ascontiguousarray(np.concatenate(sp + [np.zeros(1, np.int32)]), np.int32)
+    L = api.lib()
+    carr = (C.c_char_p * max(len(contigs), 1))(*[c.encode() for c in contigs])
+    narr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+    L.vrp_write_context_bed.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_char_p), C.c_int32, A.P_i64, A.P_i32, A.P_i32]
+    _check(L.vrp_write_context_bed(prefix.encode(), carr, len(contigs), narr, len(names), A._ptr(off, C.c_int64), A._ptr(st, C.c_int32),
+                                   A._ptr(sp, C.c_int32)), "vrp_write_context_bed")
 
 
 def write_bootstrap(prefix, counts, counts_boot, seed, min_qual, max_qual):
