@@ -2392,7 +2392,7 @@ struct Exec {
         int rc = VPR_OK;
         if (phases & 1) {
         if (zero) {     // the lane kernel moves bytes per truth ROW, not per window cell: position words 16 B, cell records 8 B written
-            // + 8 B read, path_ptr words 4 B (pr_zl.hip; the walk -- k_zero_walk since round 5 -- has the other 20 of the former 56:
+            // + 8 B read, path_ptr words 4 B (pr_zl.hip; the walk -- k_zero_tail's first phase -- has the other 20 of the former 56:
             // two position words, the path_ptr word, the 8-byte step)
             ls.bytes_algorithmic = 36 * zl_rows;
             ls.cells = 8 * zl_rows;                               // cell slots per row
@@ -2487,20 +2487,13 @@ struct Exec {
             });
             if (rc) return rc;
             ws_.cells_per_thread = 3;
-            if (zero) {      // the walk of what the zero level finished (its third pass until round 5: pr_zl.hip), then the credit walk
-                ws_.bytes_algorithmic = 20 * zl_rows;
-                rc = timed(3, ws_, ks, "k_zero_walk", [&] {
-                    hipLaunchKernelGGL(k_zero_walk, dim3((cnt + 63) / 64), dim3(64), 0, ks, h->d_descs, list, cnt, h->d_zl_hdr + zl_wave0,
-                                       h->d_zl_in, h->d_zl_log, h->d_outs, a_path, (h->cfg.flags & VPR_CFG_KEEP_PATHS) ? 1 : 0, tag,
-                                       h->lane_prio_rows);
-                });
-                if (rc) return rc;
-                ws_.bytes_algorithmic = 0;
-            }
-            if (zero) rc = timed(3, ws_, ks, "k_zero_credit", [&] {
-                hipLaunchKernelGGL(k_zero_credit, dim3((cnt + 63) / 64), dim3(64), 0, ks, h->dB, h->d_descs, list, cnt,
-                                   h->d_zl_hdr + zl_wave0, h->d_zl_log, h->d_outs, h->d_secs, h->d_fp_table, h->d_jobs,
-                                   h->d_njobs, h->jobs_cap, tag);
+            // the zero level's tail: the walk of what it finished (its third pass until round 5: pr_zl.hip) and the credit walk,
+            // one launch (k_zero_tail)
+            if (zero) ws_.bytes_algorithmic = 20 * zl_rows;      // (the walk's: two position words, the path_ptr word, the 8-byte step)
+            if (zero) rc = timed(3, ws_, ks, "k_zero_tail", [&] {
+                hipLaunchKernelGGL(k_zero_tail, dim3((cnt + 63) / 64), dim3(64), 0, ks, h->dB, h->d_descs, list, cnt, h->d_zl_hdr + zl_wave0,
+                                   h->d_zl_in, h->d_zl_log, h->d_outs, a_path, (h->cfg.flags & VPR_CFG_KEEP_PATHS) ? 1 : 0, h->d_secs,
+                                   h->d_fp_table, h->d_jobs, h->d_njobs, h->jobs_cap, tag, h->lane_prio_rows);
             });
             // (a launch of a few thousand alignments -- a tie round, a late retry round -- lasts as long as its longest member:
             // a wavefront per alignment reads the path in coalesced chunks, 0.45 us per row against 1.3 for a lane)
@@ -2638,15 +2631,10 @@ struct Exec {
             ordered_fails(list, n_all, h->d_d1_fail, h->d_d1_info + 2, n_dev, ks);
         } else if (ph == 4) {
             ls.cells_per_thread = 3;
-            rc = timed(3, ls, ks, "k_one_walk", [&] {
-                hipLaunchKernelGGL(k_one_walk, dim3(nw), dim3(64), 0, ks, h->d_descs, list, n_dev, cap, h->d_d1_hdr, h->d_d1_in, h->d_d1_log,
+            rc = timed(3, ls, ks, "k_one_tail", [&] {
+                hipLaunchKernelGGL(k_one_tail, dim3(nw), dim3(64), 0, ks, h->dB, h->d_descs, list, n_dev, cap, h->d_d1_hdr, h->d_d1_in, h->d_d1_log,
                                    h->d_outs, reinterpret_cast<PathEnt *>(h->plan0.arena), (h->cfg.flags & VPR_CFG_KEEP_PATHS) ? 1 : 0, h->d_d1_info,
-                                   std::max(1, h->lane_prio_rows / 4));
-            });
-            if (rc) return rc;
-            rc = timed(3, ls, ks, "k_one_credit", [&] {
-                hipLaunchKernelGGL(k_one_credit, dim3(nw), dim3(64), 0, ks, h->dB, h->d_descs, list, n_dev, cap, h->d_d1_hdr, h->d_d1_log,
-                                   h->d_outs, h->d_secs, h->d_fp_table, h->d_jobs, h->d_njobs, h->jobs_cap, ztag);
+                                   h->d_secs, h->d_fp_table, h->d_jobs, h->d_njobs, h->jobs_cap, ztag, std::max(1, h->lane_prio_rows / 4));
             });
         }
         return rc;

@@ -24,7 +24,7 @@
 //            INS / DEL into G1), and per cell THE move the walk will take: among the moves that reach the maximum the first by
 //            the walk's priority (dist.cpp:907-935), with the slot it lands in.  One byte per cell.
 //   pass 4   the walk + sync flags (dist.cpp:865-998) along those bytes; the steps are the 8-byte records of k_zero_lane plus an
-//            edit bit and "truth row = step - 1" behind an INS step; k_one_credit reads them like k_zero_credit.
+//            edit bit and "truth row = step - 1" behind an INS step; k_one_tail's credit phase reads them like k_zero_tail's.
 //
 // Not taken (the lane stays rejected and re-runs in place with the 16-cell kernels, as before): s >= 2; s = 1 only at the REF
 // plane's end cell; a fifth B0 / F0 cell of a plane in one row; a position with three or more swap sources; the tie above.
@@ -695,20 +695,40 @@ __global__ void __launch_bounds__(64, 3) k_one_lane(const AlnDesc *__restrict__ 
     }
 
     lapck(2);
-    // (pass 4, the walk, is a kernel of its own -- k_one_walk, on the side stream in front of k_one_credit -- like the zero level's:
+    // (pass 4, the walk, is the first phase of a kernel of its own -- k_one_tail, on the side stream -- like the zero level's:
     // this launch is on the short part's chain)
     if (ok) { AlnOut &o = outs[a]; o.beg_plane = beg_plane; o.path_len = -1; }       // (-1: walk pending)
 }
 
 // ===========================================================================
-// K1Lw: pass 4 of the distance-1 lane level -- the walk + sync flags (dist.cpp:865-998) along the move bytes k_one_lane left; the
-// steps are the 8-byte records of k_zero_walk plus an edit bit and "truth row one behind the index" (after an INS step)
+// K1Lt: the tail of the distance-1 lane level, both passes in one wave like the zero level's (k_zero_tail, pr_zl.hip):
+//   phase A  pass 4 -- the walk + sync flags (dist.cpp:865-998) along the move bytes k_one_lane left; the steps are the 8-byte
+//            records of the zero level's walk plus an edit bit and "truth row one behind the index" (after an INS step)
+//   phase B  the credit sections of the alignments k_one_lane finished (credit_walk), read from those records
 // ===========================================================================
-__global__ void __launch_bounds__(64, 8) k_one_walk(const AlnDesc *__restrict__ descs, const int32_t *__restrict__ list,
-                                                    const int32_t *__restrict__ n_dev, int n_cap, const ZlWave *__restrict__ hdr,
-                                                    const uint32_t *__restrict__ zin, uint4 *__restrict__ zlog,
-                                                    AlnOut *__restrict__ outs, PathEnt *__restrict__ paths, int keep_paths,
-                                                    int32_t *__restrict__ info, int prio_rows) {
+struct D1Fetch {
+    const uint2 *log;
+    int64_t pre_i;
+    uint2 pre;
+    __device__ PathEnt operator()(int64_t i) {
+        const uint2 v = (i == pre_i) ? pre : log[i * 64];
+        if (i > 0) { pre_i = i - 1; pre = log[(i - 1) * 64]; }
+        PathEnt e;
+        e.a = (v.x & 0xffffu) | (((v.x >> 16) & 1u) << 31);
+        e.b = uint32_t(i - int64_t((v.x >> 21) & 1u)) | (((v.x >> 17) & 1u) << 31) | (((v.x >> 20) & 1u) << 30) | (((v.x >> 18) & 3u) << 28);
+        e.qref = int(v.y & 0xffffu) - 1;
+        e.tref = int(v.y >> 16) - 1;
+        return e;
+    }
+};
+
+__global__ void __launch_bounds__(64) k_one_tail(DevBatch B, const AlnDesc *__restrict__ descs, const int32_t *__restrict__ list,
+                                                 const int32_t *__restrict__ n_dev, int n_cap, const ZlWave *__restrict__ hdr,
+                                                 const uint32_t *__restrict__ zin, uint4 *__restrict__ zlog,
+                                                 AlnOut *__restrict__ outs, PathEnt *__restrict__ paths, int keep_paths,
+                                                 int32_t *__restrict__ info, Section *__restrict__ secs,
+                                                 int32_t *const *__restrict__ fp_group, EdJob *__restrict__ jobs,
+                                                 int32_t *__restrict__ n_jobs, int32_t jobs_cap, int ztag, int prio_rows) {
     const int w = blockIdx.x, lane = threadIdx.x;
     const ZlWave H = hdr[w];
     if (H.mt <= 0) return;
@@ -716,32 +736,37 @@ __global__ void __launch_bounds__(64, 8) k_one_walk(const AlnDesc *__restrict__ 
     const int n_list = min(*n_dev, n_cap);
     const int wi = w * 64 + lane;
     const int a_ = wi < n_list ? list[wi] : -1;
+    const bool live = a_ >= 0;
     const int a = max(a_, 0);
-    const AlnDesc *dp = descs + a;
-    const bool ok = a_ >= 0 && outs[a].band_ok == D1_TAG && outs[a].path_len == -1;
-    const int Lq = ok ? dp->Lq : 1, Lr = ok ? dp->Lr : 1;
+    const AlnDesc d = descs[a];         // (a lane without an alignment reads the list's first: loaded, never used)
+    AlnOut &O = outs[a];
+    const bool here = live && O.band_ok == D1_TAG;       // finished by k_one_lane
+    int path_len = here ? O.path_len : 0;                // (-1: walk pending)
+    uint32_t status = here ? O.status : 0u;              // what earlier launches left + what the walk finds: phase B's test
+    const bool ok = here && path_len == -1;
+    const int Lq = ok ? d.Lq : 1, Lr = ok ? d.Lr : 1;
     const int L[2] = {Lq, Lr};
-    const int nrow = ok ? dp->Lt : 0;
+    const int nrow = ok ? d.Lt : 0;
     int bmax = nrow;
 #pragma unroll
     for (int o = 32; o; o >>= 1) bmax = max(bmax, __shfl_xor(bmax, o));
-    if (bmax == 0) return;
-    const auto rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(zin + H.in_off), 0, 256 * (2 * H.mq + 2 * H.mr + H.mt), 0x00020000);
-    const auto rlog = __builtin_amdgcn_make_buffer_rsrc(zlog + H.log_off, 0, 2560 * (H.mt + 1), 0x00020000);
-    const uint32_t lane4 = uint32_t(lane) << 2, lane8 = uint32_t(lane) << 3, lane16 = uint32_t(lane) << 4;
-    const uint32_t posW[2] = {0u, uint32_t(2 * H.mq) << 8};
-    const uint32_t post = uint32_t(2 * H.mq + 2 * H.mr) << 8;
-    const uint32_t logB1 = uint32_t(H.mt + 1) << 10;
-    auto in_at = [&](uint32_t off) -> uint32_t { return __builtin_amdgcn_raw_buffer_load_b32(rin, off, 0, 0); };
-    auto word_at = [&](int p, int x, bool on) -> uint32_t { return in_at(on ? posW[p] + (uint32_t(x) << 8) + lane4 : ZL_OOB); };
-    auto t_at = [&](int t, bool on) -> uint32_t { return in_at(on ? post + (uint32_t(t) << 8) + lane4 : ZL_OOB); };
-    const int beg_plane = ok ? outs[a].beg_plane : 0;
-    auto lapck = [&](int) {};
+    if (!__any(here)) return;          // (wave-uniform: phase A's loop below is the whole wave's)
     {
-        PathEnt *path = paths + dp->path_off;
+        // ---------------- phase A: the walk
+        const auto rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(zin + H.in_off), 0, 256 * (2 * H.mq + 2 * H.mr + H.mt), 0x00020000);
+        const auto rlog = __builtin_amdgcn_make_buffer_rsrc(zlog + H.log_off, 0, 2560 * (H.mt + 1), 0x00020000);
+        const uint32_t lane4 = uint32_t(lane) << 2, lane8 = uint32_t(lane) << 3, lane16 = uint32_t(lane) << 4;
+        const uint32_t posW[2] = {0u, uint32_t(2 * H.mq) << 8};
+        const uint32_t post = uint32_t(2 * H.mq + 2 * H.mr) << 8;
+        const uint32_t logB1 = uint32_t(H.mt + 1) << 10;
+        auto in_at = [&](uint32_t off) -> uint32_t { return __builtin_amdgcn_raw_buffer_load_b32(rin, off, 0, 0); };
+        auto word_at = [&](int p, int x, bool on) -> uint32_t { return in_at(on ? posW[p] + (uint32_t(x) << 8) + lane4 : ZL_OOB); };
+        auto t_at = [&](int t, bool on) -> uint32_t { return in_at(on ? post + (uint32_t(t) << 8) + lane4 : ZL_OOB); };
+        const int beg_plane = ok ? O.beg_plane : 0;
+        PathEnt *path = paths + d.path_off;
         const uint32_t logS0 = logB1;           // the steps replace the F0 flag bytes
         int hi = beg_plane, slot = 0, layer = 0, x = 0, ti = 0, mv_in = -1;
-        uint32_t status = 0;
+        uint32_t wstatus = 0;
         bool wok = ok, done = !ok;
         int plen = 0;
         for (int i = 0; i <= bmax; i++) {
@@ -779,72 +804,38 @@ __global__ void __launch_bounds__(64, 8) k_one_walk(const AlnDesc *__restrict__ 
                 else {
                     const uint32_t m = (mvw >> (8 * slot)) & 0xffu;
                     const int rank = int(m & 7u), to = int((m >> 3) & 3u);
-                    if (m == 0xffu) { status |= VPR_ST_ERR_NO_PTR; wok = false; }
+                    if (m == 0xffu) { wstatus |= VPR_ST_ERR_NO_PTR; wok = false; }
                     else if (rank == MV_MAT) { x++; ti++; }
                     else if (rank == MV_SWP_R || rank == MV_SWP_Q) { x = ZW_PTR(cw) + 1; hi = 1 - hi; slot = to; ti++; }
                     else if (rank == MV_SUB) { x++; ti++; layer = 1; slot = to; }
                     else if (rank == MV_INS) { x++; layer = 1; slot = to; }
                     else { ti++; layer = 1; slot = to; }          // MV_DEL
                     mv_in = rank;
-                    if (ti >= nrow || x >= L[hi]) { status |= VPR_ST_ERR_NO_PTR; wok = false; }
+                    if (ti >= nrow || x >= L[hi]) { wstatus |= VPR_ST_ERR_NO_PTR; wok = false; }
                 }
             }
         }
-        lapck(3);
         {
             const int nf = __popcll(__ballot(ok && wok && done));
             if (lane == 0 && nf) atomicAdd(info + 4, nf);
         }
         if (ok) {
-            AlnOut &o = outs[a];
             wok = wok && done;
-            if (!wok) status |= VPR_ST_ERR_NO_PTR;
-            o.beg_plane = beg_plane;
-            o.path_len = wok ? plen : 0;
-            if (!wok) o.n_sec = 0;
-            if (status) atomicOr(&o.status, status);
+            if (!wok) wstatus |= VPR_ST_ERR_NO_PTR;
+            O.beg_plane = beg_plane;
+            path_len = wok ? plen : 0;
+            O.path_len = path_len;
+            if (!wok) O.n_sec = 0;
+            if (wstatus) atomicOr(&O.status, wstatus);
+            status |= wstatus;
         }
     }
-}
-
-// ===========================================================================
-// K1Lc: credit sections of the alignments k_one_lane finished (as k_zero_credit; a step carries its edit bit and how far its
-// truth row lies behind its index -- one behind an INS step)
-// ===========================================================================
-struct D1Fetch {
-    const uint2 *log;
-    int64_t pre_i;
-    uint2 pre;
-    __device__ PathEnt operator()(int64_t i) {
-        const uint2 v = (i == pre_i) ? pre : log[i * 64];
-        if (i > 0) { pre_i = i - 1; pre = log[(i - 1) * 64]; }
-        PathEnt e;
-        e.a = (v.x & 0xffffu) | (((v.x >> 16) & 1u) << 31);
-        e.b = uint32_t(i - int64_t((v.x >> 21) & 1u)) | (((v.x >> 17) & 1u) << 31) | (((v.x >> 20) & 1u) << 30) | (((v.x >> 18) & 3u) << 28);
-        e.qref = int(v.y & 0xffffu) - 1;
-        e.tref = int(v.y >> 16) - 1;
-        return e;
-    }
-};
-
-__global__ void __launch_bounds__(64) k_one_credit(DevBatch B, const AlnDesc *__restrict__ descs, const int32_t *__restrict__ list,
-                                                   const int32_t *__restrict__ n_dev, int n_cap, const ZlWave *__restrict__ hdr,
-                                                   const uint4 *__restrict__ zlog, AlnOut *__restrict__ outs, Section *__restrict__ secs,
-                                                   int32_t *const *__restrict__ fp_group, EdJob *__restrict__ jobs,
-                                                   int32_t *__restrict__ n_jobs, int32_t jobs_cap, int ztag) {
-    const int w = blockIdx.x, lane = threadIdx.x;
-    const ZlWave H = hdr[w];
-    if (H.mt <= 0) return;
-    const int wi = w * 64 + lane;
-    if (wi >= min(*n_dev, n_cap)) return;
-    const int a = list[wi];
-    if (a < 0) return;
-    const AlnDesc d = descs[a];
-    AlnOut &O = outs[a];
-    if (d.band_pad != ztag || O.band_ok != D1_TAG) return;
-    if (O.status & (VPR_ST_ERR_NO_PTR | VPR_ST_ERR_LIMIT)) return;
+    // the wave's own step records before its loads of the same addresses (see k_zero_tail)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // ---------------- phase B: the credit sections
+    if (!here || d.band_pad != ztag || (status & (VPR_ST_ERR_NO_PTR | VPR_ST_ERR_LIMIT))) return;
     D1Fetch f{reinterpret_cast<const uint2 *>(zlog + H.log_off + 64 * (int64_t(H.mt) + 1)) + lane, -1, make_uint2(0, 0)};     // behind region A
-    credit_walk<false, D1Fetch, true>(B, d, O, a, nullptr, int64_t(O.path_len), 0u, secs, fp_group, jobs, n_jobs, jobs_cap, true, f);
+    credit_walk<false, D1Fetch, true>(B, d, O, a, nullptr, int64_t(path_len), 0u, secs, fp_group, jobs, n_jobs, jobs_cap, true, f);
 }
 
 #endif

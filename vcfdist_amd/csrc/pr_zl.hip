@@ -18,7 +18,7 @@
 //             they and the slot of the SWP successor are a second, 4-byte record per row.
 //   walk      get_prec_recall_path_sync (dist.cpp:865-998): from the begin cell along the path_ptr bits by the
 //             reference's priorities (REF plane: SWP first; then MAT; QUERY plane: SWP last), sync flag per step; the
-//             steps are 8-byte records for k_zero_credit (16-byte path entries on request, VPR_CFG_KEEP_PATHS).
+//             steps are 8-byte records for the credit walk (16-byte path entries on request, VPR_CFG_KEEP_PATHS).
 //
 // What it does not take: an alignment whose end cells are not reached at distance 0 (s > 0), a row with more than four
 // diagonals on a plane, lengths that do not fit the 16-bit position fields, and a cell that receives a SWP edge from two
@@ -439,99 +439,24 @@ __global__ void __launch_bounds__(64, 6) k_zero_lane(const AlnDesc *__restrict__
     // (QUERY, 0, 0) on a path to the end?  dist.cpp:811-814
     const int beg_plane = sc[0][0] >= 0 ? VPR_PLANE_QUERY : VPR_PLANE_REF;
 
-    // (the walk -- a third pass of dependent loads, the address of a row's position word comes out of the row before -- is a
-    // kernel of its own, k_zero_walk, on the side stream of the credit walks: this launch is on the short part's chain, that one
-    // runs beside the distance-1 level and the in-place 16-cell round)
+    // (the walk -- a third pass of dependent loads, the address of a row's position word comes out of the row before -- is the
+    // first phase of a kernel of its own, k_zero_tail, on the side stream of the credit walks: this launch is on the short part's
+    // chain, that one runs beside the distance-1 level and the in-place 16-cell round)
     if (ok) outs[a].beg_plane = beg_plane;
 }
 
 // ===========================================================================
-// KZw: the walk of the alignments k_zero_lane finished (get_prec_recall_path_sync, dist.cpp:905-982, sync flags :949-968), one
-// lane per alignment over the wave's log: path_ptr words in, step records out (what k_zero_credit reads).
-// ===========================================================================
-__global__ void __launch_bounds__(64, 8) k_zero_walk(const AlnDesc *__restrict__ descs, const int32_t *__restrict__ list, int n_list,
-                                                  const ZlWave *__restrict__ hdr, const uint32_t *__restrict__ zin,
-                                                  uint4 *__restrict__ zlog, AlnOut *__restrict__ outs, PathEnt *__restrict__ paths,
-                                                  int keep_paths, int tag, int prio_rows) {
-    const int w = blockIdx.x, lane = threadIdx.x;
-    const ZlWave H = hdr[w];
-    if (H.mt >= prio_rows) __builtin_amdgcn_s_setprio(2);
-    const int wi = w * 64 + lane;
-    const int a_ = wi < n_list ? list[wi] : -1;
-    const bool live = a_ >= 0;
-    const int a = max(a_, 0);
-    const AlnDesc *dp = descs + a;
-    const auto rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(zin + H.in_off), 0, 256 * (H.mq + H.mr + H.mt), 0x00020000);
-    const auto rlog = __builtin_amdgcn_make_buffer_rsrc(zlog + H.log_off, 0, 1280 * H.mt, 0x00020000);
-    const uint32_t lane4 = uint32_t(lane) << 2, lane8 = uint32_t(lane) << 3;
-    const uint32_t pos0[2] = {0u, uint32_t(H.mq) << 8}, post = uint32_t(H.mq + H.mr) << 8;
-    const uint32_t logP0 = uint32_t(H.mt) << 9, logS0 = logP0 + (uint32_t(H.mt) << 8);
-    auto in_at = [&](uint32_t off) -> uint32_t { return __builtin_amdgcn_raw_buffer_load_b32(rin, off, 0, 0); };
-    // finished by k_zero_lane: accepted by its exit test (k_fwd_band_finish) at this level
-    const bool ok = live && dp->band_pad == tag && outs[a].band_ok == tag;
-    const int nrow = ok ? dp->Lt : 0;
-    int bmax = nrow;
-#pragma unroll
-    for (int o = 32; o; o >>= 1) bmax = max(bmax, __shfl_xor(bmax, o));
-    if (bmax == 0) return;
-    const int beg_plane = ok ? outs[a].beg_plane : 0;
-    // ---------------- walk (dist.cpp:905-982) + sync flags (dist.cpp:949-968)
-    PathEnt *path = paths + dp->path_off;
-    int hi = beg_plane, slot = 0, mv_in = 0, x = 0;
-    uint32_t status = 0;
-    bool wok = ok;
-    for (int t = 0; t < bmax; t++) {
-        const bool act = wok && t < nrow;
-        const uint32_t ppw = __builtin_amdgcn_raw_buffer_load_b32(rlog, (act && t + 1 < nrow) ? logP0 + (uint32_t(t) << 8) + lane4 : ZL_OOB, 0, 0);
-        const uint32_t tw = in_at(act ? post + (uint32_t(t) << 8) + lane4 : ZL_OOB);
-        const uint32_t cw = in_at(act ? pos0[hi] + (uint32_t(x) << 8) + lane4 : ZL_OOB);
-        const int trv = ZW_PTR(tw), qref = hi ? x : ZW_PTR(cw);
-        uint32_t sync = 1;
-        if (mv_in) {
-            const bool in_t = (tw & ZW_PV) && !(tw & ZW_PB);
-            const bool in_q = hi == 0 && (cw & ZW_PV) && !(cw & ZW_PB);
-            sync = (!in_t && !in_q && !((tw | cw) & ZW_INS) && trv == qref) ? 1u : 0u;
-        }
-        // "the reference base at this step's reference coordinate equals its truth base": what the credit walk compares for the
-        // one-base sections between neighbouring sync points (nearly every step), from the words at hand instead of two scattered
-        // byte loads per lane and step in k_zero_credit.  On the REF plane the cell's base IS that reference base; on the QUERY
-        // plane it is wherever the hap position lies outside a variant (generate_ptrs_strs copies the reference there); inside
-        // one the bit is marked invalid and the credit walk loads the bases.
-        const uint32_t eqb = (ZW_BASE(cw) == ZW_BASE(tw) ? 1u : 0u) | ((hi || !(cw & ZW_PV)) ? 2u : 0u);
-        zl_u2 st;           // the step as k_zero_credit reads it
-        st.x = uint32_t(x) | (uint32_t(hi) << 16) | (sync << 17) | (eqb << 18);
-        st.y = uint32_t(qref + 1) | (uint32_t(trv + 1) << 16);
-        __builtin_amdgcn_raw_buffer_store_b64(st, rlog, act ? logS0 + (uint32_t(t) << 9) + lane8 : ZL_OOB, 0, 0);
-        if ((keep_paths & 1) && act) {       // VPR_CFG_KEEP_PATHS: also as a 16-byte path entry (vpr_download_path)
-            uint4 pe;
-            pe.x = uint32_t(x) | (uint32_t(hi) << 31);
-            pe.y = uint32_t(t) | (sync << 31);
-            pe.z = uint32_t(qref);
-            pe.w = uint32_t(trv);
-            *reinterpret_cast<uint4 *>(path + t) = pe;
-        }
-        if (act && t + 1 < nrow) {      // the move out of the cell, by priority; a SWP edge lands behind the cell's pointer
-            const uint32_t nb = (ppw >> (4 * ((hi << 2) | slot))) & 15u;
-            if (hi == 1 && (nb & 2u)) { hi = 0; slot = int(nb >> 2); x = ZW_PTR(cw) + 1; }
-            else if (nb & 1u) { x = x + 1; }
-            else if (hi == 0 && (nb & 2u)) { hi = 1; slot = int(nb >> 2); x = ZW_PTR(cw) + 1; }
-            else { status |= VPR_ST_ERR_NO_PTR; wok = false; }
-            mv_in = 1;
-        }
-    }
-    if (ok) {
-        AlnOut &o = outs[a];
-        o.path_len = wok ? nrow : 0;
-        if (!wok) o.n_sec = 0;
-        if (status) atomicOr(&o.status, status);
-    }
-}
-
-// ===========================================================================
-// KZc: the credit sections of the alignments k_zero_lane finished (integer part of calc_prec_recall, dist.cpp:1035-1400:
-// credit_walk), one lane per alignment.  The path comes from the walk's step records: row t of lane l is 8 bytes at
-// (t * 64 + l) * 8 of the wave's third log region, so a wave's load of a step is one 512-byte stretch instead of 64 lines
-// of 64 different path blocks.
+// KZt: the tail of the alignments k_zero_lane finished, one lane per alignment, both passes in one wave:
+//   phase A  the walk (get_prec_recall_path_sync, dist.cpp:905-982, sync flags :949-968) over the wave's log: path_ptr words in,
+//            8-byte step records out
+//   phase B  the credit sections (integer part of calc_prec_recall, dist.cpp:1035-1400: credit_walk) over those records: row t
+//            of lane l is 8 bytes at (t * 64 + l) * 8 of the wave's third log region, so a wave's load of a step is one 512-byte
+//            stretch instead of 64 lines of 64 different path blocks.
+// The two were launches of their own (k_zero_walk, k_zero_credit) until the records' round trip through HBM -- 1.36 GB written,
+// read back behind a launch boundary when they had long left the caches -- and the second launch's descriptor, AlnOut, list and
+// header loads were found to be a fifth of the zero level's traffic.  Here a lane reads back what it wrote itself a few
+// microseconds earlier (same thread, same address: no visibility beyond the wave's own is needed), and what phase A loaded of
+// the alignment stays in registers for phase B.
 // ===========================================================================
 struct ZlFetch {
     const uint2 *log;       // this lane's column of the wave's step records
@@ -549,23 +474,96 @@ struct ZlFetch {
     }
 };
 
-__global__ void __launch_bounds__(64) k_zero_credit(DevBatch B, const AlnDesc *__restrict__ descs, const int32_t *__restrict__ list,
-                                                    int n_list, const ZlWave *__restrict__ hdr, const uint4 *__restrict__ zlog,
-                                                    AlnOut *__restrict__ outs, Section *__restrict__ secs,
-                                                    int32_t *const *__restrict__ fp_group, EdJob *__restrict__ jobs,
-                                                    int32_t *__restrict__ n_jobs, int32_t jobs_cap, int tag) {
+__global__ void __launch_bounds__(64) k_zero_tail(DevBatch B, const AlnDesc *__restrict__ descs, const int32_t *__restrict__ list, int n_list,
+                                                  const ZlWave *__restrict__ hdr, const uint32_t *__restrict__ zin,
+                                                  uint4 *__restrict__ zlog, AlnOut *__restrict__ outs, PathEnt *__restrict__ paths,
+                                                  int keep_paths, Section *__restrict__ secs, int32_t *const *__restrict__ fp_group,
+                                                  EdJob *__restrict__ jobs, int32_t *__restrict__ n_jobs, int32_t jobs_cap, int tag,
+                                                  int prio_rows) {
     const int w = blockIdx.x, lane = threadIdx.x;
-    const int wi = w * 64 + lane;
-    if (wi >= n_list) return;
-    const int a = list[wi];
-    if (a < 0) return;
-    const AlnDesc d = descs[a];
-    AlnOut &O = outs[a];
-    if (d.band_pad != tag || O.band_ok != tag) return;       // not finished by k_zero_lane: the in-place 16-cell round has it
-    if (O.status & (VPR_ST_ERR_NO_PTR | VPR_ST_ERR_LIMIT)) return;
     const ZlWave H = hdr[w];
+    if (H.mt >= prio_rows) __builtin_amdgcn_s_setprio(2);
+    const int wi = w * 64 + lane;
+    const int a_ = wi < n_list ? list[wi] : -1;
+    const bool live = a_ >= 0;
+    const int a = max(a_, 0);
+    const AlnDesc d = descs[a];         // (a lane without an alignment reads the list's first: loaded, never used)
+    AlnOut &O = outs[a];
+    // finished by k_zero_lane: accepted by its exit test (k_fwd_band_finish) at this level
+    const bool ok = live && d.band_pad == tag && O.band_ok == tag;
+    const int nrow = ok ? d.Lt : 0;
+    int bmax = nrow;
+#pragma unroll
+    for (int o = 32; o; o >>= 1) bmax = max(bmax, __shfl_xor(bmax, o));
+    if (bmax == 0) return;
+    uint32_t status = ok ? O.status : 0u;       // what earlier launches left + what the walk finds: phase B's test, from the register
+    bool wok = ok;
+    {
+        // ---------------- phase A: walk (dist.cpp:905-982) + sync flags (dist.cpp:949-968)
+        const auto rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(zin + H.in_off), 0, 256 * (H.mq + H.mr + H.mt), 0x00020000);
+        const auto rlog = __builtin_amdgcn_make_buffer_rsrc(zlog + H.log_off, 0, 1280 * H.mt, 0x00020000);
+        const uint32_t lane4 = uint32_t(lane) << 2, lane8 = uint32_t(lane) << 3;
+        const uint32_t pos0[2] = {0u, uint32_t(H.mq) << 8}, post = uint32_t(H.mq + H.mr) << 8;
+        const uint32_t logP0 = uint32_t(H.mt) << 9, logS0 = logP0 + (uint32_t(H.mt) << 8);
+        auto in_at = [&](uint32_t off) -> uint32_t { return __builtin_amdgcn_raw_buffer_load_b32(rin, off, 0, 0); };
+        const int beg_plane = ok ? O.beg_plane : 0;
+        PathEnt *path = paths + d.path_off;
+        int hi = beg_plane, slot = 0, mv_in = 0, x = 0;
+        uint32_t wstatus = 0;
+        for (int t = 0; t < bmax; t++) {
+            const bool act = wok && t < nrow;
+            const uint32_t ppw = __builtin_amdgcn_raw_buffer_load_b32(rlog, (act && t + 1 < nrow) ? logP0 + (uint32_t(t) << 8) + lane4 : ZL_OOB, 0, 0);
+            const uint32_t tw = in_at(act ? post + (uint32_t(t) << 8) + lane4 : ZL_OOB);
+            const uint32_t cw = in_at(act ? pos0[hi] + (uint32_t(x) << 8) + lane4 : ZL_OOB);
+            const int trv = ZW_PTR(tw), qref = hi ? x : ZW_PTR(cw);
+            uint32_t sync = 1;
+            if (mv_in) {
+                const bool in_t = (tw & ZW_PV) && !(tw & ZW_PB);
+                const bool in_q = hi == 0 && (cw & ZW_PV) && !(cw & ZW_PB);
+                sync = (!in_t && !in_q && !((tw | cw) & ZW_INS) && trv == qref) ? 1u : 0u;
+            }
+            // "the reference base at this step's reference coordinate equals its truth base": what the credit walk compares for the
+            // one-base sections between neighbouring sync points (nearly every step), from the words at hand instead of two scattered
+            // byte loads per lane and step in phase B.  On the REF plane the cell's base IS that reference base; on the QUERY
+            // plane it is wherever the hap position lies outside a variant (generate_ptrs_strs copies the reference there); inside
+            // one the bit is marked invalid and the credit walk loads the bases.
+            const uint32_t eqb = (ZW_BASE(cw) == ZW_BASE(tw) ? 1u : 0u) | ((hi || !(cw & ZW_PV)) ? 2u : 0u);
+            zl_u2 st;           // the step as phase B reads it (ZlFetch)
+            st.x = uint32_t(x) | (uint32_t(hi) << 16) | (sync << 17) | (eqb << 18);
+            st.y = uint32_t(qref + 1) | (uint32_t(trv + 1) << 16);
+            __builtin_amdgcn_raw_buffer_store_b64(st, rlog, act ? logS0 + (uint32_t(t) << 9) + lane8 : ZL_OOB, 0, 0);
+            if ((keep_paths & 1) && act) {       // VPR_CFG_KEEP_PATHS: also as a 16-byte path entry (vpr_download_path)
+                uint4 pe;
+                pe.x = uint32_t(x) | (uint32_t(hi) << 31);
+                pe.y = uint32_t(t) | (sync << 31);
+                pe.z = uint32_t(qref);
+                pe.w = uint32_t(trv);
+                *reinterpret_cast<uint4 *>(path + t) = pe;
+            }
+            if (act && t + 1 < nrow) {      // the move out of the cell, by priority; a SWP edge lands behind the cell's pointer
+                const uint32_t nb = (ppw >> (4 * ((hi << 2) | slot))) & 15u;
+                if (hi == 1 && (nb & 2u)) { hi = 0; slot = int(nb >> 2); x = ZW_PTR(cw) + 1; }
+                else if (nb & 1u) { x = x + 1; }
+                else if (hi == 0 && (nb & 2u)) { hi = 1; slot = int(nb >> 2); x = ZW_PTR(cw) + 1; }
+                else { wstatus |= VPR_ST_ERR_NO_PTR; wok = false; }
+                mv_in = 1;
+            }
+        }
+        if (ok) {
+            O.path_len = wok ? nrow : 0;
+            if (!wok) O.n_sec = 0;
+            if (wstatus) atomicOr(&O.status, wstatus);
+        }
+        status |= wstatus;
+    }
+    // The wave's own step records have to be in place before its loads of the same addresses: the stores went through a buffer
+    // descriptor, the loads are plain global ones.  Once per wave; nothing beyond the wave's own view is needed -- a lane reads
+    // only the column it wrote.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // ---------------- phase B: the credit sections, for the lanes the walk brought to their end
+    if (!ok || (status & (VPR_ST_ERR_NO_PTR | VPR_ST_ERR_LIMIT))) return;
     ZlFetch f{reinterpret_cast<const uint2 *>(zlog + H.log_off + 48 * int64_t(H.mt)) + lane, -1, make_uint2(0, 0)};     // behind 512 + 256 bytes per row
-    credit_walk<false, ZlFetch, true>(B, d, O, a, nullptr, int64_t(O.path_len), 0u, secs, fp_group, jobs, n_jobs, jobs_cap, true, f);
+    credit_walk<false, ZlFetch, true>(B, d, O, a, nullptr, int64_t(wok ? nrow : 0), 0u, secs, fp_group, jobs, n_jobs, jobs_cap, true, f);
 }
 
 #endif
