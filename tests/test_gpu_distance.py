@@ -84,8 +84,13 @@ def test_wgs_slice_level_b_upload_and_other_penalties():
 JOINT = dict(n_sc=300, seed=11, len_mode=1, len_a=20.0, len_b=1.2, len_min=4, len_max=10002, p_sv=0.1, sv_min=50, sv_max=3000)
 
 
+# JOINT with 500 superclusters: the CPU model gives 1 249 edit records with every supercluster in its original phasing, 1 475 with every
+# one swapped, and 1 249 as the sum of the per-supercluster minima -- above the record buffer's first 1 024 whatever the phasing
+JOINT_EDITS = dict(JOINT, n_sc=500)
+
+
 def test_joint_batch_with_sv_indels_and_small_rounds():
-    syn = _synth(**JOINT)
+    syn = _synth(**JOINT_EDITS)
     pr, res, got = _run(syn)
     v = syn.variants()
     assert max(int(np.max(v.var_ref_len[s], initial=0)) for s in range(4)) >= 50      # SV-sized indels are there
@@ -95,6 +100,10 @@ def test_joint_batch_with_sv_indels_and_small_rounds():
     small = pr.distance(v, round_bytes=1 << 16)
     assert small["info"].n_rounds > 1 and small["info"].n_hist_rounds > small["info"].n_rounds
     _check(small, jobs, recs, qd)
+    # a handle whose record buffer starts empty: it grows between sub-rounds and has to keep what it holds
+    _, _, fresh = _run(syn, round_bytes=1 << 16)
+    assert fresh["info"].n_edits > 1024 and fresh["info"].n_hist_rounds >= 2
+    _check(fresh, jobs, recs, qd)
 
 
 def test_two_executes_give_identical_output():

@@ -1,15 +1,16 @@
-// pr_boot.hip -- the bootstrap replicates of the precision/recall counters (include/vcfdist_bootstrap.h): k_pr_hist
-// (pr_collect.hip) repeated n_rep times with every supercluster's variants counted w(seed, replicate, key) times.
+// pr_boot.hip -- the bootstrap replicates of the precision/recall counters (include/vcfdist_bootstrap.h): the counters of
+// pr_collect.hip n_rep times, with every supercluster's variants counted w(seed, replicate, key) times.
 // k_pr_boot is the transpose of k_pr_hist_strata (pr_strata.hip): there a lane is a variant and the lanes of a wave pile
 // onto the few bins most variants share; here a LANE IS A REPLICATE, the LDS table is [bin][64 replicates], and the 64
-// increments of a wave-instruction fall on 64 consecutive words whatever the data.  The host fold of a histogram, the
-// inputs of a counters call and the all-reduce are the ones of pr_collect.hip.
+// increments of a wave-instruction fall on 64 consecutive words whatever the data.  The bin rule is pr_counts.h's; the host
+// fold of a histogram and the front and back of a counters call are the ones of pr_collect.hip.
 #include "pr_host.h"
+#include "pr_counts.h"
 #include "../../include/vcfdist_bootstrap.h"
 
 struct BootState {
-    unsigned long long *hist = nullptr; size_t hist_cap = 0;     // [2][3 classes][3][nq + 1][groups * 64]: replicate-minor
-    uint64_t *keys = nullptr; size_t keys_cap = 0;               // the caller's sc_key
+    DevBuf<unsigned long long> hist;                             // [2][3 classes][3][nq + 1][groups * 64]: replicate-minor
+    DevBuf<uint64_t> keys;                                       // the caller's sc_key
     hipEvent_t ev[2] = {nullptr, nullptr};
     int32_t grid[3] = {0, 0, 0};                                 // vpr_boot_info: spans, replicate groups, quality slices
     double ms = 0;
@@ -33,13 +34,6 @@ const int64_t BOOT_SPAN_MAX = int64_t(1) << 24;   // x 12 < 2^32: a uint32 bin o
 const int64_t BOOT_WG_TARGET = 512;
 
 __device__ const uint32_t BOOT_T[VPR_BOOT_MAX_WEIGHT] = VPR_BOOT_T;
-
-// supercluster of variant v: the largest sc with var_off[sc] <= v (as k_pr_hist)
-__device__ inline int sc_of_var(const int64_t *__restrict__ var_off, int n_sc, int64_t v) {
-    int lo = 0, hi = n_sc;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (var_off[mid] <= v) lo = mid; else hi = mid; }
-    return lo;
-}
 
 // w(seed, r, key): `salt` is the lane's 0x9E3779B97F4A7C15 * (r + 1) + seed * 0xD1B54A32D192ED03
 __device__ inline uint32_t boot_weight(uint64_t key, uint64_t salt) {
@@ -89,18 +83,9 @@ __global__ void __launch_bounds__(1024) k_pr_boot(const int64_t *__restrict__ va
         uint64_t key = 0;
         if (v < v1 && (!word || ((word[v] >> bit) & 1))) {
             sc = sc_of_var(var_off, n_sc, v);
-            const int ph = sc_phase[sc];
-            const int swap = ph == VPR_PHASE_ORIG ? 0 : (ph == VPR_PHASE_SWAP ? 1 : (pb_phase ? (pb_phase[sc] != 0) : 0));
-            const VarCols &C = swap ? c1 : c0;
-            const int e = C.errtype[v];
-            if (e < 3) {                                         // ERRTYPE_UN etc.: skipped, as in k_pr_hist
-                const float q = C.callq[v];
-                int b = (q < float(min_qual)) ? -1 : int(floorf(q)) - min_qual;   // last threshold index the variant counts at
-                if (b >= nq) b = nq - 1;
-                if (b < 0) b = nq;                                              // bin nq: counts at no threshold
-                const int t = cls[v] > 2 ? 2 : cls[v];
-                if (b >= q_lo && b < q_lo + n_qs) { bin = (t * 3 + e) * n_qs + (b - q_lo); key = sc_key[sc]; }
-            }
+            int b = 0;
+            const int row = pr_count_row(sc, v, sc_phase, pb_phase, c0.errtype, c1.errtype, c0.callq, c1.callq, cls, min_qual, nq, &b);
+            if (row >= 0 && b >= q_lo && b < q_lo + n_qs) { bin = row * n_qs + (b - q_lo); key = sc_key[sc]; }
         }
         // ---- lane = replicate
         uint64_t todo = __ballot(bin >= 0);
@@ -156,22 +141,14 @@ int boot_counts_impl(vpr_handle *h, void *comm, const uint8_t *const var_class[V
     if (n_rep < 1 || n_rep > VPR_BOOT_MAX_REPLICATES)
         return fail(h, VPR_ERR_ARG, "vpr_pr_counts_boot: %d replicates (1 to %d)", n_rep, VPR_BOOT_MAX_REPLICATES);
     if (stratum < -1) return fail(h, VPR_ERR_ARG, "vpr_pr_counts_boot: stratum %d", stratum);
-    if (comm && !rccl_has_allreduce()) return fail(h, VPR_ERR_STATE, "no RCCL in this process (librccl.so.1 not found)");
-    if (!h->executed) return fail(h, VPR_ERR_STATE, "vpr_pr_counts_boot before vpr_execute");
+    if (int rc = pr_counts_begin(h, "vpr_pr_counts_boot", comm)) return rc;
     const uint64_t *words[VPR_HAPS] = {nullptr, nullptr, nullptr, nullptr};
     if (stratum >= 0) {
         int32_t n_strata = 0;
-        int64_t n_var[VPR_HAPS];
-        if (!strata_view(h, &n_strata, n_var, words))
-            return fail(h, VPR_ERR_STATE, "vpr_pr_counts_boot: no membership words (call vpr_strata_masks or vpr_strata_upload_masks after the upload)");
-        for (int s = 0; s < VPR_HAPS; s++)
-            if (n_var[s] != h->n_var[s])
-                return fail(h, VPR_ERR_STATE, "vpr_pr_counts_boot: the membership words hold %lld variants of hap slot %d, the executed batch has %lld",
-                            (long long)n_var[s], s, (long long)h->n_var[s]);
+        if (int rc = strata_view(h, "vpr_pr_counts_boot", &n_strata, words)) return rc;
         if (stratum >= n_strata) return fail(h, VPR_ERR_ARG, "vpr_pr_counts_boot: stratum %d of %d", stratum, n_strata);
-        for (int s = 0; s < VPR_HAPS; s++) words[s] += size_t(stratum >> 6) * size_t(n_var[s]);      // word-major
+        for (int s = 0; s < VPR_HAPS; s++) words[s] += size_t(stratum >> 6) * size_t(h->n_var[s]);      // word-major
     }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
     if (!h->boot) h->boot = new BootState();
     BootState *S = h->boot;
     for (int k = 0; k < 2; k++) if (!S->ev[k]) HIPCHK(h, hipEventCreate(&S->ev[k]));
@@ -182,56 +159,34 @@ int boot_counts_impl(vpr_handle *h, void *comm, const uint8_t *const var_class[V
     const int qs_max = int(BOOT_LDS_BUDGET / (9 * 64 * 4));
     const int n_slices = (nq + 1 + qs_max - 1) / qs_max, n_qs = (nq + 1 + n_slices - 1) / n_slices;
     const size_t lds = size_t(9) * size_t(n_qs) * 64 * 4;
-    if (nh > S->hist_cap) {
-        if (S->hist) (void)x_free(h, S->hist, SITE);
-        S->hist = nullptr; S->hist_cap = 0;
-        if (x_malloc(h, reinterpret_cast<void **>(&S->hist), nh * 8, SITE) != hipSuccess) {
-            S->hist = nullptr;
-            (void)hipGetLastError();
-            return fail(h, VPR_ERR_NOMEM, "replicate histogram: cannot allocate %zu bytes on the device", nh * 8);
-        }
-        S->hist_cap = nh;
-    }
-    const size_t n_keys = size_t(std::max(h->n_sc, 1));
-    if (n_keys > S->keys_cap) {
-        if (S->keys) (void)x_free(h, S->keys, SITE);
-        S->keys = nullptr; S->keys_cap = 0;
-        if (x_malloc(h, reinterpret_cast<void **>(&S->keys), n_keys * 8, SITE) != hipSuccess) {
-            S->keys = nullptr;
-            (void)hipGetLastError();
-            return fail(h, VPR_ERR_NOMEM, "supercluster keys: cannot allocate %zu bytes on the device", n_keys * 8);
-        }
-        S->keys_cap = n_keys;
-    }
+    if (int rc = S->hist.reserve(h, nh, "replicate histogram: cannot allocate %zu bytes on the device")) return rc;
+    if (int rc = S->keys.reserve(h, size_t(std::max(h->n_sc, 1)), "supercluster keys: cannot allocate %zu bytes on the device")) return rc;
     std::vector<unsigned long long> hist;
     try { hist.resize(nh); } catch (const std::bad_alloc &) {
         return fail(h, VPR_ERR_NOMEM, "replicate histogram: cannot allocate %zu bytes on the host", nh * 8);
     }
     HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_pr_boot), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-    HIPCHK(h, hipMemsetAsync(S->hist, 0, nh * 8, h->stream));
-    if (h->n_sc) HIPCHK(h, hipMemcpyAsync(S->keys, sc_key, size_t(h->n_sc) * 8, hipMemcpyHostToDevice, h->stream));
-    int32_t *d_pb = nullptr;
-    if (int rc = pr_counts_inputs(h, var_class, pb_phase, &d_pb)) return rc;
-    const int n_waves = boot_waves();
+    HIPCHK(h, hipMemsetAsync(S->hist.p, 0, nh * 8, h->stream));
+    if (h->n_sc) HIPCHK(h, hipMemcpyAsync(S->keys.p, sc_key, size_t(h->n_sc) * 8, hipMemcpyHostToDevice, h->stream));
     S->grid[0] = 0; S->grid[1] = n_groups; S->grid[2] = n_slices;
     S->ms = 0; S->ran = false;
+    int32_t *d_pb = nullptr;
+    if (int rc = pr_counts_inputs(h, "vpr_pr_counts_boot", var_class, pb_phase, &d_pb)) return rc;
+    const int n_waves = boot_waves();
     HIPCHK(h, hipEventRecord(S->ev[0], h->stream));
     for (int s = 0; s < VPR_HAPS; s++) {
         const int64_t nv = h->n_var[s];
         if (!nv) continue;
-        if (!h->d_cls[s]) return fail(h, VPR_ERR_STATE, "vpr_pr_counts_boot: no variant classes (pass var_class or call vpr_upload_var_class)");
         const int64_t span = boot_span(nv, int64_t(n_groups) * n_slices);
         const int64_t n_spans = (nv + span - 1) / span;
         S->grid[0] = std::max<int32_t>(S->grid[0], int32_t(n_spans));
         hipLaunchKernelGGL(k_pr_boot, dim3(unsigned(n_spans), unsigned(n_groups), unsigned(n_slices)), dim3(unsigned(n_waves) * 64), lds,
                            h->stream, h->dB.var_off[s], h->n_sc, nv, h->d_cls[s], h->dR.sc_phase, d_pb, h->dR.v[s][0], h->dR.v[s][1],
-                           s >> 1, min_qual, max_qual, S->keys, seed, n_rep, words[s], stratum >= 0 ? (stratum & 63) : 0, span, n_qs, S->hist);
+                           s >> 1, min_qual, max_qual, S->keys.p, seed, n_rep, words[s], stratum >= 0 ? (stratum & 63) : 0, span, n_qs, S->hist.p);
         HIPCHK(h, hipGetLastError());
     }
     HIPCHK(h, hipEventRecord(S->ev[1], h->stream));
-    if (comm) if (int rc = rccl_allreduce_u64(h, S->hist, nh, comm)) return rc;
-    HIPCHK(h, hipMemcpyAsync(hist.data(), S->hist, nh * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, x_sync(h, h->stream, SITE));
+    if (int rc = pr_counts_finish(h, comm, S->hist.p, nh, hist.data())) return rc;
     float ms = 0;
     (void)hipEventElapsedTime(&ms, S->ev[0], S->ev[1]);
     S->ms = ms; S->ran = true;
@@ -250,8 +205,7 @@ int boot_counts_impl(vpr_handle *h, void *comm, const uint8_t *const var_class[V
 void boot_free(vpr_handle *h) {
     BootState *S = h->boot;
     if (!S) return;
-    if (S->hist) (void)x_free(h, S->hist, SITE);
-    if (S->keys) (void)x_free(h, S->keys, SITE);
+    dev_release(h, S->hist, S->keys);
     for (int k = 0; k < 2; k++) if (S->ev[k]) (void)hipEventDestroy(S->ev[k]);
     delete S;
     h->boot = nullptr;

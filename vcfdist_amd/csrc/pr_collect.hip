@@ -5,6 +5,7 @@
 #include <dlfcn.h>
 
 #include "pr_host.h"
+#include "pr_counts.h"
 
 extern "C" {
 
@@ -20,20 +21,10 @@ __global__ void __launch_bounds__(256) k_pr_hist(const int64_t *__restrict__ var
     __syncthreads();
     const int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (v < n_var) {
-        int lo = 0, hi = n_sc;   // supercluster of the variant: largest sc with var_off[sc] <= v
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (var_off[mid] <= v) lo = mid; else hi = mid; }
-        const int ph = sc_phase[lo];
-        const int swap = ph == VPR_PHASE_ORIG ? 0 : (ph == VPR_PHASE_SWAP ? 1 : (pb_phase ? (pb_phase[lo] != 0) : 0));
-        const VarCols &C = swap ? c1 : c0;
-        const int e = C.errtype[v];
-        if (e < 3) {                                         // ERRTYPE_UN etc.: skipped with a warning (print.cpp:374)
-            const float q = C.callq[v];
-            int b = (q < float(min_qual)) ? -1 : int(floorf(q)) - min_qual;   // last threshold index the variant counts at
-            if (b >= nq) b = nq - 1;
-            const int t = cls[v] > 2 ? 2 : cls[v];
-            // bin nq collects the variants that count at no threshold (callq < min_qual)
-            atomicAdd(&blk[(t * 3 + e) * (nq + 1) + (b < 0 ? nq : b)], 1u);
-        }
+        int bin = 0;
+        const int row = pr_count_row(sc_of_var(var_off, n_sc, v), v, sc_phase, pb_phase, c0.errtype, c1.errtype, c0.callq, c1.callq, cls,
+                                     min_qual, nq, &bin);
+        if (row >= 0) atomicAdd(&blk[row * (nq + 1) + bin], 1u);
     }
     __syncthreads();
     for (int k = threadIdx.x; k < nb; k += blockDim.x)
@@ -130,18 +121,15 @@ const char *vpr_rccl_library(void) { return Rccl::get().path.c_str(); }
 
 }   // extern "C"
 
-// ---- what the stratified counters (pr_strata.hip) share with vpr_pr_counts
-bool rccl_has_allreduce() { return Rccl::get().all_reduce != nullptr; }
-
-// the one collective of the path (SURVEY 8(e)): histogram words summed over the ranks, in place on the device
-int rccl_allreduce_u64(vpr_handle *h, unsigned long long *d_buf, size_t n, void *comm) {
-    const int e = Rccl::get().all_reduce(d_buf, d_buf, n, RCCL_UINT64, RCCL_SUM, comm, h->stream);
-    if (e) return fail(h, VPR_ERR_DEVICE, "ncclAllReduce failed: %s", Rccl::get().err_str ? Rccl::get().err_str(e) : "?");
+// ---- what the three counters entries share (pr_host.h)
+int pr_counts_begin(vpr_handle *h, const char *entry, void *comm) {
+    if (comm && !Rccl::get().all_reduce) return fail(h, VPR_ERR_STATE, "no RCCL in this process (librccl.so.1 not found)");
+    if (!h->executed) return fail(h, VPR_ERR_STATE, "%s before vpr_execute", entry);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
     return VPR_OK;
 }
 
-// the caller's phase-block phasing and variant classes on the device (*d_pb stays null without pb_phase)
-int pr_counts_inputs(vpr_handle *h, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase, int32_t **d_pb) {
+int pr_counts_inputs(vpr_handle *h, const char *entry, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase, int32_t **d_pb) {
     int rc;
     *d_pb = nullptr;
     if (pb_phase && h->n_sc) {
@@ -150,6 +138,20 @@ int pr_counts_inputs(vpr_handle *h, const uint8_t *const var_class[VPR_HAPS], co
         HIPCHK(h, hipMemcpyAsync(*d_pb, pb_phase, size_t(h->n_sc) * 4, hipMemcpyHostToDevice, h->stream));
     }
     if (var_class && (rc = vpr_upload_var_class(h, var_class))) return rc;
+    for (int s = 0; s < VPR_HAPS; s++)
+        if (h->n_var[s] && !h->d_cls[s])
+            return fail(h, VPR_ERR_STATE, "%s: no variant classes (pass var_class or call vpr_upload_var_class)", entry);
+    return VPR_OK;
+}
+
+// the one collective of the path (SURVEY 8(e)): histogram words summed over the ranks, in place on the device
+int pr_counts_finish(vpr_handle *h, void *comm, unsigned long long *d_hist, size_t nh, unsigned long long *hist) {
+    if (comm) {
+        const int e = Rccl::get().all_reduce(d_hist, d_hist, nh, RCCL_UINT64, RCCL_SUM, comm, h->stream);
+        if (e) return fail(h, VPR_ERR_DEVICE, "ncclAllReduce failed: %s", Rccl::get().err_str ? Rccl::get().err_str(e) : "?");
+    }
+    HIPCHK(h, hipMemcpyAsync(hist, d_hist, nh * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, x_sync(h, h->stream, SITE));
     return VPR_OK;
 }
 
@@ -186,12 +188,10 @@ extern "C" {
 static int pr_counts_impl(vpr_handle *h, void *comm, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase,
                           int32_t min_qual, int32_t max_qual, int64_t *counts) {
     if (!h || !counts || max_qual < min_qual) return VPR_ERR_ARG;
-    if (comm && !rccl_has_allreduce()) return fail(h, VPR_ERR_STATE, "no RCCL in this process (librccl.so.1 not found)");
-    if (!h->executed) return fail(h, VPR_ERR_STATE, "vpr_pr_counts before vpr_execute");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc;
+    if ((rc = pr_counts_begin(h, "vpr_pr_counts", comm))) return rc;
     const int nq = max_qual - min_qual + 1;
     const size_t nh = size_t(2) * 3 * 3 * size_t(nq + 1);
-    int rc;
     if (nh > h->hist_cap) {
         if ((rc = dev_alloc(h, &h->d_hist, nh))) return rc;
         h->hist_cap = nh;
@@ -199,19 +199,16 @@ static int pr_counts_impl(vpr_handle *h, void *comm, const uint8_t *const var_cl
     unsigned long long *d_hist = h->d_hist;
     int32_t *d_pb = nullptr;
     HIPCHK(h, hipMemsetAsync(d_hist, 0, nh * 8, h->stream));
-    if ((rc = pr_counts_inputs(h, var_class, pb_phase, &d_pb))) return rc;
+    if ((rc = pr_counts_inputs(h, "vpr_pr_counts", var_class, pb_phase, &d_pb))) return rc;
     for (int s = 0; s < VPR_HAPS; s++) {
         const int64_t nv = h->n_var[s];
         if (!nv) continue;
-        if (!h->d_cls[s]) return fail(h, VPR_ERR_STATE, "vpr_pr_counts: no variant classes (pass var_class or call vpr_upload_var_class)");
         hipLaunchKernelGGL(k_pr_hist, dim3(unsigned((nv + 255) / 256)), dim3(256), size_t(9) * (nq + 1) * 4, h->stream,
                            h->dB.var_off[s], h->n_sc, nv, h->d_cls[s], h->dR.sc_phase, d_pb, h->dR.v[s][0], h->dR.v[s][1],
                            s >> 1, min_qual, max_qual, d_hist);
     }
-    if (comm && (rc = rccl_allreduce_u64(h, d_hist, nh, comm))) return rc;
     std::vector<unsigned long long> hist(nh);
-    HIPCHK(h, hipMemcpyAsync(hist.data(), d_hist, nh * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, x_sync(h, h->stream, SITE));
+    if ((rc = pr_counts_finish(h, comm, d_hist, nh, hist.data()))) return rc;
     pr_fold_counts(hist.data(), nq, counts);
     return VPR_OK;
 }

@@ -27,9 +27,8 @@ struct ContextState {
     int32_t n_spec = 0, n_ctg = 0, n_bed = 0;
     int64_t n_iv_bed = 0, n_iv_ctx = 0;
     // one table for the mask kernel: the rows of the BED strata first, the context rows behind them
-    int64_t *d_off = nullptr;                          // [(n_bed + n_spec) * n_ctg + 1]
-    int32_t *d_start = nullptr, *d_stop = nullptr;     // [n_iv_bed + n_iv_ctx]
-    size_t iv_cap = 0;
+    DevBuf<int64_t> d_off;                             // [(n_bed + n_spec) * n_ctg + 1]
+    DevBuf<int32_t> d_start, d_stop;                   // [n_iv_bed + n_iv_ctx]
     hipEvent_t ev[2] = {nullptr, nullptr};
     double ms_intervals = 0, ms_mask = 0;
     bool valid = false;
@@ -389,39 +388,25 @@ __global__ void __launch_bounds__(256) k_ctx_rows(const int32_t *__restrict__ ou
 
 namespace {
 
-// a device buffer that only grows; the old block is released once the stream has drained (grow() synchronises)
-struct Buf {
-    void *p = nullptr; size_t cap = 0;
-    template <typename T> T *as() const { return static_cast<T *>(p); }
-};
+// room for `bytes` in a buffer of the call, a quarter more than asked for when it has to grow; keep_bytes of the old content survive
+template <typename T>
+int ctx_need(vpr_handle *h, DevBuf<T> &b, size_t bytes, const char *what, size_t keep_bytes = 0) {
+    if (b.cap * sizeof(T) >= bytes) return VPR_OK;
+    const std::string nomem = std::string("vpr_context_masks: cannot allocate %zu bytes on the device (") + what + ")";
+    return b.reserve(h, std::max<size_t>((bytes + bytes / 4 + 255) & ~size_t(255), 256) / sizeof(T), nomem.c_str(), keep_bytes / sizeof(T));
+}
+template <typename T>
+T *as(const DevBuf<uint8_t> &b) { return reinterpret_cast<T *>(b.p); }
 
 struct Work {
     vpr_handle *h;
-    Buf seq, ctg_off, bits, cnt, runs, keep, kept, out_ctg, tmp, small;
+    DevBuf<uint8_t> seq, ctg_off, bits, cnt, runs, keep, kept, out_ctg, tmp, small;
     explicit Work(vpr_handle *h_) : h(h_) {}
     ~Work() {
         (void)hipStreamSynchronize(h->stream);
-        for (Buf *b : {&seq, &ctg_off, &bits, &cnt, &runs, &keep, &kept, &out_ctg, &tmp, &small})
-            if (b->p) (void)x_free(h, b->p, SITE);
+        dev_release(h, seq, ctg_off, bits, cnt, runs, keep, kept, out_ctg, tmp, small);
     }
-    // room for `bytes`; keep_bytes of the old content survive
-    int need(Buf &b, size_t bytes, const char *what, size_t keep_bytes = 0) { return grow(h, &b.p, &b.cap, bytes, what, keep_bytes); }
-    static int grow(vpr_handle *h, void **p, size_t *cap, size_t bytes, const char *what, size_t keep_bytes) {
-        if (bytes <= *cap) return VPR_OK;
-        const size_t want = std::max<size_t>((bytes + bytes / 4 + 255) & ~size_t(255), 256);
-        void *q = nullptr;
-        if (x_malloc(h, &q, want, SITE) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(h, VPR_ERR_NOMEM, "vpr_context_masks: cannot allocate %zu bytes on the device (%s)", want, what);
-        }
-        if (*p) {
-            if (keep_bytes) HIPCHK(h, hipMemcpyAsync(q, *p, keep_bytes, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            (void)x_free(h, *p, SITE);
-        }
-        *p = q; *cap = want;
-        return VPR_OK;
-    }
+    int need(DevBuf<uint8_t> &b, size_t bytes, const char *what) { return ctx_need(h, b, bytes, what); }
 };
 
 int check_spec(vpr_handle *h, const vpr_context_stratum *spec, int32_t n_spec) {
@@ -472,9 +457,7 @@ void context_free(vpr_handle *h) {
     ContextState *S = h->context;
     if (!S) return;
     (void)hipStreamSynchronize(h->stream);
-    if (S->d_off) (void)x_free(h, S->d_off, SITE);
-    if (S->d_start) (void)x_free(h, S->d_start, SITE);
-    if (S->d_stop) (void)x_free(h, S->d_stop, SITE);
+    dev_release(h, S->d_off, S->d_start, S->d_stop);
     for (int k = 0; k < 2; k++) if (S->ev[k]) (void)hipEventDestroy(S->ev[k]);
     delete S;
     h->context = nullptr;
@@ -512,19 +495,15 @@ int vpr_context_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *be
     const size_t bed_rows = size_t(n_bed) * size_t(n_ctg), all_rows = bed_rows + size_t(n_spec) * size_t(n_ctg);
     const int64_t n_iv_bed = bed ? bed->iv_off[bed_rows] : 0;
     S->n_spec = n_spec; S->n_ctg = n_ctg; S->n_bed = n_bed; S->n_iv_bed = n_iv_bed;
-    size_t cap = 0;
-    if (int rc = Work::grow(h, reinterpret_cast<void **>(&S->d_off), &cap, 8 * (all_rows + 1), "row offsets", 0)) return rc;
+    if (int rc = ctx_need(h, S->d_off, 8 * (all_rows + 1), "row offsets")) return rc;
     const size_t iv0 = size_t(n_iv_bed) + 1024;
-    cap = 0;
-    if (int rc = Work::grow(h, reinterpret_cast<void **>(&S->d_start), &cap, 4 * iv0, "intervals", 0)) return rc;
-    cap = 0;
-    if (int rc = Work::grow(h, reinterpret_cast<void **>(&S->d_stop), &cap, 4 * iv0, "intervals", 0)) return rc;
-    S->iv_cap = cap;
+    if (int rc = ctx_need(h, S->d_start, 4 * iv0, "intervals")) return rc;
+    if (int rc = ctx_need(h, S->d_stop, 4 * iv0, "intervals")) return rc;
     if (bed) {
-        HIPCHK(h, hipMemcpyAsync(S->d_off, bed->iv_off, 8 * (bed_rows + 1), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(S->d_off.p, bed->iv_off, 8 * (bed_rows + 1), hipMemcpyHostToDevice, h->stream));
         if (n_iv_bed) {
-            HIPCHK(h, hipMemcpyAsync(S->d_start, bed->iv_start, 4 * size_t(n_iv_bed), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(S->d_stop, bed->iv_stop, 4 * size_t(n_iv_bed), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(S->d_start.p, bed->iv_start, 4 * size_t(n_iv_bed), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(S->d_stop.p, bed->iv_stop, 4 * size_t(n_iv_bed), hipMemcpyHostToDevice, h->stream));
         }
     }
 
@@ -535,11 +514,11 @@ int vpr_context_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *be
     if (int rc = W.need(W.ctg_off, 8 * (size_t(n_ctg) + 1), "contig offsets")) return rc;
     if (int rc = W.need(W.small, 256, "counters")) return rc;
     if (N) HIPCHK(h, hipMemcpyAsync(W.seq.p, v->ctg_seq, size_t(N), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemsetAsync(W.seq.as<uint8_t>() + N, 0, size_t(n_pad - N), h->stream));
+    HIPCHK(h, hipMemsetAsync(as<uint8_t>(W.seq) + N, 0, size_t(n_pad - N), h->stream));
     HIPCHK(h, hipMemcpyAsync(W.ctg_off.p, v->ctg_off, 8 * (size_t(n_ctg) + 1), hipMemcpyHostToDevice, h->stream));
-    const uint8_t *d_seq = W.seq.as<uint8_t>();
-    const int64_t *d_ctg = W.ctg_off.as<int64_t>();
-    uint32_t *d_nkept = W.small.as<uint32_t>();
+    const uint8_t *d_seq = as<uint8_t>(W.seq);
+    const int64_t *d_ctg = as<int64_t>(W.ctg_off);
+    uint32_t *d_nkept = as<uint32_t>(W.small);
 
     // pieces of whole contigs
     struct Piece { int c0, c1; };       // contigs [c0, c1)
@@ -571,7 +550,7 @@ int vpr_context_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *be
         const bool gc = sp.kind == VPR_CTX_GC;
         // flags a run must have for its tract to reach min_len, where the run passes can apply that themselves (run_masks)
         const int min_run = (!gc && sp.min_len - sp.period <= 64) ? sp.min_len - sp.period : 1;
-        int64_t *row_off = S->d_off + bed_rows + size_t(k) * size_t(n_ctg);
+        int64_t *row_off = S->d_off.p + bed_rows + size_t(k) * size_t(n_ctg);
         for (const Piece &pc : pieces) {
             const int64_t g0 = v->ctg_off[pc.c0], g1 = v->ctg_off[pc.c1], T0 = g0 / CTX_TILE * CTX_TILE;
             const int64_t n_tiles = (g1 - T0 + CTX_TILE - 1) / CTX_TILE, nw = n_tiles * (CTX_TILE / 64), n_blk = (nw + 255) / 256;
@@ -580,13 +559,13 @@ int vpr_context_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *be
             if (n_tiles) {
                 if (int rc = W.need(W.bits, size_t(nw) * 8, "flag bits")) return rc;
                 if (int rc = W.need(W.cnt, size_t(n_blk + 1) * 16, "workgroup counts")) return rc;
-                uint16_t *bits = W.bits.as<uint16_t>();
-                const uint64_t *words = W.bits.as<uint64_t>();
-                uint32_t *cnt_st = W.cnt.as<uint32_t>(), *cnt_en = cnt_st + (n_blk + 1), *off_st = cnt_en + (n_blk + 1), *off_en = off_st + (n_blk + 1);
+                uint16_t *bits = as<uint16_t>(W.bits);
+                const uint64_t *words = as<uint64_t>(W.bits);
+                uint32_t *cnt_st = as<uint32_t>(W.cnt), *cnt_en = cnt_st + (n_blk + 1), *off_st = cnt_en + (n_blk + 1), *off_en = off_st + (n_blk + 1);
                 if (gc) {
                     if (sp.window <= GC_LDS_MAX_W)
                         hipLaunchKernelGGL(k_ctx_flags_gc, dim3(unsigned(n_tiles)), dim3(CTX_WG), size_t(4) * size_t(CTX_TILE + sp.window + 48), h->stream,
-                                           d_seq, n_pad, d_ctg, n_ctg, T0, g0, g1, sp.window, sp.gc_lo, sp.gc_hi, W.bits.as<uint64_t>());
+                                           d_seq, n_pad, d_ctg, n_ctg, T0, g0, g1, sp.window, sp.gc_lo, sp.gc_hi, as<uint64_t>(W.bits));
                     else
                         hipLaunchKernelGGL(k_ctx_flags_gc_wide, dim3(unsigned(n_tiles)), dim3(CTX_WG), 0, h->stream, d_seq, n_pad, d_ctg, n_ctg, T0, g0, g1,
                                            sp.window, sp.gc_lo, sp.gc_hi, bits);
@@ -616,9 +595,9 @@ int vpr_context_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *be
                     if (int rc = W.need(W.runs, n1 * 8, "run lists")) return rc;
                     if (int rc = W.need(W.keep, n1 * 8, "tract flags")) return rc;
                     if (int rc = W.need(W.kept, n1 * 12, "kept tracts")) return rc;
-                    uint32_t *run_st = W.runs.as<uint32_t>(), *run_en = run_st + n1;
-                    uint32_t *flag = W.keep.as<uint32_t>(), *flag_scan = flag + n1;
-                    int32_t *k_ctg = W.kept.as<int32_t>(), *k_ps = k_ctg + n1, *k_pe = k_ps + n1;
+                    uint32_t *run_st = as<uint32_t>(W.runs), *run_en = run_st + n1;
+                    uint32_t *flag = as<uint32_t>(W.keep), *flag_scan = flag + n1;
+                    int32_t *k_ctg = as<int32_t>(W.kept), *k_ps = k_ctg + n1, *k_pe = k_ps + n1;
                     const int p = gc ? 0 : sp.period, min_len = gc ? 1 : sp.min_len, max_len = gc ? 0 : sp.max_len;
                     if (int rc = seg_begin()) return rc;
                     hipLaunchKernelGGL(k_ctx_run_write, dim3(unsigned(n_blk)), dim3(256), 0, h->stream, words, nw, T0, d_ctg, n_ctg, g0, min_run, off_st, off_en,
@@ -637,24 +616,20 @@ int vpr_context_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *be
                     HIPCHK(h, hipMemcpyAsync(&n_out, flag_scan + n_run, 4, hipMemcpyDeviceToHost, h->stream));
                     if (int rc = seg_end()) return rc;
                     const size_t have = size_t(n_iv_bed + n_ctx), want = have + n_out;
-                    if (want * 4 > S->iv_cap) {
-                        size_t c1 = S->iv_cap, c2 = S->iv_cap;
-                        if (int rc = Work::grow(h, reinterpret_cast<void **>(&S->d_start), &c1, want * 4, "intervals", have * 4)) return rc;
-                        if (int rc = Work::grow(h, reinterpret_cast<void **>(&S->d_stop), &c2, want * 4, "intervals", have * 4)) return rc;
-                        S->iv_cap = std::min(c1, c2);
-                    }
+                    if (int rc = ctx_need(h, S->d_start, want * 4, "intervals", have * 4)) return rc;
+                    if (int rc = ctx_need(h, S->d_stop, want * 4, "intervals", have * 4)) return rc;
                     if (int rc = W.need(W.out_ctg, (size_t(n_out) + 1) * 4, "interval contigs")) return rc;
                     if (int rc = seg_begin()) return rc;
                     if (n_out) {
                         hipLaunchKernelGGL(k_ctx_merge, dim3(blocks_of(n_run)), dim3(256), 0, h->stream, d_nkept, k_ctg, k_ps, k_pe, flag, flag_scan,
-                                           W.out_ctg.as<int32_t>(), S->d_start + have, S->d_stop + have);
+                                           as<int32_t>(W.out_ctg), S->d_start.p + have, S->d_stop.p + have);
                         HIPCHK(h, hipGetLastError());
                     }
                 }
             }
             if (int rc = W.need(W.out_ctg, 4, "interval contigs")) return rc;
             if (int rc = seg_begin()) return rc;
-            hipLaunchKernelGGL(k_ctx_rows, dim3(blocks_of(pc.c1 - pc.c0 + 1)), dim3(256), 0, h->stream, W.out_ctg.as<int32_t>(), int64_t(n_out), pc.c0, pc.c1,
+            hipLaunchKernelGGL(k_ctx_rows, dim3(blocks_of(pc.c1 - pc.c0 + 1)), dim3(256), 0, h->stream, as<int32_t>(W.out_ctg), int64_t(n_out), pc.c0, pc.c1,
                                n_iv_bed + n_ctx, row_off);
             HIPCHK(h, hipGetLastError());
             n_ctx += n_out;
@@ -663,7 +638,7 @@ int vpr_context_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *be
     if (open) if (int rc = seg_end()) return rc;
     S->n_iv_ctx = n_ctx;
     S->ms_intervals = ms;
-    if (int rc = strata_masks_device(h, v, n_bed + n_spec, S->d_off, S->d_start, S->d_stop)) return rc;
+    if (int rc = strata_masks_device(h, v, n_bed + n_spec, S->d_off.p, S->d_start.p, S->d_stop.p)) return rc;
     double ms_hist = 0;
     (void)vpr_strata_timing(h, &S->ms_mask, &ms_hist);
     S->valid = true;
@@ -676,7 +651,7 @@ int vpr_context_interval_counts(vpr_handle *h, int64_t *iv_off) {
     if (!S || !S->valid) return fail(h, VPR_ERR_STATE, "vpr_context_interval_counts before vpr_context_masks");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t bed_rows = size_t(S->n_bed) * size_t(S->n_ctg), rows = size_t(S->n_spec) * size_t(S->n_ctg);
-    HIPCHK(h, hipMemcpyAsync(iv_off, S->d_off + bed_rows, 8 * (rows + 1), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(iv_off, S->d_off.p + bed_rows, 8 * (rows + 1), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, x_sync(h, h->stream, SITE));
     for (size_t r = 0; r <= rows; r++) iv_off[r] -= S->n_iv_bed;
     return VPR_OK;
@@ -689,8 +664,8 @@ int vpr_context_download_intervals(vpr_handle *h, int32_t *start, int32_t *stop)
     if (!S->n_iv_ctx) return VPR_OK;
     if (!start || !stop) return fail(h, VPR_ERR_ARG, "vpr_context_download_intervals: null buffer");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipMemcpyAsync(start, S->d_start + S->n_iv_bed, 4 * size_t(S->n_iv_ctx), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(stop, S->d_stop + S->n_iv_bed, 4 * size_t(S->n_iv_ctx), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(start, S->d_start.p + S->n_iv_bed, 4 * size_t(S->n_iv_ctx), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(stop, S->d_stop.p + S->n_iv_bed, 4 * size_t(S->n_iv_ctx), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, x_sync(h, h->stream, SITE));
     return VPR_OK;
 }

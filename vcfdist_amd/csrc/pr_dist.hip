@@ -252,16 +252,16 @@ __global__ void k_dist_back(DTab T, const DJob *__restrict__ jobs, int64_t j0, i
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
 struct DistState {
-    uint8_t *in_blk = nullptr; size_t in_bytes = 0;         // the uploaded tables
-    DJob *jobs = nullptr; size_t job_cap = 0;               // job tables (grown on demand)
-    int64_t *need1 = nullptr, *need2 = nullptr, *cells = nullptr, *slice = nullptr, *nrec = nullptr, *recoff = nullptr;
-    int32_t *score = nullptr, *dist = nullptr;
-    uint8_t *status = nullptr;
-    int64_t *cnt = nullptr, *cnt_off = nullptr; size_t cnt_cap = 0, cnt_off_cap = 0;
-    void *scan_tmp = nullptr; size_t scan_tmp_bytes = 0;
-    unsigned long long *qdiff = nullptr; size_t qdiff_cap = 0;
-    uint8_t *arena = nullptr; int64_t arena_bytes = 0;
-    DEdit *edits = nullptr; int64_t edit_cap = 0;
+    DevBuf<uint8_t> in_blk;                                 // the uploaded tables
+    DevBuf<DJob> jobs;                                      // job tables (grown on demand)
+    DevBuf<int64_t> need1, need2, cells, slice, nrec, recoff;
+    DevBuf<int32_t> score, dist;
+    DevBuf<uint8_t> status;
+    DevBuf<int64_t> cnt, cnt_off;
+    DevBuf<uint8_t> scan_tmp;
+    DevBuf<unsigned long long> qdiff;
+    DevBuf<uint8_t> arena;
+    DevBuf<DEdit> edits;
     hipEvent_t ev[2] = {nullptr, nullptr};
     int32_t max_qual = 0;
     bool valid = false;
@@ -270,26 +270,11 @@ struct DistState {
 
 namespace {
 
-template <typename T>
-int dist_grow(vpr_handle *h, T **p, size_t *cap, size_t n, const char *site) {
-    if (*p && *cap >= n) return VPR_OK;
-    if (*p) (void)x_free(h, *p, site);
-    *p = nullptr;
-    const size_t want = std::max<size_t>(n, 1);
-    if (x_malloc(h, reinterpret_cast<void **>(p), want * sizeof(T), site) != hipSuccess) {
-        *p = nullptr; *cap = 0;
-        (void)hipGetLastError();
-        return fail(h, VPR_ERR_NOMEM, "vpr_distance: cannot allocate %zu bytes on the device (%s)", want * sizeof(T), site);
-    }
-    *cap = want;
-    return VPR_OK;
-}
-
 int scan_i64(vpr_handle *h, DistState *D, const int64_t *in, int64_t *out, size_t n) {
     size_t need = 0;
     if (vplan_exclusive_scan_i64(nullptr, &need, in, out, n, h->stream)) return fail(h, VPR_ERR_DEVICE, "vpr_distance: scan sizing failed");
-    if (int rc = dist_grow(h, reinterpret_cast<uint8_t **>(&D->scan_tmp), &D->scan_tmp_bytes, need, SITE)) return rc;
-    if (vplan_exclusive_scan_i64(D->scan_tmp, &need, in, out, n, h->stream)) return fail(h, VPR_ERR_DEVICE, "vpr_distance: scan failed");
+    if (int rc = D->scan_tmp.reserve(h, need, "vpr_distance: cannot allocate %zu bytes on the device (scan workspace)")) return rc;
+    if (vplan_exclusive_scan_i64(D->scan_tmp.p, &need, in, out, n, h->stream)) return fail(h, VPR_ERR_DEVICE, "vpr_distance: scan failed");
     return VPR_OK;
 }
 
@@ -306,14 +291,7 @@ double ev_ms(DistState *D) {
 // memory the next vpr_execute plans with is not held by the distance step.  What vpr_distance_download reads stays.
 void dist_release_work(vpr_handle *h) {
     DistState *D = h->dist;
-    if (!D) return;
-    void **ps[] = {reinterpret_cast<void **>(&D->in_blk), reinterpret_cast<void **>(&D->need1), reinterpret_cast<void **>(&D->need2),
-                   reinterpret_cast<void **>(&D->cells), reinterpret_cast<void **>(&D->slice), reinterpret_cast<void **>(&D->nrec),
-                   reinterpret_cast<void **>(&D->recoff), reinterpret_cast<void **>(&D->score), reinterpret_cast<void **>(&D->cnt),
-                   reinterpret_cast<void **>(&D->cnt_off), reinterpret_cast<void **>(&D->scan_tmp), reinterpret_cast<void **>(&D->arena)};
-    for (void **p : ps) { if (*p) (void)x_free(h, *p, SITE); *p = nullptr; }
-    D->in_bytes = 0; D->cnt_cap = D->cnt_off_cap = 0; D->scan_tmp_bytes = 0; D->arena_bytes = 0;
-    D->job_cap = 0;         // (the per-job tables are allocated together: with their work columns gone the next call renews them all)
+    if (D) dev_release(h, D->in_blk, D->need1, D->need2, D->cells, D->slice, D->nrec, D->recoff, D->score, D->cnt, D->cnt_off, D->scan_tmp, D->arena);
 }
 
 // everything of the distance step, results included: called by vpr_destroy, by every upload (free_batch) and at the start of
@@ -321,9 +299,8 @@ void dist_release_work(vpr_handle *h) {
 void dist_free(vpr_handle *h) {
     DistState *D = h->dist;
     if (!D) return;
-    void *ps[] = {D->in_blk, D->jobs, D->need1, D->need2, D->cells, D->slice, D->nrec, D->recoff, D->score, D->dist, D->status,
-                  D->cnt, D->cnt_off, D->scan_tmp, D->qdiff, D->arena, D->edits};
-    for (void *p : ps) if (p) (void)x_free(h, p, SITE);
+    dist_release_work(h);
+    dev_release(h, D->jobs, D->dist, D->status, D->qdiff, D->edits);
     for (int k = 0; k < 2; k++) if (D->ev[k]) (void)hipEventDestroy(D->ev[k]);
     delete D;
     h->dist = nullptr;
@@ -355,8 +332,8 @@ extern "C" int vpr_distance(vpr_handle *h, const vpr_variants *v, const vpr_dist
     const int P = std::max(pen.x, pen.o + pen.e) + 1;
     D->max_qual = cfg->max_qual;
     const int nqd = cfg->max_qual + 3;
-    if (int rc = dist_grow(h, &D->qdiff, &D->qdiff_cap, size_t(nqd), SITE)) return rc;
-    HIPCHK(h, hipMemsetAsync(D->qdiff, 0, sizeof(unsigned long long) * nqd, h->stream));
+    if (int rc = D->qdiff.reserve(h, size_t(nqd), "vpr_distance: cannot allocate %zu bytes on the device (quality totals)")) return rc;
+    HIPCHK(h, hipMemsetAsync(D->qdiff.p, 0, sizeof(unsigned long long) * nqd, h->stream));
     if (n_sc == 0) { D->valid = true; I.ms_wall = wall_ms() - t_wall; return VPR_OK; }
 
     // ---- the tables the jobs read, one block (the resident Level A arrays hold the unfiltered strings only)
@@ -383,11 +360,11 @@ extern "C" int vpr_distance(vpr_handle *h, const vpr_variants *v, const vpr_dist
         i_var[s][6] = add(v->var_alt_off[s], 8 * size_t(nv));
         i_var[s][7] = add(v->allele_pool[s], size_t(nv ? pool : 0));
     }
-    if (int rc = dist_grow(h, &D->in_blk, &D->in_bytes, total, SITE)) return rc;
+    if (int rc = D->in_blk.reserve(h, total, "vpr_distance: cannot allocate %zu bytes on the device (input tables)")) return rc;
     for (const Piece &p : pieces)
-        if (p.bytes && p.src) HIPCHK(h, hipMemcpyAsync(D->in_blk + p.at, p.src, p.bytes, hipMemcpyHostToDevice, h->stream));
+        if (p.bytes && p.src) HIPCHK(h, hipMemcpyAsync(D->in_blk.p + p.at, p.src, p.bytes, hipMemcpyHostToDevice, h->stream));
     I.input_bytes = int64_t(total);
-    auto at = [&](size_t i) { return D->in_blk + pieces[i].at; };
+    auto at = [&](size_t i) { return D->in_blk.p + pieces[i].at; };
     DTab T;
     T.ctg_off = reinterpret_cast<const int64_t *>(at(i_ctg_off));
     T.ctg_seq = at(i_ctg_seq);
@@ -412,49 +389,34 @@ extern "C" int vpr_distance(vpr_handle *h, const vpr_variants *v, const vpr_dist
 
     // ---- the jobs
     const size_t n_hs = size_t(2 * n_sc);
-    if (int rc = dist_grow(h, &D->cnt, &D->cnt_cap, n_hs + 1, SITE)) return rc;
-    if (int rc = dist_grow(h, &D->cnt_off, &D->cnt_off_cap, n_hs + 1, SITE)) return rc;
+    if (int rc = D->cnt.reserve(h, n_hs + 1, "vpr_distance: cannot allocate %zu bytes on the device (job counts)")) return rc;
+    if (int rc = D->cnt_off.reserve(h, n_hs + 1, "vpr_distance: cannot allocate %zu bytes on the device (job offsets)")) return rc;
     HIPCHK(h, hipEventRecord(D->ev[0], h->stream));
-    hipLaunchKernelGGL(k_dist_count, dim3(unsigned((n_hs + 255) / 256)), dim3(256), 0, h->stream, T, D->cnt);
-    HIPCHK(h, hipMemsetAsync(D->cnt + n_hs, 0, sizeof(int64_t), h->stream));
-    if (int rc = scan_i64(h, D, D->cnt, D->cnt_off, n_hs + 1)) return rc;
+    hipLaunchKernelGGL(k_dist_count, dim3(unsigned((n_hs + 255) / 256)), dim3(256), 0, h->stream, T, D->cnt.p);
+    HIPCHK(h, hipMemsetAsync(D->cnt.p + n_hs, 0, sizeof(int64_t), h->stream));
+    if (int rc = scan_i64(h, D, D->cnt.p, D->cnt_off.p, n_hs + 1)) return rc;
     int64_t n_jobs = 0;
-    HIPCHK(h, hipMemcpyAsync(&n_jobs, D->cnt_off + n_hs, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&n_jobs, D->cnt_off.p + n_hs, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, x_sync(h, h->stream, SITE));
     I.n_jobs = n_jobs;
-    {
-        size_t c = D->job_cap;
+    {   // the per-job tables: one entry more than the jobs, at least 256 bytes each
         const size_t nj = size_t(std::max<int64_t>(n_jobs, 1)) + 1;
-        if (c < nj) {
-            void **arr[] = {reinterpret_cast<void **>(&D->jobs), reinterpret_cast<void **>(&D->need1), reinterpret_cast<void **>(&D->need2),
-                            reinterpret_cast<void **>(&D->cells), reinterpret_cast<void **>(&D->slice), reinterpret_cast<void **>(&D->nrec),
-                            reinterpret_cast<void **>(&D->recoff), reinterpret_cast<void **>(&D->score), reinterpret_cast<void **>(&D->dist),
-                            reinterpret_cast<void **>(&D->status)};
-            const size_t sz[] = {sizeof(DJob), 8, 8, 8, 8, 8, 8, 4, 4, 1};
-            for (int k = 0; k < 10; k++) {
-                if (*arr[k]) (void)x_free(h, *arr[k], SITE);
-                *arr[k] = nullptr;
-            }
-            D->job_cap = 0;
-            for (int k = 0; k < 10; k++)
-                if (x_malloc(h, arr[k], std::max<size_t>(nj * sz[k], 256), SITE) != hipSuccess) {
-                    (void)hipGetLastError();
-                    return fail(h, VPR_ERR_NOMEM, "vpr_distance: cannot allocate the tables of %lld jobs", (long long)n_jobs);
-                }
-            D->job_cap = nj;
-        }
+        auto table = [&](auto &b) { return b.reserve(h, std::max(nj, 256 / sizeof(*b.p)), "") != VPR_OK; };
+        if (table(D->jobs) || table(D->need1) || table(D->need2) || table(D->cells) || table(D->slice) || table(D->nrec) ||
+            table(D->recoff) || table(D->score) || table(D->dist) || table(D->status))
+            return fail(h, VPR_ERR_NOMEM, "vpr_distance: cannot allocate the tables of %lld jobs", (long long)n_jobs);
     }
     if (n_jobs > 0)
-        hipLaunchKernelGGL(k_dist_jobs, dim3(unsigned((n_hs + 255) / 256)), dim3(256), 0, h->stream, T, D->cnt_off, D->jobs, D->need1,
-                           D->status, P);
+        hipLaunchKernelGGL(k_dist_jobs, dim3(unsigned((n_hs + 255) / 256)), dim3(256), 0, h->stream, T, D->cnt_off.p, D->jobs.p, D->need1.p,
+                           D->status.p, P);
     HIPCHK(h, hipEventRecord(D->ev[1], h->stream));
     HIPCHK(h, hipGetLastError());
     I.ms_jobs = ev_ms(D);
-    std::vector<int64_t> n1(static_cast<size_t>(n_jobs)), n2;
+    std::vector<int64_t> n1(static_cast<size_t>(n_jobs));
     std::vector<uint8_t> st(static_cast<size_t>(n_jobs));
     if (n_jobs) {
-        HIPCHK(h, hipMemcpyAsync(n1.data(), D->need1, 8 * size_t(n_jobs), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(st.data(), D->status, size_t(n_jobs), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(n1.data(), D->need1.p, 8 * size_t(n_jobs), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(st.data(), D->status.p, size_t(n_jobs), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, x_sync(h, h->stream, SITE));
     }
 
@@ -469,112 +431,57 @@ extern "C" int vpr_distance(vpr_handle *h, const vpr_variants *v, const vpr_dist
     const int64_t round_cap1 = std::min<int64_t>(cfg->round_bytes > 0 ? cfg->round_bytes : int64_t(4) << 30, plan);
     const int64_t round_cap2 = cfg->round_bytes > 0 ? std::min<int64_t>(cfg->round_bytes, plan) : plan;
     I.plan_bytes = plan;
-    auto ensure_arena = [&](int64_t bytes) -> int {
-        I.arena_bytes = std::max(I.arena_bytes, bytes);          // peak bytes a round occupies
-        if (bytes <= D->arena_bytes) return VPR_OK;
-        if (D->arena) (void)x_free(h, D->arena, SITE);
-        D->arena = nullptr; D->arena_bytes = 0;
-        if (x_malloc(h, reinterpret_cast<void **>(&D->arena), size_t(bytes), SITE) != hipSuccess) {
-            (void)hipGetLastError();
-            D->arena = nullptr;
-            return fail(h, VPR_ERR_NOMEM, "vpr_distance: cannot allocate a round arena of %lld bytes", (long long)bytes);
+    int64_t n_edits = 0, got = 0;
+    // the backtrack of a sub-round: count, scan, room for the records (the buffer doubles and keeps what it holds), write
+    auto back = [&](int64_t c, int64_t m, uint8_t *arena) -> int {
+        const unsigned gb = unsigned((m + 63) / 64);
+        hipLaunchKernelGGL(k_dist_back<false>, dim3(gb), dim3(64), 0, h->stream, T, D->jobs.p, c, m, D->slice.p, int64_t(0), arena,
+                           D->status.p, D->score.p, D->cells.p, D->dist.p, D->nrec.p, D->recoff.p, int64_t(0), D->edits.p, D->qdiff.p, pen);
+        HIPCHK(h, hipMemsetAsync(D->nrec.p + m, 0, sizeof(int64_t), h->stream));
+        if (int rc = scan_i64(h, D, D->nrec.p, D->recoff.p, size_t(m) + 1)) return rc;
+        HIPCHK(h, hipMemcpyAsync(&got, D->recoff.p + m, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, x_sync(h, h->stream, SITE));
+        if (size_t(n_edits + got) > D->edits.cap) {
+            const size_t cap = std::max(D->edits.cap * 2, std::max<size_t>(size_t(n_edits + got), 1024));
+            if (int rc = D->edits.reserve(h, cap, "", size_t(n_edits)))
+                return rc == VPR_ERR_NOMEM ? fail(h, rc, "vpr_distance: cannot allocate %lld edit records", (long long)cap) : rc;
         }
-        D->arena_bytes = bytes;
+        if (got)
+            hipLaunchKernelGGL(k_dist_back<true>, dim3(gb), dim3(64), 0, h->stream, T, D->jobs.p, c, m, D->slice.p, int64_t(0), arena,
+                               D->status.p, D->score.p, D->cells.p, D->dist.p, D->nrec.p, D->recoff.p, -n_edits, D->edits.p, D->qdiff.p, pen);
         return VPR_OK;
     };
-    // greedy rounds over [a, b): sum of `need` within the round budget, a larger job alone, a job beyond the plan marked
-    auto next_round = [&](const std::vector<int64_t> &need, int64_t a, int64_t b, int64_t off0, std::vector<int64_t> &slice, int64_t round_cap) {
-        int64_t sum = 0, k = a;
-        for (; k < b; k++) {
-            const int64_t nb = need[size_t(k - off0)];
-            if (st[size_t(k)]) { slice[size_t(k - off0)] = sum; continue; }
-            if (nb > plan) { st[size_t(k)] = VPR_DIST_ST_LIMIT; slice[size_t(k - off0)] = sum; continue; }
-            if (sum > 0 && sum + nb > round_cap) break;
-            slice[size_t(k - off0)] = sum;
-            sum += nb;
-        }
-        return std::make_pair(k, sum);
-    };
-    int64_t n_edits = 0;
-    double ms_score = 0, ms_hist = 0, ms_back = 0;
-    std::vector<int64_t> sl1(static_cast<size_t>(n_jobs)), sl2;
-    for (int64_t a = 0; a < n_jobs;) {
-        const auto r1 = next_round(n1, a, n_jobs, 0, sl1, round_cap1);
-        const int64_t b = r1.first;
-        I.n_rounds++;
-        if (int rc = ensure_arena(std::max<int64_t>(r1.second, 16))) return rc;
-        const int64_t nr = b - a;
-        HIPCHK(h, hipMemcpyAsync(D->slice + a, sl1.data() + a, 8 * size_t(nr), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(D->status + a, st.data() + a, size_t(nr), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipEventRecord(D->ev[0], h->stream));
-        hipLaunchKernelGGL(k_dist_wave<false>, dim3(unsigned(nr)), dim3(64), 0, h->stream, T, D->jobs, a, nr, D->slice, int64_t(0), D->arena,
-                           D->status, D->score, D->need2, D->cells, pen);
-        HIPCHK(h, hipEventRecord(D->ev[1], h->stream));
-        HIPCHK(h, hipGetLastError());
-        n2.assign(size_t(nr), 0);
-        HIPCHK(h, hipMemcpyAsync(n2.data(), D->need2 + a, 8 * size_t(nr), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(st.data() + a, D->status + a, size_t(nr), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, x_sync(h, h->stream, SITE));
-        ms_score += ev_ms(D);
-        sl2.assign(size_t(nr), 0);
-        for (int64_t c = a; c < b;) {
-            const auto r2 = next_round(n2, c, b, a, sl2, round_cap2);
-            const int64_t dd = r2.first, m = dd - c;
-            I.n_hist_rounds++;
-            if (int rc = ensure_arena(std::max<int64_t>(r2.second, 16))) return rc;
-            HIPCHK(h, hipMemcpyAsync(D->slice + c, sl2.data() + (c - a), 8 * size_t(m), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(D->status + c, st.data() + c, size_t(m), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipEventRecord(D->ev[0], h->stream));
-            hipLaunchKernelGGL(k_dist_wave<true>, dim3(unsigned(m)), dim3(64), 0, h->stream, T, D->jobs, c, m, D->slice, int64_t(0), D->arena,
-                               D->status, D->score, D->need2, D->cells, pen);
-            HIPCHK(h, hipEventRecord(D->ev[1], h->stream));
-            ms_hist += ev_ms(D);
-            HIPCHK(h, hipEventRecord(D->ev[0], h->stream));
-            const unsigned gb = unsigned((m + 63) / 64);
-            hipLaunchKernelGGL(k_dist_back<false>, dim3(gb), dim3(64), 0, h->stream, T, D->jobs, c, m, D->slice, int64_t(0), D->arena,
-                               D->status, D->score, D->cells, D->dist, D->nrec, D->recoff, int64_t(0), D->edits, D->qdiff, pen);
-            HIPCHK(h, hipMemsetAsync(D->nrec + m, 0, sizeof(int64_t), h->stream));
-            if (int rc = scan_i64(h, D, D->nrec, D->recoff, size_t(m) + 1)) return rc;
-            int64_t got = 0;
-            HIPCHK(h, hipMemcpyAsync(&got, D->recoff + m, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, x_sync(h, h->stream, SITE));
-            if (n_edits + got > D->edit_cap) {              // grow the record buffer, keeping what it holds
-                int64_t cap = std::max<int64_t>(D->edit_cap * 2, std::max<int64_t>(n_edits + got, 1024));
-                DEdit *nb = nullptr;
-                if (x_malloc(h, reinterpret_cast<void **>(&nb), size_t(cap) * sizeof(DEdit), SITE) != hipSuccess) {
-                    (void)hipGetLastError();
-                    return fail(h, VPR_ERR_NOMEM, "vpr_distance: cannot allocate %lld edit records", (long long)cap);
-                }
-                if (n_edits) HIPCHK(h, hipMemcpyAsync(nb, D->edits, size_t(n_edits) * sizeof(DEdit), hipMemcpyDeviceToDevice, h->stream));
-                HIPCHK(h, x_sync(h, h->stream, SITE));
-                if (D->edits) (void)x_free(h, D->edits, SITE);
-                D->edits = nb; D->edit_cap = cap;
-            }
-            if (got)
-                hipLaunchKernelGGL(k_dist_back<true>, dim3(gb), dim3(64), 0, h->stream, T, D->jobs, c, m, D->slice, int64_t(0), D->arena,
-                                   D->status, D->score, D->cells, D->dist, D->nrec, D->recoff, -n_edits, D->edits, D->qdiff, pen);
-            HIPCHK(h, hipEventRecord(D->ev[1], h->stream));
-            HIPCHK(h, hipGetLastError());
-            ms_back += ev_ms(D);
-            n_edits += got;
-            c = dd;
-        }
-        HIPCHK(h, hipMemcpyAsync(st.data() + a, D->status + a, size_t(nr), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, x_sync(h, h->stream, SITE));
-        a = b;
-    }
+    int rc_back = VPR_OK;
+    swg::Rounds R{h->stream, {D->ev[0], D->ev[1]}, plan, round_cap1, round_cap2, VPR_DIST_ST_LIMIT, D->slice.p, D->status.p, D->need2.p};
+    const int rr = R.run(
+        n1, st, [&] { return x_sync(h, h->stream, SITE); },
+        [&](int64_t bytes) { return D->arena.reserve(h, size_t(bytes), "vpr_distance: cannot allocate a round arena of %zu bytes") ? nullptr : D->arena.p; },
+        [&](bool hist, int64_t a, int64_t n, uint8_t *arena) {
+            if (hist)
+                hipLaunchKernelGGL(k_dist_wave<true>, dim3(unsigned(n)), dim3(64), 0, h->stream, T, D->jobs.p, a, n, D->slice.p, int64_t(0), arena,
+                                   D->status.p, D->score.p, D->need2.p, D->cells.p, pen);
+            else
+                hipLaunchKernelGGL(k_dist_wave<false>, dim3(unsigned(n)), dim3(64), 0, h->stream, T, D->jobs.p, a, n, D->slice.p, int64_t(0), arena,
+                                   D->status.p, D->score.p, D->need2.p, D->cells.p, pen);
+        },
+        [&](int64_t c, int64_t m, uint8_t *arena) { return (rc_back = back(c, m, arena)) ? int(ROUNDS_DEVICE) : int(ROUNDS_OK); },
+        [&](int64_t, int64_t) { n_edits += got; return int(ROUNDS_OK); });
+    I.n_rounds = R.n_rounds; I.n_hist_rounds = R.n_hist_rounds; I.arena_bytes = R.arena_bytes;
+    if (rc_back) return rc_back;
+    if (rr == ROUNDS_NOMEM) return VPR_ERR_NOMEM;           // (the message is the arena's)
+    if (rr) return fail(h, VPR_ERR_DEVICE, "vpr_distance: %s failed: %s", R.what, hipGetErrorString(R.err));
     // cells of the histories, for the statistics
     if (n_jobs) {
         std::vector<int64_t> cl(static_cast<size_t>(n_jobs));
-        HIPCHK(h, hipMemcpyAsync(cl.data(), D->cells, 8 * size_t(n_jobs), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(cl.data(), D->cells.p, 8 * size_t(n_jobs), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, x_sync(h, h->stream, SITE));
         for (int64_t k = 0; k < n_jobs; k++) if (!st[size_t(k)]) I.history_cells += cl[size_t(k)];
         for (uint8_t s : st) { I.n_limit += (s & VPR_DIST_ST_LIMIT) != 0; I.n_error += (s & VPR_DIST_ST_ERROR) != 0; }
         // jobs that never ran keep no distance
-        HIPCHK(h, hipMemcpyAsync(D->status, st.data(), size_t(n_jobs), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(D->status.p, st.data(), size_t(n_jobs), hipMemcpyHostToDevice, h->stream));
     }
     I.n_edits = n_edits;
-    I.ms_score = ms_score; I.ms_hist = ms_hist; I.ms_back = ms_back;
+    I.ms_score = R.ms_score; I.ms_hist = R.ms_hist; I.ms_back = R.ms_back;
     HIPCHK(h, x_sync(h, h->stream, SITE));
     I.ms_wall = wall_ms() - t_wall;
     D->valid = true;
@@ -600,12 +507,12 @@ extern "C" int vpr_distance_download(vpr_handle *h, vpr_dist_results *r) {
     std::vector<DEdit> ed(static_cast<size_t>(ne));
     std::vector<unsigned long long> qd(size_t(nq) + 1);
     if (nj) {
-        HIPCHK(h, hipMemcpyAsync(jobs.data(), D->jobs, sizeof(DJob) * size_t(nj), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(dist.data(), D->dist, 4 * size_t(nj), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(st.data(), D->status, size_t(nj), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(jobs.data(), D->jobs.p, sizeof(DJob) * size_t(nj), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(dist.data(), D->dist.p, 4 * size_t(nj), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(st.data(), D->status.p, size_t(nj), hipMemcpyDeviceToHost, h->stream));
     }
-    if (ne) HIPCHK(h, hipMemcpyAsync(ed.data(), D->edits, sizeof(DEdit) * size_t(ne), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(qd.data(), D->qdiff, sizeof(unsigned long long) * (size_t(nq) + 1), hipMemcpyDeviceToHost, h->stream));
+    if (ne) HIPCHK(h, hipMemcpyAsync(ed.data(), D->edits.p, sizeof(DEdit) * size_t(ne), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(qd.data(), D->qdiff.p, sizeof(unsigned long long) * (size_t(nq) + 1), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, x_sync(h, h->stream, SITE));
     for (int64_t k = 0; k < nj; k++) {
         const DJob &J = jobs[size_t(k)];

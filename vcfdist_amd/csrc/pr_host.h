@@ -3,7 +3,8 @@
 //   pr_api.hip      planner, vpr_create / vpr_upload (memory plan) / vpr_execute (Exec), all device kernels of the path
 //   pr_mem.hip      allocator wrappers, the process-wide books of device memory, block caches (dev_alloc, pin_alloc, exec_alloc)
 //   pr_results.hip  vpr_download, vpr_results_alloc, tallies, timing and launch statistics
-//   pr_collect.hip  the counters histogram, vpr_pr_counts, and the RCCL collectives (vpr_allreduce_counts, vpr_allgather_phase)
+//   pr_collect.hip  the counters histogram, vpr_pr_counts, and the RCCL collectives (vpr_allreduce_counts, vpr_allgather_phase);
+//                   the front and back of a counters call that pr_strata.hip and pr_boot.hip share (the bin rule: pr_counts.h)
 //   pr_strata.hip   the region-stratified counters (include/vcfdist_strata.h): membership words, the stratified histogram
 //   pr_context.hip  the sequence-context strata (include/vcfdist_context.h): interval lists built from the contig sequences
 //   pr_boot.hip     the bootstrap replicates of the counters (include/vcfdist_bootstrap.h): the replicate histogram
@@ -455,8 +456,9 @@ void free_batch(vpr_handle *h);
 void dist_free(vpr_handle *h);                                       // pr_dist.hip: all of the distance step's device memory
 void dist_release_work(vpr_handle *h);                               // pr_dist.hip: all but what vpr_distance_download reads
 void strata_free(vpr_handle *h);                                     // pr_strata.hip: the membership words and the stratified histogram
-// pr_strata.hip: the resident membership words (word-major per slot) for pr_boot.hip's stratum cut; false without valid words
-bool strata_view(const vpr_handle *h, int32_t *n_strata, int64_t n_var[VPR_HAPS], const uint64_t *words[VPR_HAPS]);
+// pr_strata.hip: the resident membership words (word-major per slot) of the executed batch for a counters entry (`entry`: its
+// name, for the messages); VPR_ERR_STATE without valid words or with words of another batch's variant counts
+int strata_view(vpr_handle *h, const char *entry, int32_t *n_strata, const uint64_t *words[VPR_HAPS]);
 // pr_strata.hip, shared with pr_context.hip: the argument checks of vpr_strata_masks (s null: the variant tables alone) and the
 // membership words of the checked variants against interval tables that are already on the device
 int strata_check(vpr_handle *h, const vpr_variants *v, const struct vpr_strata *s);
@@ -464,11 +466,14 @@ int strata_masks_device(vpr_handle *h, const vpr_variants *v, int32_t n_strata, 
                         const int32_t *d_iv_stop);
 void context_free(vpr_handle *h);                                    // pr_context.hip: the resident context intervals
 void boot_free(vpr_handle *h);                                       // pr_boot.hip: the replicate histogram and the keys
-// pr_collect.hip, shared with pr_strata.hip: the inputs of a counters call, the host fold of one histogram, the all-reduce
-int pr_counts_inputs(vpr_handle *h, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase, int32_t **d_pb);
+// pr_collect.hip, shared by the three counters entries (vpr_pr_counts, _strata, _boot; `entry`: the entry's name, for the
+// messages).  pr_counts_begin: the state checks and the device, before the entry's own buffers; pr_counts_inputs: the caller's
+// phase-block phasing and variant classes on the device (*d_pb stays null without pb_phase), every slot with variants has classes;
+// pr_counts_finish: the all-reduce (comm non-null), the nh histogram words to the host, the wait; then the host fold of one histogram
+int pr_counts_begin(vpr_handle *h, const char *entry, void *comm);
+int pr_counts_inputs(vpr_handle *h, const char *entry, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase, int32_t **d_pb);
+int pr_counts_finish(vpr_handle *h, void *comm, unsigned long long *d_hist, size_t nh, unsigned long long *hist);
 void pr_fold_counts(const unsigned long long *hist, int nq, int64_t *counts);
-bool rccl_has_allreduce();
-int rccl_allreduce_u64(vpr_handle *h, unsigned long long *d_buf, size_t n, void *comm);
 template <typename T>
 int dev_alloc(vpr_handle *h, T **p, size_t n) {
     void *q = nullptr;
@@ -476,6 +481,38 @@ int dev_alloc(vpr_handle *h, T **p, size_t n) {
     *p = static_cast<T *>(q);
     return rc;
 }
+// A device buffer that only grows, through the counted allocator calls.  reserve() makes room for n elements and allocates exactly
+// that many (how far ahead to grow is the caller's policy).  Without `keep` the old block is freed first; with it the first `keep`
+// elements are copied into the new block and the stream drained before the old one is freed.  nomem: the message of a refused
+// allocation, a format with one %zu for its bytes.
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;                      // elements
+    int reserve(vpr_handle *h, size_t n, const char *nomem, size_t keep = 0) {
+        if (p && cap >= n) return VPR_OK;
+        n = std::max<size_t>(n, 1);
+        if (!keep) release(h);
+        void *q = nullptr;
+        if (x_malloc(h, &q, n * sizeof(T), SITE) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, VPR_ERR_NOMEM, nomem, n * sizeof(T));
+        }
+        if (keep) {
+            HIPCHK(h, hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(h, x_sync(h, h->stream, SITE));
+            release(h);
+        }
+        p = static_cast<T *>(q); cap = n;
+        return VPR_OK;
+    }
+    void release(vpr_handle *h) {
+        if (p) (void)x_free(h, p, SITE);
+        p = nullptr; cap = 0;
+    }
+};
+template <typename... B>
+void dev_release(vpr_handle *h, B &...bufs) { (bufs.release(h), ...); }
 template <typename T>
 int dev_upload(vpr_handle *h, const T **dst, const T *src, size_t n) {
     T *p;

@@ -9,8 +9,7 @@
 //   k_rl_back      one thread per job: the walk of pr_swg.h with add_variants as a state machine over its forward steps (one SUB
 //                  record per base, then DEL runs and INS runs).  Launched twice: count (records, allele bytes), then, after a
 //                  scan of both, write the records and copy their allele bytes out of the arena in the same round
-// Rounds and the memory plan as in pr_dist.hip.  The host then merges the records with the kept clusters' variants and runs
-// left_shift.
+// The rounds are pr_swg.h's.  The host then merges the records with the kept clusters' variants and runs left_shift.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -321,13 +320,13 @@ extern "C" int vrl_realign(const vcl_hap_seq *hs, const float *var_qual, const f
         (void)hipEventRecord(D.ev[1], D.st);
         if (hipGetLastError() != hipSuccess) return VRL_ERR_DEVICE;
         I.ms_jobs = D.ms();
-        std::vector<int64_t> n1(static_cast<size_t>(n_cl)), n2;
+        std::vector<int64_t> n1(static_cast<size_t>(n_cl));
         if (hipMemcpyAsync(n1.data(), d_need1, 8 * size_t(n_cl), hipMemcpyDeviceToHost, D.st) != hipSuccess ||
             hipMemcpyAsync(st.data(), d_status, size_t(n_cl), hipMemcpyDeviceToHost, D.st) != hipSuccess ||
             hipStreamSynchronize(D.st) != hipSuccess)
             return VRL_ERR_DEVICE;
 
-        // ---- memory plan: half of what the device has free for one job (or the caller's limit); rounds as in pr_dist.hip
+        // ---- memory plan: half of what the device has free for one job (or the caller's limit)
         size_t fr = 0, tt = 0;
         if (hipMemGetInfo(&fr, &tt) != hipSuccess) return VRL_ERR_DEVICE;
         const int64_t plan = std::max<int64_t>(int64_t(fr) / 2, int64_t(1) << 20);
@@ -336,27 +335,6 @@ extern "C" int vrl_realign(const vcl_hap_seq *hs, const float *var_qual, const f
         const int64_t cap2 = cfg->round_bytes > 0 ? std::min<int64_t>(cfg->round_bytes, limit) : limit;
         I.plan_bytes = limit;
         uint8_t *arena = nullptr;
-        int64_t arena_cap = 0;
-        auto ensure_arena = [&](int64_t bytes) -> bool {
-            I.arena_bytes = std::max(I.arena_bytes, bytes);
-            if (bytes <= arena_cap) return true;
-            D.release(arena);
-            arena = D.alloc<uint8_t>(size_t(bytes));
-            arena_cap = arena ? bytes : 0;
-            return arena != nullptr;
-        };
-        auto next_round = [&](const std::vector<int64_t> &need, int64_t a, int64_t b, int64_t off0, std::vector<int64_t> &slice, int64_t cap) {
-            int64_t sum = 0, k = a;
-            for (; k < b; k++) {
-                const int64_t nb = need[size_t(k - off0)];
-                if (st[size_t(k)]) { slice[size_t(k - off0)] = sum; continue; }
-                if (nb > limit) { st[size_t(k)] = VRL_ST_LIMIT; slice[size_t(k - off0)] = sum; continue; }
-                if (sum > 0 && sum + nb > cap) break;
-                slice[size_t(k - off0)] = sum;
-                sum += nb;
-            }
-            return std::make_pair(k, sum);
-        };
         void *scan_tmp = nullptr;
         size_t scan_cap = 0;
         auto scan = [&](const int64_t *in, int64_t *o, size_t n) -> bool {
@@ -372,79 +350,56 @@ extern "C" int vrl_realign(const vcl_hap_seq *hs, const float *var_qual, const f
         };
         RRec *d_recs = nullptr;
         uint8_t *d_pool = nullptr;
-        int64_t rec_cap = 0, pool_cap = 0;
-        std::vector<int64_t> sl1(static_cast<size_t>(n_cl)), sl2;
-        for (int64_t a = 0; a < n_cl;) {
-            const auto r1 = next_round(n1, a, n_cl, 0, sl1, cap1);
-            const int64_t b = r1.first, nr = b - a;
-            I.n_rounds++;
-            if (!ensure_arena(std::max<int64_t>(r1.second, 16))) return VRL_ERR_NOMEM;
-            if (hipMemcpyAsync(d_slice + a, sl1.data() + a, 8 * size_t(nr), hipMemcpyHostToDevice, D.st) != hipSuccess ||
-                hipMemcpyAsync(d_status + a, st.data() + a, size_t(nr), hipMemcpyHostToDevice, D.st) != hipSuccess)
-                return VRL_ERR_DEVICE;
-            (void)hipEventRecord(D.ev[0], D.st);
-            hipLaunchKernelGGL(k_rl_wave<false>, dim3(unsigned(nr)), dim3(64), 0, D.st, T, d_jobs, a, nr, d_slice, arena, d_status, d_score,
-                               d_need2, d_cells, pen);
-            (void)hipEventRecord(D.ev[1], D.st);
-            if (hipGetLastError() != hipSuccess) return VRL_ERR_DEVICE;
-            n2.assign(size_t(nr), 0);
-            if (hipMemcpyAsync(n2.data(), d_need2 + a, 8 * size_t(nr), hipMemcpyDeviceToHost, D.st) != hipSuccess ||
-                hipMemcpyAsync(st.data() + a, d_status + a, size_t(nr), hipMemcpyDeviceToHost, D.st) != hipSuccess ||
+        int64_t rec_cap = 0, pool_cap = 0, got[2] = {0, 0};
+        // the backtrack of a sub-round: count records and bytes, scan both, write them into buffers of the sub-round's own
+        auto back = [&](int64_t c, int64_t m, uint8_t *ar) -> int {
+            const unsigned gb = unsigned((m + 63) / 64);
+            hipLaunchKernelGGL(k_rl_back<false>, dim3(gb), dim3(64), 0, D.st, d_jobs, c, m, d_slice, ar, d_status, d_score, d_cells,
+                               d_nrec, d_nbyte, d_roff, d_boff, int64_t(0), int64_t(0), d_recs, d_pool, pen);
+            if (hipMemsetAsync(d_nrec + m, 0, 8, D.st) != hipSuccess || hipMemsetAsync(d_nbyte + m, 0, 8, D.st) != hipSuccess)
+                return ROUNDS_DEVICE;
+            if (!scan(d_nrec, d_roff, size_t(m) + 1) || !scan(d_nbyte, d_boff, size_t(m) + 1)) return ROUNDS_DEVICE;
+            if (hipMemcpyAsync(&got[0], d_roff + m, 8, hipMemcpyDeviceToHost, D.st) != hipSuccess ||
+                hipMemcpyAsync(&got[1], d_boff + m, 8, hipMemcpyDeviceToHost, D.st) != hipSuccess ||
+                hipMemcpyAsync(nrec.data() + c, d_nrec, 8 * size_t(m), hipMemcpyDeviceToHost, D.st) != hipSuccess ||
+                hipMemcpyAsync(nbyte.data() + c, d_nbyte, 8 * size_t(m), hipMemcpyDeviceToHost, D.st) != hipSuccess ||
                 hipStreamSynchronize(D.st) != hipSuccess)
-                return VRL_ERR_DEVICE;
-            I.ms_score += D.ms();
-            sl2.assign(size_t(nr), 0);
-            for (int64_t c = a; c < b;) {
-                const auto r2 = next_round(n2, c, b, a, sl2, cap2);
-                const int64_t dd = r2.first, m = dd - c;
-                I.n_hist_rounds++;
-                if (!ensure_arena(std::max<int64_t>(r2.second, 16))) return VRL_ERR_NOMEM;
-                if (hipMemcpyAsync(d_slice + c, sl2.data() + (c - a), 8 * size_t(m), hipMemcpyHostToDevice, D.st) != hipSuccess ||
-                    hipMemcpyAsync(d_status + c, st.data() + c, size_t(m), hipMemcpyHostToDevice, D.st) != hipSuccess)
-                    return VRL_ERR_DEVICE;
-                (void)hipEventRecord(D.ev[0], D.st);
-                hipLaunchKernelGGL(k_rl_wave<true>, dim3(unsigned(m)), dim3(64), 0, D.st, T, d_jobs, c, m, d_slice, arena, d_status, d_score,
-                                   d_need2, d_cells, pen);
-                (void)hipEventRecord(D.ev[1], D.st);
-                I.ms_hist += D.ms();
-                (void)hipEventRecord(D.ev[0], D.st);
-                const unsigned gb = unsigned((m + 63) / 64);
-                hipLaunchKernelGGL(k_rl_back<false>, dim3(gb), dim3(64), 0, D.st, d_jobs, c, m, d_slice, arena, d_status, d_score, d_cells,
+                return ROUNDS_DEVICE;
+            if (got[0] > rec_cap) { D.release(d_recs); d_recs = D.alloc<RRec>(size_t(got[0])); rec_cap = d_recs ? got[0] : 0; if (!d_recs) return ROUNDS_NOMEM; }
+            if (got[1] > pool_cap) { D.release(d_pool); d_pool = D.alloc<uint8_t>(size_t(got[1])); pool_cap = d_pool ? got[1] : 0; if (!d_pool) return ROUNDS_NOMEM; }
+            if (got[0])
+                hipLaunchKernelGGL(k_rl_back<true>, dim3(gb), dim3(64), 0, D.st, d_jobs, c, m, d_slice, ar, d_status, d_score, d_cells,
                                    d_nrec, d_nbyte, d_roff, d_boff, int64_t(0), int64_t(0), d_recs, d_pool, pen);
-                if (hipMemsetAsync(d_nrec + m, 0, 8, D.st) != hipSuccess || hipMemsetAsync(d_nbyte + m, 0, 8, D.st) != hipSuccess)
-                    return VRL_ERR_DEVICE;
-                if (!scan(d_nrec, d_roff, size_t(m) + 1) || !scan(d_nbyte, d_boff, size_t(m) + 1)) return VRL_ERR_DEVICE;
-                int64_t got[2] = {0, 0};
-                if (hipMemcpyAsync(&got[0], d_roff + m, 8, hipMemcpyDeviceToHost, D.st) != hipSuccess ||
-                    hipMemcpyAsync(&got[1], d_boff + m, 8, hipMemcpyDeviceToHost, D.st) != hipSuccess ||
-                    hipMemcpyAsync(nrec.data() + c, d_nrec, 8 * size_t(m), hipMemcpyDeviceToHost, D.st) != hipSuccess ||
-                    hipMemcpyAsync(nbyte.data() + c, d_nbyte, 8 * size_t(m), hipMemcpyDeviceToHost, D.st) != hipSuccess ||
-                    hipStreamSynchronize(D.st) != hipSuccess)
-                    return VRL_ERR_DEVICE;
-                // this sub-round's records and bytes go to buffers of their own, downloaded before the arena is reused
-                if (got[0] > rec_cap) { D.release(d_recs); d_recs = D.alloc<RRec>(size_t(got[0])); rec_cap = d_recs ? got[0] : 0; if (!d_recs) return VRL_ERR_NOMEM; }
-                if (got[1] > pool_cap) { D.release(d_pool); d_pool = D.alloc<uint8_t>(size_t(got[1])); pool_cap = d_pool ? got[1] : 0; if (!d_pool) return VRL_ERR_NOMEM; }
-                if (got[0])
-                    hipLaunchKernelGGL(k_rl_back<true>, dim3(gb), dim3(64), 0, D.st, d_jobs, c, m, d_slice, arena, d_status, d_score, d_cells,
-                                       d_nrec, d_nbyte, d_roff, d_boff, int64_t(0), int64_t(0), d_recs, d_pool, pen);
-                (void)hipEventRecord(D.ev[1], D.st);
-                if (hipGetLastError() != hipSuccess) return VRL_ERR_DEVICE;
-                I.ms_back += D.ms();
-                const size_t r0 = recs.size(), p0 = rpool.size();
-                recs.resize(r0 + size_t(got[0]));
-                rpool.resize(p0 + size_t(got[1]));
-                if ((got[0] && hipMemcpyAsync(recs.data() + r0, d_recs, sizeof(RRec) * size_t(got[0]), hipMemcpyDeviceToHost, D.st) != hipSuccess) ||
-                    (got[1] && hipMemcpyAsync(rpool.data() + p0, d_pool, size_t(got[1]), hipMemcpyDeviceToHost, D.st) != hipSuccess) ||
-                    hipStreamSynchronize(D.st) != hipSuccess)
-                    return VRL_ERR_DEVICE;
-                for (size_t k = r0; k < recs.size(); k++) recs[k].boff += int64_t(p0);
-                c = dd;
-            }
-            if (hipMemcpyAsync(st.data() + a, d_status + a, size_t(nr), hipMemcpyDeviceToHost, D.st) != hipSuccess ||
+            return ROUNDS_OK;
+        };
+        // its records and bytes come down before the arena and the two buffers are reused
+        auto collect = [&](int64_t, int64_t) -> int {
+            const size_t r0 = recs.size(), p0 = rpool.size();
+            recs.resize(r0 + size_t(got[0]));
+            rpool.resize(p0 + size_t(got[1]));
+            if ((got[0] && hipMemcpyAsync(recs.data() + r0, d_recs, sizeof(RRec) * size_t(got[0]), hipMemcpyDeviceToHost, D.st) != hipSuccess) ||
+                (got[1] && hipMemcpyAsync(rpool.data() + p0, d_pool, size_t(got[1]), hipMemcpyDeviceToHost, D.st) != hipSuccess) ||
                 hipStreamSynchronize(D.st) != hipSuccess)
-                return VRL_ERR_DEVICE;
-            a = b;
-        }
+                return ROUNDS_DEVICE;
+            for (size_t k = r0; k < recs.size(); k++) recs[k].boff += int64_t(p0);
+            return ROUNDS_OK;
+        };
+        Rounds R{D.st, {D.ev[0], D.ev[1]}, limit, cap1, cap2, VRL_ST_LIMIT, d_slice, d_status, d_need2};
+        const int rr = R.run(
+            n1, st, [&] { return hipStreamSynchronize(D.st); },
+            [&](int64_t bytes) { D.release(arena); return arena = D.alloc<uint8_t>(size_t(bytes)); },
+            [&](bool hist, int64_t a, int64_t n, uint8_t *ar) {
+                if (hist)
+                    hipLaunchKernelGGL(k_rl_wave<true>, dim3(unsigned(n)), dim3(64), 0, D.st, T, d_jobs, a, n, d_slice, ar, d_status, d_score,
+                                       d_need2, d_cells, pen);
+                else
+                    hipLaunchKernelGGL(k_rl_wave<false>, dim3(unsigned(n)), dim3(64), 0, D.st, T, d_jobs, a, n, d_slice, ar, d_status, d_score,
+                                       d_need2, d_cells, pen);
+            },
+            back, collect);
+        if (rr) return rr == ROUNDS_NOMEM ? VRL_ERR_NOMEM : VRL_ERR_DEVICE;
+        I.n_rounds = R.n_rounds; I.n_hist_rounds = R.n_hist_rounds; I.arena_bytes = R.arena_bytes;
+        I.ms_score = R.ms_score; I.ms_hist = R.ms_hist; I.ms_back = R.ms_back;
     }
 
     // ---- merge: each cluster's records, or its original variants where it carries a status bit; then left_shift

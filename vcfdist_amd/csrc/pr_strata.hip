@@ -1,16 +1,17 @@
 // pr_strata.hip -- the region-stratified precision/recall counters (include/vcfdist_strata.h): one evaluation, cut by region
 // afterwards.  k_strata_mask gives every variant a bit per stratum (the membership rule is the host's vio_bed_contains ==
-// VIO_BED_INSIDE, vcf_io.cpp, which follows bedData::contains, bed.cpp:73-121); k_pr_hist_strata is k_pr_hist
-// (pr_collect.hip) repeated into every stratum whose bit is set.  The host fold of a histogram, the inputs of a counters
-// call and the all-reduce are the ones of pr_collect.hip.
+// VIO_BED_INSIDE, vcf_io.cpp, which follows bedData::contains, bed.cpp:73-121); k_pr_hist_strata counts a variant's bin
+// (pr_counts.h) into every stratum whose bit is set.  The host fold of a histogram and the front and back of a counters call
+// are the ones of pr_collect.hip.
 #include "pr_host.h"
+#include "pr_counts.h"
 #include "../../include/vcfdist_strata.h"
 
 struct StrataState {
     int32_t n_strata = 0, n_words = 0;
     int64_t n_var[VPR_HAPS] = {0, 0, 0, 0};
-    uint64_t *words[VPR_HAPS] = {nullptr, nullptr, nullptr, nullptr};   // word-major: [n_words][n_var[slot]]
-    unsigned long long *hist = nullptr; size_t hist_cap = 0;            // [n_strata][2][3 classes][3][nq + 1]
+    DevBuf<uint64_t> words[VPR_HAPS];                                   // word-major: [n_words][n_var[slot]]
+    DevBuf<unsigned long long> hist;                                    // [n_strata][2][3 classes][3][nq + 1]
     bool valid = false;
     // device time of the last k_strata_mask launches / k_pr_hist_strata launches (vpr_strata_timing)
     hipEvent_t ev[2] = {nullptr, nullptr};
@@ -30,13 +31,6 @@ int hist_chunk(int nq) {
     int c = 64;
     while (c > 1 && size_t(c) * per > HIST_LDS_BUDGET) c >>= 1;
     return c;
-}
-
-// supercluster of variant v: the largest sc with var_off[sc] <= v (as k_pr_hist)
-__device__ inline int sc_of_var(const int64_t *__restrict__ var_off, int n_sc, int64_t v) {
-    int lo = 0, hi = n_sc;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (var_off[mid] <= v) lo = mid; else hi = mid; }
-    return lo;
 }
 
 }  // namespace
@@ -98,22 +92,14 @@ __global__ void __launch_bounds__(256) k_pr_hist_strata(const int64_t *__restric
         uint64_t bits = words[size_t(k0 >> 6) * size_t(n_var) + size_t(v)] >> (k0 & 63);
         if (nk < 64) bits &= (uint64_t(1) << nk) - 1;
         if (bits) {
-            const int sc = sc_of_var(var_off, n_sc, v);
-            const int ph = sc_phase[sc];
-            const int swap = ph == VPR_PHASE_ORIG ? 0 : (ph == VPR_PHASE_SWAP ? 1 : (pb_phase ? (pb_phase[sc] != 0) : 0));
-            const VarCols &C = swap ? c1 : c0;
-            const int e = C.errtype[v];
-            if (e < 3) {                                         // ERRTYPE_UN etc.: skipped, as in k_pr_hist
-                const float q = C.callq[v];
-                int b = (q < float(min_qual)) ? -1 : int(floorf(q)) - min_qual;   // last threshold index the variant counts at
-                if (b >= nq) b = nq - 1;
-                const int t = cls[v] > 2 ? 2 : cls[v];
-                const int bin = (t * 3 + e) * (nq + 1) + (b < 0 ? nq : b);      // bin nq: counts at no threshold
-                while (bits) {
-                    const int j = __ffsll((long long)bits) - 1;
-                    bits &= bits - 1;
-                    atomicAdd(&blk[j * nb + bin], 1u);
-                }
+            int b = 0;
+            const int row = pr_count_row(sc_of_var(var_off, n_sc, v), v, sc_phase, pb_phase, c0.errtype, c1.errtype, c0.callq, c1.callq, cls,
+                                         min_qual, nq, &b);
+            const int bin = row * (nq + 1) + b;
+            while (row >= 0 && bits) {
+                const int j = __ffsll((long long)bits) - 1;
+                bits &= bits - 1;
+                atomicAdd(&blk[j * nb + bin], 1u);
             }
         }
     }
@@ -133,10 +119,7 @@ double ev_ms(const StrataState *S) {     // (both events have completed: the cal
 }
 
 void release_words(vpr_handle *h, StrataState *S) {
-    for (int s = 0; s < VPR_HAPS; s++) {
-        if (S->words[s]) (void)x_free(h, S->words[s], SITE);
-        S->words[s] = nullptr; S->n_var[s] = 0;
-    }
+    for (int s = 0; s < VPR_HAPS; s++) { S->words[s].release(h); S->n_var[s] = 0; }
     S->valid = false;
 }
 
@@ -149,12 +132,10 @@ int strata_prepare(vpr_handle *h, int32_t n_strata, const int64_t n_var[VPR_HAPS
     S->ms_mask = S->ms_hist = 0;
     S->n_strata = n_strata; S->n_words = (n_strata + 63) / 64;
     for (int s = 0; s < VPR_HAPS; s++) {
-        const size_t bytes = std::max<size_t>(size_t(S->n_words) * size_t(n_var[s]) * 8, 256);
-        if (x_malloc(h, reinterpret_cast<void **>(&S->words[s]), bytes, SITE) != hipSuccess) {
-            S->words[s] = nullptr;
-            (void)hipGetLastError();
+        const size_t n = std::max<size_t>(size_t(S->n_words) * size_t(n_var[s]), 32);
+        if (int rc = S->words[s].reserve(h, n, "stratum membership words: cannot allocate %zu bytes on the device")) {
             release_words(h, S);
-            return fail(h, VPR_ERR_NOMEM, "stratum membership words: cannot allocate %zu bytes on the device", bytes);
+            return rc;
         }
         S->n_var[s] = n_var[s];
     }
@@ -164,51 +145,35 @@ int strata_prepare(vpr_handle *h, int32_t n_strata, const int64_t n_var[VPR_HAPS
 int strata_counts_impl(vpr_handle *h, void *comm, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase,
                        int32_t min_qual, int32_t max_qual, int64_t *counts) {
     if (!h || !counts || max_qual < min_qual) return VPR_ERR_ARG;
-    if (comm && !rccl_has_allreduce()) return fail(h, VPR_ERR_STATE, "no RCCL in this process (librccl.so.1 not found)");
-    if (!h->executed) return fail(h, VPR_ERR_STATE, "vpr_pr_counts_strata before vpr_execute");
+    if (int rc = pr_counts_begin(h, "vpr_pr_counts_strata", comm)) return rc;
+    int32_t n_strata = 0;
+    const uint64_t *words[VPR_HAPS];
+    if (int rc = strata_view(h, "vpr_pr_counts_strata", &n_strata, words)) return rc;
     StrataState *S = h->strata;
-    if (!S || !S->valid) return fail(h, VPR_ERR_STATE, "vpr_pr_counts_strata: no membership words (call vpr_strata_masks or vpr_strata_upload_masks after the upload)");
-    for (int s = 0; s < VPR_HAPS; s++)
-        if (S->n_var[s] != h->n_var[s])
-            return fail(h, VPR_ERR_STATE, "vpr_pr_counts_strata: the membership words hold %lld variants of hap slot %d, the executed batch has %lld",
-                        (long long)S->n_var[s], s, (long long)h->n_var[s]);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
     const int nq = max_qual - min_qual + 1;
-    const size_t nb = size_t(9) * size_t(nq + 1), nh1 = 2 * nb, nh = size_t(S->n_strata) * nh1;
-    if (nh > S->hist_cap) {
-        if (S->hist) (void)x_free(h, S->hist, SITE);
-        S->hist = nullptr; S->hist_cap = 0;
-        if (x_malloc(h, reinterpret_cast<void **>(&S->hist), nh * 8, SITE) != hipSuccess) {
-            S->hist = nullptr;
-            (void)hipGetLastError();
-            return fail(h, VPR_ERR_NOMEM, "stratified histogram: cannot allocate %zu bytes on the device", nh * 8);
-        }
-        S->hist_cap = nh;
-    }
-    HIPCHK(h, hipMemsetAsync(S->hist, 0, nh * 8, h->stream));
+    const size_t nb = size_t(9) * size_t(nq + 1), nh1 = 2 * nb, nh = size_t(n_strata) * nh1;
+    if (int rc = S->hist.reserve(h, nh, "stratified histogram: cannot allocate %zu bytes on the device")) return rc;
+    HIPCHK(h, hipMemsetAsync(S->hist.p, 0, nh * 8, h->stream));
     int32_t *d_pb = nullptr;
-    if (int rc = pr_counts_inputs(h, var_class, pb_phase, &d_pb)) return rc;
+    if (int rc = pr_counts_inputs(h, "vpr_pr_counts_strata", var_class, pb_phase, &d_pb)) return rc;
     const int chunk = hist_chunk(nq);
-    const unsigned n_chunks = unsigned((S->n_strata + chunk - 1) / chunk);
-    const size_t lds = size_t(std::min(chunk, S->n_strata)) * nb * 4;
+    const unsigned n_chunks = unsigned((n_strata + chunk - 1) / chunk);
+    const size_t lds = size_t(std::min(chunk, n_strata)) * nb * 4;
     HIPCHK(h, hipEventRecord(S->ev[0], h->stream));
     for (int s = 0; s < VPR_HAPS; s++) {
         const int64_t nv = h->n_var[s];
         if (!nv) continue;
-        if (!h->d_cls[s]) return fail(h, VPR_ERR_STATE, "vpr_pr_counts_strata: no variant classes (pass var_class or call vpr_upload_var_class)");
         hipLaunchKernelGGL(k_pr_hist_strata, dim3(unsigned((nv + 255) / 256), n_chunks), dim3(256), lds, h->stream,
                            h->dB.var_off[s], h->n_sc, nv, h->d_cls[s], h->dR.sc_phase, d_pb, h->dR.v[s][0], h->dR.v[s][1],
-                           s >> 1, min_qual, max_qual, S->words[s], S->n_strata, chunk, S->hist);
+                           s >> 1, min_qual, max_qual, words[s], n_strata, chunk, S->hist.p);
         HIPCHK(h, hipGetLastError());
     }
     HIPCHK(h, hipEventRecord(S->ev[1], h->stream));
-    if (comm) if (int rc = rccl_allreduce_u64(h, S->hist, nh, comm)) return rc;
     std::vector<unsigned long long> hist(nh);
-    HIPCHK(h, hipMemcpyAsync(hist.data(), S->hist, nh * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, x_sync(h, h->stream, SITE));
+    if (int rc = pr_counts_finish(h, comm, S->hist.p, nh, hist.data())) return rc;
     S->ms_hist = ev_ms(S);
     const size_t nc1 = size_t(2) * VPR_VARTYPES * 3 * size_t(nq);
-    for (int k = 0; k < S->n_strata; k++) pr_fold_counts(hist.data() + size_t(k) * nh1, nq, counts + size_t(k) * nc1);
+    for (int k = 0; k < n_strata; k++) pr_fold_counts(hist.data() + size_t(k) * nh1, nq, counts + size_t(k) * nc1);
     return VPR_OK;
 }
 
@@ -218,7 +183,7 @@ void strata_free(vpr_handle *h) {
     StrataState *S = h->strata;
     if (!S) return;
     release_words(h, S);
-    if (S->hist) (void)x_free(h, S->hist, SITE);
+    S->hist.release(h);
     for (int k = 0; k < 2; k++) if (S->ev[k]) (void)hipEventDestroy(S->ev[k]);
     delete S;
     h->strata = nullptr;
@@ -302,7 +267,7 @@ int strata_masks_device(vpr_handle *h, const vpr_variants *v, int32_t n_strata, 
         hipLaunchKernelGGL(k_strata_mask, dim3(unsigned((n_var[i] + 255) / 256), unsigned(S->n_words)), dim3(256), 0, h->stream,
                            reinterpret_cast<const int64_t *>(at(i_var[i][0])), int(n_sc), n_var[i], reinterpret_cast<const int32_t *>(at(i_ctg)),
                            reinterpret_cast<const int32_t *>(at(i_var[i][1])), reinterpret_cast<const int32_t *>(at(i_var[i][2])), at(i_var[i][3]),
-                           d_iv_off, d_iv_start, d_iv_stop, n_strata, v->n_ctg, S->words[i]);
+                           d_iv_off, d_iv_start, d_iv_stop, n_strata, v->n_ctg, S->words[i].p);
         HIPCHK(h, hipGetLastError());
     }
     HIPCHK(h, hipEventRecord(S->ev[1], h->stream));
@@ -312,12 +277,18 @@ int strata_masks_device(vpr_handle *h, const vpr_variants *v, int32_t n_strata, 
     return VPR_OK;
 }
 
-bool strata_view(const vpr_handle *h, int32_t *n_strata, int64_t n_var[VPR_HAPS], const uint64_t *words[VPR_HAPS]) {
+int strata_view(vpr_handle *h, const char *entry, int32_t *n_strata, const uint64_t *words[VPR_HAPS]) {
     const StrataState *S = h->strata;
-    if (!S || !S->valid) return false;
+    if (!S || !S->valid)
+        return fail(h, VPR_ERR_STATE, "%s: no membership words (call vpr_strata_masks or vpr_strata_upload_masks after the upload)", entry);
+    for (int s = 0; s < VPR_HAPS; s++) {
+        if (S->n_var[s] != h->n_var[s])
+            return fail(h, VPR_ERR_STATE, "%s: the membership words hold %lld variants of hap slot %d, the executed batch has %lld", entry,
+                        (long long)S->n_var[s], s, (long long)h->n_var[s]);
+        words[s] = S->words[s].p;
+    }
     *n_strata = S->n_strata;
-    for (int s = 0; s < VPR_HAPS; s++) { n_var[s] = S->n_var[s]; words[s] = S->words[s]; }
-    return true;
+    return VPR_OK;
 }
 
 extern "C" {
@@ -361,7 +332,7 @@ int vpr_strata_download_masks(vpr_handle *h, uint64_t *const mask[VPR_HAPS]) {
         const size_t bytes = size_t(S->n_words) * size_t(S->n_var[s]) * 8;
         if (!bytes) continue;
         if (!mask[s]) return fail(h, VPR_ERR_ARG, "vpr_strata_download_masks: null buffer");
-        HIPCHK(h, hipMemcpyAsync(mask[s], S->words[s], bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(mask[s], S->words[s].p, bytes, hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, x_sync(h, h->stream, SITE));
     return VPR_OK;
@@ -378,7 +349,7 @@ int vpr_strata_upload_masks(vpr_handle *h, int32_t n_strata, const int64_t n_var
     StrataState *S = h->strata;
     for (int s = 0; s < VPR_HAPS; s++) {
         const size_t bytes = size_t(S->n_words) * size_t(n_var[s]) * 8;
-        if (bytes) HIPCHK(h, hipMemcpyAsync(S->words[s], mask[s], bytes, hipMemcpyHostToDevice, h->stream));
+        if (bytes) HIPCHK(h, hipMemcpyAsync(S->words[s].p, mask[s], bytes, hipMemcpyHostToDevice, h->stream));
     }
     HIPCHK(h, x_sync(h, h->stream, SITE));
     S->valid = true;

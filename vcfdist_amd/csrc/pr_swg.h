@@ -3,7 +3,8 @@
 //
 // A job's slice of the round arena holds, in order: the reversed query (pad16(q) bytes), the reversed truth / reference
 // (pad16(t)), the row headers (16 B each) and the cells (int32 offsets, then uint8 pointer flags in the history pass).  The caller
-// decides how a job's two strings are loaded (swg_wave's `load`) and what the walk emits (swg_walk's `emit`).
+// decides how a job's two strings are loaded (swg_wave's `load`) and what the walk emits (swg_walk's `emit`).  The host half at
+// the end (Rounds) runs the jobs of either step in rounds that fit the arena.
 //
 // The band: a row's cells can be set only from rows s-x, s-(o+e), s-e one diagonal apart at most, so every row s has a diagonal
 // range [lo_s, hi_s] that the previous ranges bound (arithmetic, the same in both passes); a cell outside it is provably never
@@ -11,8 +12,10 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <climits>
 #include <cstdint>
+#include <vector>
 
 namespace swg {
 
@@ -213,5 +216,115 @@ __device__ bool swg_walk(const uint8_t *base, int q, int t, int s_fin, int64_t c
     }
     return !bad;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side: the rounds both steps run their jobs in
+// ---------------------------------------------------------------------------------------------------------------------
+// Pass-1 scratch and pass-2 histories share one round arena.  Pass-1 rounds pack jobs up to cap1 bytes of scratch; inside each,
+// pass-2 sub-rounds pack its jobs up to cap2 bytes of history, and every sub-round is followed by the caller's backtrack step while
+// its histories are in the arena.  A job larger than its cap runs alone, a job larger than `limit` gets `limit_bit` and never runs,
+// a job that already carries a status is skipped.
+enum { ROUNDS_OK = 0, ROUNDS_NOMEM, ROUNDS_DEVICE };
+#define SWG_TRY(call) do { if ((err = (call)) != hipSuccess) { what = #call; return ROUNDS_DEVICE; } } while (0)
+struct Rounds {
+    hipStream_t st;
+    hipEvent_t ev[2];
+    int64_t limit, cap1, cap2;
+    uint8_t limit_bit;
+    int64_t *d_slice;               // the job columns on the device: arena offset (written here), status (both ways), pass-2 bytes (read here)
+    uint8_t *d_status;
+    const int64_t *d_need2;
+    // what a run leaves: rounds of either level, the peak bytes a round occupied, device time of the three phases, and the call
+    // that failed where run() returns ROUNDS_DEVICE of its own
+    int64_t n_rounds = 0, n_hist_rounds = 0, arena_bytes = 0;
+    double ms_score = 0, ms_hist = 0, ms_back = 0;
+    hipError_t err = hipSuccess;
+    const char *what = "";
+
+    // need1: the jobs' pass-1 bytes; status: the host copy, kept current.  The caller's pieces, all on `st`:
+    //   sync()                       waits for the stream (hipError_t)
+    //   arena(bytes)                 an arena of at least `bytes` from the caller's allocator, the previous one released; null: no memory
+    //   pass(hist, a, n, arena)      launches pass 1 / pass 2 of jobs [a, a + n)
+    //   back(c, m, arena)            the backtrack of sub-round [c, c + m) on the device (timed as ms_back); ROUNDS_*
+    //   collect(c, m)                what the host takes from that sub-round before the arena is reused; ROUNDS_*
+    template <typename Sync, typename Arena, typename Pass, typename Back, typename Collect>
+    int run(const std::vector<int64_t> &need1, std::vector<uint8_t> &status, Sync sync, Arena arena, Pass pass, Back back, Collect collect) {
+        const int64_t n_jobs = int64_t(need1.size());
+        uint8_t *d_arena = nullptr;
+        int64_t arena_cap = 0;
+        // greedy round over [a, b): the jobs' slices into `slice` (indexed from off0), -> (end of the round, its bytes)
+        auto next_round = [&](const std::vector<int64_t> &need, int64_t a, int64_t b, int64_t off0, std::vector<int64_t> &slice, int64_t cap) {
+            int64_t sum = 0, k = a;
+            for (; k < b; k++) {
+                const int64_t nb = need[size_t(k - off0)];
+                slice[size_t(k - off0)] = sum;
+                if (status[size_t(k)]) continue;
+                if (nb > limit) { status[size_t(k)] = limit_bit; continue; }
+                if (sum > 0 && sum + nb > cap) break;
+                sum += nb;
+            }
+            return std::make_pair(k, std::max<int64_t>(sum, 16));
+        };
+        auto ensure_arena = [&](int64_t bytes) {
+            arena_bytes = std::max(arena_bytes, bytes);
+            if (bytes > arena_cap) { d_arena = arena(bytes); arena_cap = d_arena ? bytes : 0; }
+            return d_arena != nullptr;
+        };
+        // slices and statuses of jobs [a, a + n) up, the pass, its device time
+        auto run_pass = [&](bool hist, int64_t a, int64_t n, const int64_t *slice, double *ms) -> int {
+            SWG_TRY(hipMemcpyAsync(d_slice + a, slice, 8 * size_t(n), hipMemcpyHostToDevice, st));
+            SWG_TRY(hipMemcpyAsync(d_status + a, status.data() + a, size_t(n), hipMemcpyHostToDevice, st));
+            SWG_TRY(hipEventRecord(ev[0], st));
+            pass(hist, a, n, d_arena);
+            SWG_TRY(hipEventRecord(ev[1], st));
+            return hist ? elapsed(ms) : ROUNDS_OK;       // (pass 1 is read after the downloads its round waits for anyway)
+        };
+        auto status_down = [&](int64_t a, int64_t n) -> int {
+            SWG_TRY(hipMemcpyAsync(status.data() + a, d_status + a, size_t(n), hipMemcpyDeviceToHost, st));
+            SWG_TRY(sync());
+            return ROUNDS_OK;
+        };
+        std::vector<int64_t> sl1(need1.size()), sl2, n2;
+        for (int64_t a = 0; a < n_jobs;) {
+            const auto r1 = next_round(need1, a, n_jobs, 0, sl1, cap1);
+            const int64_t b = r1.first, nr = b - a;
+            n_rounds++;
+            if (!ensure_arena(r1.second)) return ROUNDS_NOMEM;
+            if (int rc = run_pass(false, a, nr, sl1.data() + a, nullptr)) return rc;
+            SWG_TRY(hipGetLastError());
+            n2.assign(size_t(nr), 0);
+            SWG_TRY(hipMemcpyAsync(n2.data(), d_need2 + a, 8 * size_t(nr), hipMemcpyDeviceToHost, st));
+            if (int rc = status_down(a, nr)) return rc;
+            if (int rc = elapsed(&ms_score)) return rc;
+            sl2.assign(size_t(nr), 0);
+            for (int64_t c = a; c < b;) {
+                const auto r2 = next_round(n2, c, b, a, sl2, cap2);
+                const int64_t m = r2.first - c;
+                n_hist_rounds++;
+                if (!ensure_arena(r2.second)) return ROUNDS_NOMEM;
+                if (int rc = run_pass(true, c, m, sl2.data() + (c - a), &ms_hist)) return rc;
+                SWG_TRY(hipEventRecord(ev[0], st));
+                if (int rc = back(c, m, d_arena)) return rc;
+                SWG_TRY(hipEventRecord(ev[1], st));
+                SWG_TRY(hipGetLastError());
+                if (int rc = elapsed(&ms_back)) return rc;
+                if (int rc = collect(c, m)) return rc;
+                c = r2.first;
+            }
+            if (int rc = status_down(a, nr)) return rc;
+            a = b;
+        }
+        return ROUNDS_OK;
+    }
+    // *ms += the device time between the two events
+    int elapsed(double *ms) {
+        float t = 0;
+        SWG_TRY(hipEventSynchronize(ev[1]));
+        SWG_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
+        *ms += t;
+        return ROUNDS_OK;
+    }
+};
+#undef SWG_TRY
 
 }  // namespace swg
