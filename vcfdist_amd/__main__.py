@@ -12,7 +12,10 @@ GPU before the evaluation (include/vcfdist_realign.h): orig-query.vcf / orig-tru
 counters of the one evaluation are also cut by region on the GPU (include/vcfdist_strata.h): stratified-precision-recall.tsv and
 stratified-precision-recall-summary.tsv; works under several ranks in both --shard modes.  With --stratify-context the default
 sequence-context strata (include/vcfdist_context.h: intervals built on the GPU from the FASTA) follow the list's strata, or stand
-alone, and context-strata.bed holds their intervals.  With --bootstrap N the counters are
+alone, and context-strata.bed holds their intervals.  With --stratify-variants the default variant strata
+(include/vcfdist_varstrata.h: transitions / transversions, indel size bins, hom / het, isolated / crowded -- bits made on the GPU from
+the variant tables) follow those, or stand alone, and variant-strata.tsv lists them with their numbers of members.  With --bootstrap N
+the counters are
 resampled N times on the GPU (include/vcfdist_bootstrap.h: a Poisson bootstrap over superclusters, conditional on the phasing, the
 BEST threshold kept at the point estimate's): bootstrap-precision-recall-summary.tsv with 95 % percentile intervals for precision,
 recall and F1, bootstrap-replicates.tsv, and with --stratify stratified-bootstrap-precision-recall-summary.tsv; --bootstrap-seed S
@@ -134,8 +137,12 @@ def stratify_contig(pr, prep, strat, args, pb, part_idx=None):
     if strat["ctx"]:        # --stratify-context: the context intervals are built on the device and go to the same mask kernel
         pr.context_masks(prep["variants"], strat["ctx"], IO.contig_strata(strat["beds"], [name]) if strat["beds"] else None)
         keep_context_intervals(pr, strat, name)
-    else:
+    elif strat["beds"]:
         pr.strata_masks(prep["variants"], IO.contig_strata(strat["beds"], [name]))
+    n_pre = n_strata - len(strat["vs"] or ())
+    if strat["vs"]:         # --stratify-variants: the bits made from the variant tables follow in the same words
+        pr.varstrata_masks(prep["variants"], strat["vs"], append=n_pre > 0)
+        strat["vs_ms"] += pr.varstrata_timing()
     words = pr.download_strata_masks()
     if part_idx is not None:
         words = [np.stack([shard.subset_per_variant(w, whole.var_off[s], part_idx) for w in words[s]]) for s in range(4)]
@@ -144,6 +151,9 @@ def stratify_contig(pr, prep, strat, args, pb, part_idx=None):
     for w in words:
         strat["vars"] += w.shape[1]
         strat["none"] += int((np.bitwise_or.reduce(w, axis=0) == 0).sum())
+    for k in range(n_pre, n_strata):      # variant-strata.tsv: the members of every variant stratum, per callset
+        for s, w in enumerate(words):
+            strat["vs_members"][s >> 1, k - n_pre] += int(((w[k >> 6] >> np.uint64(k & 63)) & np.uint64(1)).sum())
 
 
 def keep_context_intervals(pr, strat, name):
@@ -405,6 +415,10 @@ def main(argv=None):
     ap.add_argument("--stratify-context", action="store_true",
                     help="the default sequence-context strata (homopolymers, short tandem repeats, GC bands), built on the GPU from the "
                          "FASTA, behind those of --stratify or alone; their intervals are written to context-strata.bed")
+    ap.add_argument("--stratify-variants", action="store_true",
+                    help="the default variant strata (transitions / transversions, indel size bins, hom / het, isolated / crowded), made "
+                         "on the GPU from the variant tables, behind those of --stratify and --stratify-context or alone; "
+                         "variant-strata.tsv lists them with their numbers of members")
     ap.add_argument("--bootstrap", metavar="N", type=bootstrap_replicates, default=0,
                     help="resample the counters N times (1 to 100000) over superclusters on the GPU: 95 %% percentile intervals for "
                          "precision, recall and F1 (bootstrap-precision-recall-summary.tsv, bootstrap-replicates.tsv)")
@@ -451,14 +465,15 @@ def main(argv=None):
             torch.cuda.set_device(device)
         dist.init_process_group(backend=backend)
     strat = None
-    if args.stratify or args.stratify_context:       # the strata list and every BED it names are read and checked before anything is evaluated
+    if args.stratify or args.stratify_context or args.stratify_variants:       # the strata list and every BED it names are read and checked before anything is evaluated
         names, beds = [], []
         if args.stratify:
             try:
                 names, beds = IO.read_strata(args.stratify)
             except IOError as e:
                 raise SystemExit(f"ERROR: {e}")
-        strat = dict(names=list(names), beds=beds, counts=None, vars=0, none=0, ctx=None, ctx_names=[], intervals={}, ctx_ms={})
+        strat = dict(names=list(names), beds=beds, counts=None, vars=0, none=0, ctx=None, ctx_names=[], intervals={}, ctx_ms={},
+                     vs=None, vs_names=[], vs_members=np.zeros((2, 0), np.int64), vs_ms=0.0)
         if args.stratify_context:       # the default sequence-context strata (include/vcfdist_context.h) behind the list's
             strat["ctx_names"], strat["ctx"] = api.context_default()
             for n in strat["ctx_names"]:
@@ -466,6 +481,14 @@ def main(argv=None):
                     raise SystemExit(f"ERROR: strata list '{args.stratify}': duplicate stratum name '{n}' (a sequence-context stratum of "
                                      "--stratify-context)")
             strat["names"] += strat["ctx_names"]
+        if args.stratify_variants:      # the default variant strata (include/vcfdist_varstrata.h) behind the list's and the context strata
+            strat["vs_names"], strat["vs"] = api.varstrata_default()
+            for n in strat["vs_names"]:
+                if n in names:
+                    raise SystemExit(f"ERROR: strata list '{args.stratify}': duplicate stratum name '{n}' (a variant stratum of "
+                                     "--stratify-variants)")
+            strat["names"] += strat["vs_names"]
+            strat["vs_members"] = np.zeros((2, len(strat["vs"])), np.int64)
     filters = tuple(f for f in args.filter.split(",") if f)
     bed = IO.Bed(args.bed) if args.bed else None
     kw = dict(min_qual=args.min_qual, max_qual=args.max_qual, max_size=args.max_size, cluster_min_gap=args.cluster_gap, filters=filters)
@@ -551,7 +574,7 @@ def main(argv=None):
     if dist is not None:
         # the one all-reduce: counts[2][4][3][nq] summed over the ranks, with --stratify the stratified ones behind them
         # and with --bootstrap the replicate ones behind those
-        tail = [] if strat is None else [strat["counts"].ravel(), np.asarray([strat["vars"], strat["none"]], np.int64)]
+        tail = [] if strat is None else [strat["counts"].ravel(), np.asarray([strat["vars"], strat["none"]], np.int64), strat["vs_members"].ravel()]
         if boot is not None:
             tail += [boot["counts"].ravel()] + ([] if strat is None else [boot["strat"].ravel()])
         summed = shard.allreduce_tally(np.concatenate([total.ravel()] + tail), device=cdev)
@@ -562,6 +585,8 @@ def main(argv=None):
             at += strat["counts"].size
             strat["vars"], strat["none"] = int(summed[at]), int(summed[at + 1])
             at += 2
+            strat["vs_members"] = summed[at:at + strat["vs_members"].size].reshape(strat["vs_members"].shape)
+            at += strat["vs_members"].size
         if boot is not None:
             boot["counts"] = summed[at:at + boot["counts"].size].reshape(boot["counts"].shape)
             at += boot["counts"].size
@@ -575,6 +600,9 @@ def main(argv=None):
                 dist.all_gather_object(gathered, (strat["intervals"], strat["ctx_ms"]))
                 strat["intervals"] = {k: v for part in gathered for k, v in part[0].items()}
                 strat["ctx_ms"] = {k: v for part in gathered for k, v in part[1].items()}
+            if strat is not None and strat["vs"]:
+                dist.all_gather_object(gathered, strat["vs_ms"])
+                strat["vs_ms"] = sum(gathered)
     rows = S.pr_summary(total, args.min_qual, args.max_qual)
     if dist_sets is not None:       # write_distance (printed even with -n) and write_edits, edit.cpp:134-280
         text = RP.write_distance(args.prefix, dist_sets, args.min_qual, args.max_qual, args.eval_sub, args.eval_open, args.eval_extend,
@@ -590,6 +618,8 @@ def main(argv=None):
                 RP.write_stratified(args.prefix, strat["names"], strat["counts"], args.min_qual, args.max_qual)
                 if strat["ctx"]:
                     RP.write_context_bed(args.prefix, contigs, strat["ctx_names"], strat["intervals"])
+                if strat["vs"]:
+                    RP.write_variant_strata(args.prefix, strat["vs_names"], strat["vs"], strat["vs_members"][0], strat["vs_members"][1])
             if boot is not None:
                 RP.write_bootstrap(args.prefix, total, boot["counts"], boot["seed"], args.min_qual, args.max_qual)
                 if strat is not None:
@@ -608,6 +638,8 @@ def main(argv=None):
                 n_iv = sum(len(a) for rows in strat["intervals"].values() for a, _ in rows)
                 print(f"[vcfdist_amd] context strata: {n_iv} intervals of {len(strat['ctx'])} strata, {sum(strat['ctx_ms'].values()):.3f} ms "
                       "on the device", file=sys.stderr)
+            if strat["vs"]:
+                print(f"[vcfdist_amd] variant strata: {len(strat['vs'])} strata, {strat['vs_ms']:.3f} ms on the device", file=sys.stderr)
         if boot is not None:
             print(f"[vcfdist_amd] bootstrap: {boot['n']} replicates, seed {boot['seed']}, {boot['ms']:.3f} ms on the device", file=sys.stderr)
         print("PRECISION-RECALL SUMMARY\n")

@@ -539,6 +539,37 @@ def ctx_gc(lo, hi, window, slop=0):
     return VprContextStratum(CTX_GC, 0, 0, 0, lo, hi, window, slop)
 
 
+# ---- include/vcfdist_varstrata.h
+VS_SIZE, VS_TI, VS_TV, VS_HOM, VS_HET, VS_NEAR = range(6)
+VS_MAX_SPEC = 64
+
+
+class VprVariantStratum(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("kind", "type", "min_len", "max_len", "window", "min_n", "max_n")]
+
+    def __repr__(self):
+        if self.kind == VS_SIZE:
+            return f"size(type={self.type}, {self.min_len}..{self.max_len or ''})"
+        if self.kind == VS_NEAR:
+            return f"near(W={self.window}, {self.min_n}..{'' if self.max_n < 0 else self.max_n})"
+        return ("size", "ti", "tv", "hom", "het", "near")[self.kind] if 0 <= self.kind < 6 else f"kind {self.kind}"
+
+
+def vs_size(type, min_len, max_len=0):
+    """a size stratum: insertions (TYPE_INS, by alt_len) or deletions (TYPE_DEL, by ref_len) of min_len..max_len (0: unbounded) bases"""
+    return VprVariantStratum(VS_SIZE, type, min_len, max_len, 0, 0, 0)
+
+
+def vs_kind(kind):
+    """VS_TI, VS_TV, VS_HOM or VS_HET: the kinds without parameters"""
+    return VprVariantStratum(kind, 0, 0, 0, 0, 0, 0)
+
+
+def vs_near(window, min_n, max_n=-1):
+    """a crowding stratum: min_n <= N(v) <= max_n (-1: unbounded) other variants of the callset start within `window` bases"""
+    return VprVariantStratum(VS_NEAR, 0, 0, 0, window, min_n, max_n)
+
+
 # ---- include/vcfdist_realign.h
 RL_ST_EDGE = 1
 RL_ST_LIMIT = 2

@@ -95,6 +95,9 @@ def lib():
     L.vpr_context_download_intervals.argtypes = [H, A.P_i32, A.P_i32]
     L.vpr_context_info.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.vpr_context_timing.argtypes = [H, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.vpr_varstrata_default.argtypes = [C.POINTER(C.POINTER(A.VprVariantStratum)), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.c_int32)]
+    L.vpr_varstrata_masks.argtypes = [H, C.POINTER(A.VprVariants), C.POINTER(A.VprVariantStratum), C.c_int32, C.c_int32]
+    L.vpr_varstrata_timing.argtypes = [H, C.POINTER(C.c_double)]
     boot = [C.c_void_p, A.P_i32, C.c_int32, C.c_int32, P_u64, C.c_uint64, C.c_int32, C.c_int32, A.P_i64]
     L.vpr_pr_counts_boot.argtypes = [H] + boot
     L.vpr_allreduce_counts_boot.argtypes = [H, C.c_void_p] + boot
@@ -123,6 +126,8 @@ STRATA_EXPORTED = ["vpr_strata_masks", "vpr_strata_download_masks", "vpr_strata_
 # include/vcfdist_context.h
 CONTEXT_EXPORTED = ["vpr_context_default", "vpr_context_masks", "vpr_context_interval_counts", "vpr_context_download_intervals",
                     "vpr_context_info", "vpr_context_timing"]
+# include/vcfdist_varstrata.h
+VARSTRATA_EXPORTED = ["vpr_varstrata_default", "vpr_varstrata_masks", "vpr_varstrata_timing", "vrp_write_variant_strata"]
 # include/vcfdist_bootstrap.h
 BOOT_EXPORTED = ["vpr_pr_counts_boot", "vpr_allreduce_counts_boot", "vpr_boot_info", "vrp_write_bootstrap", "vrp_write_bootstrap_stratified"]
 # include/vcfdist_realign.h
@@ -183,6 +188,15 @@ def context_default():
     if rc:
         raise VprError(f"vpr_context_default failed ({rc})")
     return [names[k].decode() for k in range(n.value)], [A.VprContextStratum.from_buffer_copy(spec[k]) for k in range(n.value)]
+
+
+def varstrata_default():
+    """the command lines' default variant strata (vpr_varstrata_default): (names, [A.VprVariantStratum])"""
+    spec, names, n = C.POINTER(A.VprVariantStratum)(), C.POINTER(C.c_char_p)(), C.c_int32()
+    rc = lib().vpr_varstrata_default(C.byref(spec), C.byref(names), C.byref(n))
+    if rc:
+        raise VprError(f"vpr_varstrata_default failed ({rc})")
+    return [names[k].decode() for k in range(n.value)], [A.VprVariantStratum.from_buffer_copy(spec[k]) for k in range(n.value)]
 
 
 def context_info():
@@ -448,6 +462,23 @@ class PrecisionRecall:
         a, b = C.c_double(), C.c_double()
         self._chk(lib().vpr_context_timing(self._h, C.byref(a), C.byref(b)), "vpr_context_timing")
         return a.value, b.value
+
+    def varstrata_masks(self, variants, spec, append=False):
+        """The variant strata (include/vcfdist_varstrata.h): the bits of every entry of `spec` (A.vs_size / A.vs_kind / A.vs_near)
+        are made on the device from the variant tables and become the resident membership words (append False), or follow the
+        resident ones of strata_masks / context_masks / upload_strata_masks for the same variant counts (append True)."""
+        vs = variants.as_struct() if isinstance(variants, A.Variants) else variants
+        n_sc = int(vs.n_sc)
+        arr = (A.VprVariantStratum * max(len(spec), 1))(*spec)
+        self._chk(lib().vpr_varstrata_masks(self._h, C.byref(vs), arr, len(spec), 1 if append else 0), "vpr_varstrata_masks")
+        n_old = self._strata[0] if append else 0
+        self._strata = (n_old + len(spec), [int(vs.var_off[h][n_sc]) for h in range(A.HAPS)])
+
+    def varstrata_timing(self):
+        """ms of the last varstrata_masks' kernel launches, from HIP events on the handle's stream"""
+        a = C.c_double()
+        self._chk(lib().vpr_varstrata_timing(self._h, C.byref(a)), "vpr_varstrata_timing")
+        return a.value
 
     def pr_counts_boot(self, var_class_per_slot, pb_phase, sc_key, n_rep, seed=1, min_qual=0, max_qual=60, stratum=-1, comm=None):
         """The bootstrap replicates of the counters of the last execute (include/vcfdist_bootstrap.h): replicate r counts every

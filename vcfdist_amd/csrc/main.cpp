@@ -10,6 +10,7 @@
 //               [-l max variant size] [-s max supercluster size] [-mn / -mx qual] [-f filters] [-i iterations] [-x -o -e penalties]
 //               [-ct credit threshold] [-pt phasing threshold] [-sv threshold] [--reach-min-gap N] [--strict] [--device N]
 //               [-d] [-ex -eo -ee evaluation penalties] [-rq] [-rt] [-ro] [--stratify strata.tsv] [--stratify-context]
+//               [--stratify-variants]
 //               [--bootstrap N] [--bootstrap-seed S]
 // With -d the distance metrics (edits_wrapper, dist.cpp:1908-2077) run on the GPU after each contig's precision/recall path
 // (include/vcfdist_distance.h), as the reference's main.cpp:223-238 runs them after precision_recall_threads_wrapper.
@@ -19,6 +20,9 @@
 // by region on the GPU (include/vcfdist_strata.h): stratified-precision-recall.tsv and stratified-precision-recall-summary.tsv.
 // With --stratify-context the default sequence-context strata (homopolymers, short tandem repeats, GC bands: intervals built on
 // the GPU from the FASTA, include/vcfdist_context.h) follow the list's strata, or stand alone; context-strata.bed holds them.
+// With --stratify-variants the default variant strata (transitions / transversions, indel size bins, hom / het, isolated / crowded:
+// bits made on the GPU from the variant tables, include/vcfdist_varstrata.h) follow those, or stand alone; variant-strata.tsv lists
+// them with their numbers of members.
 // With --bootstrap N the counters are resampled N times on the GPU (include/vcfdist_bootstrap.h: a Poisson bootstrap over
 // superclusters, conditional on the phasing): bootstrap-precision-recall-summary.tsv with 95 % percentile intervals,
 // bootstrap-replicates.tsv, and with --stratify stratified-bootstrap-precision-recall-summary.tsv.
@@ -44,12 +48,13 @@
 #include "../../include/vcfdist_report.h"
 #include "../../include/vcfdist_context.h"
 #include "../../include/vcfdist_strata.h"
+#include "../../include/vcfdist_varstrata.h"
 
 namespace {
 
 struct Args {
     std::string query, truth, fasta, bed, filter, prefix = "./", cluster = "biwfa", stratify;
-    bool stratify_context = false;
+    bool stratify_context = false, stratify_variants = false;
     int max_size = 5000, min_qual = 0, max_qual = 60, cluster_gap = 50, max_iterations = 4, max_supercluster_size = 10000;
     int sub = 5, open = 6, extend = 2, sv_threshold = 50, reach_min_gap = 10, device = 0;
     int eval_sub = 3, eval_open = 2, eval_extend = 1;      // globals.h:52-55
@@ -126,6 +131,7 @@ Args parse(int argc, char **argv) {
         else if (o == "-d" || o == "--distance") a.distance = true;
         else if (o == "--stratify") a.stratify = need(i);
         else if (o == "--stratify-context") a.stratify_context = true;
+        else if (o == "--stratify-variants") a.stratify_variants = true;
         else if (o == "--bootstrap") a.bootstrap = bootstrap_replicates(need(i));
         else if (o == "--bootstrap-seed") a.bootstrap_seed = bootstrap_seed(need(i));
         else if (o == "-rq" || o == "--realign-query") a.realign_query = true;
@@ -381,6 +387,21 @@ int main(int argc, char **argv) {
             strata.names.push_back(ctx_names[k]);
         }
     }
+    // --stratify-variants: the default variant strata (include/vcfdist_varstrata.h) behind the list's and the context strata
+    const int n_pre = int(strata.names.size());
+    const vpr_variant_stratum *vs_spec = nullptr;
+    const char *const *vs_names = nullptr;
+    int32_t n_vs = 0;
+    if (A.stratify_variants) {
+        if (vpr_varstrata_default(&vs_spec, &vs_names, &n_vs)) die("ERROR: vpr_varstrata_default failed");
+        for (int k = 0; k < n_vs; k++) {
+            if (find(strata.names, vs_names[k]) >= 0)
+                die("ERROR: strata list '%s': duplicate stratum name '%s' (a variant stratum of --stratify-variants)", A.stratify.c_str(), vs_names[k]);
+            strata.names.push_back(vs_names[k]);
+        }
+    }
+    std::vector<int64_t> vs_query(size_t(n_vs), 0), vs_truth(size_t(n_vs), 0);    // variant-strata.tsv: members per callset
+    double vs_ms = 0;
     const int n_strata = int(strata.names.size());
     std::vector<std::string> ctx_contigs;                                       // context-strata.bed: contigs, rows contig-major
     std::vector<int64_t> ctx_off(1, 0);
@@ -570,7 +591,15 @@ int main(int argc, char **argv) {
                 const vpr_strata ST = {n_bed, 1, iv_off.data(), iv_start.data(), iv_stop.data()};
                 std::vector<int64_t> sc_counts(strat_total.size(), 0);
                 // (with --stratify-context the context intervals are built on the device and go to the same mask kernel)
-                if ((n_ctx ? vpr_context_masks(h, &V, n_bed ? &ST : nullptr, ctx_spec, n_ctx) : vpr_strata_masks(h, &V, &ST)) || vpr_pr_counts_strata(h, nullptr, C->pb.data(), A.min_qual, A.max_qual, sc_counts.data()))
+                if (n_pre && (n_ctx ? vpr_context_masks(h, &V, n_bed ? &ST : nullptr, ctx_spec, n_ctx) : vpr_strata_masks(h, &V, &ST)))
+                    die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+                // (with --stratify-variants the bits made from the variant tables follow in the same words)
+                if (n_vs) {
+                    double ms = 0;
+                    if (vpr_varstrata_masks(h, &V, vs_spec, n_vs, n_pre ? 1 : 0) || vpr_varstrata_timing(h, &ms)) die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+                    vs_ms += ms;
+                }
+                if (vpr_pr_counts_strata(h, nullptr, C->pb.data(), A.min_qual, A.max_qual, sc_counts.data()))
                     die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
                 for (size_t k = 0; k < strat_total.size(); k++) strat_total[k] += sc_counts[k];
                 const size_t n_words = (size_t(n_strata) + 63) / 64;
@@ -585,6 +614,8 @@ int main(int argc, char **argv) {
                         uint64_t any = 0;
                         for (size_t w = 0; w < n_words; w++) any |= words[i][w * nv + v];
                         strat_none += any == 0;
+                        for (int k = 0; k < n_vs; k++)
+                            (i < 2 ? vs_query : vs_truth)[size_t(k)] += int64_t(words[i][size_t((n_pre + k) >> 6) * nv + v] >> ((n_pre + k) & 63) & 1);
                     }
                     strat_vars += int64_t(nv);
                 }
@@ -686,6 +717,7 @@ int main(int argc, char **argv) {
                 if (vrp_write_context_bed(A.prefix.c_str(), cn.data(), int32_t(cn.size()), ctx_names, n_ctx, ctx_off.data(), ctx_start.data(), ctx_stop.data()))
                     die("ERROR: %s", vrp_last_error());
             }
+            if (n_vs && vrp_write_variant_strata(A.prefix.c_str(), vs_names, vs_spec, n_vs, vs_query.data(), vs_truth.data())) die("ERROR: %s", vrp_last_error());
         }
         if (A.bootstrap && vrp_write_bootstrap(A.prefix.c_str(), total.data(), boot_total.data(), A.bootstrap, A.bootstrap_seed, A.min_qual, A.max_qual))
             die("ERROR: %s", vrp_last_error());
@@ -731,6 +763,8 @@ int main(int argc, char **argv) {
                 (long long)strat_vars);
     if (n_ctx)
         fprintf(stderr, "[vcfdist_amd] context strata: %lld intervals of %d strata, %.3f ms on the device\n", (long long)ctx_start.size(), n_ctx, ctx_ms);
+    if (n_vs)
+        fprintf(stderr, "[vcfdist_amd] variant strata: %d strata, %.3f ms on the device\n", n_vs, vs_ms);
     if (A.bootstrap)
         fprintf(stderr, "[vcfdist_amd] bootstrap: %d replicates, seed %llu, %.3f ms on the device\n", A.bootstrap, (unsigned long long)A.bootstrap_seed, boot_ms);
     printf("PRECISION-RECALL SUMMARY\n\n");

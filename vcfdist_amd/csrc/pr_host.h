@@ -7,6 +7,7 @@
 //                   the front and back of a counters call that pr_strata.hip and pr_boot.hip share (the bin rule: pr_counts.h)
 //   pr_strata.hip   the region-stratified counters (include/vcfdist_strata.h): membership words, the stratified histogram
 //   pr_context.hip  the sequence-context strata (include/vcfdist_context.h): interval lists built from the contig sequences
+//   pr_varstrata.hip the variant strata (include/vcfdist_varstrata.h): bits made from the variant tables themselves
 //   pr_boot.hip     the bootstrap replicates of the counters (include/vcfdist_bootstrap.h): the replicate histogram
 #ifndef PR_HOST_H_
 #define PR_HOST_H_
@@ -418,6 +419,7 @@ struct vpr_handle {
     StrataState *strata = nullptr;       // vpr_strata_masks / vpr_strata_upload_masks (pr_strata.hip), released with the batch
     ContextState *context = nullptr;     // vpr_context_masks (pr_context.hip), released by the next one or vpr_destroy
     BootState *boot = nullptr;           // vpr_pr_counts_boot (pr_boot.hip), created by its first call, released with the batch
+    double varstrata_ms = 0;             // device time of the last vpr_varstrata_masks' kernel launches (pr_varstrata.hip)
     vpr_timing timing;
     bool uploaded = false, executed = false;
 };
@@ -464,6 +466,11 @@ int strata_view(vpr_handle *h, const char *entry, int32_t *n_strata, const uint6
 int strata_check(vpr_handle *h, const vpr_variants *v, const struct vpr_strata *s);
 int strata_masks_device(vpr_handle *h, const vpr_variants *v, int32_t n_strata, const int64_t *d_iv_off, const int32_t *d_iv_start,
                         const int32_t *d_iv_stop);
+// pr_strata.hip, for pr_varstrata.hip: room in the membership words for n_add strata that the caller's kernel writes at bit
+// offset *n_prev -- alone (append false) or behind the resident ones, which are kept; the words are invalid until strata_commit
+int strata_extend(vpr_handle *h, const char *entry, int32_t n_add, const int64_t n_var[VPR_HAPS], bool append, int32_t *n_prev,
+                  uint64_t *words[VPR_HAPS], int32_t *n_words);
+void strata_commit(vpr_handle *h);
 void context_free(vpr_handle *h);                                    // pr_context.hip: the resident context intervals
 void boot_free(vpr_handle *h);                                       // pr_boot.hip: the replicate histogram and the keys
 // pr_collect.hip, shared by the three counters entries (vpr_pr_counts, _strata, _boot; `entry`: the entry's name, for the

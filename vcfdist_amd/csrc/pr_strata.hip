@@ -277,6 +277,41 @@ int strata_masks_device(vpr_handle *h, const vpr_variants *v, int32_t n_strata, 
     return VPR_OK;
 }
 
+// Room for n_add strata that a kernel of the caller's writes: alone (append false: as strata_prepare, *n_prev = 0) or behind the
+// resident ones, whose words are kept (the word-major layout keeps the old words in front; a word array that crosses a 64-bit
+// boundary is reallocated and copied).  The words are invalid until strata_commit.
+int strata_extend(vpr_handle *h, const char *entry, int32_t n_add, const int64_t n_var[VPR_HAPS], bool append, int32_t *n_prev,
+                  uint64_t *words[VPR_HAPS], int32_t *n_words) {
+    if (!append) {
+        if (int rc = strata_prepare(h, n_add, n_var)) return rc;
+        *n_prev = 0;
+    } else {
+        StrataState *S = h->strata;
+        if (!S || !S->valid)
+            return fail(h, VPR_ERR_STATE, "%s: append without resident membership words (call vpr_strata_masks, vpr_context_masks or vpr_strata_upload_masks first)", entry);
+        for (int s = 0; s < VPR_HAPS; s++)
+            if (S->n_var[s] != n_var[s])
+                return fail(h, VPR_ERR_STATE, "%s: append: the membership words hold %lld variants of hap slot %d, the variant tables %lld", entry,
+                            (long long)S->n_var[s], s, (long long)n_var[s]);
+        const int32_t old_words = S->n_words, new_words = (S->n_strata + n_add + 63) / 64;
+        S->valid = false;
+        for (int s = 0; s < VPR_HAPS; s++) {
+            const size_t n = std::max<size_t>(size_t(new_words) * size_t(n_var[s]), 32);
+            if (int rc = S->words[s].reserve(h, n, "stratum membership words: cannot allocate %zu bytes on the device", size_t(old_words) * size_t(n_var[s]))) {
+                release_words(h, S);
+                return rc;
+            }
+        }
+        *n_prev = S->n_strata;
+        S->n_strata += n_add; S->n_words = new_words;
+    }
+    for (int s = 0; s < VPR_HAPS; s++) words[s] = h->strata->words[s].p;
+    *n_words = h->strata->n_words;
+    return VPR_OK;
+}
+
+void strata_commit(vpr_handle *h) { h->strata->valid = true; }
+
 int strata_view(vpr_handle *h, const char *entry, int32_t *n_strata, const uint64_t *words[VPR_HAPS]) {
     const StrataState *S = h->strata;
     if (!S || !S->valid)

@@ -15,6 +15,7 @@
 #include "../../include/vcfdist_pr.h"
 #include "../../include/vcfdist_report.h"
 #include "../../include/vcfdist_bootstrap.h"
+#include "../../include/vcfdist_varstrata.h"
 
 namespace {
 
@@ -212,6 +213,30 @@ extern "C" int vrp_write_context_bed(const char *prefix, const char *const *cont
         for (int64_t j = iv_off[r]; j < iv_off[r + 1]; j++)
             fprintf(bed, "%s\t%d\t%d\t%s\n", contigs[r / size_t(n_strata)], start[j], stop[j], names[r % size_t(n_strata)]);
     if (!bed.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn);
+    return VRP_OK;
+}
+
+extern "C" int vrp_write_variant_strata(const char *prefix, const char *const *names, const vpr_variant_stratum *spec, int32_t n_spec,
+                                        const int64_t *n_query, const int64_t *n_truth) {
+    if (!prefix || !names || !spec || n_spec < 0 || !n_query || !n_truth) return fail(VRP_ERR_ARG, "vrp_write_variant_strata: bad argument");
+    static const char *const KIND[] = {"SIZE", "TI", "TV", "HOM", "HET", "NEAR"};
+    for (int32_t k = 0; k < n_spec; k++) {
+        if (!names[k]) return fail(VRP_ERR_ARG, "vrp_write_variant_strata: null stratum name");
+        if (spec[k].kind < VPR_VS_SIZE || spec[k].kind > VPR_VS_NEAR) return fail(VRP_ERR_ARG, "vrp_write_variant_strata: unknown kind");
+    }
+    const std::string fn = std::string(prefix) + "variant-strata.tsv";
+    File out(fn.c_str());
+    if (!out) return fail(VRP_ERR_OPEN, "cannot create " + fn);
+    fputs("STRATUM\tKIND\tTYPE\tMIN_LEN\tMAX_LEN\tWINDOW\tMIN_N\tMAX_N\tQUERY_VARS\tTRUTH_VARS\n", out);
+    auto num = [](bool set, int32_t x) { return set ? std::to_string(x) : std::string("."); };      // '.': no such parameter, or an open bound
+    for (int32_t k = 0; k < n_spec; k++) {
+        const vpr_variant_stratum &s = spec[k];
+        const bool size = s.kind == VPR_VS_SIZE, near = s.kind == VPR_VS_NEAR;
+        fprintf(out, "%s\t%s\t%s\t%s\t%s\t%s\t%s\t%s\t%lld\t%lld\n", names[k], KIND[s.kind], size ? TYPE_STR[s.type == VPR_TYPE_INS ? 2 : 3] : ".",
+                num(size, s.min_len).c_str(), num(size && s.max_len != 0, s.max_len).c_str(), num(near, s.window).c_str(), num(near, s.min_n).c_str(),
+                num(near && s.max_n >= 0, s.max_n).c_str(), (long long)n_query[k], (long long)n_truth[k]);
+    }
+    if (!out.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn);
     return VRP_OK;
 }
 

@@ -161,6 +161,22 @@ def write_context_bed(prefix, contigs, names, intervals):
                                    A._ptr(sp, C.c_int32)), "vrp_write_context_bed")
 
 
+def write_variant_strata(prefix, names, spec, n_query, n_truth):
+    """variant-strata.tsv (include/vcfdist_varstrata.h): one row per variant stratum -- name, kind, parameters, and the numbers of
+    query and of truth hap-variants that are members"""
+    if not len(names) == len(spec) == len(n_query) == len(n_truth):
+        raise ReportError(f"{len(names)} names, {len(spec)} spec entries, {len(n_query)} / {len(n_truth)} member counts")
+    nq, nt = np.ascontiguousarray(n_query, np.int64), np.ascontiguousarray(n_truth, np.int64)
+    if nq.size == 0:
+        nq = nt = np.zeros(1, np.int64)
+    L = api.lib()
+    narr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+    sarr = (A.VprVariantStratum * max(len(spec), 1))(*spec)
+    L.vrp_write_variant_strata.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(A.VprVariantStratum), C.c_int32, A.P_i64, A.P_i64]
+    _check(L.vrp_write_variant_strata(prefix.encode(), narr, sarr, len(names), A._ptr(nq, C.c_int64), A._ptr(nt, C.c_int64)),
+           "vrp_write_variant_strata")
+
+
 def write_bootstrap(prefix, counts, counts_boot, seed, min_qual, max_qual):
     """bootstrap-precision-recall-summary.tsv and bootstrap-replicates.tsv (include/vcfdist_bootstrap.h): counts int64
     [2][4][3][nq] (summary.pr_counts), counts_boot int64 [n_rep][2][4][3][nq] (summary.pr_counts_boot)"""
