@@ -19,7 +19,10 @@ the counters are
 resampled N times on the GPU (include/vcfdist_bootstrap.h: a Poisson bootstrap over superclusters, conditional on the phasing, the
 BEST threshold kept at the point estimate's): bootstrap-precision-recall-summary.tsv with 95 % percentile intervals for precision,
 recall and F1, bootstrap-replicates.tsv, and with --stratify stratified-bootstrap-precision-recall-summary.tsv; --bootstrap-seed S
-(default 1); works under several ranks in both --shard modes."""
+(default 1); works under several ranks in both --shard modes.  With --classify-errors every query FP and truth FN gets the first
+error class that applies (include/vcfdist_errclass.h: the right allele with the wrong genotype, on the aligned or on the other
+haplotype, another allele at the site, something within --error-window N bases (default 50), nothing), joined across the callsets on
+the GPU: error-classes.tsv and error-classes-summary.tsv; works under several ranks in both --shard modes."""
 import argparse
 import sys
 
@@ -188,7 +191,13 @@ def bootstrap_contig(pr, boot, strat, args, pb, keys):
             boot["ms"] += pr.boot_info()[1]
 
 
-def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None, boot=None, ordinal=0):
+def classify_contig(pr, variants, ec, args, pb):
+    """--classify-errors: the error classes of the executed batch, added to ec['counts'] (the variant classes are resident: pr_counts)"""
+    ec["counts"] += pr.errclass(variants, None, pb, ec["window"], args.min_qual, args.max_qual)
+    ec["ms"] += pr.errclass_timing()
+
+
+def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None, boot=None, ordinal=0, ec=None):
     """the precision/recall path on the GPU, phasing and counters for a prepared contig.  -> int64 counters [2][4][3][nq],
     n_sc, and what the writers need: (clusters after splitting, superclusters, results, phase sets, pb_phase, switches, flips).
     part = (rank, world, collective device): this rank evaluates its share of the contig's SUPERCLUSTERS -- dealt by the
@@ -227,6 +236,8 @@ def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None,
         mask_unevaluated(res)
         pb, sw, fl = S.phase(res.sc_phase, phase_sets)
         counts = S.pr_counts(pr, cls, pb, args.min_qual, args.max_qual)
+        if ec is not None:
+            classify_contig(pr, prep["variants"], ec, args, pb)
         if strat is not None:
             stratify_contig(pr, prep, strat, args, pb)
         if boot is not None:
@@ -252,6 +263,8 @@ def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None,
         if len(idx):
             cls_mine = [shard.subset_per_variant(cls[s], whole.var_off[s], idx) for s in range(4)]
             counts = S.pr_counts(pr, cls_mine, pb[idx], args.min_qual, args.max_qual)
+            if ec is not None:      # (everything is local to the supercluster: the rank classifies its share from its share's tables)
+                classify_contig(pr, shard.subset_variants(prep["variants"], idx), ec, args, pb[idx])
             if strat is not None:
                 stratify_contig(pr, prep, strat, args, pb[idx], part_idx=idx)
             if boot is not None:
@@ -377,6 +390,16 @@ def bootstrap_seed(v):
     return s
 
 
+def error_window(v):
+    try:
+        n = int(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"Invalid error window '{v}'")
+    if not 0 <= n < 2 ** 31:
+        raise argparse.ArgumentTypeError("Must provide an error window of 0 to 2147483647 bases")
+    return n
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m vcfdist_amd", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("query"); ap.add_argument("truth"); ap.add_argument("fasta")
@@ -423,6 +446,12 @@ def main(argv=None):
                     help="resample the counters N times (1 to 100000) over superclusters on the GPU: 95 %% percentile intervals for "
                          "precision, recall and F1 (bootstrap-precision-recall-summary.tsv, bootstrap-replicates.tsv)")
     ap.add_argument("--bootstrap-seed", metavar="S", type=bootstrap_seed, default=1, help="seed of the bootstrap weights (default 1)")
+    ap.add_argument("--classify-errors", action="store_true",
+                    help="why each query FP and truth FN is wrong (right allele with the wrong genotype / on the aligned / on the other "
+                         "haplotype, another allele at the site, something near, nothing), classified on the GPU: error-classes.tsv, "
+                         "error-classes-summary.tsv")
+    ap.add_argument("--error-window", metavar="N", type=error_window, default=None,
+                    help="bases within which a variant of the other callset counts as near (default 50; needs --classify-errors)")
     ap.add_argument("--shard", default="superclusters", choices=["superclusters", "contigs"],
                     help="several ranks (torch.distributed.run, one per GPU): deal every contig's superclusters over the ranks "
                          "(default; balanced whatever the contigs' sizes) or whole contigs")
@@ -433,6 +462,8 @@ def main(argv=None):
     args.cluster = args.cluster[0]
     if args.max_size + 2 > args.max_supercluster_size:          # globals.cpp:478-481
         raise SystemExit("ERROR: Max supercluster size (-s) must be at least two larger than max variant size (-l).")
+    if args.error_window is not None and not args.classify_errors:
+        raise SystemExit("ERROR: --error-window needs --classify-errors")
     realigning = args.realign_query or args.realign_truth
     if realigning and (args.sub < 1 or args.extend < 1):
         raise SystemExit("ERROR: realignment needs a mismatch penalty (-x) and a gap-extension penalty (-e) of at least 1")
@@ -523,6 +554,10 @@ def main(argv=None):
     if args.bootstrap:
         boot = dict(n=args.bootstrap, seed=args.bootstrap_seed, ms=0.0, counts=np.zeros((args.bootstrap, 2, 4, 3, nq), np.int64),
                     strat=None if strat is None else np.zeros((len(strat["names"]), args.bootstrap, 2, 4, 3, nq), np.int64))
+    ec = None
+    if args.classify_errors:
+        ec = dict(window=A.EC_DEFAULT_WINDOW if args.error_window is None else args.error_window, ms=0.0,
+                  counts=np.zeros((2, 4, A.EC_CLASSES, nq), np.int64))
     empty = dict(pos=np.zeros(0, np.int32), rlen=np.zeros(0, np.int32), type=np.zeros(0, np.uint8), var_qual=np.zeros(0, np.float32),
                  phase_set=np.zeros(0, np.int32), ref_len=np.zeros(0, np.int32), alt_len=np.zeros(0, np.int32),
                  ref_off=np.zeros(0, np.int64), alt_off=np.zeros(0, np.int64), pool=np.zeros(1, np.uint8))
@@ -554,7 +589,7 @@ def main(argv=None):
         ctg = contigs[k]
         try:
             counts, n_sc, tables = evaluate_contig(prepared.pop(k), args, device=device, part=(rank, world, cdev) if by_sc else None,
-                                                   dist_sets=dist_sets, strat=strat, boot=boot, ordinal=k)
+                                                   dist_sets=dist_sets, strat=strat, boot=boot, ordinal=k, ec=ec)
         except api.VprError as e:     # the library's explicit refusals end the run like the reference's ERROR()
             raise SystemExit(f"ERROR: contig '{ctg}': {e}")
         total += counts
@@ -577,6 +612,8 @@ def main(argv=None):
         tail = [] if strat is None else [strat["counts"].ravel(), np.asarray([strat["vars"], strat["none"]], np.int64), strat["vs_members"].ravel()]
         if boot is not None:
             tail += [boot["counts"].ravel()] + ([] if strat is None else [boot["strat"].ravel()])
+        if ec is not None:
+            tail += [ec["counts"].ravel()]
         summed = shard.allreduce_tally(np.concatenate([total.ravel()] + tail), device=cdev)
         total = summed[:total.size].reshape(total.shape)
         at = total.size
@@ -592,6 +629,9 @@ def main(argv=None):
             at += boot["counts"].size
             if strat is not None:
                 boot["strat"] = summed[at:at + boot["strat"].size].reshape(boot["strat"].shape)
+                at += boot["strat"].size
+        if ec is not None:
+            ec["counts"] = summed[at:at + ec["counts"].size].reshape(ec["counts"].shape)
         if not by_sc:       # (by superclusters every rank already holds every contig's gathered tables)
             gathered = [None] * world
             dist.all_gather_object(gathered, reports)
@@ -603,6 +643,9 @@ def main(argv=None):
             if strat is not None and strat["vs"]:
                 dist.all_gather_object(gathered, strat["vs_ms"])
                 strat["vs_ms"] = sum(gathered)
+            if ec is not None:
+                dist.all_gather_object(gathered, ec["ms"])
+                ec["ms"] = sum(gathered)
     rows = S.pr_summary(total, args.min_qual, args.max_qual)
     if dist_sets is not None:       # write_distance (printed even with -n) and write_edits, edit.cpp:134-280
         text = RP.write_distance(args.prefix, dist_sets, args.min_qual, args.max_qual, args.eval_sub, args.eval_open, args.eval_extend,
@@ -620,6 +663,8 @@ def main(argv=None):
                     RP.write_context_bed(args.prefix, contigs, strat["ctx_names"], strat["intervals"])
                 if strat["vs"]:
                     RP.write_variant_strata(args.prefix, strat["vs_names"], strat["vs"], strat["vs_members"][0], strat["vs_members"][1])
+            if ec is not None:
+                RP.write_error_classes(args.prefix, ec["counts"], total, args.min_qual, args.max_qual)
             if boot is not None:
                 RP.write_bootstrap(args.prefix, total, boot["counts"], boot["seed"], args.min_qual, args.max_qual)
                 if strat is not None:
@@ -640,6 +685,9 @@ def main(argv=None):
                       "on the device", file=sys.stderr)
             if strat["vs"]:
                 print(f"[vcfdist_amd] variant strata: {len(strat['vs'])} strata, {strat['vs_ms']:.3f} ms on the device", file=sys.stderr)
+        if ec is not None:
+            print(f"[vcfdist_amd] error classes: window {ec['window']}, {int(ec['counts'][0, 3, :, 0].sum())} query FP and "
+                  f"{int(ec['counts'][1, 3, :, 0].sum())} truth FN classified, {ec['ms']:.3f} ms on the device", file=sys.stderr)
         if boot is not None:
             print(f"[vcfdist_amd] bootstrap: {boot['n']} replicates, seed {boot['seed']}, {boot['ms']:.3f} ms on the device", file=sys.stderr)
         print("PRECISION-RECALL SUMMARY\n")

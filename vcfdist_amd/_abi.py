@@ -570,6 +570,13 @@ def vs_near(window, min_n, max_n=-1):
     return VprVariantStratum(VS_NEAR, 0, 0, 0, window, min_n, max_n)
 
 
+# ---- include/vcfdist_errclass.h
+EC_GT, EC_SYNC, EC_PHASE, EC_SITE, EC_NEAR, EC_ALONE, EC_LOWQ = range(7)
+EC_CLASSES = 7
+EC_NONE = 255
+EC_DEFAULT_WINDOW = 50
+
+
 # ---- include/vcfdist_realign.h
 RL_ST_EDGE = 1
 RL_ST_LIMIT = 2

@@ -98,6 +98,13 @@ def lib():
     L.vpr_varstrata_default.argtypes = [C.POINTER(C.POINTER(A.VprVariantStratum)), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.c_int32)]
     L.vpr_varstrata_masks.argtypes = [H, C.POINTER(A.VprVariants), C.POINTER(A.VprVariantStratum), C.c_int32, C.c_int32]
     L.vpr_varstrata_timing.argtypes = [H, C.POINTER(C.c_double)]
+    ec = [C.POINTER(A.VprVariants), C.c_void_p, A.P_i32, C.c_int32, C.c_int32, C.c_int32, A.P_i64]
+    L.vpr_errclass.argtypes = [H] + ec
+    L.vpr_allreduce_errclass.argtypes = [H, C.c_void_p] + ec
+    L.vpr_errclass_download.argtypes = [H, A.P_u8 * A.HAPS]
+    L.vpr_errclass_timing.argtypes = [H, C.POINTER(C.c_double)]
+    L.vpr_errclass_names.restype = C.POINTER(C.c_char_p)
+    L.vpr_errclass_names.argtypes = []
     boot = [C.c_void_p, A.P_i32, C.c_int32, C.c_int32, P_u64, C.c_uint64, C.c_int32, C.c_int32, A.P_i64]
     L.vpr_pr_counts_boot.argtypes = [H] + boot
     L.vpr_allreduce_counts_boot.argtypes = [H, C.c_void_p] + boot
@@ -128,6 +135,9 @@ CONTEXT_EXPORTED = ["vpr_context_default", "vpr_context_masks", "vpr_context_int
                     "vpr_context_info", "vpr_context_timing"]
 # include/vcfdist_varstrata.h
 VARSTRATA_EXPORTED = ["vpr_varstrata_default", "vpr_varstrata_masks", "vpr_varstrata_timing", "vrp_write_variant_strata"]
+# include/vcfdist_errclass.h
+ERRCLASS_EXPORTED = ["vpr_errclass", "vpr_allreduce_errclass", "vpr_errclass_download", "vpr_errclass_timing", "vpr_errclass_names",
+                     "vrp_write_error_classes"]
 # include/vcfdist_bootstrap.h
 BOOT_EXPORTED = ["vpr_pr_counts_boot", "vpr_allreduce_counts_boot", "vpr_boot_info", "vrp_write_bootstrap", "vrp_write_bootstrap_stratified"]
 # include/vcfdist_realign.h
@@ -197,6 +207,12 @@ def varstrata_default():
     if rc:
         raise VprError(f"vpr_varstrata_default failed ({rc})")
     return [names[k].decode() for k in range(n.value)], [A.VprVariantStratum.from_buffer_copy(spec[k]) for k in range(n.value)]
+
+
+def errclass_names():
+    """the names of the seven error classes (vpr_errclass_names), in the order of their codes A.EC_*"""
+    names = lib().vpr_errclass_names()
+    return [names[k].decode() for k in range(A.EC_CLASSES)]
 
 
 def context_info():
@@ -478,6 +494,39 @@ class PrecisionRecall:
         """ms of the last varstrata_masks' kernel launches, from HIP events on the handle's stream"""
         a = C.c_double()
         self._chk(lib().vpr_varstrata_timing(self._h, C.byref(a)), "vpr_varstrata_timing")
+        return a.value
+
+    def errclass(self, variants, var_class_per_slot, pb_phase=None, window=A.EC_DEFAULT_WINDOW, min_qual=0, max_qual=60, comm=None):
+        """The error classes of the last execute (include/vcfdist_errclass.h): every query FP and truth FN gets the first class
+        that applies (A.EC_*), joined across the callsets inside its supercluster on the device -> int64 [2][4][7][nq].
+        variants: the A.Variants (or a VprVariants struct) the batch was made from; var_class_per_slot None: the classes are
+        resident; comm: an ncclComm_t (as an integer) for vpr_allreduce_errclass."""
+        vs = variants.as_struct() if isinstance(variants, A.Variants) else variants
+        nq = max_qual - min_qual + 1
+        out = np.zeros((2, 4, A.EC_CLASSES, max(nq, 1)), np.int64)      # (min_qual > max_qual: the call refuses)
+        pb = None if pb_phase is None else np.ascontiguousarray(pb_phase, dtype=np.int32)
+        arr = None
+        if var_class_per_slot is not None:
+            cls = [np.ascontiguousarray(c, dtype=np.uint8) for c in var_class_per_slot]
+            arr = (A.P_u8 * 4)(*[A._ptr(c, C.c_uint8) for c in cls])
+        args = (C.byref(vs), arr, None if pb is None else A._ptr(pb, C.c_int32), int(window), min_qual, max_qual, A._ptr(out, C.c_int64))
+        L = lib()
+        rc = L.vpr_errclass(self._h, *args) if comm is None else L.vpr_allreduce_errclass(self._h, comm if isinstance(comm, C.c_void_p) else C.c_void_p(comm), *args)
+        self._chk(rc, "vpr_errclass")
+        return out
+
+    def errclass_download(self):
+        """the class bytes (A.EC_*, A.EC_NONE) of the last errclass: one uint8 array per hap slot"""
+        out = [np.zeros(self._batch.n_vars(h) if self._batch is not None else 0, np.uint8) for h in range(A.HAPS)]
+        keep = [o if o.size else np.zeros(1, np.uint8) for o in out]
+        arr = (A.P_u8 * A.HAPS)(*[A._ptr(k, C.c_uint8) for k in keep])
+        self._chk(lib().vpr_errclass_download(self._h, arr), "vpr_errclass_download")
+        return out
+
+    def errclass_timing(self):
+        """ms of the last errclass' kernel launches, from HIP events on the handle's stream"""
+        a = C.c_double()
+        self._chk(lib().vpr_errclass_timing(self._h, C.byref(a)), "vpr_errclass_timing")
         return a.value
 
     def pr_counts_boot(self, var_class_per_slot, pb_phase, sc_key, n_rep, seed=1, min_qual=0, max_qual=60, stratum=-1, comm=None):

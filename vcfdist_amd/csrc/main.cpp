@@ -12,6 +12,7 @@
 //               [-d] [-ex -eo -ee evaluation penalties] [-rq] [-rt] [-ro] [--stratify strata.tsv] [--stratify-context]
 //               [--stratify-variants]
 //               [--bootstrap N] [--bootstrap-seed S]
+//               [--classify-errors] [--error-window N]
 // With -d the distance metrics (edits_wrapper, dist.cpp:1908-2077) run on the GPU after each contig's precision/recall path
 // (include/vcfdist_distance.h), as the reference's main.cpp:223-238 runs them after precision_recall_threads_wrapper.
 // With -rq / -rt a callset is clustered and realigned on the GPU (include/vcfdist_realign.h) before the evaluation, in the order of
@@ -23,6 +24,9 @@
 // With --stratify-variants the default variant strata (transitions / transversions, indel size bins, hom / het, isolated / crowded:
 // bits made on the GPU from the variant tables, include/vcfdist_varstrata.h) follow those, or stand alone; variant-strata.tsv lists
 // them with their numbers of members.
+// With --classify-errors every query FP and truth FN gets the first error class that applies (include/vcfdist_errclass.h: right
+// allele with the wrong genotype, on the aligned or on the other haplotype, another allele at the site, something within
+// --error-window N bases (default 50), nothing), joined across the callsets on the GPU: error-classes.tsv, error-classes-summary.tsv.
 // With --bootstrap N the counters are resampled N times on the GPU (include/vcfdist_bootstrap.h: a Poisson bootstrap over
 // superclusters, conditional on the phasing): bootstrap-precision-recall-summary.tsv with 95 % percentile intervals,
 // bootstrap-replicates.tsv, and with --stratify stratified-bootstrap-precision-recall-summary.tsv.
@@ -49,6 +53,7 @@
 #include "../../include/vcfdist_context.h"
 #include "../../include/vcfdist_strata.h"
 #include "../../include/vcfdist_varstrata.h"
+#include "../../include/vcfdist_errclass.h"
 
 namespace {
 
@@ -63,6 +68,8 @@ struct Args {
     double credit_threshold = 0.7, phase_threshold = 0.6;
     bool no_output_files = false, strict = false;
     int bootstrap = 0;                 // --bootstrap: replicates (0: none)
+    bool classify_errors = false;      // --classify-errors
+    int error_window = -1;             // --error-window: -1 not given (VPR_EC_DEFAULT_WINDOW)
     uint64_t bootstrap_seed = 1;
 };
 
@@ -96,6 +103,15 @@ uint64_t bootstrap_seed(const char *v) {
     const unsigned long long s = strtoull(v, &end, 10);
     if (end == v || *end || errno || v[0] == '-') die("ERROR: Invalid bootstrap seed '%s'", v);
     return s;
+}
+// --error-window N: a non-negative 32-bit integer
+int error_window(const char *v) {
+    char *end = nullptr;
+    errno = 0;
+    const long long n = strtoll(v, &end, 10);
+    if (end == v || *end || errno) die("ERROR: Invalid error window '%s'", v);
+    if (n < 0 || n > INT32_MAX) die("ERROR: Must provide an error window of 0 to %d bases", INT32_MAX);
+    return int(n);
 }
 void warn(const std::string &m) { fprintf(stderr, "[WARN  vcfdist] %s\n", m.c_str()); }
 
@@ -134,6 +150,8 @@ Args parse(int argc, char **argv) {
         else if (o == "--stratify-variants") a.stratify_variants = true;
         else if (o == "--bootstrap") a.bootstrap = bootstrap_replicates(need(i));
         else if (o == "--bootstrap-seed") a.bootstrap_seed = bootstrap_seed(need(i));
+        else if (o == "--classify-errors") a.classify_errors = true;
+        else if (o == "--error-window") a.error_window = error_window(need(i));
         else if (o == "-rq" || o == "--realign-query") a.realign_query = true;
         else if (o == "-rt" || o == "--realign-truth") a.realign_truth = true;
         else if (o == "-ro" || o == "--realign-only") a.realign_only = true;
@@ -147,6 +165,8 @@ Args parse(int argc, char **argv) {
     a.query = pos[0]; a.truth = pos[1]; a.fasta = pos[2];
     if (a.max_size + 2 > a.max_supercluster_size)          // globals.cpp:478-481
         die("ERROR: Max supercluster size (-s) must be at least two larger than max variant size (-l).");
+    if (a.error_window >= 0 && !a.classify_errors) die("ERROR: --error-window needs --classify-errors");
+    if (a.error_window < 0) a.error_window = VPR_EC_DEFAULT_WINDOW;
     if ((a.realign_query || a.realign_truth) && (a.sub < 1 || a.extend < 1))
         die("ERROR: realignment needs a mismatch penalty (-x) and a gap-extension penalty (-e) of at least 1");
     return a;
@@ -467,6 +487,9 @@ int main(int argc, char **argv) {
     std::vector<int64_t> total(size_t(2) * VPR_VARTYPES * 3 * size_t(nq), 0);
     std::vector<int64_t> strat_total(total.size() * size_t(n_strata), 0);      // --stratify: counts[n_strata][2][4][3][nq]
     int64_t strat_vars = 0, strat_none = 0;                                     // hap-variants seen / in no stratum
+    // --classify-errors: counts[2][4][VPR_EC_CLASSES][nq] summed over the contigs; device ms of the launches
+    std::vector<int64_t> ec_total(A.classify_errors ? total.size() / 3 * VPR_EC_CLASSES : 0, 0);
+    double ec_ms = 0;
     // --bootstrap: counts[n_rep][2][4][3][nq], with --stratify also [n_strata][n_rep][2][4][3][nq]; device ms of the launches
     std::vector<int64_t> boot_total(total.size() * size_t(A.bootstrap), 0), boot_strat(boot_total.size() * size_t(n_strata), 0);
     double boot_ms = 0;
@@ -578,6 +601,14 @@ int main(int argc, char **argv) {
             std::vector<int64_t> counts(total.size(), 0);
             if (vpr_pr_counts(h, clsp, C->pb.data(), A.min_qual, A.max_qual, counts.data())) die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
             for (size_t k = 0; k < total.size(); k++) total[k] += counts[k];
+            if (A.classify_errors) {      // the same evaluation, its FP and FN cut by why they are wrong (the classes are resident)
+                std::vector<int64_t> ec(ec_total.size(), 0);
+                double ms = 0;
+                if (vpr_errclass(h, &V, nullptr, C->pb.data(), A.error_window, A.min_qual, A.max_qual, ec.data()) || vpr_errclass_timing(h, &ms))
+                    die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+                for (size_t k = 0; k < ec.size(); k++) ec_total[k] += ec[k];
+                ec_ms += ms;
+            }
             if (n_strata) {        // the same evaluation, cut by region: membership words, then the histogram per stratum
                 std::vector<int64_t> iv_off(size_t(n_bed) + 1, 0);
                 std::vector<int32_t> iv_start, iv_stop;
@@ -719,6 +750,8 @@ int main(int argc, char **argv) {
             }
             if (n_vs && vrp_write_variant_strata(A.prefix.c_str(), vs_names, vs_spec, n_vs, vs_query.data(), vs_truth.data())) die("ERROR: %s", vrp_last_error());
         }
+        if (A.classify_errors && vrp_write_error_classes(A.prefix.c_str(), ec_total.data(), total.data(), A.min_qual, A.max_qual))
+            die("ERROR: %s", vrp_last_error());
         if (A.bootstrap && vrp_write_bootstrap(A.prefix.c_str(), total.data(), boot_total.data(), A.bootstrap, A.bootstrap_seed, A.min_qual, A.max_qual))
             die("ERROR: %s", vrp_last_error());
         std::vector<vrp_contig> ctgs(outs.size());
@@ -765,6 +798,16 @@ int main(int argc, char **argv) {
         fprintf(stderr, "[vcfdist_amd] context strata: %lld intervals of %d strata, %.3f ms on the device\n", (long long)ctx_start.size(), n_ctx, ctx_ms);
     if (n_vs)
         fprintf(stderr, "[vcfdist_amd] variant strata: %d strata, %.3f ms on the device\n", n_vs, vs_ms);
+    if (A.classify_errors) {      // the classified errors at threshold NONE: the ALL rows' classes of both callsets
+        const size_t nq = size_t(A.max_qual - A.min_qual + 1);
+        long long n_fp = 0, n_fn = 0;
+        for (int c = 0; c < VPR_EC_CLASSES; c++) {
+            n_fp += ec_total[((size_t(0) * VPR_VARTYPES + VPR_VARTYPE_ALL) * VPR_EC_CLASSES + size_t(c)) * nq];
+            n_fn += ec_total[((size_t(1) * VPR_VARTYPES + VPR_VARTYPE_ALL) * VPR_EC_CLASSES + size_t(c)) * nq];
+        }
+        fprintf(stderr, "[vcfdist_amd] error classes: window %d, %lld query FP and %lld truth FN classified, %.3f ms on the device\n", A.error_window,
+                n_fp, n_fn, ec_ms);
+    }
     if (A.bootstrap)
         fprintf(stderr, "[vcfdist_amd] bootstrap: %d replicates, seed %llu, %.3f ms on the device\n", A.bootstrap, (unsigned long long)A.bootstrap_seed, boot_ms);
     printf("PRECISION-RECALL SUMMARY\n\n");

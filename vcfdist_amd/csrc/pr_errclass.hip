@@ -1,0 +1,286 @@
+// pr_errclass.hip -- the error classes (include/vcfdist_errclass.h): why each query FP and truth FN is wrong.  k_errclass joins the
+// two callsets inside each supercluster -- one lane per hap-variant, bisections over the supercluster's sorted positions, as
+// k_varstrata_mask (pr_varstrata.hip) does inside a contig -- writes a class byte per hap-variant and counts the classes in a
+// block histogram, as k_pr_hist (pr_collect.hip) counts the errtypes.  The bin rule is pr_counts.h's; the front and back of a
+// counters call are the ones of pr_collect.hip.
+#include "pr_host.h"
+#include "pr_counts.h"
+#include "pr_varscan.h"
+#include "../../include/vcfdist_errclass.h"
+
+struct ErrclassState {
+    DevBuf<uint8_t> cls[VPR_HAPS];                               // the class bytes of the last call
+    DevBuf<unsigned long long> hist;                             // [2][3 types][VPR_EC_CLASSES][nq + 1]
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double ms = 0;
+    bool valid = false;
+};
+
+namespace {
+
+const char *const EC_NAMES[VPR_EC_CLASSES] = {"gt", "sync", "phase", "site", "near", "alone", "lowq"};
+
+// the run of variants of slot x's range [lo, hi) that start at pos: *site = it is not empty; true iff it holds a copy
+__device__ __forceinline__ bool ec_copy_at(const VsCols &x, int64_t lo, int64_t hi, int32_t pos, uint8_t type, int32_t ref_len, int32_t alt_len,
+                                           const uint8_t *__restrict__ alt, bool *site) {
+    int64_t u = vs_lower(x.pos, lo, hi, pos);
+    *site = u < hi && x.pos[u] == pos;
+    for (; u < hi && x.pos[u] == pos; u++)
+        if (vs_is_copy(x, u, type, ref_len, alt_len, alt)) return true;
+    return false;
+}
+
+// some variant of slot x's range [lo, hi) starts within W bases of pos and not at pos: the window's first or last one
+__device__ __forceinline__ bool ec_near(const VsCols &x, int64_t lo, int64_t hi, int32_t pos, int32_t W) {
+    const int64_t a = vs_lower(x.pos, lo, hi, int64_t(pos) - W), b = vs_upper(x.pos, lo, hi, int64_t(pos) + W);
+    return a < b && (x.pos[a] != pos || x.pos[b - 1] != pos);
+}
+
+}  // namespace
+
+extern "C" {
+
+// One lane per hap-variant of slot `own`.  par: the partner slot; oa / ob: the slots of the other callset with the same / the
+// other haplotype index, so that the compared slot is oa under ORIG and ob under SWAP.  e0 / e1 / q0 / q1: the lane's errtype and
+// callq columns of the two phasings (four pointers, as pr_count_row takes them); pe0 / pe1: the partner slot's errtype columns.
+// A variant that is no error leaves after the loads k_pr_hist makes; an error walks the class list -- the searches are divergent,
+// few lanes of a wave run them.  Classes are counted in LDS ([3 types][VPR_EC_CLASSES][nq + 1] words) and flushed once.
+__global__ void __launch_bounds__(256) k_errclass(VsCols own, VsCols par, VsCols oa, VsCols ob, int64_t n_var, int n_sc,
+                                                  const uint8_t *__restrict__ cls, const int32_t *__restrict__ sc_phase,
+                                                  const int32_t *__restrict__ pb_phase, const uint8_t *e0, const uint8_t *e1, const float *q0,
+                                                  const float *q1, const uint8_t *pe0, const uint8_t *pe1, int callset, int window, int min_qual,
+                                                  int max_qual, uint8_t *__restrict__ out,
+                                                  unsigned long long *__restrict__ hist /* [2][3][VPR_EC_CLASSES][nq + 1] */) {
+    extern __shared__ unsigned int blk[];      // [3][VPR_EC_CLASSES][nq + 1]
+    const int nq = max_qual - min_qual + 1, nb = 3 * VPR_EC_CLASSES * (nq + 1);
+    for (int k = threadIdx.x; k < nb; k += blockDim.x) blk[k] = 0;
+    __syncthreads();
+    const int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (v < n_var) {
+        const int sc = sc_of_var(own.var_off, n_sc, v);
+        int bin = 0, c = VPR_EC_NONE, t = 0;
+        const int row = pr_count_row(sc, v, sc_phase, pb_phase, e0, e1, q0, q1, cls, min_qual, nq, &bin);
+        if (row >= 0) {
+            t = row / 3;
+            const int e = row - 3 * t;
+            if (e == (callset ? VPR_ERRTYPE_FN : VPR_ERRTYPE_FP)) {
+                const int w = pr_phase_swap(sc, sc_phase, pb_phase);
+                const int32_t pos = own.pos[v], ref_len = own.ref_len[v], alt_len = own.alt_len[v];
+                const uint8_t type = own.type[v];
+                const uint8_t *__restrict__ alt = own.pool + own.alt_off[v];
+                const uint8_t *pe = w ? pe1 : pe0;
+                bool gt = false;
+                const int64_t p1 = par.var_off[sc + 1];
+                for (int64_t u = vs_lower(par.pos, par.var_off[sc], p1, pos); !gt && u < p1 && par.pos[u] == pos; u++)
+                    gt = pe[u] == VPR_ERRTYPE_TP && vs_is_copy(par, u, type, ref_len, alt_len, alt);
+                if (gt) {
+                    c = VPR_EC_GT;
+                } else {
+                    const int64_t a0 = oa.var_off[sc], a1 = oa.var_off[sc + 1], b0 = ob.var_off[sc], b1 = ob.var_off[sc + 1];
+                    bool site_a, site_b;
+                    const bool copy_a = ec_copy_at(oa, a0, a1, pos, type, ref_len, alt_len, alt, &site_a);
+                    const bool copy_b = ec_copy_at(ob, b0, b1, pos, type, ref_len, alt_len, alt, &site_b);
+                    if (w ? copy_b : copy_a) c = VPR_EC_SYNC;
+                    else if (w ? copy_a : copy_b) c = VPR_EC_PHASE;
+                    else if (site_a || site_b) c = VPR_EC_SITE;
+                    else c = ec_near(oa, a0, a1, pos, window) || ec_near(ob, b0, b1, pos, window) ? VPR_EC_NEAR : VPR_EC_ALONE;
+                }
+            } else if (callset && e == VPR_ERRTYPE_TP) {
+                c = VPR_EC_LOWQ;
+            }
+        }
+        out[v] = uint8_t(c);
+        if (c != VPR_EC_NONE) atomicAdd(&blk[(t * VPR_EC_CLASSES + c) * (nq + 1) + bin], 1u);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < nb; k += blockDim.x)
+        if (blk[k]) atomicAdd(&hist[size_t(callset) * nb + k], (unsigned long long)blk[k]);
+}
+
+}  // extern "C"
+
+namespace {
+
+// the variant tables the kernel reads against the resident batch: the preconditions of include/vcfdist_errclass.h, and per slot
+// the bytes of allele_pool the variants' ALT alleles name (the pool's extent is not part of vpr_variants)
+int check_variants(vpr_handle *h, const vpr_variants *v, size_t pool_len[VPR_HAPS]) {
+    if (v->n_sc != h->n_sc)
+        return fail(h, VPR_ERR_STATE, "vpr_errclass: the variant tables hold %d superclusters, the resident batch %d", v->n_sc, h->n_sc);
+    const int64_t n_sc = v->n_sc;
+    for (int i = 0; i < VPR_HAPS; i++) {
+        pool_len[i] = 0;
+        const int64_t *off = v->var_off[i];
+        if (!off) return fail(h, VPR_ERR_ARG, "vpr_errclass: null var_off");
+        if (off[0] != 0) return fail(h, VPR_ERR_ARG, "vpr_errclass: hap slot %d: var_off[0] is not 0", i);
+        for (int64_t k = 0; k < n_sc; k++)
+            if (off[k + 1] < off[k]) return fail(h, VPR_ERR_ARG, "vpr_errclass: hap slot %d: var_off decreases at supercluster %lld", i, (long long)k);
+        if (off[n_sc] != h->n_var[i])
+            return fail(h, VPR_ERR_STATE, "vpr_errclass: hap slot %d: the variant tables hold %lld variants, the resident batch %lld", i,
+                        (long long)off[n_sc], (long long)h->n_var[i]);
+        if (!off[n_sc]) continue;
+        if (!v->var_pos[i] || !v->var_type[i] || !v->var_ref_len[i] || !v->var_alt_off[i] || !v->var_alt_len[i] || !v->allele_pool[i])
+            return fail(h, VPR_ERR_ARG, "vpr_errclass: hap slot %d: null variant column", i);
+        for (int64_t k = 0; k < n_sc; k++)
+            for (int64_t j = off[k]; j < off[k + 1]; j++) {
+                if (j > off[k] && v->var_pos[i][j] < v->var_pos[i][j - 1])
+                    return fail(h, VPR_ERR_ARG, "vpr_errclass: hap slot %d: var_pos is unsorted inside supercluster %lld: variant %lld at %d follows one at %d",
+                                i, (long long)k, (long long)j, v->var_pos[i][j], v->var_pos[i][j - 1]);
+                const int64_t ao = v->var_alt_off[i][j];
+                const int32_t rl = v->var_ref_len[i][j], al = v->var_alt_len[i][j];
+                if (ao < 0 || rl < 0 || al < 0)
+                    return fail(h, VPR_ERR_ARG, "vpr_errclass: hap slot %d: variant %lld has a negative allele offset or length", i, (long long)j);
+                pool_len[i] = std::max(pool_len[i], size_t(ao) + size_t(al));
+            }
+    }
+    return VPR_OK;
+}
+
+// histogram [2][3 types][VPR_EC_CLASSES][nq + 1] -> counts [2][VPR_VARTYPES][VPR_EC_CLASSES][nq]: pr_fold_counts' rule cut by class.
+// A query FP counts at the threshold indices <= its bin; a truth FN at every threshold; a LOWQ truth variant at the thresholds
+// above its bin (bin nq, callq < min_qual: at every one)
+void fold_classes(const unsigned long long *hist, int nq, int64_t *counts) {
+    std::fill(counts, counts + size_t(2) * VPR_VARTYPES * VPR_EC_CLASSES * size_t(nq), 0);
+    auto C = [&](int cs, int t, int c, int k) -> int64_t & { return counts[((size_t(cs) * VPR_VARTYPES + t) * VPR_EC_CLASSES + c) * nq + k]; };
+    for (int cs = 0; cs < 2; cs++)
+        for (int t = 0; t < 3; t++)
+            for (int c = 0; c < VPR_EC_CLASSES; c++) {
+                const unsigned long long *b = hist + ((size_t(cs) * 3 + t) * VPR_EC_CLASSES + c) * (nq + 1);
+                int64_t acc = 0;
+                if (cs == 0) {
+                    for (int k = nq - 1; k >= 0; k--) { acc += int64_t(b[k]); C(cs, t, c, k) = acc; }
+                } else if (c != VPR_EC_LOWQ) {
+                    for (int k = 0; k <= nq; k++) acc += int64_t(b[k]);
+                    for (int k = 0; k < nq; k++) C(cs, t, c, k) = acc;
+                } else {
+                    acc = int64_t(b[nq]);
+                    for (int k = 0; k < nq; k++) { C(cs, t, c, k) = acc; acc += int64_t(b[k]); }
+                }
+                for (int k = 0; k < nq; k++) C(cs, VPR_VARTYPE_ALL, c, k) += C(cs, t, c, k);
+            }
+}
+
+int errclass_impl(vpr_handle *h, void *comm, const vpr_variants *v, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase,
+                  int32_t window, int32_t min_qual, int32_t max_qual, int64_t *counts) {
+    if (!h) return VPR_ERR_ARG;
+    if (!v || !counts) return fail(h, VPR_ERR_ARG, "vpr_errclass: null argument");
+    if (window < 0) return fail(h, VPR_ERR_ARG, "vpr_errclass: window %d is negative", window);
+    if (max_qual < min_qual) return fail(h, VPR_ERR_ARG, "vpr_errclass: max_qual %d is below min_qual %d", max_qual, min_qual);
+    if (int rc = pr_counts_begin(h, "vpr_errclass", comm)) return rc;
+    size_t pool_len[VPR_HAPS];
+    if (int rc = check_variants(h, v, pool_len)) return rc;
+    if (!h->errclass) h->errclass = new ErrclassState();
+    ErrclassState *S = h->errclass;
+    S->valid = false; S->ms = 0;
+    for (int k = 0; k < 2; k++) if (!S->ev[k]) HIPCHK(h, hipEventCreate(&S->ev[k]));
+    const int64_t n_sc = v->n_sc;
+    const int nq = max_qual - min_qual + 1;
+    const size_t nb = size_t(3) * VPR_EC_CLASSES * size_t(nq + 1), nh = 2 * nb;
+    for (int i = 0; i < VPR_HAPS; i++)
+        if (int rc = S->cls[i].reserve(h, size_t(h->n_var[i]), "vpr_errclass: class bytes: cannot allocate %zu bytes on the device")) return rc;
+    if (int rc = S->hist.reserve(h, nh, "vpr_errclass: class histogram: cannot allocate %zu bytes on the device")) return rc;
+    // ---- the columns and the pools: one block that lives as long as the call
+    struct Piece { const void *src; size_t bytes; size_t at; };
+    std::vector<Piece> pieces;
+    size_t total = 0;
+    auto add = [&](const void *src, size_t bytes) { pieces.push_back({src, bytes, total}); total += (bytes + 255) & ~size_t(255); return pieces.size() - 1; };
+    size_t i_var[VPR_HAPS][7];
+    for (int i = 0; i < VPR_HAPS; i++) {
+        const size_t n = size_t(h->n_var[i]);
+        i_var[i][0] = add(v->var_off[i], 8 * (size_t(n_sc) + 1));
+        i_var[i][1] = add(v->var_alt_off[i], 8 * n);
+        i_var[i][2] = add(v->var_pos[i], 4 * n);
+        i_var[i][3] = add(v->var_ref_len[i], 4 * n);
+        i_var[i][4] = add(v->var_alt_len[i], 4 * n);
+        i_var[i][5] = add(v->var_type[i], n);
+        i_var[i][6] = add(v->allele_pool[i], n ? pool_len[i] : 0);
+    }
+    uint8_t *blk = nullptr;
+    if (x_malloc(h, reinterpret_cast<void **>(&blk), std::max<size_t>(total, 256), SITE) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, VPR_ERR_NOMEM, "vpr_errclass: cannot allocate %zu bytes on the device", total);
+    }
+    struct Release {
+        vpr_handle *h; uint8_t *p;
+        ~Release() {
+            (void)hipStreamSynchronize(h->stream);
+            (void)x_free(h, p, SITE);
+        }
+    } R{h, blk};
+    for (const Piece &p : pieces)
+        if (p.bytes && p.src) HIPCHK(h, hipMemcpyAsync(blk + p.at, p.src, p.bytes, hipMemcpyHostToDevice, h->stream));
+    auto at = [&](size_t i) { return blk + pieces[i].at; };
+    VsCols cols[VPR_HAPS];
+    for (int i = 0; i < VPR_HAPS; i++)
+        cols[i] = VsCols{reinterpret_cast<const int64_t *>(at(i_var[i][0])), nullptr, reinterpret_cast<const int64_t *>(at(i_var[i][1])),
+                         reinterpret_cast<const int32_t *>(at(i_var[i][2])), reinterpret_cast<const int32_t *>(at(i_var[i][3])),
+                         reinterpret_cast<const int32_t *>(at(i_var[i][4])), at(i_var[i][5]), at(i_var[i][6])};
+    HIPCHK(h, hipMemsetAsync(S->hist.p, 0, nh * 8, h->stream));
+    int32_t *d_pb = nullptr;
+    if (int rc = pr_counts_inputs(h, "vpr_errclass", var_class, pb_phase, &d_pb)) return rc;
+    HIPCHK(h, hipEventRecord(S->ev[0], h->stream));
+    for (int s = 0; s < VPR_HAPS; s++) {
+        const int64_t nv = h->n_var[s];
+        if (!nv) continue;
+        const int oa = (s ^ 2), ob = (s ^ 3);      // the other callset's slot of the same / of the other haplotype index
+        hipLaunchKernelGGL(k_errclass, dim3(unsigned((nv + 255) / 256)), dim3(256), nb * 4, h->stream, cols[s], cols[s ^ 1], cols[oa], cols[ob], nv,
+                           int(n_sc), h->d_cls[s], h->dR.sc_phase, d_pb, h->dR.v[s][0].errtype, h->dR.v[s][1].errtype, h->dR.v[s][0].callq,
+                           h->dR.v[s][1].callq, h->dR.v[s ^ 1][0].errtype, h->dR.v[s ^ 1][1].errtype, s >> 1, int(window), int(min_qual), int(max_qual),
+                           S->cls[s].p, S->hist.p);
+        HIPCHK(h, hipGetLastError());
+    }
+    HIPCHK(h, hipEventRecord(S->ev[1], h->stream));
+    std::vector<unsigned long long> hist(nh);
+    if (int rc = pr_counts_finish(h, comm, S->hist.p, nh, hist.data())) return rc;
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, S->ev[0], S->ev[1]);
+    S->ms = ms; S->valid = true;
+    fold_classes(hist.data(), nq, counts);
+    return VPR_OK;
+}
+
+}  // namespace
+
+void errclass_free(vpr_handle *h) {
+    ErrclassState *S = h->errclass;
+    if (!S) return;
+    dev_release(h, S->cls[0], S->cls[1], S->cls[2], S->cls[3], S->hist);
+    for (int k = 0; k < 2; k++) if (S->ev[k]) (void)hipEventDestroy(S->ev[k]);
+    delete S;
+    h->errclass = nullptr;
+}
+
+extern "C" {
+
+int vpr_errclass(vpr_handle *h, const vpr_variants *v, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase, int32_t window,
+                 int32_t min_qual, int32_t max_qual, int64_t *counts) {
+    return errclass_impl(h, nullptr, v, var_class, pb_phase, window, min_qual, max_qual, counts);
+}
+
+int vpr_allreduce_errclass(vpr_handle *h, void *nccl_comm, const vpr_variants *v, const uint8_t *const var_class[VPR_HAPS],
+                           const int32_t *pb_phase, int32_t window, int32_t min_qual, int32_t max_qual, int64_t *counts) {
+    if (!nccl_comm) return VPR_ERR_ARG;
+    return errclass_impl(h, nccl_comm, v, var_class, pb_phase, window, min_qual, max_qual, counts);
+}
+
+int vpr_errclass_download(vpr_handle *h, uint8_t *const cls[VPR_HAPS]) {
+    if (!h || !cls) return VPR_ERR_ARG;
+    if (!h->errclass || !h->errclass->valid) return fail(h, VPR_ERR_STATE, "vpr_errclass_download: no class bytes (before vpr_errclass, or after the next upload)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    for (int s = 0; s < VPR_HAPS; s++) {
+        if (!h->n_var[s]) continue;
+        if (!cls[s]) return fail(h, VPR_ERR_ARG, "vpr_errclass_download: hap slot %d: null array", s);
+        HIPCHK(h, hipMemcpyAsync(cls[s], h->errclass->cls[s].p, size_t(h->n_var[s]), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, x_sync(h, h->stream, SITE));
+    return VPR_OK;
+}
+
+int vpr_errclass_timing(const vpr_handle *h, double *ms) {
+    if (!h || !ms) return VPR_ERR_ARG;
+    *ms = h->errclass ? h->errclass->ms : 0;
+    return VPR_OK;
+}
+
+const char *const *vpr_errclass_names(void) { return EC_NAMES; }
+
+}  // extern "C"

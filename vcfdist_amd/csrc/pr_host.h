@@ -268,6 +268,7 @@ using namespace vprh;
 struct DistState;                        // the distance step's tables and arena (pr_dist.hip)
 struct StrataState;                      // the membership words and the stratified histogram (pr_strata.hip)
 struct ContextState;                     // the sequence-context intervals (pr_context.hip)
+struct ErrclassState;                    // the class bytes and the class histogram (pr_errclass.hip)
 struct BootState;                        // the replicate histogram and the supercluster keys (pr_boot.hip)
 
 struct vpr_handle {
@@ -419,6 +420,7 @@ struct vpr_handle {
     StrataState *strata = nullptr;       // vpr_strata_masks / vpr_strata_upload_masks (pr_strata.hip), released with the batch
     ContextState *context = nullptr;     // vpr_context_masks (pr_context.hip), released by the next one or vpr_destroy
     BootState *boot = nullptr;           // vpr_pr_counts_boot (pr_boot.hip), created by its first call, released with the batch
+    ErrclassState *errclass = nullptr;   // vpr_errclass (pr_errclass.hip), created by its first call, released with the batch
     double varstrata_ms = 0;             // device time of the last vpr_varstrata_masks' kernel launches (pr_varstrata.hip)
     vpr_timing timing;
     bool uploaded = false, executed = false;
@@ -472,6 +474,7 @@ int strata_extend(vpr_handle *h, const char *entry, int32_t n_add, const int64_t
                   uint64_t *words[VPR_HAPS], int32_t *n_words);
 void strata_commit(vpr_handle *h);
 void context_free(vpr_handle *h);                                    // pr_context.hip: the resident context intervals
+void errclass_free(vpr_handle *h);                                   // pr_errclass.hip: the class bytes and the class histogram
 void boot_free(vpr_handle *h);                                       // pr_boot.hip: the replicate histogram and the keys
 // pr_collect.hip, shared by the three counters entries (vpr_pr_counts, _strata, _boot; `entry`: the entry's name, for the
 // messages).  pr_counts_begin: the state checks and the device, before the entry's own buffers; pr_counts_inputs: the caller's

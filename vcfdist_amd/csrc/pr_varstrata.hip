@@ -4,16 +4,10 @@
 // behind the words (k_pr_hist_strata, the bootstrap's stratum cut) is the code of pr_strata.hip / pr_boot.hip.
 #include "pr_host.h"
 #include "pr_counts.h"
+#include "pr_varscan.h"
 #include "../../include/vcfdist_varstrata.h"
 
 namespace {
-
-// the columns of one hap slot the kernel reads
-struct VsCols {
-    const int64_t *var_off, *ref_off, *alt_off;
-    const int32_t *pos, *ref_len, *alt_len;
-    const uint8_t *type, *pool;
-};
 
 const vpr_variant_stratum DEFAULT_SPEC[] = {
     {VPR_VS_TI, 0, 0, 0, 0, 0, 0},
@@ -33,31 +27,6 @@ const vpr_variant_stratum DEFAULT_SPEC[] = {
 };
 const char *const DEFAULT_NAMES[] = {"snp_ti", "snp_tv", "ins_1to5", "ins_6to15", "ins_16to49", "ins_ge50", "del_1to5", "del_6to15",
                                      "del_16to49", "del_ge50", "hom", "het", "iso_50", "near_10"};
-
-// first index of [lo, hi) whose position is >= key (lower) / > key (upper); the keys are 64-bit so that pos +- W cannot wrap
-__device__ __forceinline__ int64_t vs_lower(const int32_t *__restrict__ pos, int64_t lo, int64_t hi, int64_t key) {
-    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (int64_t(pos[mid]) < key) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-__device__ __forceinline__ int64_t vs_upper(const int32_t *__restrict__ pos, int64_t lo, int64_t hi, int64_t key) {
-    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (int64_t(pos[mid]) <= key) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-
-// copies of a variant (pos, type, both lengths, ALT bytes at `alt`) among the variants [lo, hi) of slot x -- one contig's -- other
-// than index `skip`: a scan of the run of equal pos; the ALT bytes are compared only where everything else agrees
-__device__ __forceinline__ int vs_copies(const VsCols &x, int64_t lo, int64_t hi, int64_t skip, int32_t pos, uint8_t type, int32_t ref_len,
-                                         int32_t alt_len, const uint8_t *__restrict__ alt) {
-    int n = 0;
-    for (int64_t u = vs_lower(x.pos, lo, hi, pos); u < hi && x.pos[u] == pos; u++) {
-        if (u == skip || x.type[u] != type || x.ref_len[u] != ref_len || x.alt_len[u] != alt_len) continue;
-        const uint8_t *__restrict__ b = x.pool + x.alt_off[u];
-        int32_t j = 0;
-        while (j < alt_len && b[j] == alt[j]) j++;
-        n += j == alt_len;
-    }
-    return n;
-}
 
 // A, G (the purines) -> 0, 1; C, T (the pyrimidines) -> 2, 3; anything else -1
 __device__ __forceinline__ int vs_base(uint8_t b) { return b == 'A' ? 0 : b == 'G' ? 1 : b == 'C' ? 2 : b == 'T' ? 3 : -1; }

@@ -16,6 +16,7 @@
 #include "../../include/vcfdist_report.h"
 #include "../../include/vcfdist_bootstrap.h"
 #include "../../include/vcfdist_varstrata.h"
+#include "../../include/vcfdist_errclass.h"
 
 namespace {
 
@@ -237,6 +238,47 @@ extern "C" int vrp_write_variant_strata(const char *prefix, const char *const *n
                 num(near && s.max_n >= 0, s.max_n).c_str(), (long long)n_query[k], (long long)n_truth[k]);
     }
     if (!out.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn);
+    return VRP_OK;
+}
+
+extern "C" int vrp_write_error_classes(const char *prefix, const int64_t *class_counts, const int64_t *pr_counts, int32_t min_qual,
+                                       int32_t max_qual) {
+    if (!prefix || !class_counts || !pr_counts || max_qual < min_qual) return fail(VRP_ERR_ARG, "vrp_write_error_classes: bad argument");
+    const int nq = max_qual - min_qual + 1;
+    const std::string fn_all = std::string(prefix) + "error-classes.tsv", fn_sum = std::string(prefix) + "error-classes-summary.tsv";
+    File all(fn_all.c_str());
+    if (!all) return fail(VRP_ERR_OPEN, "cannot create " + fn_all);
+    File sum(fn_sum.c_str());
+    if (!sum) return fail(VRP_ERR_OPEN, "cannot create " + fn_sum);
+    static const char *const COLS = "QUERY_FP\tFP_GT\tFP_SYNC\tFP_PHASE\tFP_SITE\tFP_NEAR\tFP_ALONE\tTRUTH_FN\tFN_GT\tFN_SYNC\tFN_PHASE\tFN_SITE\tFN_NEAR\tFN_ALONE\tFN_LOWQ\n";
+    fprintf(all, "VAR_TYPE\tMIN_QUAL\t%s", COLS);
+    fprintf(sum, "VAR_TYPE\tTHRESHOLD\tMIN_QUAL\t%s", COLS);
+    // the fifteen cells of one (type, threshold index): each callset's total, then its classes (the query has no LOWQ)
+    auto cells = [&](FILE *f, int type, int k) {
+        for (int cs = 0; cs < 2; cs++) {
+            const int n = cs ? VPR_EC_CLASSES : VPR_EC_CLASSES - 1;
+            const int64_t *c = class_counts + (size_t(cs) * VPR_VARTYPES + type) * VPR_EC_CLASSES * size_t(nq) + k;
+            long long tot = 0;
+            for (int j = 0; j < n; j++) tot += c[size_t(j) * nq];
+            fprintf(f, "%s%lld", cs ? "\t" : "", tot);
+            for (int j = 0; j < n; j++) fprintf(f, "\t%lld", (long long)c[size_t(j) * nq]);
+        }
+        fputc('\n', f);
+    };
+    for (int type = 0; type < VPR_VARTYPES; type++)
+        for (int qual = min_qual; qual <= max_qual; qual++) {
+            fprintf(all, "%s\t%d\t", VARTYPE_STR[type], qual);
+            cells(all, type, qual - min_qual);
+        }
+    for (int type = 0; type < VPR_VARTYPES; type++) {
+        const int quals[2] = {min_qual, best_qual_of(pr_counts, type, min_qual, max_qual)};
+        const char *const thresh[2] = {"NONE", "BEST"};
+        for (int i = 0; i < 2; i++) {
+            fprintf(sum, "%s\t%s\t%d\t", VARTYPE_STR[type], thresh[i], quals[i]);
+            cells(sum, type, quals[i] - min_qual);
+        }
+    }
+    if (!all.finish() || !sum.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn_all + " / " + fn_sum);
     return VRP_OK;
 }
 

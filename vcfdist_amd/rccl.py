@@ -156,6 +156,11 @@ def allreduce_counts_boot(pr, comm: Comm, var_class_per_slot, pb_phase, sc_key, 
     return summary.pr_counts_boot(pr, var_class_per_slot, pb_phase, sc_key, n_rep, seed, min_qual, max_qual, stratum, comm=comm._c)
 
 
+def allreduce_errclass(pr, comm: Comm, variants, var_class_per_slot=None, pb_phase=None, window=A.EC_DEFAULT_WINDOW, min_qual=0, max_qual=60):
+    """PrecisionRecall.errclass summed over the ranks of `comm`: one all-reduce of the class histogram on the device"""
+    return pr.errclass(variants, var_class_per_slot, pb_phase, window, min_qual, max_qual, comm=comm._c)
+
+
 def allgather_phase(pr, comm: Comm, idx_local, n_total: int):
     """(sc_phase, orig_phase_dist, swap_phase_dist) of all n_total superclusters on every rank; idx_local[k] = global index of
     this rank's k-th supercluster"""

@@ -177,6 +177,19 @@ def write_variant_strata(prefix, names, spec, n_query, n_truth):
            "vrp_write_variant_strata")
 
 
+def write_error_classes(prefix, class_counts, counts, min_qual, max_qual):
+    """error-classes.tsv and error-classes-summary.tsv (include/vcfdist_errclass.h): class_counts int64 [2][4][7][nq]
+    (PrecisionRecall.errclass), counts int64 [2][4][3][nq] (summary.pr_counts) of the same evaluation, for the BEST threshold"""
+    nq = max_qual - min_qual + 1
+    cc, cnt = np.ascontiguousarray(class_counts, np.int64), np.ascontiguousarray(counts, np.int64)
+    if cc.shape != (2, 4, A.EC_CLASSES, nq) or cnt.shape != (2, 4, 3, nq):
+        raise ReportError(f"write_error_classes: counts of shapes {cc.shape} and {cnt.shape} for {nq} thresholds")
+    L = api.lib()
+    L.vrp_write_error_classes.argtypes = [C.c_char_p, A.P_i64, A.P_i64, C.c_int32, C.c_int32]
+    _check(L.vrp_write_error_classes(prefix.encode(), A._ptr(cc, C.c_int64), A._ptr(cnt, C.c_int64), min_qual, max_qual),
+           "vrp_write_error_classes")
+
+
 def write_bootstrap(prefix, counts, counts_boot, seed, min_qual, max_qual):
     """bootstrap-precision-recall-summary.tsv and bootstrap-replicates.tsv (include/vcfdist_bootstrap.h): counts int64
     [2][4][3][nq] (summary.pr_counts), counts_boot int64 [n_rep][2][4][3][nq] (summary.pr_counts_boot)"""

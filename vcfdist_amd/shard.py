@@ -154,6 +154,21 @@ def subset_per_variant(arr, var_off, idx):
     return np.asarray(arr)[pos]
 
 
+def subset_variants(v, idx):
+    """the variant tables of the superclusters `idx` of an A.Variants, in that order (a rank's share of a contig): the offsets and
+    the per-variant columns are cut, the contigs and the allele pools are shared with `v`"""
+    from . import _abi as A
+    idx = np.asarray(idx, np.int64)
+    off = []
+    for s in range(A.HAPS):
+        o = np.zeros(len(idx) + 1, np.int64)
+        np.cumsum(v.var_off[s][idx + 1] - v.var_off[s][idx], out=o[1:])
+        off.append(o)
+    cut = lambda cols: [subset_per_variant(cols[s], v.var_off[s], idx) for s in range(A.HAPS)]
+    return A.Variants(v.ctg_off, v.ctg_seq, v.sc_ctg[idx], v.sc_beg[idx], v.sc_end[idx], off, cut(v.var_pos), cut(v.var_type), cut(v.var_qual),
+                      cut(v.var_ref_off), cut(v.var_ref_len), cut(v.var_alt_off), cut(v.var_alt_len), v.allele_pool)
+
+
 def deal_contigs(weights, world: int):
     """contig indices of every rank (command line: a contig is evaluated by one rank): heaviest first to the least loaded"""
     order = sorted(range(len(weights)), key=lambda k: (-int(weights[k]), k))
