@@ -22,7 +22,10 @@ recall and F1, bootstrap-replicates.tsv, and with --stratify stratified-bootstra
 (default 1); works under several ranks in both --shard modes.  With --classify-errors every query FP and truth FN gets the first
 error class that applies (include/vcfdist_errclass.h: the right allele with the wrong genotype, on the aligned or on the other
 haplotype, another allele at the site, something within --error-window N bases (default 50), nothing), joined across the callsets on
-the GPU: error-classes.tsv and error-classes-summary.tsv; works under several ranks in both --shard modes."""
+the GPU: error-classes.tsv and error-classes-summary.tsv; works under several ranks in both --shard modes.  With --classify-matches
+every TP of either callset gets the first match kind that applies (include/vcfdist_matchkind.h: exact -- what an allele-for-allele
+comparison finds --, shifted, regrouped, partial), from the resident sync groups on the GPU: match-kinds.tsv and
+match-kinds-summary.tsv; works under several ranks in both --shard modes."""
 import argparse
 import sys
 
@@ -197,7 +200,13 @@ def classify_contig(pr, variants, ec, args, pb):
     ec["ms"] += pr.errclass_timing()
 
 
-def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None, boot=None, ordinal=0, ec=None):
+def match_kinds_contig(pr, variants, mk, args, pb):
+    """--classify-matches: the match kinds of the executed batch, added to mk['counts'] (the variant classes are resident: pr_counts)"""
+    mk["counts"] += pr.matchkind(variants, None, pb, args.min_qual, args.max_qual)
+    mk["ms"] += pr.matchkind_timing()
+
+
+def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None, boot=None, ordinal=0, ec=None, mk=None):
     """the precision/recall path on the GPU, phasing and counters for a prepared contig.  -> int64 counters [2][4][3][nq],
     n_sc, and what the writers need: (clusters after splitting, superclusters, results, phase sets, pb_phase, switches, flips).
     part = (rank, world, collective device): this rank evaluates its share of the contig's SUPERCLUSTERS -- dealt by the
@@ -238,6 +247,8 @@ def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None,
         counts = S.pr_counts(pr, cls, pb, args.min_qual, args.max_qual)
         if ec is not None:
             classify_contig(pr, prep["variants"], ec, args, pb)
+        if mk is not None:
+            match_kinds_contig(pr, prep["variants"], mk, args, pb)
         if strat is not None:
             stratify_contig(pr, prep, strat, args, pb)
         if boot is not None:
@@ -265,6 +276,8 @@ def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None,
             counts = S.pr_counts(pr, cls_mine, pb[idx], args.min_qual, args.max_qual)
             if ec is not None:      # (everything is local to the supercluster: the rank classifies its share from its share's tables)
                 classify_contig(pr, shard.subset_variants(prep["variants"], idx), ec, args, pb[idx])
+            if mk is not None:      # (the same: sync groups never leave the supercluster)
+                match_kinds_contig(pr, shard.subset_variants(prep["variants"], idx), mk, args, pb[idx])
             if strat is not None:
                 stratify_contig(pr, prep, strat, args, pb[idx], part_idx=idx)
             if boot is not None:
@@ -452,6 +465,9 @@ def main(argv=None):
                          "error-classes-summary.tsv")
     ap.add_argument("--error-window", metavar="N", type=error_window, default=None,
                     help="bases within which a variant of the other callset counts as near (default 50; needs --classify-errors)")
+    ap.add_argument("--classify-matches", action="store_true",
+                    help="how each TP was matched (exact: an allele-for-allele comparison finds it; shifted; regrouped; partial), "
+                         "from the sync groups on the GPU: match-kinds.tsv, match-kinds-summary.tsv")
     ap.add_argument("--shard", default="superclusters", choices=["superclusters", "contigs"],
                     help="several ranks (torch.distributed.run, one per GPU): deal every contig's superclusters over the ranks "
                          "(default; balanced whatever the contigs' sizes) or whole contigs")
@@ -558,6 +574,9 @@ def main(argv=None):
     if args.classify_errors:
         ec = dict(window=A.EC_DEFAULT_WINDOW if args.error_window is None else args.error_window, ms=0.0,
                   counts=np.zeros((2, 4, A.EC_CLASSES, nq), np.int64))
+    mk = None
+    if args.classify_matches:
+        mk = dict(ms=0.0, counts=np.zeros((2, 4, A.MK_KINDS, nq), np.int64))
     empty = dict(pos=np.zeros(0, np.int32), rlen=np.zeros(0, np.int32), type=np.zeros(0, np.uint8), var_qual=np.zeros(0, np.float32),
                  phase_set=np.zeros(0, np.int32), ref_len=np.zeros(0, np.int32), alt_len=np.zeros(0, np.int32),
                  ref_off=np.zeros(0, np.int64), alt_off=np.zeros(0, np.int64), pool=np.zeros(1, np.uint8))
@@ -589,7 +608,7 @@ def main(argv=None):
         ctg = contigs[k]
         try:
             counts, n_sc, tables = evaluate_contig(prepared.pop(k), args, device=device, part=(rank, world, cdev) if by_sc else None,
-                                                   dist_sets=dist_sets, strat=strat, boot=boot, ordinal=k, ec=ec)
+                                                   dist_sets=dist_sets, strat=strat, boot=boot, ordinal=k, ec=ec, mk=mk)
         except api.VprError as e:     # the library's explicit refusals end the run like the reference's ERROR()
             raise SystemExit(f"ERROR: contig '{ctg}': {e}")
         total += counts
@@ -614,6 +633,8 @@ def main(argv=None):
             tail += [boot["counts"].ravel()] + ([] if strat is None else [boot["strat"].ravel()])
         if ec is not None:
             tail += [ec["counts"].ravel()]
+        if mk is not None:
+            tail += [mk["counts"].ravel()]
         summed = shard.allreduce_tally(np.concatenate([total.ravel()] + tail), device=cdev)
         total = summed[:total.size].reshape(total.shape)
         at = total.size
@@ -632,6 +653,9 @@ def main(argv=None):
                 at += boot["strat"].size
         if ec is not None:
             ec["counts"] = summed[at:at + ec["counts"].size].reshape(ec["counts"].shape)
+            at += ec["counts"].size
+        if mk is not None:
+            mk["counts"] = summed[at:at + mk["counts"].size].reshape(mk["counts"].shape)
         if not by_sc:       # (by superclusters every rank already holds every contig's gathered tables)
             gathered = [None] * world
             dist.all_gather_object(gathered, reports)
@@ -646,6 +670,9 @@ def main(argv=None):
             if ec is not None:
                 dist.all_gather_object(gathered, ec["ms"])
                 ec["ms"] = sum(gathered)
+            if mk is not None:
+                dist.all_gather_object(gathered, mk["ms"])
+                mk["ms"] = sum(gathered)
     rows = S.pr_summary(total, args.min_qual, args.max_qual)
     if dist_sets is not None:       # write_distance (printed even with -n) and write_edits, edit.cpp:134-280
         text = RP.write_distance(args.prefix, dist_sets, args.min_qual, args.max_qual, args.eval_sub, args.eval_open, args.eval_extend,
@@ -665,6 +692,8 @@ def main(argv=None):
                     RP.write_variant_strata(args.prefix, strat["vs_names"], strat["vs"], strat["vs_members"][0], strat["vs_members"][1])
             if ec is not None:
                 RP.write_error_classes(args.prefix, ec["counts"], total, args.min_qual, args.max_qual)
+            if mk is not None:
+                RP.write_match_kinds(args.prefix, mk["counts"], total, args.min_qual, args.max_qual)
             if boot is not None:
                 RP.write_bootstrap(args.prefix, total, boot["counts"], boot["seed"], args.min_qual, args.max_qual)
                 if strat is not None:
@@ -688,6 +717,11 @@ def main(argv=None):
         if ec is not None:
             print(f"[vcfdist_amd] error classes: window {ec['window']}, {int(ec['counts'][0, 3, :, 0].sum())} query FP and "
                   f"{int(ec['counts'][1, 3, :, 0].sum())} truth FN classified, {ec['ms']:.3f} ms on the device", file=sys.stderr)
+        if mk is not None:
+            q, t = mk["counts"][0, 3, :, 0], mk["counts"][1, 3, :, 0]
+            print(f"[vcfdist_amd] match kinds: query TP {int(q[0])} exact, {int(q[1])} shifted, {int(q[2])} regrouped, {int(q[3])} partial; "
+                  f"truth TP {int(t[0])} exact, {int(t[1])} shifted, {int(t[2])} regrouped, {int(t[3])} partial, {mk['ms']:.3f} ms on the device",
+                  file=sys.stderr)
         if boot is not None:
             print(f"[vcfdist_amd] bootstrap: {boot['n']} replicates, seed {boot['seed']}, {boot['ms']:.3f} ms on the device", file=sys.stderr)
         print("PRECISION-RECALL SUMMARY\n")

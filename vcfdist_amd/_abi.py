@@ -576,6 +576,11 @@ EC_CLASSES = 7
 EC_NONE = 255
 EC_DEFAULT_WINDOW = 50
 
+# ---- include/vcfdist_matchkind.h
+MK_EXACT, MK_SHIFTED, MK_REGROUPED, MK_PARTIAL = range(4)
+MK_KINDS = 4
+MK_NONE = 255
+
 
 # ---- include/vcfdist_realign.h
 RL_ST_EDGE = 1

@@ -105,6 +105,13 @@ def lib():
     L.vpr_errclass_timing.argtypes = [H, C.POINTER(C.c_double)]
     L.vpr_errclass_names.restype = C.POINTER(C.c_char_p)
     L.vpr_errclass_names.argtypes = []
+    mk = [C.POINTER(A.VprVariants), C.c_void_p, A.P_i32, C.c_int32, C.c_int32, A.P_i64]
+    L.vpr_matchkind.argtypes = [H] + mk
+    L.vpr_allreduce_matchkind.argtypes = [H, C.c_void_p] + mk
+    L.vpr_matchkind_download.argtypes = [H, A.P_u8 * A.HAPS]
+    L.vpr_matchkind_timing.argtypes = [H, C.POINTER(C.c_double)]
+    L.vpr_matchkind_names.restype = C.POINTER(C.c_char_p)
+    L.vpr_matchkind_names.argtypes = []
     boot = [C.c_void_p, A.P_i32, C.c_int32, C.c_int32, P_u64, C.c_uint64, C.c_int32, C.c_int32, A.P_i64]
     L.vpr_pr_counts_boot.argtypes = [H] + boot
     L.vpr_allreduce_counts_boot.argtypes = [H, C.c_void_p] + boot
@@ -138,6 +145,9 @@ VARSTRATA_EXPORTED = ["vpr_varstrata_default", "vpr_varstrata_masks", "vpr_varst
 # include/vcfdist_errclass.h
 ERRCLASS_EXPORTED = ["vpr_errclass", "vpr_allreduce_errclass", "vpr_errclass_download", "vpr_errclass_timing", "vpr_errclass_names",
                      "vrp_write_error_classes"]
+# include/vcfdist_matchkind.h
+MATCHKIND_EXPORTED = ["vpr_matchkind", "vpr_allreduce_matchkind", "vpr_matchkind_download", "vpr_matchkind_timing", "vpr_matchkind_names",
+                      "vrp_write_match_kinds"]
 # include/vcfdist_bootstrap.h
 BOOT_EXPORTED = ["vpr_pr_counts_boot", "vpr_allreduce_counts_boot", "vpr_boot_info", "vrp_write_bootstrap", "vrp_write_bootstrap_stratified"]
 # include/vcfdist_realign.h
@@ -213,6 +223,12 @@ def errclass_names():
     """the names of the seven error classes (vpr_errclass_names), in the order of their codes A.EC_*"""
     names = lib().vpr_errclass_names()
     return [names[k].decode() for k in range(A.EC_CLASSES)]
+
+
+def matchkind_names():
+    """the names of the four match kinds (vpr_matchkind_names), in the order of their codes A.MK_*"""
+    names = lib().vpr_matchkind_names()
+    return [names[k].decode() for k in range(A.MK_KINDS)]
 
 
 def context_info():
@@ -527,6 +543,39 @@ class PrecisionRecall:
         """ms of the last errclass' kernel launches, from HIP events on the handle's stream"""
         a = C.c_double()
         self._chk(lib().vpr_errclass_timing(self._h, C.byref(a)), "vpr_errclass_timing")
+        return a.value
+
+    def matchkind(self, variants, var_class_per_slot, pb_phase=None, min_qual=0, max_qual=60, comm=None):
+        """The match kinds of the last execute (include/vcfdist_matchkind.h): every TP of either callset gets the first kind that
+        applies (A.MK_*), joined across the callsets inside its supercluster on the device -> int64 [2][4][4][nq].
+        variants: the A.Variants (or a VprVariants struct) the batch was made from; var_class_per_slot None: the classes are
+        resident; comm: an ncclComm_t (as an integer) for vpr_allreduce_matchkind."""
+        vs = variants.as_struct() if isinstance(variants, A.Variants) else variants
+        nq = max_qual - min_qual + 1
+        out = np.zeros((2, 4, A.MK_KINDS, max(nq, 1)), np.int64)      # (min_qual > max_qual: the call refuses)
+        pb = None if pb_phase is None else np.ascontiguousarray(pb_phase, dtype=np.int32)
+        arr = None
+        if var_class_per_slot is not None:
+            cls = [np.ascontiguousarray(c, dtype=np.uint8) for c in var_class_per_slot]
+            arr = (A.P_u8 * 4)(*[A._ptr(c, C.c_uint8) for c in cls])
+        args = (C.byref(vs), arr, None if pb is None else A._ptr(pb, C.c_int32), min_qual, max_qual, A._ptr(out, C.c_int64))
+        L = lib()
+        rc = L.vpr_matchkind(self._h, *args) if comm is None else L.vpr_allreduce_matchkind(self._h, comm if isinstance(comm, C.c_void_p) else C.c_void_p(comm), *args)
+        self._chk(rc, "vpr_matchkind")
+        return out
+
+    def matchkind_download(self):
+        """the kind bytes (A.MK_*, A.MK_NONE) of the last matchkind: one uint8 array per hap slot"""
+        out = [np.zeros(self._batch.n_vars(h) if self._batch is not None else 0, np.uint8) for h in range(A.HAPS)]
+        keep = [o if o.size else np.zeros(1, np.uint8) for o in out]
+        arr = (A.P_u8 * A.HAPS)(*[A._ptr(k, C.c_uint8) for k in keep])
+        self._chk(lib().vpr_matchkind_download(self._h, arr), "vpr_matchkind_download")
+        return out
+
+    def matchkind_timing(self):
+        """ms of the last matchkind's kernel launches, from HIP events on the handle's stream"""
+        a = C.c_double()
+        self._chk(lib().vpr_matchkind_timing(self._h, C.byref(a)), "vpr_matchkind_timing")
         return a.value
 
     def pr_counts_boot(self, var_class_per_slot, pb_phase, sc_key, n_rep, seed=1, min_qual=0, max_qual=60, stratum=-1, comm=None):

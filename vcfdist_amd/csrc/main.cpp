@@ -13,6 +13,7 @@
 //               [--stratify-variants]
 //               [--bootstrap N] [--bootstrap-seed S]
 //               [--classify-errors] [--error-window N]
+//               [--classify-matches]
 // With -d the distance metrics (edits_wrapper, dist.cpp:1908-2077) run on the GPU after each contig's precision/recall path
 // (include/vcfdist_distance.h), as the reference's main.cpp:223-238 runs them after precision_recall_threads_wrapper.
 // With -rq / -rt a callset is clustered and realigned on the GPU (include/vcfdist_realign.h) before the evaluation, in the order of
@@ -27,6 +28,9 @@
 // With --classify-errors every query FP and truth FN gets the first error class that applies (include/vcfdist_errclass.h: right
 // allele with the wrong genotype, on the aligned or on the other haplotype, another allele at the site, something within
 // --error-window N bases (default 50), nothing), joined across the callsets on the GPU: error-classes.tsv, error-classes-summary.tsv.
+// With --classify-matches every TP of either callset gets the first match kind that applies (include/vcfdist_matchkind.h: exact --
+// what an allele-for-allele comparison finds --, shifted, regrouped, partial), from the resident sync groups on the GPU:
+// match-kinds.tsv, match-kinds-summary.tsv.
 // With --bootstrap N the counters are resampled N times on the GPU (include/vcfdist_bootstrap.h: a Poisson bootstrap over
 // superclusters, conditional on the phasing): bootstrap-precision-recall-summary.tsv with 95 % percentile intervals,
 // bootstrap-replicates.tsv, and with --stratify stratified-bootstrap-precision-recall-summary.tsv.
@@ -54,6 +58,7 @@
 #include "../../include/vcfdist_strata.h"
 #include "../../include/vcfdist_varstrata.h"
 #include "../../include/vcfdist_errclass.h"
+#include "../../include/vcfdist_matchkind.h"
 
 namespace {
 
@@ -70,6 +75,7 @@ struct Args {
     int bootstrap = 0;                 // --bootstrap: replicates (0: none)
     bool classify_errors = false;      // --classify-errors
     int error_window = -1;             // --error-window: -1 not given (VPR_EC_DEFAULT_WINDOW)
+    bool classify_matches = false;     // --classify-matches
     uint64_t bootstrap_seed = 1;
 };
 
@@ -152,6 +158,7 @@ Args parse(int argc, char **argv) {
         else if (o == "--bootstrap-seed") a.bootstrap_seed = bootstrap_seed(need(i));
         else if (o == "--classify-errors") a.classify_errors = true;
         else if (o == "--error-window") a.error_window = error_window(need(i));
+        else if (o == "--classify-matches") a.classify_matches = true;
         else if (o == "-rq" || o == "--realign-query") a.realign_query = true;
         else if (o == "-rt" || o == "--realign-truth") a.realign_truth = true;
         else if (o == "-ro" || o == "--realign-only") a.realign_only = true;
@@ -490,6 +497,9 @@ int main(int argc, char **argv) {
     // --classify-errors: counts[2][4][VPR_EC_CLASSES][nq] summed over the contigs; device ms of the launches
     std::vector<int64_t> ec_total(A.classify_errors ? total.size() / 3 * VPR_EC_CLASSES : 0, 0);
     double ec_ms = 0;
+    // --classify-matches: counts[2][4][VPR_MK_KINDS][nq] summed over the contigs; device ms of the launches
+    std::vector<int64_t> mk_total(A.classify_matches ? total.size() / 3 * VPR_MK_KINDS : 0, 0);
+    double mk_ms = 0;
     // --bootstrap: counts[n_rep][2][4][3][nq], with --stratify also [n_strata][n_rep][2][4][3][nq]; device ms of the launches
     std::vector<int64_t> boot_total(total.size() * size_t(A.bootstrap), 0), boot_strat(boot_total.size() * size_t(n_strata), 0);
     double boot_ms = 0;
@@ -608,6 +618,14 @@ int main(int argc, char **argv) {
                     die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
                 for (size_t k = 0; k < ec.size(); k++) ec_total[k] += ec[k];
                 ec_ms += ms;
+            }
+            if (A.classify_matches) {     // the same evaluation, its TP cut by how they were matched (the classes are resident)
+                std::vector<int64_t> mk(mk_total.size(), 0);
+                double ms = 0;
+                if (vpr_matchkind(h, &V, nullptr, C->pb.data(), A.min_qual, A.max_qual, mk.data()) || vpr_matchkind_timing(h, &ms))
+                    die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+                for (size_t k = 0; k < mk.size(); k++) mk_total[k] += mk[k];
+                mk_ms += ms;
             }
             if (n_strata) {        // the same evaluation, cut by region: membership words, then the histogram per stratum
                 std::vector<int64_t> iv_off(size_t(n_bed) + 1, 0);
@@ -752,6 +770,8 @@ int main(int argc, char **argv) {
         }
         if (A.classify_errors && vrp_write_error_classes(A.prefix.c_str(), ec_total.data(), total.data(), A.min_qual, A.max_qual))
             die("ERROR: %s", vrp_last_error());
+        if (A.classify_matches && vrp_write_match_kinds(A.prefix.c_str(), mk_total.data(), total.data(), A.min_qual, A.max_qual))
+            die("ERROR: %s", vrp_last_error());
         if (A.bootstrap && vrp_write_bootstrap(A.prefix.c_str(), total.data(), boot_total.data(), A.bootstrap, A.bootstrap_seed, A.min_qual, A.max_qual))
             die("ERROR: %s", vrp_last_error());
         std::vector<vrp_contig> ctgs(outs.size());
@@ -807,6 +827,14 @@ int main(int argc, char **argv) {
         }
         fprintf(stderr, "[vcfdist_amd] error classes: window %d, %lld query FP and %lld truth FN classified, %.3f ms on the device\n", A.error_window,
                 n_fp, n_fn, ec_ms);
+    }
+    if (A.classify_matches) {     // the matched variants at threshold NONE: the ALL rows' kinds of both callsets
+        const size_t nq = size_t(A.max_qual - A.min_qual + 1);
+        long long n[2][VPR_MK_KINDS];
+        for (int cs = 0; cs < 2; cs++)
+            for (int c = 0; c < VPR_MK_KINDS; c++) n[cs][c] = mk_total[((size_t(cs) * VPR_VARTYPES + VPR_VARTYPE_ALL) * VPR_MK_KINDS + size_t(c)) * nq];
+        fprintf(stderr, "[vcfdist_amd] match kinds: query TP %lld exact, %lld shifted, %lld regrouped, %lld partial; truth TP %lld exact, %lld shifted, "
+                "%lld regrouped, %lld partial, %.3f ms on the device\n", n[0][0], n[0][1], n[0][2], n[0][3], n[1][0], n[1][1], n[1][2], n[1][3], mk_ms);
     }
     if (A.bootstrap)
         fprintf(stderr, "[vcfdist_amd] bootstrap: %d replicates, seed %llu, %.3f ms on the device\n", A.bootstrap, (unsigned long long)A.bootstrap_seed, boot_ms);

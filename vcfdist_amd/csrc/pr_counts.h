@@ -1,5 +1,5 @@
 // pr_counts.h -- what the three counter kernels (k_pr_hist, pr_collect.hip; k_pr_hist_strata, pr_strata.hip; k_pr_boot, pr_boot.hip)
-// and k_errclass (pr_errclass.hip) decide alike: the supercluster of a variant and the bin the variant counts in (print.cpp:328-438).
+// and the two join kernels (k_errclass, pr_errclass.hip; k_matchkind, pr_matchkind.hip) decide alike: the supercluster of a variant and the bin the variant counts in (print.cpp:328-438).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,7 +15,7 @@ __device__ __forceinline__ int sc_of_var(const int64_t *__restrict__ var_off, in
 }
 
 // The phasing supercluster sc selects, as pr_count_row settles it: 0 the original, 1 the swapped one (for a kernel that needs the
-// choice itself, k_errclass; the counter kernels get it inside pr_count_row)
+// choice itself, k_errclass and k_matchkind; the counter kernels get it inside pr_count_row)
 __device__ __forceinline__ int pr_phase_swap(int sc, const int32_t *__restrict__ sc_phase, const int32_t *__restrict__ pb_phase) {
     const int ph = sc_phase[sc];
     return ph == VPR_PHASE_ORIG ? 0 : (ph == VPR_PHASE_SWAP ? 1 : (pb_phase ? (pb_phase[sc] != 0) : 0));

@@ -6,6 +6,7 @@
 #include "pr_host.h"
 #include "pr_counts.h"
 #include "pr_varscan.h"
+#include "pr_vartab.h"
 #include "../../include/vcfdist_errclass.h"
 
 struct ErrclassState {
@@ -101,40 +102,6 @@ __global__ void __launch_bounds__(256) k_errclass(VsCols own, VsCols par, VsCols
 
 namespace {
 
-// the variant tables the kernel reads against the resident batch: the preconditions of include/vcfdist_errclass.h, and per slot
-// the bytes of allele_pool the variants' ALT alleles name (the pool's extent is not part of vpr_variants)
-int check_variants(vpr_handle *h, const vpr_variants *v, size_t pool_len[VPR_HAPS]) {
-    if (v->n_sc != h->n_sc)
-        return fail(h, VPR_ERR_STATE, "vpr_errclass: the variant tables hold %d superclusters, the resident batch %d", v->n_sc, h->n_sc);
-    const int64_t n_sc = v->n_sc;
-    for (int i = 0; i < VPR_HAPS; i++) {
-        pool_len[i] = 0;
-        const int64_t *off = v->var_off[i];
-        if (!off) return fail(h, VPR_ERR_ARG, "vpr_errclass: null var_off");
-        if (off[0] != 0) return fail(h, VPR_ERR_ARG, "vpr_errclass: hap slot %d: var_off[0] is not 0", i);
-        for (int64_t k = 0; k < n_sc; k++)
-            if (off[k + 1] < off[k]) return fail(h, VPR_ERR_ARG, "vpr_errclass: hap slot %d: var_off decreases at supercluster %lld", i, (long long)k);
-        if (off[n_sc] != h->n_var[i])
-            return fail(h, VPR_ERR_STATE, "vpr_errclass: hap slot %d: the variant tables hold %lld variants, the resident batch %lld", i,
-                        (long long)off[n_sc], (long long)h->n_var[i]);
-        if (!off[n_sc]) continue;
-        if (!v->var_pos[i] || !v->var_type[i] || !v->var_ref_len[i] || !v->var_alt_off[i] || !v->var_alt_len[i] || !v->allele_pool[i])
-            return fail(h, VPR_ERR_ARG, "vpr_errclass: hap slot %d: null variant column", i);
-        for (int64_t k = 0; k < n_sc; k++)
-            for (int64_t j = off[k]; j < off[k + 1]; j++) {
-                if (j > off[k] && v->var_pos[i][j] < v->var_pos[i][j - 1])
-                    return fail(h, VPR_ERR_ARG, "vpr_errclass: hap slot %d: var_pos is unsorted inside supercluster %lld: variant %lld at %d follows one at %d",
-                                i, (long long)k, (long long)j, v->var_pos[i][j], v->var_pos[i][j - 1]);
-                const int64_t ao = v->var_alt_off[i][j];
-                const int32_t rl = v->var_ref_len[i][j], al = v->var_alt_len[i][j];
-                if (ao < 0 || rl < 0 || al < 0)
-                    return fail(h, VPR_ERR_ARG, "vpr_errclass: hap slot %d: variant %lld has a negative allele offset or length", i, (long long)j);
-                pool_len[i] = std::max(pool_len[i], size_t(ao) + size_t(al));
-            }
-    }
-    return VPR_OK;
-}
-
 // histogram [2][3 types][VPR_EC_CLASSES][nq + 1] -> counts [2][VPR_VARTYPES][VPR_EC_CLASSES][nq]: pr_fold_counts' rule cut by class.
 // A query FP counts at the threshold indices <= its bin; a truth FN at every threshold; a LOWQ truth variant at the thresholds
 // above its bin (bin nq, callq < min_qual: at every one)
@@ -167,7 +134,7 @@ int errclass_impl(vpr_handle *h, void *comm, const vpr_variants *v, const uint8_
     if (max_qual < min_qual) return fail(h, VPR_ERR_ARG, "vpr_errclass: max_qual %d is below min_qual %d", max_qual, min_qual);
     if (int rc = pr_counts_begin(h, "vpr_errclass", comm)) return rc;
     size_t pool_len[VPR_HAPS];
-    if (int rc = check_variants(h, v, pool_len)) return rc;
+    if (int rc = vartab_check(h, "vpr_errclass", v, pool_len)) return rc;
     if (!h->errclass) h->errclass = new ErrclassState();
     ErrclassState *S = h->errclass;
     S->valid = false; S->ms = 0;
@@ -179,41 +146,9 @@ int errclass_impl(vpr_handle *h, void *comm, const vpr_variants *v, const uint8_
         if (int rc = S->cls[i].reserve(h, size_t(h->n_var[i]), "vpr_errclass: class bytes: cannot allocate %zu bytes on the device")) return rc;
     if (int rc = S->hist.reserve(h, nh, "vpr_errclass: class histogram: cannot allocate %zu bytes on the device")) return rc;
     // ---- the columns and the pools: one block that lives as long as the call
-    struct Piece { const void *src; size_t bytes; size_t at; };
-    std::vector<Piece> pieces;
-    size_t total = 0;
-    auto add = [&](const void *src, size_t bytes) { pieces.push_back({src, bytes, total}); total += (bytes + 255) & ~size_t(255); return pieces.size() - 1; };
-    size_t i_var[VPR_HAPS][7];
-    for (int i = 0; i < VPR_HAPS; i++) {
-        const size_t n = size_t(h->n_var[i]);
-        i_var[i][0] = add(v->var_off[i], 8 * (size_t(n_sc) + 1));
-        i_var[i][1] = add(v->var_alt_off[i], 8 * n);
-        i_var[i][2] = add(v->var_pos[i], 4 * n);
-        i_var[i][3] = add(v->var_ref_len[i], 4 * n);
-        i_var[i][4] = add(v->var_alt_len[i], 4 * n);
-        i_var[i][5] = add(v->var_type[i], n);
-        i_var[i][6] = add(v->allele_pool[i], n ? pool_len[i] : 0);
-    }
-    uint8_t *blk = nullptr;
-    if (x_malloc(h, reinterpret_cast<void **>(&blk), std::max<size_t>(total, 256), SITE) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(h, VPR_ERR_NOMEM, "vpr_errclass: cannot allocate %zu bytes on the device", total);
-    }
-    struct Release {
-        vpr_handle *h; uint8_t *p;
-        ~Release() {
-            (void)hipStreamSynchronize(h->stream);
-            (void)x_free(h, p, SITE);
-        }
-    } R{h, blk};
-    for (const Piece &p : pieces)
-        if (p.bytes && p.src) HIPCHK(h, hipMemcpyAsync(blk + p.at, p.src, p.bytes, hipMemcpyHostToDevice, h->stream));
-    auto at = [&](size_t i) { return blk + pieces[i].at; };
-    VsCols cols[VPR_HAPS];
-    for (int i = 0; i < VPR_HAPS; i++)
-        cols[i] = VsCols{reinterpret_cast<const int64_t *>(at(i_var[i][0])), nullptr, reinterpret_cast<const int64_t *>(at(i_var[i][1])),
-                         reinterpret_cast<const int32_t *>(at(i_var[i][2])), reinterpret_cast<const int32_t *>(at(i_var[i][3])),
-                         reinterpret_cast<const int32_t *>(at(i_var[i][4])), at(i_var[i][5]), at(i_var[i][6])};
+    VarTables T;
+    if (int rc = vartab_upload(h, "vpr_errclass", v, pool_len, &T)) return rc;
+    const VsCols *cols = T.cols;
     HIPCHK(h, hipMemsetAsync(S->hist.p, 0, nh * 8, h->stream));
     int32_t *d_pb = nullptr;
     if (int rc = pr_counts_inputs(h, "vpr_errclass", var_class, pb_phase, &d_pb)) return rc;

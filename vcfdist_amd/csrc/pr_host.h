@@ -9,6 +9,9 @@
 //   pr_context.hip  the sequence-context strata (include/vcfdist_context.h): interval lists built from the contig sequences
 //   pr_varstrata.hip the variant strata (include/vcfdist_varstrata.h): bits made from the variant tables themselves
 //   pr_boot.hip     the bootstrap replicates of the counters (include/vcfdist_bootstrap.h): the replicate histogram
+//   pr_errclass.hip the error classes (include/vcfdist_errclass.h): why each FP and FN is wrong
+//   pr_matchkind.hip the match kinds (include/vcfdist_matchkind.h): how each TP was matched
+//   pr_vartab.hip   the host check and the one-block upload of the variant tables those two share (pr_vartab.h)
 #ifndef PR_HOST_H_
 #define PR_HOST_H_
 #include <hip/hip_runtime.h>
@@ -269,6 +272,7 @@ struct DistState;                        // the distance step's tables and arena
 struct StrataState;                      // the membership words and the stratified histogram (pr_strata.hip)
 struct ContextState;                     // the sequence-context intervals (pr_context.hip)
 struct ErrclassState;                    // the class bytes and the class histogram (pr_errclass.hip)
+struct MatchkindState;                   // the kind bytes and the kind histogram (pr_matchkind.hip)
 struct BootState;                        // the replicate histogram and the supercluster keys (pr_boot.hip)
 
 struct vpr_handle {
@@ -421,6 +425,7 @@ struct vpr_handle {
     ContextState *context = nullptr;     // vpr_context_masks (pr_context.hip), released by the next one or vpr_destroy
     BootState *boot = nullptr;           // vpr_pr_counts_boot (pr_boot.hip), created by its first call, released with the batch
     ErrclassState *errclass = nullptr;   // vpr_errclass (pr_errclass.hip), created by its first call, released with the batch
+    MatchkindState *matchkind = nullptr; // vpr_matchkind (pr_matchkind.hip), created by its first call, released with the batch
     double varstrata_ms = 0;             // device time of the last vpr_varstrata_masks' kernel launches (pr_varstrata.hip)
     vpr_timing timing;
     bool uploaded = false, executed = false;
@@ -475,6 +480,7 @@ int strata_extend(vpr_handle *h, const char *entry, int32_t n_add, const int64_t
 void strata_commit(vpr_handle *h);
 void context_free(vpr_handle *h);                                    // pr_context.hip: the resident context intervals
 void errclass_free(vpr_handle *h);                                   // pr_errclass.hip: the class bytes and the class histogram
+void matchkind_free(vpr_handle *h);                                  // pr_matchkind.hip: the kind bytes and the kind histogram
 void boot_free(vpr_handle *h);                                       // pr_boot.hip: the replicate histogram and the keys
 // pr_collect.hip, shared by the three counters entries (vpr_pr_counts, _strata, _boot; `entry`: the entry's name, for the
 // messages).  pr_counts_begin: the state checks and the device, before the entry's own buffers; pr_counts_inputs: the caller's

@@ -1,0 +1,208 @@
+// pr_matchkind.hip -- the match kinds (include/vcfdist_matchkind.h): how each true positive was matched.  k_matchkind is the
+// counterpart of k_errclass (pr_errclass.hip) on the TP side: one lane per hap-variant, the same join of the two callsets inside
+// the supercluster (pr_varscan.h), here on the resident sync groups and query_ed; a kind byte per hap-variant and a block
+// histogram flushed as k_pr_hist's (pr_collect.hip).  The bin rule is pr_counts.h's; the host check and the upload of the variant
+// tables are pr_vartab.h's; the front and back of a counters call are the ones of pr_collect.hip.
+#include "pr_host.h"
+#include "pr_counts.h"
+#include "pr_varscan.h"
+#include "pr_vartab.h"
+#include "../../include/vcfdist_matchkind.h"
+
+struct MatchkindState {
+    DevBuf<uint8_t> kind[VPR_HAPS];                              // the kind bytes of the last call
+    DevBuf<unsigned long long> hist;                             // [2][3 types][VPR_MK_KINDS][nq + 1]
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double ms = 0;
+    bool valid = false;
+};
+
+namespace {
+
+const char *const MK_NAMES[VPR_MK_KINDS] = {"exact", "shifted", "regrouped", "partial"};
+// thresholds of one call: the block histogram, 3 * VPR_MK_KINDS * (nq + 1) words of dynamic LDS, stays within 64 KiB
+const int MK_MAX_NQ = 64 * 1024 / 4 / (3 * VPR_MK_KINDS) - 1;
+
+// members of sync group g among the variants [lo, hi) of a slot, up to 2 ("0, 1, more than 1" decides every kind): e / grp are
+// the slot's errtype and sync_group columns of the selected phasing.  The members are not contiguous (a REF-plane FP with a group
+// of its own can sit between two of them), so this is a scan of the range that stops at the second one
+__device__ __forceinline__ int mk_members(const uint8_t *__restrict__ e, const int32_t *__restrict__ grp, int64_t lo, int64_t hi, int32_t g) {
+    int n = 0;
+    for (int64_t u = lo; u < hi && n < 2; u++) n += e[u] < 3 && grp[u] == g;
+    return n;
+}
+
+}  // namespace
+
+extern "C" {
+
+// One lane per hap-variant of slot `own`.  oa / ob: the slots of the other callset with the same / the other haplotype index, so
+// that the compared slot is oa under ORIG and ob under SWAP.  e0 / e1 / q0 / q1: the lane's errtype and callq columns of the two
+// phasings (four pointers, as pr_count_row takes them); g0 / g1 / d0 / d1: its sync_group and query_ed columns; ae0 / ag0: oa's
+// errtype and sync_group in the original phasing, be1 / bg1: ob's in the swapped one (the only phasing each is compared in).
+// A variant that is no TP leaves after the loads k_pr_hist makes; a TP bisects the compared slot's range for its position and
+// tests the run for a copy of its group, and only where there is none and query_ed is 0 counts the members of both ranges.
+// Kinds are counted in LDS ([3 types][VPR_MK_KINDS][nq + 1] words) and flushed once.
+__global__ void __launch_bounds__(256) k_matchkind(VsCols own, VsCols oa, VsCols ob, int64_t n_var, int n_sc, const uint8_t *__restrict__ cls,
+                                                   const int32_t *__restrict__ sc_phase, const int32_t *__restrict__ pb_phase, const uint8_t *e0,
+                                                   const uint8_t *e1, const float *q0, const float *q1, const int32_t *g0, const int32_t *g1,
+                                                   const int32_t *d0, const int32_t *d1, const uint8_t *ae0, const int32_t *ag0, const uint8_t *be1,
+                                                   const int32_t *bg1, int callset, int min_qual, int max_qual, uint8_t *__restrict__ out,
+                                                   unsigned long long *__restrict__ hist /* [2][3][VPR_MK_KINDS][nq + 1] */) {
+    extern __shared__ unsigned int blk[];      // [3][VPR_MK_KINDS][nq + 1]
+    const int nq = max_qual - min_qual + 1, nb = 3 * VPR_MK_KINDS * (nq + 1);
+    for (int k = threadIdx.x; k < nb; k += blockDim.x) blk[k] = 0;
+    __syncthreads();
+    const int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (v < n_var) {
+        const int sc = sc_of_var(own.var_off, n_sc, v);
+        int bin = 0, c = VPR_MK_NONE, t = 0;
+        const int row = pr_count_row(sc, v, sc_phase, pb_phase, e0, e1, q0, q1, cls, min_qual, nq, &bin);
+        if (row >= 0 && row % 3 == VPR_ERRTYPE_TP) {
+            t = row / 3;
+            const int w = pr_phase_swap(sc, sc_phase, pb_phase);
+            const int32_t g = (w ? g1 : g0)[v];
+            const int32_t pos = own.pos[v], ref_len = own.ref_len[v], alt_len = own.alt_len[v];
+            const uint8_t type = own.type[v];
+            const uint8_t *__restrict__ alt = own.pool + own.alt_off[v];
+            // the compared slot: its columns and its errtype / sync_group in the selected phasing
+            VsCols cmp;
+            cmp.var_off = w ? ob.var_off : oa.var_off; cmp.ref_off = nullptr; cmp.alt_off = w ? ob.alt_off : oa.alt_off;
+            cmp.pos = w ? ob.pos : oa.pos; cmp.ref_len = w ? ob.ref_len : oa.ref_len; cmp.alt_len = w ? ob.alt_len : oa.alt_len;
+            cmp.type = w ? ob.type : oa.type; cmp.pool = w ? ob.pool : oa.pool;
+            const uint8_t *ce = w ? be1 : ae0;
+            const int32_t *cg = w ? bg1 : ag0;
+            const int64_t c0 = cmp.var_off[sc], c1 = cmp.var_off[sc + 1];
+            bool exact = false;
+            for (int64_t u = vs_lower(cmp.pos, c0, c1, pos); !exact && u < c1 && cmp.pos[u] == pos; u++)
+                exact = ce[u] < 3 && cg[u] == g && vs_is_copy(cmp, u, type, ref_len, alt_len, alt);
+            if (exact) {
+                c = VPR_MK_EXACT;
+            } else if ((w ? d1 : d0)[v] > 0) {
+                c = VPR_MK_PARTIAL;
+            } else {
+                c = VPR_MK_REGROUPED;
+                if (mk_members(w ? e1 : e0, w ? g1 : g0, own.var_off[sc], own.var_off[sc + 1], g) == 1 && mk_members(ce, cg, c0, c1, g) == 1)
+                    c = VPR_MK_SHIFTED;
+            }
+        }
+        out[v] = uint8_t(c);
+        if (c != VPR_MK_NONE) atomicAdd(&blk[(t * VPR_MK_KINDS + c) * (nq + 1) + bin], 1u);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < nb; k += blockDim.x)
+        if (blk[k]) atomicAdd(&hist[size_t(callset) * nb + k], (unsigned long long)blk[k]);
+}
+
+}  // extern "C"
+
+namespace {
+
+// histogram [2][3 types][VPR_MK_KINDS][nq + 1] -> counts [2][VPR_VARTYPES][VPR_MK_KINDS][nq]: pr_fold_counts' TP rule cut by kind.
+// A matched variant of either callset counts at the threshold indices <= its bin (bin nq, callq < min_qual: at none)
+void fold_kinds(const unsigned long long *hist, int nq, int64_t *counts) {
+    std::fill(counts, counts + size_t(2) * VPR_VARTYPES * VPR_MK_KINDS * size_t(nq), 0);
+    auto C = [&](int cs, int t, int c, int k) -> int64_t & { return counts[((size_t(cs) * VPR_VARTYPES + t) * VPR_MK_KINDS + c) * nq + k]; };
+    for (int cs = 0; cs < 2; cs++)
+        for (int t = 0; t < 3; t++)
+            for (int c = 0; c < VPR_MK_KINDS; c++) {
+                const unsigned long long *b = hist + ((size_t(cs) * 3 + t) * VPR_MK_KINDS + c) * (nq + 1);
+                int64_t acc = 0;
+                for (int k = nq - 1; k >= 0; k--) { acc += int64_t(b[k]); C(cs, t, c, k) = acc; }
+                for (int k = 0; k < nq; k++) C(cs, VPR_VARTYPE_ALL, c, k) += C(cs, t, c, k);
+            }
+}
+
+int matchkind_impl(vpr_handle *h, void *comm, const vpr_variants *v, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase,
+                   int32_t min_qual, int32_t max_qual, int64_t *counts) {
+    if (!h) return VPR_ERR_ARG;
+    if (!v || !counts) return fail(h, VPR_ERR_ARG, "vpr_matchkind: null argument");
+    if (max_qual < min_qual) return fail(h, VPR_ERR_ARG, "vpr_matchkind: max_qual %d is below min_qual %d", max_qual, min_qual);
+    if (int64_t(max_qual) - min_qual >= MK_MAX_NQ)
+        return fail(h, VPR_ERR_ARG, "vpr_matchkind: the quality range %d..%d holds more than %d thresholds (the block histogram is in LDS)", min_qual, max_qual,
+                    MK_MAX_NQ);
+    if (int rc = pr_counts_begin(h, "vpr_matchkind", comm)) return rc;
+    size_t pool_len[VPR_HAPS];
+    if (int rc = vartab_check(h, "vpr_matchkind", v, pool_len)) return rc;
+    if (!h->matchkind) h->matchkind = new MatchkindState();
+    MatchkindState *S = h->matchkind;
+    S->valid = false; S->ms = 0;
+    for (int k = 0; k < 2; k++) if (!S->ev[k]) HIPCHK(h, hipEventCreate(&S->ev[k]));
+    const int nq = max_qual - min_qual + 1;
+    const size_t nb = size_t(3) * VPR_MK_KINDS * size_t(nq + 1), nh = 2 * nb;
+    for (int i = 0; i < VPR_HAPS; i++)
+        if (int rc = S->kind[i].reserve(h, size_t(h->n_var[i]), "vpr_matchkind: kind bytes: cannot allocate %zu bytes on the device")) return rc;
+    if (int rc = S->hist.reserve(h, nh, "vpr_matchkind: kind histogram: cannot allocate %zu bytes on the device")) return rc;
+    VarTables T;      // the columns and the pools: one block that lives as long as the call
+    if (int rc = vartab_upload(h, "vpr_matchkind", v, pool_len, &T)) return rc;
+    HIPCHK(h, hipMemsetAsync(S->hist.p, 0, nh * 8, h->stream));
+    int32_t *d_pb = nullptr;
+    if (int rc = pr_counts_inputs(h, "vpr_matchkind", var_class, pb_phase, &d_pb)) return rc;
+    HIPCHK(h, hipEventRecord(S->ev[0], h->stream));
+    for (int s = 0; s < VPR_HAPS; s++) {
+        const int64_t nv = h->n_var[s];
+        if (!nv) continue;
+        const int oa = (s ^ 2), ob = (s ^ 3);      // the other callset's slot of the same / of the other haplotype index
+        hipLaunchKernelGGL(k_matchkind, dim3(unsigned((nv + 255) / 256)), dim3(256), nb * 4, h->stream, T.cols[s], T.cols[oa], T.cols[ob], nv,
+                           int(v->n_sc), h->d_cls[s], h->dR.sc_phase, d_pb, h->dR.v[s][0].errtype, h->dR.v[s][1].errtype, h->dR.v[s][0].callq,
+                           h->dR.v[s][1].callq, h->dR.v[s][0].sync_group, h->dR.v[s][1].sync_group, h->dR.v[s][0].query_ed, h->dR.v[s][1].query_ed,
+                           h->dR.v[oa][0].errtype, h->dR.v[oa][0].sync_group, h->dR.v[ob][1].errtype, h->dR.v[ob][1].sync_group, s >> 1,
+                           int(min_qual), int(max_qual), S->kind[s].p, S->hist.p);
+        HIPCHK(h, hipGetLastError());
+    }
+    HIPCHK(h, hipEventRecord(S->ev[1], h->stream));
+    std::vector<unsigned long long> hist(nh);
+    if (int rc = pr_counts_finish(h, comm, S->hist.p, nh, hist.data())) return rc;
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, S->ev[0], S->ev[1]);
+    S->ms = ms; S->valid = true;
+    fold_kinds(hist.data(), nq, counts);
+    return VPR_OK;
+}
+
+}  // namespace
+
+void matchkind_free(vpr_handle *h) {
+    MatchkindState *S = h->matchkind;
+    if (!S) return;
+    dev_release(h, S->kind[0], S->kind[1], S->kind[2], S->kind[3], S->hist);
+    for (int k = 0; k < 2; k++) if (S->ev[k]) (void)hipEventDestroy(S->ev[k]);
+    delete S;
+    h->matchkind = nullptr;
+}
+
+extern "C" {
+
+int vpr_matchkind(vpr_handle *h, const vpr_variants *v, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase, int32_t min_qual,
+                  int32_t max_qual, int64_t *counts) {
+    return matchkind_impl(h, nullptr, v, var_class, pb_phase, min_qual, max_qual, counts);
+}
+
+int vpr_allreduce_matchkind(vpr_handle *h, void *nccl_comm, const vpr_variants *v, const uint8_t *const var_class[VPR_HAPS],
+                            const int32_t *pb_phase, int32_t min_qual, int32_t max_qual, int64_t *counts) {
+    if (!nccl_comm) return VPR_ERR_ARG;
+    return matchkind_impl(h, nccl_comm, v, var_class, pb_phase, min_qual, max_qual, counts);
+}
+
+int vpr_matchkind_download(vpr_handle *h, uint8_t *const kind[VPR_HAPS]) {
+    if (!h || !kind) return VPR_ERR_ARG;
+    if (!h->matchkind || !h->matchkind->valid) return fail(h, VPR_ERR_STATE, "vpr_matchkind_download: no kind bytes (before vpr_matchkind, or after the next upload)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    for (int s = 0; s < VPR_HAPS; s++) {
+        if (!h->n_var[s]) continue;
+        if (!kind[s]) return fail(h, VPR_ERR_ARG, "vpr_matchkind_download: hap slot %d: null array", s);
+        HIPCHK(h, hipMemcpyAsync(kind[s], h->matchkind->kind[s].p, size_t(h->n_var[s]), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, x_sync(h, h->stream, SITE));
+    return VPR_OK;
+}
+
+int vpr_matchkind_timing(const vpr_handle *h, double *ms) {
+    if (!h || !ms) return VPR_ERR_ARG;
+    *ms = h->matchkind ? h->matchkind->ms : 0;
+    return VPR_OK;
+}
+
+const char *const *vpr_matchkind_names(void) { return MK_NAMES; }
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // pr_varscan.h -- what the kernels that join hap-variants by position share (k_varstrata_mask, pr_varstrata.hip; k_errclass,
-// pr_errclass.hip): the columns of one hap slot, the two bisections over a range of sorted positions, and the test and the scan
+// pr_errclass.hip; k_matchkind, pr_matchkind.hip): the columns of one hap slot, the two bisections over a range of sorted positions, and the test and the scan
 // for copies of a variant in the run of equal position.
 #pragma once
 

@@ -17,6 +17,7 @@
 #include "../../include/vcfdist_bootstrap.h"
 #include "../../include/vcfdist_varstrata.h"
 #include "../../include/vcfdist_errclass.h"
+#include "../../include/vcfdist_matchkind.h"
 
 namespace {
 
@@ -262,6 +263,46 @@ extern "C" int vrp_write_error_classes(const char *prefix, const int64_t *class_
             for (int j = 0; j < n; j++) tot += c[size_t(j) * nq];
             fprintf(f, "%s%lld", cs ? "\t" : "", tot);
             for (int j = 0; j < n; j++) fprintf(f, "\t%lld", (long long)c[size_t(j) * nq]);
+        }
+        fputc('\n', f);
+    };
+    for (int type = 0; type < VPR_VARTYPES; type++)
+        for (int qual = min_qual; qual <= max_qual; qual++) {
+            fprintf(all, "%s\t%d\t", VARTYPE_STR[type], qual);
+            cells(all, type, qual - min_qual);
+        }
+    for (int type = 0; type < VPR_VARTYPES; type++) {
+        const int quals[2] = {min_qual, best_qual_of(pr_counts, type, min_qual, max_qual)};
+        const char *const thresh[2] = {"NONE", "BEST"};
+        for (int i = 0; i < 2; i++) {
+            fprintf(sum, "%s\t%s\t%d\t", VARTYPE_STR[type], thresh[i], quals[i]);
+            cells(sum, type, quals[i] - min_qual);
+        }
+    }
+    if (!all.finish() || !sum.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn_all + " / " + fn_sum);
+    return VRP_OK;
+}
+
+extern "C" int vrp_write_match_kinds(const char *prefix, const int64_t *kind_counts, const int64_t *pr_counts, int32_t min_qual,
+                                     int32_t max_qual) {
+    if (!prefix || !kind_counts || !pr_counts || max_qual < min_qual) return fail(VRP_ERR_ARG, "vrp_write_match_kinds: bad argument");
+    const int nq = max_qual - min_qual + 1;
+    const std::string fn_all = std::string(prefix) + "match-kinds.tsv", fn_sum = std::string(prefix) + "match-kinds-summary.tsv";
+    File all(fn_all.c_str());
+    if (!all) return fail(VRP_ERR_OPEN, "cannot create " + fn_all);
+    File sum(fn_sum.c_str());
+    if (!sum) return fail(VRP_ERR_OPEN, "cannot create " + fn_sum);
+    static const char *const COLS = "QUERY_TP\tQTP_EXACT\tQTP_SHIFTED\tQTP_REGROUPED\tQTP_PARTIAL\tTRUTH_TP\tTTP_EXACT\tTTP_SHIFTED\tTTP_REGROUPED\tTTP_PARTIAL\n";
+    fprintf(all, "VAR_TYPE\tMIN_QUAL\t%s", COLS);
+    fprintf(sum, "VAR_TYPE\tTHRESHOLD\tMIN_QUAL\t%s", COLS);
+    // the ten cells of one (type, threshold index): each callset's total, then its four kinds
+    auto cells = [&](FILE *f, int type, int k) {
+        for (int cs = 0; cs < 2; cs++) {
+            const int64_t *c = kind_counts + (size_t(cs) * VPR_VARTYPES + type) * VPR_MK_KINDS * size_t(nq) + k;
+            long long tot = 0;
+            for (int j = 0; j < VPR_MK_KINDS; j++) tot += c[size_t(j) * nq];
+            fprintf(f, "%s%lld", cs ? "\t" : "", tot);
+            for (int j = 0; j < VPR_MK_KINDS; j++) fprintf(f, "\t%lld", (long long)c[size_t(j) * nq]);
         }
         fputc('\n', f);
     };

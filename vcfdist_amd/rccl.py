@@ -161,6 +161,11 @@ def allreduce_errclass(pr, comm: Comm, variants, var_class_per_slot=None, pb_pha
     return pr.errclass(variants, var_class_per_slot, pb_phase, window, min_qual, max_qual, comm=comm._c)
 
 
+def allreduce_matchkind(pr, comm: Comm, variants, var_class_per_slot=None, pb_phase=None, min_qual=0, max_qual=60):
+    """PrecisionRecall.matchkind summed over the ranks of `comm`: one all-reduce of the kind histogram on the device"""
+    return pr.matchkind(variants, var_class_per_slot, pb_phase, min_qual, max_qual, comm=comm._c)
+
+
 def allgather_phase(pr, comm: Comm, idx_local, n_total: int):
     """(sc_phase, orig_phase_dist, swap_phase_dist) of all n_total superclusters on every rank; idx_local[k] = global index of
     this rank's k-th supercluster"""

@@ -190,6 +190,19 @@ def write_error_classes(prefix, class_counts, counts, min_qual, max_qual):
            "vrp_write_error_classes")
 
 
+def write_match_kinds(prefix, kind_counts, counts, min_qual, max_qual):
+    """match-kinds.tsv and match-kinds-summary.tsv (include/vcfdist_matchkind.h): kind_counts int64 [2][4][4][nq]
+    (PrecisionRecall.matchkind), counts int64 [2][4][3][nq] (summary.pr_counts) of the same evaluation, for the BEST threshold"""
+    nq = max_qual - min_qual + 1
+    kc, cnt = np.ascontiguousarray(kind_counts, np.int64), np.ascontiguousarray(counts, np.int64)
+    if kc.shape != (2, 4, A.MK_KINDS, nq) or cnt.shape != (2, 4, 3, nq):
+        raise ReportError(f"write_match_kinds: counts of shapes {kc.shape} and {cnt.shape} for {nq} thresholds")
+    L = api.lib()
+    L.vrp_write_match_kinds.argtypes = [C.c_char_p, A.P_i64, A.P_i64, C.c_int32, C.c_int32]
+    _check(L.vrp_write_match_kinds(prefix.encode(), A._ptr(kc, C.c_int64), A._ptr(cnt, C.c_int64), min_qual, max_qual),
+           "vrp_write_match_kinds")
+
+
 def write_bootstrap(prefix, counts, counts_boot, seed, min_qual, max_qual):
     """bootstrap-precision-recall-summary.tsv and bootstrap-replicates.tsv (include/vcfdist_bootstrap.h): counts int64
     [2][4][3][nq] (summary.pr_counts), counts_boot int64 [n_rep][2][4][3][nq] (summary.pr_counts_boot)"""

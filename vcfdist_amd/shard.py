@@ -155,7 +155,8 @@ def subset_per_variant(arr, var_off, idx):
 
 
 def subset_variants(v, idx):
-    """the variant tables of the superclusters `idx` of an A.Variants, in that order (a rank's share of a contig): the offsets and
+    """the variant tables of the superclusters `idx` of an A.Variants, in that order (a rank's share of a contig, from which
+    it classifies its errors and its matches: both are local to the supercluster): the offsets and
     the per-variant columns are cut, the contigs and the allele pools are shared with `v`"""
     from . import _abi as A
     idx = np.asarray(idx, np.int64)
