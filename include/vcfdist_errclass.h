@@ -66,8 +66,8 @@ extern "C" {
    var_type, var_ref_len, var_alt_len, var_alt_off and allele_pool.  var_class / pb_phase as for vpr_pr_counts (var_class may be
    NULL when the classes are resident).  Checked on the host before anything is launched (VPR_ERR_ARG with a message that names
    the place): var_off starts at 0 and is monotone; var_pos is non-decreasing within each supercluster's range (no order between
-   superclusters is required); allele offsets and lengths are non-negative; window >= 0; min_qual <= max_qual.  An exhausted device
-   is VPR_ERR_NOMEM.  The per-variant class bytes stay resident until the next upload or vpr_destroy. */
+   superclusters is required); allele offsets and lengths are non-negative; window >= 0; min_qual <= max_qual; a quality range of
+   at most 779 thresholds (the block histogram is in LDS).  An exhausted device is VPR_ERR_NOMEM.  The per-variant class bytes stay resident until the next upload or vpr_destroy. */
 int vpr_errclass(vpr_handle *h, const vpr_variants *v, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase,
                  int32_t window, int32_t min_qual, int32_t max_qual, int64_t *counts);
 /* The same with ONE all-reduce of the device histogram over the ranks of nccl_comm (an ncclComm_t), as vpr_allreduce_counts. */

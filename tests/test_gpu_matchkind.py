@@ -16,15 +16,12 @@ import torch  # noqa: F401 -- before the library opens the GPU: its HIP runtime 
 
 import matchkind_cases as MC
 import matchkind_model as MM
+from label_common import _without_command, _write_fasta, two_contig_run, var_classes
 from vcfdist_amd import _abi as A
 from vcfdist_amd import api, summary as S
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def var_classes(v, sv_threshold=50):
-    return [S.var_class(v.var_type[s], v.var_ref_len[s], v.var_alt_len[s], sv_threshold) for s in range(4)]
 
 
 def check(pr, v, res, cls, pb, min_qual=0, max_qual=60, first=False):
@@ -177,21 +174,6 @@ STDERR = (r"match kinds: query TP (\d+) exact, (\d+) shifted, (\d+) regrouped, (
           r"(\d+) partial, ([0-9.]+) ms on the device")
 
 
-def _without_command(path):
-    """a file's bytes without the lines that record the command line, the output prefix or the date"""
-    return b"\n".join(l for l in open(path, "rb").read().split(b"\n") if not l.startswith((b"##fileDate", b"##CL=", b"command = ", b"out_prefix = ")))
-
-
-def _write_fasta(path, seq, contigs):
-    s = bytes(seq).decode()
-    with open(path, "w") as fh:
-        for c in contigs:
-            fh.write(f">{c}\n")
-            for i in range(0, len(s), 100000):
-                fh.write(s[i:i + 100000] + "\n")
-    return str(path)
-
-
 @pytest.fixture(scope="module")
 def demo():
     """the demo callsets through the CPU oracle chain (tests/demo_pipeline.py) and the model's text of the two files"""
@@ -250,30 +232,8 @@ def test_command_lines_on_demo_files(demo, tmp_path):
 
 @pytest.fixture(scope="module")
 def two_contigs(tmp_path_factory):
-    """the demo callsets twice, as chr1 and chr2 (the inputs of tests/test_gpu_errclass.py's two-rank test), and the one-rank run
-    with --classify-matches"""
-    import gzip
-    import demo_pipeline as D
-    tmp = tmp_path_factory.mktemp("matchkind_two")
-    fa = _write_fasta(tmp / "two.fa", D.surrogate_fasta(5_100_000), ("chr1", "chr2"))
-
-    def twice(lines):
-        head = [l for l in lines if l.startswith("#")]
-        body = [l for l in lines if l and not l.startswith("#")]
-        head = [l for l in head if not l.startswith("##contig")] or head
-        ctg = ["##contig=<ID=chr1,length=5100000>", "##contig=<ID=chr2,length=5100000>"]
-        return "\n".join(head[:1] + ctg + head[1:] + body + ["chr2" + l[4:] for l in body if l.startswith("chr1\t")]) + "\n"
-    qv, tv, bed = tmp / "q.vcf", tmp / "t.vcf", tmp / "r.bed"
-    qv.write_text(twice(open(os.path.join(D.DEMO, "query.vcf")).read().split("\n")))
-    tv.write_text(twice(gzip.open(os.path.join(D.DEMO, "nist-v4.2.1_chr1_5Mb.vcf.gz"), "rt").read().split("\n")))
-    b = [l for l in open(os.path.join(D.DEMO, "nist-v4.2.1_chr1_5Mb.bed")).read().split("\n") if l]
-    bed.write_text("\n".join(b + ["chr2" + l[4:] for l in b]) + "\n")
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), VCFDIST_ONE_GPU="1")
-    base = [str(qv), str(tv), fa, "-b", str(bed), "--classify-matches"]
-    (tmp / "one").mkdir()
-    subprocess.run(["timeout", "-k", "10", "600", sys.executable, "-m", "vcfdist_amd"] + base + ["-p", str(tmp / "one") + "/"], check=True, env=env,
-                   cwd=ROOT, stdout=subprocess.DEVNULL, timeout=660)
-    return tmp, base, env
+    """the demo callsets twice, as chr1 and chr2, and the one-rank run with --classify-matches"""
+    return two_contig_run(tmp_path_factory.mktemp("matchkind_two"), ["--classify-matches"])
 
 
 @pytest.mark.parametrize("how", ["superclusters", "contigs"])

@@ -194,19 +194,15 @@ def bootstrap_contig(pr, boot, strat, args, pb, keys):
             boot["ms"] += pr.boot_info()[1]
 
 
-def classify_contig(pr, variants, ec, args, pb):
-    """--classify-errors: the error classes of the executed batch, added to ec['counts'] (the variant classes are resident: pr_counts)"""
-    ec["counts"] += pr.errclass(variants, None, pb, ec["window"], args.min_qual, args.max_qual)
-    ec["ms"] += pr.errclass_timing()
+def label_contig(pr, variants, passes, args, pb):
+    """--classify-errors / --classify-matches: the labels of the executed batch by each of `passes` (main's list), added to its
+    counts (the variant classes are resident: pr_counts)"""
+    for p in passes:
+        p["counts"] += getattr(pr, p["call"])(variants, None, pb, *p["extra"], args.min_qual, args.max_qual)
+        p["ms"] += getattr(pr, p["call"] + "_timing")()
 
 
-def match_kinds_contig(pr, variants, mk, args, pb):
-    """--classify-matches: the match kinds of the executed batch, added to mk['counts'] (the variant classes are resident: pr_counts)"""
-    mk["counts"] += pr.matchkind(variants, None, pb, args.min_qual, args.max_qual)
-    mk["ms"] += pr.matchkind_timing()
-
-
-def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None, boot=None, ordinal=0, ec=None, mk=None):
+def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None, boot=None, ordinal=0, passes=()):
     """the precision/recall path on the GPU, phasing and counters for a prepared contig.  -> int64 counters [2][4][3][nq],
     n_sc, and what the writers need: (clusters after splitting, superclusters, results, phase sets, pb_phase, switches, flips).
     part = (rank, world, collective device): this rank evaluates its share of the contig's SUPERCLUSTERS -- dealt by the
@@ -245,10 +241,7 @@ def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None,
         mask_unevaluated(res)
         pb, sw, fl = S.phase(res.sc_phase, phase_sets)
         counts = S.pr_counts(pr, cls, pb, args.min_qual, args.max_qual)
-        if ec is not None:
-            classify_contig(pr, prep["variants"], ec, args, pb)
-        if mk is not None:
-            match_kinds_contig(pr, prep["variants"], mk, args, pb)
+        label_contig(pr, prep["variants"], passes, args, pb)
         if strat is not None:
             stratify_contig(pr, prep, strat, args, pb)
         if boot is not None:
@@ -274,10 +267,8 @@ def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None,
         if len(idx):
             cls_mine = [shard.subset_per_variant(cls[s], whole.var_off[s], idx) for s in range(4)]
             counts = S.pr_counts(pr, cls_mine, pb[idx], args.min_qual, args.max_qual)
-            if ec is not None:      # (everything is local to the supercluster: the rank classifies its share from its share's tables)
-                classify_contig(pr, shard.subset_variants(prep["variants"], idx), ec, args, pb[idx])
-            if mk is not None:      # (the same: sync groups never leave the supercluster)
-                match_kinds_contig(pr, shard.subset_variants(prep["variants"], idx), mk, args, pb[idx])
+            if passes:      # (everything is local to the supercluster, sync groups too: the rank labels its share from its share's tables)
+                label_contig(pr, shard.subset_variants(prep["variants"], idx), passes, args, pb[idx])
             if strat is not None:
                 stratify_contig(pr, prep, strat, args, pb[idx], part_idx=idx)
             if boot is not None:
@@ -570,13 +561,23 @@ def main(argv=None):
     if args.bootstrap:
         boot = dict(n=args.bootstrap, seed=args.bootstrap_seed, ms=0.0, counts=np.zeros((args.bootstrap, 2, 4, 3, nq), np.int64),
                     strat=None if strat is None else np.zeros((len(strat["names"]), args.bootstrap, 2, 4, 3, nq), np.int64))
-    ec = None
+    # the label passes, in the order of their counts behind the all-reduced vector, of their files and of their stderr lines
+    passes = []
     if args.classify_errors:
-        ec = dict(window=A.EC_DEFAULT_WINDOW if args.error_window is None else args.error_window, ms=0.0,
-                  counts=np.zeros((2, 4, A.EC_CLASSES, nq), np.int64))
-    mk = None
+        window = A.EC_DEFAULT_WINDOW if args.error_window is None else args.error_window
+
+        def ec_line(p):
+            return (f"[vcfdist_amd] error classes: window {window}, {int(p['counts'][0, 3, :, 0].sum())} query FP and "
+                    f"{int(p['counts'][1, 3, :, 0].sum())} truth FN classified, {p['ms']:.3f} ms on the device")
+        passes.append(dict(call="errclass", extra=(window,), counts=np.zeros((2, 4, A.EC_CLASSES, nq), np.int64), ms=0.0,
+                           write=RP.write_error_classes, line=ec_line))
     if args.classify_matches:
-        mk = dict(ms=0.0, counts=np.zeros((2, 4, A.MK_KINDS, nq), np.int64))
+        def mk_line(p):
+            qk, tk = p["counts"][0, 3, :, 0], p["counts"][1, 3, :, 0]
+            return (f"[vcfdist_amd] match kinds: query TP {int(qk[0])} exact, {int(qk[1])} shifted, {int(qk[2])} regrouped, {int(qk[3])} partial; "
+                    f"truth TP {int(tk[0])} exact, {int(tk[1])} shifted, {int(tk[2])} regrouped, {int(tk[3])} partial, {p['ms']:.3f} ms on the device")
+        passes.append(dict(call="matchkind", extra=(), counts=np.zeros((2, 4, A.MK_KINDS, nq), np.int64), ms=0.0,
+                           write=RP.write_match_kinds, line=mk_line))
     empty = dict(pos=np.zeros(0, np.int32), rlen=np.zeros(0, np.int32), type=np.zeros(0, np.uint8), var_qual=np.zeros(0, np.float32),
                  phase_set=np.zeros(0, np.int32), ref_len=np.zeros(0, np.int32), alt_len=np.zeros(0, np.int32),
                  ref_off=np.zeros(0, np.int64), alt_off=np.zeros(0, np.int64), pool=np.zeros(1, np.uint8))
@@ -608,7 +609,7 @@ def main(argv=None):
         ctg = contigs[k]
         try:
             counts, n_sc, tables = evaluate_contig(prepared.pop(k), args, device=device, part=(rank, world, cdev) if by_sc else None,
-                                                   dist_sets=dist_sets, strat=strat, boot=boot, ordinal=k, ec=ec, mk=mk)
+                                                   dist_sets=dist_sets, strat=strat, boot=boot, ordinal=k, passes=passes)
         except api.VprError as e:     # the library's explicit refusals end the run like the reference's ERROR()
             raise SystemExit(f"ERROR: contig '{ctg}': {e}")
         total += counts
@@ -631,10 +632,7 @@ def main(argv=None):
         tail = [] if strat is None else [strat["counts"].ravel(), np.asarray([strat["vars"], strat["none"]], np.int64), strat["vs_members"].ravel()]
         if boot is not None:
             tail += [boot["counts"].ravel()] + ([] if strat is None else [boot["strat"].ravel()])
-        if ec is not None:
-            tail += [ec["counts"].ravel()]
-        if mk is not None:
-            tail += [mk["counts"].ravel()]
+        tail += [p["counts"].ravel() for p in passes]
         summed = shard.allreduce_tally(np.concatenate([total.ravel()] + tail), device=cdev)
         total = summed[:total.size].reshape(total.shape)
         at = total.size
@@ -651,11 +649,9 @@ def main(argv=None):
             if strat is not None:
                 boot["strat"] = summed[at:at + boot["strat"].size].reshape(boot["strat"].shape)
                 at += boot["strat"].size
-        if ec is not None:
-            ec["counts"] = summed[at:at + ec["counts"].size].reshape(ec["counts"].shape)
-            at += ec["counts"].size
-        if mk is not None:
-            mk["counts"] = summed[at:at + mk["counts"].size].reshape(mk["counts"].shape)
+        for p in passes:
+            p["counts"] = summed[at:at + p["counts"].size].reshape(p["counts"].shape)
+            at += p["counts"].size
         if not by_sc:       # (by superclusters every rank already holds every contig's gathered tables)
             gathered = [None] * world
             dist.all_gather_object(gathered, reports)
@@ -667,12 +663,9 @@ def main(argv=None):
             if strat is not None and strat["vs"]:
                 dist.all_gather_object(gathered, strat["vs_ms"])
                 strat["vs_ms"] = sum(gathered)
-            if ec is not None:
-                dist.all_gather_object(gathered, ec["ms"])
-                ec["ms"] = sum(gathered)
-            if mk is not None:
-                dist.all_gather_object(gathered, mk["ms"])
-                mk["ms"] = sum(gathered)
+            for p in passes:
+                dist.all_gather_object(gathered, p["ms"])
+                p["ms"] = sum(gathered)
     rows = S.pr_summary(total, args.min_qual, args.max_qual)
     if dist_sets is not None:       # write_distance (printed even with -n) and write_edits, edit.cpp:134-280
         text = RP.write_distance(args.prefix, dist_sets, args.min_qual, args.max_qual, args.eval_sub, args.eval_open, args.eval_extend,
@@ -690,10 +683,8 @@ def main(argv=None):
                     RP.write_context_bed(args.prefix, contigs, strat["ctx_names"], strat["intervals"])
                 if strat["vs"]:
                     RP.write_variant_strata(args.prefix, strat["vs_names"], strat["vs"], strat["vs_members"][0], strat["vs_members"][1])
-            if ec is not None:
-                RP.write_error_classes(args.prefix, ec["counts"], total, args.min_qual, args.max_qual)
-            if mk is not None:
-                RP.write_match_kinds(args.prefix, mk["counts"], total, args.min_qual, args.max_qual)
+            for p in passes:
+                p["write"](args.prefix, p["counts"], total, args.min_qual, args.max_qual)
             if boot is not None:
                 RP.write_bootstrap(args.prefix, total, boot["counts"], boot["seed"], args.min_qual, args.max_qual)
                 if strat is not None:
@@ -714,14 +705,8 @@ def main(argv=None):
                       "on the device", file=sys.stderr)
             if strat["vs"]:
                 print(f"[vcfdist_amd] variant strata: {len(strat['vs'])} strata, {strat['vs_ms']:.3f} ms on the device", file=sys.stderr)
-        if ec is not None:
-            print(f"[vcfdist_amd] error classes: window {ec['window']}, {int(ec['counts'][0, 3, :, 0].sum())} query FP and "
-                  f"{int(ec['counts'][1, 3, :, 0].sum())} truth FN classified, {ec['ms']:.3f} ms on the device", file=sys.stderr)
-        if mk is not None:
-            q, t = mk["counts"][0, 3, :, 0], mk["counts"][1, 3, :, 0]
-            print(f"[vcfdist_amd] match kinds: query TP {int(q[0])} exact, {int(q[1])} shifted, {int(q[2])} regrouped, {int(q[3])} partial; "
-                  f"truth TP {int(t[0])} exact, {int(t[1])} shifted, {int(t[2])} regrouped, {int(t[3])} partial, {mk['ms']:.3f} ms on the device",
-                  file=sys.stderr)
+        for p in passes:
+            print(p["line"](p), file=sys.stderr)
         if boot is not None:
             print(f"[vcfdist_amd] bootstrap: {boot['n']} replicates, seed {boot['seed']}, {boot['ms']:.3f} ms on the device", file=sys.stderr)
         print("PRECISION-RECALL SUMMARY\n")

@@ -98,20 +98,14 @@ def lib():
     L.vpr_varstrata_default.argtypes = [C.POINTER(C.POINTER(A.VprVariantStratum)), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.c_int32)]
     L.vpr_varstrata_masks.argtypes = [H, C.POINTER(A.VprVariants), C.POINTER(A.VprVariantStratum), C.c_int32, C.c_int32]
     L.vpr_varstrata_timing.argtypes = [H, C.POINTER(C.c_double)]
-    ec = [C.POINTER(A.VprVariants), C.c_void_p, A.P_i32, C.c_int32, C.c_int32, C.c_int32, A.P_i64]
-    L.vpr_errclass.argtypes = [H] + ec
-    L.vpr_allreduce_errclass.argtypes = [H, C.c_void_p] + ec
-    L.vpr_errclass_download.argtypes = [H, A.P_u8 * A.HAPS]
-    L.vpr_errclass_timing.argtypes = [H, C.POINTER(C.c_double)]
-    L.vpr_errclass_names.restype = C.POINTER(C.c_char_p)
-    L.vpr_errclass_names.argtypes = []
-    mk = [C.POINTER(A.VprVariants), C.c_void_p, A.P_i32, C.c_int32, C.c_int32, A.P_i64]
-    L.vpr_matchkind.argtypes = [H] + mk
-    L.vpr_allreduce_matchkind.argtypes = [H, C.c_void_p] + mk
-    L.vpr_matchkind_download.argtypes = [H, A.P_u8 * A.HAPS]
-    L.vpr_matchkind_timing.argtypes = [H, C.POINTER(C.c_double)]
-    L.vpr_matchkind_names.restype = C.POINTER(C.c_char_p)
-    L.vpr_matchkind_names.argtypes = []
+    for name, own in (("errclass", [C.c_int32]), ("matchkind", [])):      # the label passes; own: errclass' window
+        args = [C.POINTER(A.VprVariants), C.c_void_p, A.P_i32] + own + [C.c_int32, C.c_int32, A.P_i64]
+        getattr(L, f"vpr_{name}").argtypes = [H] + args
+        getattr(L, f"vpr_allreduce_{name}").argtypes = [H, C.c_void_p] + args
+        getattr(L, f"vpr_{name}_download").argtypes = [H, A.P_u8 * A.HAPS]
+        getattr(L, f"vpr_{name}_timing").argtypes = [H, C.POINTER(C.c_double)]
+        getattr(L, f"vpr_{name}_names").restype = C.POINTER(C.c_char_p)
+        getattr(L, f"vpr_{name}_names").argtypes = []
     boot = [C.c_void_p, A.P_i32, C.c_int32, C.c_int32, P_u64, C.c_uint64, C.c_int32, C.c_int32, A.P_i64]
     L.vpr_pr_counts_boot.argtypes = [H] + boot
     L.vpr_allreduce_counts_boot.argtypes = [H, C.c_void_p] + boot
@@ -219,16 +213,19 @@ def varstrata_default():
     return [names[k].decode() for k in range(n.value)], [A.VprVariantStratum.from_buffer_copy(spec[k]) for k in range(n.value)]
 
 
+def _label_names(entry, n):
+    names = getattr(lib(), entry)()
+    return [names[k].decode() for k in range(n)]
+
+
 def errclass_names():
     """the names of the seven error classes (vpr_errclass_names), in the order of their codes A.EC_*"""
-    names = lib().vpr_errclass_names()
-    return [names[k].decode() for k in range(A.EC_CLASSES)]
+    return _label_names("vpr_errclass_names", A.EC_CLASSES)
 
 
 def matchkind_names():
     """the names of the four match kinds (vpr_matchkind_names), in the order of their codes A.MK_*"""
-    names = lib().vpr_matchkind_names()
-    return [names[k].decode() for k in range(A.MK_KINDS)]
+    return _label_names("vpr_matchkind_names", A.MK_KINDS)
 
 
 def context_info():
@@ -506,77 +503,72 @@ class PrecisionRecall:
         n_old = self._strata[0] if append else 0
         self._strata = (n_old + len(spec), [int(vs.var_off[h][n_sc]) for h in range(A.HAPS)])
 
+    def _timing(self, entry):
+        """the one device time (ms) that `entry` returns"""
+        a = C.c_double()
+        self._chk(getattr(lib(), entry)(self._h, C.byref(a)), entry)
+        return a.value
+
     def varstrata_timing(self):
         """ms of the last varstrata_masks' kernel launches, from HIP events on the handle's stream"""
-        a = C.c_double()
-        self._chk(lib().vpr_varstrata_timing(self._h, C.byref(a)), "vpr_varstrata_timing")
-        return a.value
+        return self._timing("vpr_varstrata_timing")
+
+    def _label_pass(self, name, n_labels, variants, var_class_per_slot, pb_phase, own, min_qual, max_qual, comm):
+        """a label pass (vpr_<name>, or vpr_allreduce_<name> with comm) -> int64 [2][4][n_labels][nq]; own: the pass's own arguments"""
+        vs = variants.as_struct() if isinstance(variants, A.Variants) else variants
+        nq = max_qual - min_qual + 1
+        out = np.zeros((2, 4, n_labels, max(nq, 1)), np.int64)      # (min_qual > max_qual: the call refuses)
+        pb = None if pb_phase is None else np.ascontiguousarray(pb_phase, dtype=np.int32)
+        arr = None
+        if var_class_per_slot is not None:
+            cls = [np.ascontiguousarray(c, dtype=np.uint8) for c in var_class_per_slot]
+            arr = (A.P_u8 * 4)(*[A._ptr(c, C.c_uint8) for c in cls])
+        args = (C.byref(vs), arr, None if pb is None else A._ptr(pb, C.c_int32), *own, min_qual, max_qual, A._ptr(out, C.c_int64))
+        L = lib()
+        if comm is None:
+            rc = getattr(L, f"vpr_{name}")(self._h, *args)
+        else:
+            rc = getattr(L, f"vpr_allreduce_{name}")(self._h, comm if isinstance(comm, C.c_void_p) else C.c_void_p(comm), *args)
+        self._chk(rc, f"vpr_{name}")
+        return out
+
+    def _label_download(self, entry):
+        """the label bytes of the last call of a label pass: one uint8 array per hap slot"""
+        out = [np.zeros(self._batch.n_vars(h) if self._batch is not None else 0, np.uint8) for h in range(A.HAPS)]
+        keep = [o if o.size else np.zeros(1, np.uint8) for o in out]
+        arr = (A.P_u8 * A.HAPS)(*[A._ptr(k, C.c_uint8) for k in keep])
+        self._chk(getattr(lib(), entry)(self._h, arr), entry)
+        return out
 
     def errclass(self, variants, var_class_per_slot, pb_phase=None, window=A.EC_DEFAULT_WINDOW, min_qual=0, max_qual=60, comm=None):
         """The error classes of the last execute (include/vcfdist_errclass.h): every query FP and truth FN gets the first class
         that applies (A.EC_*), joined across the callsets inside its supercluster on the device -> int64 [2][4][7][nq].
         variants: the A.Variants (or a VprVariants struct) the batch was made from; var_class_per_slot None: the classes are
         resident; comm: an ncclComm_t (as an integer) for vpr_allreduce_errclass."""
-        vs = variants.as_struct() if isinstance(variants, A.Variants) else variants
-        nq = max_qual - min_qual + 1
-        out = np.zeros((2, 4, A.EC_CLASSES, max(nq, 1)), np.int64)      # (min_qual > max_qual: the call refuses)
-        pb = None if pb_phase is None else np.ascontiguousarray(pb_phase, dtype=np.int32)
-        arr = None
-        if var_class_per_slot is not None:
-            cls = [np.ascontiguousarray(c, dtype=np.uint8) for c in var_class_per_slot]
-            arr = (A.P_u8 * 4)(*[A._ptr(c, C.c_uint8) for c in cls])
-        args = (C.byref(vs), arr, None if pb is None else A._ptr(pb, C.c_int32), int(window), min_qual, max_qual, A._ptr(out, C.c_int64))
-        L = lib()
-        rc = L.vpr_errclass(self._h, *args) if comm is None else L.vpr_allreduce_errclass(self._h, comm if isinstance(comm, C.c_void_p) else C.c_void_p(comm), *args)
-        self._chk(rc, "vpr_errclass")
-        return out
+        return self._label_pass("errclass", A.EC_CLASSES, variants, var_class_per_slot, pb_phase, (int(window),), min_qual, max_qual, comm)
 
     def errclass_download(self):
         """the class bytes (A.EC_*, A.EC_NONE) of the last errclass: one uint8 array per hap slot"""
-        out = [np.zeros(self._batch.n_vars(h) if self._batch is not None else 0, np.uint8) for h in range(A.HAPS)]
-        keep = [o if o.size else np.zeros(1, np.uint8) for o in out]
-        arr = (A.P_u8 * A.HAPS)(*[A._ptr(k, C.c_uint8) for k in keep])
-        self._chk(lib().vpr_errclass_download(self._h, arr), "vpr_errclass_download")
-        return out
+        return self._label_download("vpr_errclass_download")
 
     def errclass_timing(self):
         """ms of the last errclass' kernel launches, from HIP events on the handle's stream"""
-        a = C.c_double()
-        self._chk(lib().vpr_errclass_timing(self._h, C.byref(a)), "vpr_errclass_timing")
-        return a.value
+        return self._timing("vpr_errclass_timing")
 
     def matchkind(self, variants, var_class_per_slot, pb_phase=None, min_qual=0, max_qual=60, comm=None):
         """The match kinds of the last execute (include/vcfdist_matchkind.h): every TP of either callset gets the first kind that
         applies (A.MK_*), joined across the callsets inside its supercluster on the device -> int64 [2][4][4][nq].
         variants: the A.Variants (or a VprVariants struct) the batch was made from; var_class_per_slot None: the classes are
         resident; comm: an ncclComm_t (as an integer) for vpr_allreduce_matchkind."""
-        vs = variants.as_struct() if isinstance(variants, A.Variants) else variants
-        nq = max_qual - min_qual + 1
-        out = np.zeros((2, 4, A.MK_KINDS, max(nq, 1)), np.int64)      # (min_qual > max_qual: the call refuses)
-        pb = None if pb_phase is None else np.ascontiguousarray(pb_phase, dtype=np.int32)
-        arr = None
-        if var_class_per_slot is not None:
-            cls = [np.ascontiguousarray(c, dtype=np.uint8) for c in var_class_per_slot]
-            arr = (A.P_u8 * 4)(*[A._ptr(c, C.c_uint8) for c in cls])
-        args = (C.byref(vs), arr, None if pb is None else A._ptr(pb, C.c_int32), min_qual, max_qual, A._ptr(out, C.c_int64))
-        L = lib()
-        rc = L.vpr_matchkind(self._h, *args) if comm is None else L.vpr_allreduce_matchkind(self._h, comm if isinstance(comm, C.c_void_p) else C.c_void_p(comm), *args)
-        self._chk(rc, "vpr_matchkind")
-        return out
+        return self._label_pass("matchkind", A.MK_KINDS, variants, var_class_per_slot, pb_phase, (), min_qual, max_qual, comm)
 
     def matchkind_download(self):
         """the kind bytes (A.MK_*, A.MK_NONE) of the last matchkind: one uint8 array per hap slot"""
-        out = [np.zeros(self._batch.n_vars(h) if self._batch is not None else 0, np.uint8) for h in range(A.HAPS)]
-        keep = [o if o.size else np.zeros(1, np.uint8) for o in out]
-        arr = (A.P_u8 * A.HAPS)(*[A._ptr(k, C.c_uint8) for k in keep])
-        self._chk(lib().vpr_matchkind_download(self._h, arr), "vpr_matchkind_download")
-        return out
+        return self._label_download("vpr_matchkind_download")
 
     def matchkind_timing(self):
         """ms of the last matchkind's kernel launches, from HIP events on the handle's stream"""
-        a = C.c_double()
-        self._chk(lib().vpr_matchkind_timing(self._h, C.byref(a)), "vpr_matchkind_timing")
-        return a.value
+        return self._timing("vpr_matchkind_timing")
 
     def pr_counts_boot(self, var_class_per_slot, pb_phase, sc_key, n_rep, seed=1, min_qual=0, max_qual=60, stratum=-1, comm=None):
         """The bootstrap replicates of the counters of the last execute (include/vcfdist_bootstrap.h): replicate r counts every

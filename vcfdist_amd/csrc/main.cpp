@@ -494,12 +494,16 @@ int main(int argc, char **argv) {
     std::vector<int64_t> total(size_t(2) * VPR_VARTYPES * 3 * size_t(nq), 0);
     std::vector<int64_t> strat_total(total.size() * size_t(n_strata), 0);      // --stratify: counts[n_strata][2][4][3][nq]
     int64_t strat_vars = 0, strat_none = 0;                                     // hap-variants seen / in no stratum
-    // --classify-errors: counts[2][4][VPR_EC_CLASSES][nq] summed over the contigs; device ms of the launches
-    std::vector<int64_t> ec_total(A.classify_errors ? total.size() / 3 * VPR_EC_CLASSES : 0, 0);
-    double ec_ms = 0;
-    // --classify-matches: counts[2][4][VPR_MK_KINDS][nq] summed over the contigs; device ms of the launches
-    std::vector<int64_t> mk_total(A.classify_matches ? total.size() / 3 * VPR_MK_KINDS : 0, 0);
-    double mk_ms = 0;
+    // --classify-errors, --classify-matches: counts[2][4][VPR_EC_CLASSES / VPR_MK_KINDS][nq] summed over the contigs (empty
+    // without the option); device ms of the launches
+    struct LabelPass {
+        std::vector<int64_t> total;
+        double ms;
+        int (*timing)(const vpr_handle *, double *);
+        int (*write)(const char *, const int64_t *, const int64_t *, int32_t, int32_t);
+    };
+    LabelPass ec{std::vector<int64_t>(A.classify_errors ? total.size() / 3 * VPR_EC_CLASSES : 0, 0), 0, vpr_errclass_timing, vrp_write_error_classes};
+    LabelPass mk{std::vector<int64_t>(A.classify_matches ? total.size() / 3 * VPR_MK_KINDS : 0, 0), 0, vpr_matchkind_timing, vrp_write_match_kinds};
     // --bootstrap: counts[n_rep][2][4][3][nq], with --stratify also [n_strata][n_rep][2][4][3][nq]; device ms of the launches
     std::vector<int64_t> boot_total(total.size() * size_t(A.bootstrap), 0), boot_strat(boot_total.size() * size_t(n_strata), 0);
     double boot_ms = 0;
@@ -611,22 +615,16 @@ int main(int argc, char **argv) {
             std::vector<int64_t> counts(total.size(), 0);
             if (vpr_pr_counts(h, clsp, C->pb.data(), A.min_qual, A.max_qual, counts.data())) die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
             for (size_t k = 0; k < total.size(); k++) total[k] += counts[k];
-            if (A.classify_errors) {      // the same evaluation, its FP and FN cut by why they are wrong (the classes are resident)
-                std::vector<int64_t> ec(ec_total.size(), 0);
+            // the same evaluation, its FP and FN cut by why they are wrong, its TP by how they were matched (the classes are resident)
+            auto label = [&](LabelPass &P, auto call) {
+                std::vector<int64_t> c(P.total.size(), 0);
                 double ms = 0;
-                if (vpr_errclass(h, &V, nullptr, C->pb.data(), A.error_window, A.min_qual, A.max_qual, ec.data()) || vpr_errclass_timing(h, &ms))
-                    die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
-                for (size_t k = 0; k < ec.size(); k++) ec_total[k] += ec[k];
-                ec_ms += ms;
-            }
-            if (A.classify_matches) {     // the same evaluation, its TP cut by how they were matched (the classes are resident)
-                std::vector<int64_t> mk(mk_total.size(), 0);
-                double ms = 0;
-                if (vpr_matchkind(h, &V, nullptr, C->pb.data(), A.min_qual, A.max_qual, mk.data()) || vpr_matchkind_timing(h, &ms))
-                    die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
-                for (size_t k = 0; k < mk.size(); k++) mk_total[k] += mk[k];
-                mk_ms += ms;
-            }
+                if (call(c.data()) || P.timing(h, &ms)) die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+                for (size_t k = 0; k < c.size(); k++) P.total[k] += c[k];
+                P.ms += ms;
+            };
+            if (A.classify_errors) label(ec, [&](int64_t *c) { return vpr_errclass(h, &V, nullptr, C->pb.data(), A.error_window, A.min_qual, A.max_qual, c); });
+            if (A.classify_matches) label(mk, [&](int64_t *c) { return vpr_matchkind(h, &V, nullptr, C->pb.data(), A.min_qual, A.max_qual, c); });
             if (n_strata) {        // the same evaluation, cut by region: membership words, then the histogram per stratum
                 std::vector<int64_t> iv_off(size_t(n_bed) + 1, 0);
                 std::vector<int32_t> iv_start, iv_stop;
@@ -768,10 +766,8 @@ int main(int argc, char **argv) {
             }
             if (n_vs && vrp_write_variant_strata(A.prefix.c_str(), vs_names, vs_spec, n_vs, vs_query.data(), vs_truth.data())) die("ERROR: %s", vrp_last_error());
         }
-        if (A.classify_errors && vrp_write_error_classes(A.prefix.c_str(), ec_total.data(), total.data(), A.min_qual, A.max_qual))
-            die("ERROR: %s", vrp_last_error());
-        if (A.classify_matches && vrp_write_match_kinds(A.prefix.c_str(), mk_total.data(), total.data(), A.min_qual, A.max_qual))
-            die("ERROR: %s", vrp_last_error());
+        for (const LabelPass *P : {&ec, &mk})
+            if (!P->total.empty() && P->write(A.prefix.c_str(), P->total.data(), total.data(), A.min_qual, A.max_qual)) die("ERROR: %s", vrp_last_error());
         if (A.bootstrap && vrp_write_bootstrap(A.prefix.c_str(), total.data(), boot_total.data(), A.bootstrap, A.bootstrap_seed, A.min_qual, A.max_qual))
             die("ERROR: %s", vrp_last_error());
         std::vector<vrp_contig> ctgs(outs.size());
@@ -822,19 +818,19 @@ int main(int argc, char **argv) {
         const size_t nq = size_t(A.max_qual - A.min_qual + 1);
         long long n_fp = 0, n_fn = 0;
         for (int c = 0; c < VPR_EC_CLASSES; c++) {
-            n_fp += ec_total[((size_t(0) * VPR_VARTYPES + VPR_VARTYPE_ALL) * VPR_EC_CLASSES + size_t(c)) * nq];
-            n_fn += ec_total[((size_t(1) * VPR_VARTYPES + VPR_VARTYPE_ALL) * VPR_EC_CLASSES + size_t(c)) * nq];
+            n_fp += ec.total[((size_t(0) * VPR_VARTYPES + VPR_VARTYPE_ALL) * VPR_EC_CLASSES + size_t(c)) * nq];
+            n_fn += ec.total[((size_t(1) * VPR_VARTYPES + VPR_VARTYPE_ALL) * VPR_EC_CLASSES + size_t(c)) * nq];
         }
         fprintf(stderr, "[vcfdist_amd] error classes: window %d, %lld query FP and %lld truth FN classified, %.3f ms on the device\n", A.error_window,
-                n_fp, n_fn, ec_ms);
+                n_fp, n_fn, ec.ms);
     }
     if (A.classify_matches) {     // the matched variants at threshold NONE: the ALL rows' kinds of both callsets
         const size_t nq = size_t(A.max_qual - A.min_qual + 1);
         long long n[2][VPR_MK_KINDS];
         for (int cs = 0; cs < 2; cs++)
-            for (int c = 0; c < VPR_MK_KINDS; c++) n[cs][c] = mk_total[((size_t(cs) * VPR_VARTYPES + VPR_VARTYPE_ALL) * VPR_MK_KINDS + size_t(c)) * nq];
+            for (int c = 0; c < VPR_MK_KINDS; c++) n[cs][c] = mk.total[((size_t(cs) * VPR_VARTYPES + VPR_VARTYPE_ALL) * VPR_MK_KINDS + size_t(c)) * nq];
         fprintf(stderr, "[vcfdist_amd] match kinds: query TP %lld exact, %lld shifted, %lld regrouped, %lld partial; truth TP %lld exact, %lld shifted, "
-                "%lld regrouped, %lld partial, %.3f ms on the device\n", n[0][0], n[0][1], n[0][2], n[0][3], n[1][0], n[1][1], n[1][2], n[1][3], mk_ms);
+                "%lld regrouped, %lld partial, %.3f ms on the device\n", n[0][0], n[0][1], n[0][2], n[0][3], n[1][0], n[1][1], n[1][2], n[1][3], mk.ms);
     }
     if (A.bootstrap)
         fprintf(stderr, "[vcfdist_amd] bootstrap: %d replicates, seed %llu, %.3f ms on the device\n", A.bootstrap, (unsigned long long)A.bootstrap_seed, boot_ms);

@@ -1,21 +1,13 @@
 // pr_errclass.hip -- the error classes (include/vcfdist_errclass.h): why each query FP and truth FN is wrong.  k_errclass joins the
 // two callsets inside each supercluster -- one lane per hap-variant, bisections over the supercluster's sorted positions, as
 // k_varstrata_mask (pr_varstrata.hip) does inside a contig -- writes a class byte per hap-variant and counts the classes in a
-// block histogram, as k_pr_hist (pr_collect.hip) counts the errtypes.  The bin rule is pr_counts.h's; the front and back of a
-// counters call are the ones of pr_collect.hip.
+// block histogram, as k_pr_hist (pr_collect.hip) counts the errtypes.  The bin rule is pr_counts.h's; the host side around the
+// launches is the label passes' (pr_label.h).
 #include "pr_host.h"
 #include "pr_counts.h"
 #include "pr_varscan.h"
-#include "pr_vartab.h"
+#include "pr_label.h"
 #include "../../include/vcfdist_errclass.h"
-
-struct ErrclassState {
-    DevBuf<uint8_t> cls[VPR_HAPS];                               // the class bytes of the last call
-    DevBuf<unsigned long long> hist;                             // [2][3 types][VPR_EC_CLASSES][nq + 1]
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    double ms = 0;
-    bool valid = false;
-};
 
 namespace {
 
@@ -102,87 +94,33 @@ __global__ void __launch_bounds__(256) k_errclass(VsCols own, VsCols par, VsCols
 
 namespace {
 
-// histogram [2][3 types][VPR_EC_CLASSES][nq + 1] -> counts [2][VPR_VARTYPES][VPR_EC_CLASSES][nq]: pr_fold_counts' rule cut by class.
-// A query FP counts at the threshold indices <= its bin; a truth FN at every threshold; a LOWQ truth variant at the thresholds
-// above its bin (bin nq, callq < min_qual: at every one)
-void fold_classes(const unsigned long long *hist, int nq, int64_t *counts) {
-    std::fill(counts, counts + size_t(2) * VPR_VARTYPES * VPR_EC_CLASSES * size_t(nq), 0);
-    auto C = [&](int cs, int t, int c, int k) -> int64_t & { return counts[((size_t(cs) * VPR_VARTYPES + t) * VPR_EC_CLASSES + c) * nq + k]; };
-    for (int cs = 0; cs < 2; cs++)
-        for (int t = 0; t < 3; t++)
-            for (int c = 0; c < VPR_EC_CLASSES; c++) {
-                const unsigned long long *b = hist + ((size_t(cs) * 3 + t) * VPR_EC_CLASSES + c) * (nq + 1);
-                int64_t acc = 0;
-                if (cs == 0) {
-                    for (int k = nq - 1; k >= 0; k--) { acc += int64_t(b[k]); C(cs, t, c, k) = acc; }
-                } else if (c != VPR_EC_LOWQ) {
-                    for (int k = 0; k <= nq; k++) acc += int64_t(b[k]);
-                    for (int k = 0; k < nq; k++) C(cs, t, c, k) = acc;
-                } else {
-                    acc = int64_t(b[nq]);
-                    for (int k = 0; k < nq; k++) { C(cs, t, c, k) = acc; acc += int64_t(b[k]); }
-                }
-                for (int k = 0; k < nq; k++) C(cs, VPR_VARTYPE_ALL, c, k) += C(cs, t, c, k);
-            }
-}
+// pr_fold_counts' rule cut by class.  A query FP counts at the threshold indices <= its bin; a truth FN at every threshold; a LOWQ
+// truth variant at the thresholds above its bin (bin nq, callq < min_qual: at every one)
+LabelFold ec_fold(int callset, int c) { return !callset ? LABEL_FOLD_UPTO : c != VPR_EC_LOWQ ? LABEL_FOLD_EVERY : LABEL_FOLD_ABOVE; }
+const LabelDesc EC = {LABEL_ERRCLASS, "vpr_errclass", "class", VPR_EC_CLASSES, ec_fold};
 
 int errclass_impl(vpr_handle *h, void *comm, const vpr_variants *v, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase,
                   int32_t window, int32_t min_qual, int32_t max_qual, int64_t *counts) {
     if (!h) return VPR_ERR_ARG;
-    if (!v || !counts) return fail(h, VPR_ERR_ARG, "vpr_errclass: null argument");
-    if (window < 0) return fail(h, VPR_ERR_ARG, "vpr_errclass: window %d is negative", window);
-    if (max_qual < min_qual) return fail(h, VPR_ERR_ARG, "vpr_errclass: max_qual %d is below min_qual %d", max_qual, min_qual);
-    if (int rc = pr_counts_begin(h, "vpr_errclass", comm)) return rc;
-    size_t pool_len[VPR_HAPS];
-    if (int rc = vartab_check(h, "vpr_errclass", v, pool_len)) return rc;
-    if (!h->errclass) h->errclass = new ErrclassState();
-    ErrclassState *S = h->errclass;
-    S->valid = false; S->ms = 0;
-    for (int k = 0; k < 2; k++) if (!S->ev[k]) HIPCHK(h, hipEventCreate(&S->ev[k]));
-    const int64_t n_sc = v->n_sc;
-    const int nq = max_qual - min_qual + 1;
-    const size_t nb = size_t(3) * VPR_EC_CLASSES * size_t(nq + 1), nh = 2 * nb;
-    for (int i = 0; i < VPR_HAPS; i++)
-        if (int rc = S->cls[i].reserve(h, size_t(h->n_var[i]), "vpr_errclass: class bytes: cannot allocate %zu bytes on the device")) return rc;
-    if (int rc = S->hist.reserve(h, nh, "vpr_errclass: class histogram: cannot allocate %zu bytes on the device")) return rc;
-    // ---- the columns and the pools: one block that lives as long as the call
-    VarTables T;
-    if (int rc = vartab_upload(h, "vpr_errclass", v, pool_len, &T)) return rc;
-    const VsCols *cols = T.cols;
-    HIPCHK(h, hipMemsetAsync(S->hist.p, 0, nh * 8, h->stream));
-    int32_t *d_pb = nullptr;
-    if (int rc = pr_counts_inputs(h, "vpr_errclass", var_class, pb_phase, &d_pb)) return rc;
-    HIPCHK(h, hipEventRecord(S->ev[0], h->stream));
+    // (the window is looked at behind the null arguments, which label_begin refuses)
+    if (v && counts && window < 0) return fail(h, VPR_ERR_ARG, "vpr_errclass: window %d is negative", window);
+    LabelCall c;
+    if (int rc = label_begin(h, EC, comm, v, var_class, pb_phase, min_qual, max_qual, counts, &c)) return rc;
+    const VsCols *cols = c.T.cols;
     for (int s = 0; s < VPR_HAPS; s++) {
         const int64_t nv = h->n_var[s];
         if (!nv) continue;
         const int oa = (s ^ 2), ob = (s ^ 3);      // the other callset's slot of the same / of the other haplotype index
-        hipLaunchKernelGGL(k_errclass, dim3(unsigned((nv + 255) / 256)), dim3(256), nb * 4, h->stream, cols[s], cols[s ^ 1], cols[oa], cols[ob], nv,
-                           int(n_sc), h->d_cls[s], h->dR.sc_phase, d_pb, h->dR.v[s][0].errtype, h->dR.v[s][1].errtype, h->dR.v[s][0].callq,
+        hipLaunchKernelGGL(k_errclass, dim3(unsigned((nv + 255) / 256)), dim3(256), c.nb * 4, h->stream, cols[s], cols[s ^ 1], cols[oa], cols[ob], nv,
+                           int(v->n_sc), h->d_cls[s], h->dR.sc_phase, c.d_pb, h->dR.v[s][0].errtype, h->dR.v[s][1].errtype, h->dR.v[s][0].callq,
                            h->dR.v[s][1].callq, h->dR.v[s ^ 1][0].errtype, h->dR.v[s ^ 1][1].errtype, s >> 1, int(window), int(min_qual), int(max_qual),
-                           S->cls[s].p, S->hist.p);
+                           c.S->bytes[s].p, c.S->hist.p);
         HIPCHK(h, hipGetLastError());
     }
-    HIPCHK(h, hipEventRecord(S->ev[1], h->stream));
-    std::vector<unsigned long long> hist(nh);
-    if (int rc = pr_counts_finish(h, comm, S->hist.p, nh, hist.data())) return rc;
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, S->ev[0], S->ev[1]);
-    S->ms = ms; S->valid = true;
-    fold_classes(hist.data(), nq, counts);
-    return VPR_OK;
+    return label_finish(h, EC, comm, &c, counts);
 }
 
 }  // namespace
-
-void errclass_free(vpr_handle *h) {
-    ErrclassState *S = h->errclass;
-    if (!S) return;
-    dev_release(h, S->cls[0], S->cls[1], S->cls[2], S->cls[3], S->hist);
-    for (int k = 0; k < 2; k++) if (S->ev[k]) (void)hipEventDestroy(S->ev[k]);
-    delete S;
-    h->errclass = nullptr;
-}
 
 extern "C" {
 
@@ -193,28 +131,12 @@ int vpr_errclass(vpr_handle *h, const vpr_variants *v, const uint8_t *const var_
 
 int vpr_allreduce_errclass(vpr_handle *h, void *nccl_comm, const vpr_variants *v, const uint8_t *const var_class[VPR_HAPS],
                            const int32_t *pb_phase, int32_t window, int32_t min_qual, int32_t max_qual, int64_t *counts) {
-    if (!nccl_comm) return VPR_ERR_ARG;
-    return errclass_impl(h, nccl_comm, v, var_class, pb_phase, window, min_qual, max_qual, counts);
+    return nccl_comm ? errclass_impl(h, nccl_comm, v, var_class, pb_phase, window, min_qual, max_qual, counts) : VPR_ERR_ARG;
 }
 
-int vpr_errclass_download(vpr_handle *h, uint8_t *const cls[VPR_HAPS]) {
-    if (!h || !cls) return VPR_ERR_ARG;
-    if (!h->errclass || !h->errclass->valid) return fail(h, VPR_ERR_STATE, "vpr_errclass_download: no class bytes (before vpr_errclass, or after the next upload)");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    for (int s = 0; s < VPR_HAPS; s++) {
-        if (!h->n_var[s]) continue;
-        if (!cls[s]) return fail(h, VPR_ERR_ARG, "vpr_errclass_download: hap slot %d: null array", s);
-        HIPCHK(h, hipMemcpyAsync(cls[s], h->errclass->cls[s].p, size_t(h->n_var[s]), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(h, x_sync(h, h->stream, SITE));
-    return VPR_OK;
-}
+int vpr_errclass_download(vpr_handle *h, uint8_t *const cls[VPR_HAPS]) { return label_download(h, EC, cls); }
 
-int vpr_errclass_timing(const vpr_handle *h, double *ms) {
-    if (!h || !ms) return VPR_ERR_ARG;
-    *ms = h->errclass ? h->errclass->ms : 0;
-    return VPR_OK;
-}
+int vpr_errclass_timing(const vpr_handle *h, double *ms) { return label_timing(h, EC, ms); }
 
 const char *const *vpr_errclass_names(void) { return EC_NAMES; }
 

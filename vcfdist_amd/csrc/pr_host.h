@@ -12,6 +12,7 @@
 //   pr_errclass.hip the error classes (include/vcfdist_errclass.h): why each FP and FN is wrong
 //   pr_matchkind.hip the match kinds (include/vcfdist_matchkind.h): how each TP was matched
 //   pr_vartab.hip   the host check and the one-block upload of the variant tables those two share (pr_vartab.h)
+//   pr_label.hip    the host side those two share (pr_label.h): the front and back of a call, the fold, download, timing, release
 #ifndef PR_HOST_H_
 #define PR_HOST_H_
 #include <hip/hip_runtime.h>
@@ -271,8 +272,8 @@ using namespace vprh;
 struct DistState;                        // the distance step's tables and arena (pr_dist.hip)
 struct StrataState;                      // the membership words and the stratified histogram (pr_strata.hip)
 struct ContextState;                     // the sequence-context intervals (pr_context.hip)
-struct ErrclassState;                    // the class bytes and the class histogram (pr_errclass.hip)
-struct MatchkindState;                   // the kind bytes and the kind histogram (pr_matchkind.hip)
+struct LabelState;                       // the label bytes and the label histogram of a label pass (pr_label.h)
+enum { LABEL_ERRCLASS, LABEL_MATCHKIND, LABEL_PASSES };     // the label passes: pr_errclass.hip, pr_matchkind.hip
 struct BootState;                        // the replicate histogram and the supercluster keys (pr_boot.hip)
 
 struct vpr_handle {
@@ -424,8 +425,7 @@ struct vpr_handle {
     StrataState *strata = nullptr;       // vpr_strata_masks / vpr_strata_upload_masks (pr_strata.hip), released with the batch
     ContextState *context = nullptr;     // vpr_context_masks (pr_context.hip), released by the next one or vpr_destroy
     BootState *boot = nullptr;           // vpr_pr_counts_boot (pr_boot.hip), created by its first call, released with the batch
-    ErrclassState *errclass = nullptr;   // vpr_errclass (pr_errclass.hip), created by its first call, released with the batch
-    MatchkindState *matchkind = nullptr; // vpr_matchkind (pr_matchkind.hip), created by its first call, released with the batch
+    LabelState *label[LABEL_PASSES] = {nullptr, nullptr};   // vpr_errclass / vpr_matchkind (pr_label.hip), created by a pass's first call, released with the batch
     double varstrata_ms = 0;             // device time of the last vpr_varstrata_masks' kernel launches (pr_varstrata.hip)
     vpr_timing timing;
     bool uploaded = false, executed = false;
@@ -479,8 +479,7 @@ int strata_extend(vpr_handle *h, const char *entry, int32_t n_add, const int64_t
                   uint64_t *words[VPR_HAPS], int32_t *n_words);
 void strata_commit(vpr_handle *h);
 void context_free(vpr_handle *h);                                    // pr_context.hip: the resident context intervals
-void errclass_free(vpr_handle *h);                                   // pr_errclass.hip: the class bytes and the class histogram
-void matchkind_free(vpr_handle *h);                                  // pr_matchkind.hip: the kind bytes and the kind histogram
+void label_free(vpr_handle *h);                                      // pr_label.hip: the label bytes and histograms of both label passes
 void boot_free(vpr_handle *h);                                       // pr_boot.hip: the replicate histogram and the keys
 // pr_collect.hip, shared by the three counters entries (vpr_pr_counts, _strata, _boot; `entry`: the entry's name, for the
 // messages).  pr_counts_begin: the state checks and the device, before the entry's own buffers; pr_counts_inputs: the caller's

@@ -1,27 +1,17 @@
 // pr_matchkind.hip -- the match kinds (include/vcfdist_matchkind.h): how each true positive was matched.  k_matchkind is the
 // counterpart of k_errclass (pr_errclass.hip) on the TP side: one lane per hap-variant, the same join of the two callsets inside
 // the supercluster (pr_varscan.h), here on the resident sync groups and query_ed; a kind byte per hap-variant and a block
-// histogram flushed as k_pr_hist's (pr_collect.hip).  The bin rule is pr_counts.h's; the host check and the upload of the variant
-// tables are pr_vartab.h's; the front and back of a counters call are the ones of pr_collect.hip.
+// histogram flushed as k_pr_hist's (pr_collect.hip).  The bin rule is pr_counts.h's; the host side around the launches is the label
+// passes' (pr_label.h).
 #include "pr_host.h"
 #include "pr_counts.h"
 #include "pr_varscan.h"
-#include "pr_vartab.h"
+#include "pr_label.h"
 #include "../../include/vcfdist_matchkind.h"
-
-struct MatchkindState {
-    DevBuf<uint8_t> kind[VPR_HAPS];                              // the kind bytes of the last call
-    DevBuf<unsigned long long> hist;                             // [2][3 types][VPR_MK_KINDS][nq + 1]
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    double ms = 0;
-    bool valid = false;
-};
 
 namespace {
 
 const char *const MK_NAMES[VPR_MK_KINDS] = {"exact", "shifted", "regrouped", "partial"};
-// thresholds of one call: the block histogram, 3 * VPR_MK_KINDS * (nq + 1) words of dynamic LDS, stays within 64 KiB
-const int MK_MAX_NQ = 64 * 1024 / 4 / (3 * VPR_MK_KINDS) - 1;
 
 // members of sync group g among the variants [lo, hi) of a slot, up to 2 ("0, 1, more than 1" decides every kind): e / grp are
 // the slot's errtype and sync_group columns of the selected phasing.  The members are not contiguous (a REF-plane FP with a group
@@ -98,78 +88,32 @@ __global__ void __launch_bounds__(256) k_matchkind(VsCols own, VsCols oa, VsCols
 
 namespace {
 
-// histogram [2][3 types][VPR_MK_KINDS][nq + 1] -> counts [2][VPR_VARTYPES][VPR_MK_KINDS][nq]: pr_fold_counts' TP rule cut by kind.
-// A matched variant of either callset counts at the threshold indices <= its bin (bin nq, callq < min_qual: at none)
-void fold_kinds(const unsigned long long *hist, int nq, int64_t *counts) {
-    std::fill(counts, counts + size_t(2) * VPR_VARTYPES * VPR_MK_KINDS * size_t(nq), 0);
-    auto C = [&](int cs, int t, int c, int k) -> int64_t & { return counts[((size_t(cs) * VPR_VARTYPES + t) * VPR_MK_KINDS + c) * nq + k]; };
-    for (int cs = 0; cs < 2; cs++)
-        for (int t = 0; t < 3; t++)
-            for (int c = 0; c < VPR_MK_KINDS; c++) {
-                const unsigned long long *b = hist + ((size_t(cs) * 3 + t) * VPR_MK_KINDS + c) * (nq + 1);
-                int64_t acc = 0;
-                for (int k = nq - 1; k >= 0; k--) { acc += int64_t(b[k]); C(cs, t, c, k) = acc; }
-                for (int k = 0; k < nq; k++) C(cs, VPR_VARTYPE_ALL, c, k) += C(cs, t, c, k);
-            }
-}
+// pr_fold_counts' TP rule cut by kind: a matched variant of either callset counts at the threshold indices <= its bin (bin nq,
+// callq < min_qual: at none)
+LabelFold mk_fold(int, int) { return LABEL_FOLD_UPTO; }
+const LabelDesc MK = {LABEL_MATCHKIND, "vpr_matchkind", "kind", VPR_MK_KINDS, mk_fold};
 
 int matchkind_impl(vpr_handle *h, void *comm, const vpr_variants *v, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase,
                    int32_t min_qual, int32_t max_qual, int64_t *counts) {
     if (!h) return VPR_ERR_ARG;
-    if (!v || !counts) return fail(h, VPR_ERR_ARG, "vpr_matchkind: null argument");
-    if (max_qual < min_qual) return fail(h, VPR_ERR_ARG, "vpr_matchkind: max_qual %d is below min_qual %d", max_qual, min_qual);
-    if (int64_t(max_qual) - min_qual >= MK_MAX_NQ)
-        return fail(h, VPR_ERR_ARG, "vpr_matchkind: the quality range %d..%d holds more than %d thresholds (the block histogram is in LDS)", min_qual, max_qual,
-                    MK_MAX_NQ);
-    if (int rc = pr_counts_begin(h, "vpr_matchkind", comm)) return rc;
-    size_t pool_len[VPR_HAPS];
-    if (int rc = vartab_check(h, "vpr_matchkind", v, pool_len)) return rc;
-    if (!h->matchkind) h->matchkind = new MatchkindState();
-    MatchkindState *S = h->matchkind;
-    S->valid = false; S->ms = 0;
-    for (int k = 0; k < 2; k++) if (!S->ev[k]) HIPCHK(h, hipEventCreate(&S->ev[k]));
-    const int nq = max_qual - min_qual + 1;
-    const size_t nb = size_t(3) * VPR_MK_KINDS * size_t(nq + 1), nh = 2 * nb;
-    for (int i = 0; i < VPR_HAPS; i++)
-        if (int rc = S->kind[i].reserve(h, size_t(h->n_var[i]), "vpr_matchkind: kind bytes: cannot allocate %zu bytes on the device")) return rc;
-    if (int rc = S->hist.reserve(h, nh, "vpr_matchkind: kind histogram: cannot allocate %zu bytes on the device")) return rc;
-    VarTables T;      // the columns and the pools: one block that lives as long as the call
-    if (int rc = vartab_upload(h, "vpr_matchkind", v, pool_len, &T)) return rc;
-    HIPCHK(h, hipMemsetAsync(S->hist.p, 0, nh * 8, h->stream));
-    int32_t *d_pb = nullptr;
-    if (int rc = pr_counts_inputs(h, "vpr_matchkind", var_class, pb_phase, &d_pb)) return rc;
-    HIPCHK(h, hipEventRecord(S->ev[0], h->stream));
+    LabelCall c;
+    if (int rc = label_begin(h, MK, comm, v, var_class, pb_phase, min_qual, max_qual, counts, &c)) return rc;
+    const VsCols *cols = c.T.cols;
     for (int s = 0; s < VPR_HAPS; s++) {
         const int64_t nv = h->n_var[s];
         if (!nv) continue;
         const int oa = (s ^ 2), ob = (s ^ 3);      // the other callset's slot of the same / of the other haplotype index
-        hipLaunchKernelGGL(k_matchkind, dim3(unsigned((nv + 255) / 256)), dim3(256), nb * 4, h->stream, T.cols[s], T.cols[oa], T.cols[ob], nv,
-                           int(v->n_sc), h->d_cls[s], h->dR.sc_phase, d_pb, h->dR.v[s][0].errtype, h->dR.v[s][1].errtype, h->dR.v[s][0].callq,
+        hipLaunchKernelGGL(k_matchkind, dim3(unsigned((nv + 255) / 256)), dim3(256), c.nb * 4, h->stream, cols[s], cols[oa], cols[ob], nv,
+                           int(v->n_sc), h->d_cls[s], h->dR.sc_phase, c.d_pb, h->dR.v[s][0].errtype, h->dR.v[s][1].errtype, h->dR.v[s][0].callq,
                            h->dR.v[s][1].callq, h->dR.v[s][0].sync_group, h->dR.v[s][1].sync_group, h->dR.v[s][0].query_ed, h->dR.v[s][1].query_ed,
                            h->dR.v[oa][0].errtype, h->dR.v[oa][0].sync_group, h->dR.v[ob][1].errtype, h->dR.v[ob][1].sync_group, s >> 1,
-                           int(min_qual), int(max_qual), S->kind[s].p, S->hist.p);
+                           int(min_qual), int(max_qual), c.S->bytes[s].p, c.S->hist.p);
         HIPCHK(h, hipGetLastError());
     }
-    HIPCHK(h, hipEventRecord(S->ev[1], h->stream));
-    std::vector<unsigned long long> hist(nh);
-    if (int rc = pr_counts_finish(h, comm, S->hist.p, nh, hist.data())) return rc;
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, S->ev[0], S->ev[1]);
-    S->ms = ms; S->valid = true;
-    fold_kinds(hist.data(), nq, counts);
-    return VPR_OK;
+    return label_finish(h, MK, comm, &c, counts);
 }
 
 }  // namespace
-
-void matchkind_free(vpr_handle *h) {
-    MatchkindState *S = h->matchkind;
-    if (!S) return;
-    dev_release(h, S->kind[0], S->kind[1], S->kind[2], S->kind[3], S->hist);
-    for (int k = 0; k < 2; k++) if (S->ev[k]) (void)hipEventDestroy(S->ev[k]);
-    delete S;
-    h->matchkind = nullptr;
-}
 
 extern "C" {
 
@@ -180,28 +124,12 @@ int vpr_matchkind(vpr_handle *h, const vpr_variants *v, const uint8_t *const var
 
 int vpr_allreduce_matchkind(vpr_handle *h, void *nccl_comm, const vpr_variants *v, const uint8_t *const var_class[VPR_HAPS],
                             const int32_t *pb_phase, int32_t min_qual, int32_t max_qual, int64_t *counts) {
-    if (!nccl_comm) return VPR_ERR_ARG;
-    return matchkind_impl(h, nccl_comm, v, var_class, pb_phase, min_qual, max_qual, counts);
+    return nccl_comm ? matchkind_impl(h, nccl_comm, v, var_class, pb_phase, min_qual, max_qual, counts) : VPR_ERR_ARG;
 }
 
-int vpr_matchkind_download(vpr_handle *h, uint8_t *const kind[VPR_HAPS]) {
-    if (!h || !kind) return VPR_ERR_ARG;
-    if (!h->matchkind || !h->matchkind->valid) return fail(h, VPR_ERR_STATE, "vpr_matchkind_download: no kind bytes (before vpr_matchkind, or after the next upload)");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    for (int s = 0; s < VPR_HAPS; s++) {
-        if (!h->n_var[s]) continue;
-        if (!kind[s]) return fail(h, VPR_ERR_ARG, "vpr_matchkind_download: hap slot %d: null array", s);
-        HIPCHK(h, hipMemcpyAsync(kind[s], h->matchkind->kind[s].p, size_t(h->n_var[s]), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(h, x_sync(h, h->stream, SITE));
-    return VPR_OK;
-}
+int vpr_matchkind_download(vpr_handle *h, uint8_t *const kind[VPR_HAPS]) { return label_download(h, MK, kind); }
 
-int vpr_matchkind_timing(const vpr_handle *h, double *ms) {
-    if (!h || !ms) return VPR_ERR_ARG;
-    *ms = h->matchkind ? h->matchkind->ms : 0;
-    return VPR_OK;
-}
+int vpr_matchkind_timing(const vpr_handle *h, double *ms) { return label_timing(h, MK, ms); }
 
 const char *const *vpr_matchkind_names(void) { return MK_NAMES; }
 

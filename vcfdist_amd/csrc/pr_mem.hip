@@ -288,8 +288,7 @@ int exec_pin(vpr_handle *h, void **out, size_t bytes) {
 void free_batch(vpr_handle *h) {
     dist_free(h);           // the distance results belong to the batch (vpr_distance_download refuses until the next vpr_distance)
     strata_free(h);         // and so do the membership words (vpr_pr_counts_strata refuses until the next vpr_strata_masks)
-    errclass_free(h);       // and the class bytes of vpr_errclass (vpr_errclass_download refuses until the next call)
-    matchkind_free(h);      // and the kind bytes of vpr_matchkind (vpr_matchkind_download refuses until the next call)
+    label_free(h);          // and the label bytes of vpr_errclass and vpr_matchkind (their downloads refuse until the next call)
     boot_free(h);           // and the replicate histogram (sized by the batch and the last call's replicates)
     for (size_t k = 0; k < h->allocs.size(); k++) {
         if (h->alloc_bytes[k]) h->dev_cache.push_back(vpr_handle::Blk{h->allocs[k], h->alloc_bytes[k]});

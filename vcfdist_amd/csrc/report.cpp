@@ -242,27 +242,27 @@ extern "C" int vrp_write_variant_strata(const char *prefix, const char *const *n
     return VRP_OK;
 }
 
-extern "C" int vrp_write_error_classes(const char *prefix, const int64_t *class_counts, const int64_t *pr_counts, int32_t min_qual,
-                                       int32_t max_qual) {
-    if (!prefix || !class_counts || !pr_counts || max_qual < min_qual) return fail(VRP_ERR_ARG, "vrp_write_error_classes: bad argument");
+// The two files of a label pass (a feature that counts a label per variant: include/vcfdist_errclass.h, vcfdist_matchkind.h):
+// <stem>.tsv with a row per (type, threshold) and <stem>-summary.tsv with the NONE and BEST rows of each type.  counts
+// [2][VPR_VARTYPES][stride][nq]; a row's cells are each callset's total, then its first n_labels[callset] labels, under `cols`
+static int write_label_counts(const char *entry, const char *prefix, const char *stem, const char *cols, const int n_labels[2], int stride,
+                              const int64_t *counts, const int64_t *pr_counts, int32_t min_qual, int32_t max_qual) {
+    if (!prefix || !counts || !pr_counts || max_qual < min_qual) return fail(VRP_ERR_ARG, std::string(entry) + ": bad argument");
     const int nq = max_qual - min_qual + 1;
-    const std::string fn_all = std::string(prefix) + "error-classes.tsv", fn_sum = std::string(prefix) + "error-classes-summary.tsv";
+    const std::string fn_all = std::string(prefix) + stem + ".tsv", fn_sum = std::string(prefix) + stem + "-summary.tsv";
     File all(fn_all.c_str());
     if (!all) return fail(VRP_ERR_OPEN, "cannot create " + fn_all);
     File sum(fn_sum.c_str());
     if (!sum) return fail(VRP_ERR_OPEN, "cannot create " + fn_sum);
-    static const char *const COLS = "QUERY_FP\tFP_GT\tFP_SYNC\tFP_PHASE\tFP_SITE\tFP_NEAR\tFP_ALONE\tTRUTH_FN\tFN_GT\tFN_SYNC\tFN_PHASE\tFN_SITE\tFN_NEAR\tFN_ALONE\tFN_LOWQ\n";
-    fprintf(all, "VAR_TYPE\tMIN_QUAL\t%s", COLS);
-    fprintf(sum, "VAR_TYPE\tTHRESHOLD\tMIN_QUAL\t%s", COLS);
-    // the fifteen cells of one (type, threshold index): each callset's total, then its classes (the query has no LOWQ)
+    fprintf(all, "VAR_TYPE\tMIN_QUAL\t%s", cols);
+    fprintf(sum, "VAR_TYPE\tTHRESHOLD\tMIN_QUAL\t%s", cols);
     auto cells = [&](FILE *f, int type, int k) {
         for (int cs = 0; cs < 2; cs++) {
-            const int n = cs ? VPR_EC_CLASSES : VPR_EC_CLASSES - 1;
-            const int64_t *c = class_counts + (size_t(cs) * VPR_VARTYPES + type) * VPR_EC_CLASSES * size_t(nq) + k;
+            const int64_t *c = counts + (size_t(cs) * VPR_VARTYPES + type) * stride * size_t(nq) + k;
             long long tot = 0;
-            for (int j = 0; j < n; j++) tot += c[size_t(j) * nq];
+            for (int j = 0; j < n_labels[cs]; j++) tot += c[size_t(j) * nq];
             fprintf(f, "%s%lld", cs ? "\t" : "", tot);
-            for (int j = 0; j < n; j++) fprintf(f, "\t%lld", (long long)c[size_t(j) * nq]);
+            for (int j = 0; j < n_labels[cs]; j++) fprintf(f, "\t%lld", (long long)c[size_t(j) * nq]);
         }
         fputc('\n', f);
     };
@@ -283,44 +283,20 @@ extern "C" int vrp_write_error_classes(const char *prefix, const int64_t *class_
     return VRP_OK;
 }
 
+extern "C" int vrp_write_error_classes(const char *prefix, const int64_t *class_counts, const int64_t *pr_counts, int32_t min_qual,
+                                       int32_t max_qual) {
+    const int n[2] = {VPR_EC_CLASSES - 1, VPR_EC_CLASSES};      // (the query has no LOWQ)
+    return write_label_counts("vrp_write_error_classes", prefix, "error-classes",
+                              "QUERY_FP\tFP_GT\tFP_SYNC\tFP_PHASE\tFP_SITE\tFP_NEAR\tFP_ALONE\tTRUTH_FN\tFN_GT\tFN_SYNC\tFN_PHASE\tFN_SITE\tFN_NEAR\tFN_ALONE\tFN_LOWQ\n",
+                              n, VPR_EC_CLASSES, class_counts, pr_counts, min_qual, max_qual);
+}
+
 extern "C" int vrp_write_match_kinds(const char *prefix, const int64_t *kind_counts, const int64_t *pr_counts, int32_t min_qual,
                                      int32_t max_qual) {
-    if (!prefix || !kind_counts || !pr_counts || max_qual < min_qual) return fail(VRP_ERR_ARG, "vrp_write_match_kinds: bad argument");
-    const int nq = max_qual - min_qual + 1;
-    const std::string fn_all = std::string(prefix) + "match-kinds.tsv", fn_sum = std::string(prefix) + "match-kinds-summary.tsv";
-    File all(fn_all.c_str());
-    if (!all) return fail(VRP_ERR_OPEN, "cannot create " + fn_all);
-    File sum(fn_sum.c_str());
-    if (!sum) return fail(VRP_ERR_OPEN, "cannot create " + fn_sum);
-    static const char *const COLS = "QUERY_TP\tQTP_EXACT\tQTP_SHIFTED\tQTP_REGROUPED\tQTP_PARTIAL\tTRUTH_TP\tTTP_EXACT\tTTP_SHIFTED\tTTP_REGROUPED\tTTP_PARTIAL\n";
-    fprintf(all, "VAR_TYPE\tMIN_QUAL\t%s", COLS);
-    fprintf(sum, "VAR_TYPE\tTHRESHOLD\tMIN_QUAL\t%s", COLS);
-    // the ten cells of one (type, threshold index): each callset's total, then its four kinds
-    auto cells = [&](FILE *f, int type, int k) {
-        for (int cs = 0; cs < 2; cs++) {
-            const int64_t *c = kind_counts + (size_t(cs) * VPR_VARTYPES + type) * VPR_MK_KINDS * size_t(nq) + k;
-            long long tot = 0;
-            for (int j = 0; j < VPR_MK_KINDS; j++) tot += c[size_t(j) * nq];
-            fprintf(f, "%s%lld", cs ? "\t" : "", tot);
-            for (int j = 0; j < VPR_MK_KINDS; j++) fprintf(f, "\t%lld", (long long)c[size_t(j) * nq]);
-        }
-        fputc('\n', f);
-    };
-    for (int type = 0; type < VPR_VARTYPES; type++)
-        for (int qual = min_qual; qual <= max_qual; qual++) {
-            fprintf(all, "%s\t%d\t", VARTYPE_STR[type], qual);
-            cells(all, type, qual - min_qual);
-        }
-    for (int type = 0; type < VPR_VARTYPES; type++) {
-        const int quals[2] = {min_qual, best_qual_of(pr_counts, type, min_qual, max_qual)};
-        const char *const thresh[2] = {"NONE", "BEST"};
-        for (int i = 0; i < 2; i++) {
-            fprintf(sum, "%s\t%s\t%d\t", VARTYPE_STR[type], thresh[i], quals[i]);
-            cells(sum, type, quals[i] - min_qual);
-        }
-    }
-    if (!all.finish() || !sum.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn_all + " / " + fn_sum);
-    return VRP_OK;
+    const int n[2] = {VPR_MK_KINDS, VPR_MK_KINDS};
+    return write_label_counts("vrp_write_match_kinds", prefix, "match-kinds",
+                              "QUERY_TP\tQTP_EXACT\tQTP_SHIFTED\tQTP_REGROUPED\tQTP_PARTIAL\tTRUTH_TP\tTTP_EXACT\tTTP_SHIFTED\tTTP_REGROUPED\tTTP_PARTIAL\n",
+                              n, VPR_MK_KINDS, kind_counts, pr_counts, min_qual, max_qual);
 }
 
 extern "C" int vrp_write_bootstrap(const char *prefix, const int64_t *counts, const int64_t *counts_boot, int32_t n_rep, uint64_t seed,

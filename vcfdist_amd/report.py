@@ -177,30 +177,27 @@ def write_variant_strata(prefix, names, spec, n_query, n_truth):
            "vrp_write_variant_strata")
 
 
+def _write_label_counts(entry, prefix, label_counts, n_labels, counts, min_qual, max_qual):
+    """the two files of a label pass (vrp_<entry>): label_counts int64 [2][4][n_labels][nq] beside counts int64 [2][4][3][nq]"""
+    nq = max_qual - min_qual + 1
+    lc, cnt = np.ascontiguousarray(label_counts, np.int64), np.ascontiguousarray(counts, np.int64)
+    if lc.shape != (2, 4, n_labels, nq) or cnt.shape != (2, 4, 3, nq):
+        raise ReportError(f"{entry}: counts of shapes {lc.shape} and {cnt.shape} for {nq} thresholds")
+    fn = getattr(api.lib(), "vrp_" + entry)
+    fn.argtypes = [C.c_char_p, A.P_i64, A.P_i64, C.c_int32, C.c_int32]
+    _check(fn(prefix.encode(), A._ptr(lc, C.c_int64), A._ptr(cnt, C.c_int64), min_qual, max_qual), "vrp_" + entry)
+
+
 def write_error_classes(prefix, class_counts, counts, min_qual, max_qual):
     """error-classes.tsv and error-classes-summary.tsv (include/vcfdist_errclass.h): class_counts int64 [2][4][7][nq]
     (PrecisionRecall.errclass), counts int64 [2][4][3][nq] (summary.pr_counts) of the same evaluation, for the BEST threshold"""
-    nq = max_qual - min_qual + 1
-    cc, cnt = np.ascontiguousarray(class_counts, np.int64), np.ascontiguousarray(counts, np.int64)
-    if cc.shape != (2, 4, A.EC_CLASSES, nq) or cnt.shape != (2, 4, 3, nq):
-        raise ReportError(f"write_error_classes: counts of shapes {cc.shape} and {cnt.shape} for {nq} thresholds")
-    L = api.lib()
-    L.vrp_write_error_classes.argtypes = [C.c_char_p, A.P_i64, A.P_i64, C.c_int32, C.c_int32]
-    _check(L.vrp_write_error_classes(prefix.encode(), A._ptr(cc, C.c_int64), A._ptr(cnt, C.c_int64), min_qual, max_qual),
-           "vrp_write_error_classes")
+    _write_label_counts("write_error_classes", prefix, class_counts, A.EC_CLASSES, counts, min_qual, max_qual)
 
 
 def write_match_kinds(prefix, kind_counts, counts, min_qual, max_qual):
     """match-kinds.tsv and match-kinds-summary.tsv (include/vcfdist_matchkind.h): kind_counts int64 [2][4][4][nq]
     (PrecisionRecall.matchkind), counts int64 [2][4][3][nq] (summary.pr_counts) of the same evaluation, for the BEST threshold"""
-    nq = max_qual - min_qual + 1
-    kc, cnt = np.ascontiguousarray(kind_counts, np.int64), np.ascontiguousarray(counts, np.int64)
-    if kc.shape != (2, 4, A.MK_KINDS, nq) or cnt.shape != (2, 4, 3, nq):
-        raise ReportError(f"write_match_kinds: counts of shapes {kc.shape} and {cnt.shape} for {nq} thresholds")
-    L = api.lib()
-    L.vrp_write_match_kinds.argtypes = [C.c_char_p, A.P_i64, A.P_i64, C.c_int32, C.c_int32]
-    _check(L.vrp_write_match_kinds(prefix.encode(), A._ptr(kc, C.c_int64), A._ptr(cnt, C.c_int64), min_qual, max_qual),
-           "vrp_write_match_kinds")
+    _write_label_counts("write_match_kinds", prefix, kind_counts, A.MK_KINDS, counts, min_qual, max_qual)
 
 
 def write_bootstrap(prefix, counts, counts_boot, seed, min_qual, max_qual):
