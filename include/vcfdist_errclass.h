@@ -38,7 +38,23 @@
  * (at every threshold when callq < min_qual); ALL is the sum of the three types.  This is the counters' rule cut by class: for every
  * type and threshold the query's classes sum to vpr_pr_counts' query FP and the truth's classes to its truth FN.
  *
- * Device code: pr_errclass.hip (k_errclass).  No CPU fallback.
+ * Cut by stratum and resampled (the declarations are in vcfdist_labelcut.h, included below; tests/labelcut_model.py states this in
+ * terms of tests/errclass_model.py).  A label pass P is the error classes or the match kinds (vcfdist_matchkind.h); its bytes are b,
+ * its counts C_P(b), [2][VPR_VARTYPES][L][nq], by the counting rule above.
+ *   Stratum cut.  counts[k] = C_P(b masked by stratum k): the mask replaces the byte of every hap-variant whose bit k of the resident
+ *     membership words (vcfdist_strata.h) is clear by "no label".  Query and truth variants are each assigned by their own
+ *     membership, as everywhere else.  So for every stratum, type and threshold the query's classes sum to QUERY_FP of
+ *     vpr_pr_counts_strata and the truth's to its TRUTH_FN (the kinds: to QUERY_TP and TRUTH_TP), and a stratum that holds every
+ *     variant reproduces the unstratified counts exactly.
+ *   Replicates.  Replicate r's counts are C_P with every labelled variant counted w(seed, r, key[sc]) times, w exactly
+ *     vcfdist_bootstrap.h's weight; conditional on the phasing, as there.  An optional stratum k restricts them as above (-1: none).
+ *     For every replicate the labels sum to the matching column of vpr_pr_counts_boot.
+ *   Intervals.  For each label-count column at the NONE and BEST rows the replicate counts are sorted as integers;
+ *     LO = x[floor(0.025 n)], HI = x[ceil(0.975 n) - 1].  BEST's quality is the point estimate's, not re-optimised per replicate.
+ *   A cut uses the phasing the bytes were made under: the label call's phase-block words stay on the device, and the cut entries
+ *   take no pb_phase and no var_class.
+ *
+ * Device code: pr_errclass.hip (k_errclass); pr_labelcut.hip for the cuts.  No CPU fallback.
  */
 #ifndef VCFDIST_ERRCLASS_H_
 #define VCFDIST_ERRCLASS_H_
@@ -92,4 +108,9 @@ int vrp_write_error_classes(const char *prefix, const int64_t *class_counts, con
 #ifdef __cplusplus
 }
 #endif
+
+/* the class counts cut by stratum and resampled: the entries and the writers of stratified-error-classes*.tsv and
+   bootstrap-error-classes-summary.tsv */
+#include "vcfdist_labelcut.h"
+
 #endif /* VCFDIST_ERRCLASS_H_ */

@@ -77,4 +77,11 @@ int vrp_write_match_kinds(const char *prefix, const int64_t *kind_counts, const 
 #ifdef __cplusplus
 }
 #endif
+
+/* The kind counts cut by stratum and resampled, by the definitions of vcfdist_errclass.h ("Cut by stratum and resampled") with
+   the kinds as labels: for every stratum (replicate), type and threshold the query's kinds sum to QUERY_TP of vpr_pr_counts_strata
+   (vpr_pr_counts_boot) and the truth's to its TRUTH_TP.  The entries and the writers of stratified-match-kinds*.tsv and
+   bootstrap-match-kinds-summary.tsv: */
+#include "vcfdist_labelcut.h"
+
 #endif /* VCFDIST_MATCHKIND_H_ */

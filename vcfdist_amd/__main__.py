@@ -22,7 +22,10 @@ recall and F1, bootstrap-replicates.tsv, and with --stratify stratified-bootstra
 (default 1); works under several ranks in both --shard modes.  With --classify-errors every query FP and truth FN gets the first
 error class that applies (include/vcfdist_errclass.h: the right allele with the wrong genotype, on the aligned or on the other
 haplotype, another allele at the site, something within --error-window N bases (default 50), nothing), joined across the callsets on
-the GPU: error-classes.tsv and error-classes-summary.tsv; works under several ranks in both --shard modes.  With --classify-matches
+the GPU: error-classes.tsv and error-classes-summary.tsv; works under several ranks in both --shard modes.  With --cut-classes
+(beside a --classify-* option and a --stratify* option or --bootstrap) the label counts are cut by the strata and resampled as
+well (include/vcfdist_labelcut.h): stratified-error-classes*.tsv, bootstrap-error-classes-summary.tsv and the match-kinds
+counterparts; works under several ranks in both --shard modes.  With --classify-matches
 every TP of either callset gets the first match kind that applies (include/vcfdist_matchkind.h: exact -- what an allele-for-allele
 comparison finds --, shifted, regrouped, partial), from the resident sync groups on the GPU: match-kinds.tsv and
 match-kinds-summary.tsv; works under several ranks in both --shard modes."""
@@ -202,6 +205,19 @@ def label_contig(pr, variants, passes, args, pb):
         p["ms"] += getattr(pr, p["call"] + "_timing")()
 
 
+def cut_contig(pr, passes, strat, boot, args, keys):
+    """--cut-classes: the label counts of every pass cut by the strata and resampled (include/vcfdist_labelcut.h), behind
+    stratify_contig and bootstrap_contig: the label bytes and the share's membership words are both resident.  Added to the
+    pass's 'strata' / 'boot'."""
+    for p in passes:
+        if strat is not None:
+            p["strata"] += getattr(pr, p["call"] + "_strata")(args.min_qual, args.max_qual)
+            p["cut_ms"] += getattr(pr, p["call"] + "_cut_timing")()[0]
+        if boot is not None:
+            p["boot"] += getattr(pr, p["call"] + "_boot")(keys, boot["n"], boot["seed"], args.min_qual, args.max_qual)
+            p["cut_ms"] += getattr(pr, p["call"] + "_cut_timing")()[1]
+
+
 def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None, boot=None, ordinal=0, passes=()):
     """the precision/recall path on the GPU, phasing and counters for a prepared contig.  -> int64 counters [2][4][3][nq],
     n_sc, and what the writers need: (clusters after splitting, superclusters, results, phase sets, pb_phase, switches, flips).
@@ -246,6 +262,8 @@ def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None,
             stratify_contig(pr, prep, strat, args, pb)
         if boot is not None:
             bootstrap_contig(pr, boot, strat, args, pb, A.boot_keys(ordinal, np.arange(sc.n)))
+        if args.cut_classes:
+            cut_contig(pr, passes, strat, boot, args, A.boot_keys(ordinal, np.arange(sc.n)))
     else:
         from . import shard
         rank, world, cdev = part
@@ -273,6 +291,8 @@ def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None,
                 stratify_contig(pr, prep, strat, args, pb[idx], part_idx=idx)
             if boot is not None:
                 bootstrap_contig(pr, boot, strat, args, pb[idx], A.boot_keys(ordinal, idx))
+            if args.cut_classes:
+                cut_contig(pr, passes, strat, boot, args, A.boot_keys(ordinal, idx))
         else:
             counts = np.zeros((2, 4, 3, nq), np.int64)
         res = shard.gather_results(local, idx, whole.var_off, device=cdev)
@@ -459,6 +479,10 @@ def main(argv=None):
     ap.add_argument("--classify-matches", action="store_true",
                     help="how each TP was matched (exact: an allele-for-allele comparison finds it; shifted; regrouped; partial), "
                          "from the sync groups on the GPU: match-kinds.tsv, match-kinds-summary.tsv")
+    ap.add_argument("--cut-classes", action="store_true",
+                    help="cut the error classes / match kinds by the strata and resample them as well (needs --classify-errors or "
+                         "--classify-matches, and a --stratify* option or --bootstrap): stratified-error-classes.tsv, "
+                         "stratified-error-classes-summary.tsv, bootstrap-error-classes-summary.tsv and the match-kinds counterparts")
     ap.add_argument("--shard", default="superclusters", choices=["superclusters", "contigs"],
                     help="several ranks (torch.distributed.run, one per GPU): deal every contig's superclusters over the ranks "
                          "(default; balanced whatever the contigs' sizes) or whole contigs")
@@ -471,6 +495,10 @@ def main(argv=None):
         raise SystemExit("ERROR: Max supercluster size (-s) must be at least two larger than max variant size (-l).")
     if args.error_window is not None and not args.classify_errors:
         raise SystemExit("ERROR: --error-window needs --classify-errors")
+    if args.cut_classes and not (args.classify_errors or args.classify_matches):
+        raise SystemExit("ERROR: --cut-classes needs --classify-errors or --classify-matches")
+    if args.cut_classes and not (args.stratify or args.stratify_context or args.stratify_variants or args.bootstrap):
+        raise SystemExit("ERROR: --cut-classes needs --stratify, --stratify-context, --stratify-variants or --bootstrap")
     realigning = args.realign_query or args.realign_truth
     if realigning and (args.sub < 1 or args.extend < 1):
         raise SystemExit("ERROR: realignment needs a mismatch penalty (-x) and a gap-extension penalty (-e) of at least 1")
@@ -570,14 +598,27 @@ def main(argv=None):
             return (f"[vcfdist_amd] error classes: window {window}, {int(p['counts'][0, 3, :, 0].sum())} query FP and "
                     f"{int(p['counts'][1, 3, :, 0].sum())} truth FN classified, {p['ms']:.3f} ms on the device")
         passes.append(dict(call="errclass", extra=(window,), counts=np.zeros((2, 4, A.EC_CLASSES, nq), np.int64), ms=0.0,
-                           write=RP.write_error_classes, line=ec_line))
+                           write=RP.write_error_classes, line=ec_line, noun="error classes", write_strata=RP.write_error_classes_stratified,
+                           write_boot=RP.write_error_classes_bootstrap))
     if args.classify_matches:
         def mk_line(p):
             qk, tk = p["counts"][0, 3, :, 0], p["counts"][1, 3, :, 0]
             return (f"[vcfdist_amd] match kinds: query TP {int(qk[0])} exact, {int(qk[1])} shifted, {int(qk[2])} regrouped, {int(qk[3])} partial; "
                     f"truth TP {int(tk[0])} exact, {int(tk[1])} shifted, {int(tk[2])} regrouped, {int(tk[3])} partial, {p['ms']:.3f} ms on the device")
         passes.append(dict(call="matchkind", extra=(), counts=np.zeros((2, 4, A.MK_KINDS, nq), np.int64), ms=0.0,
-                           write=RP.write_match_kinds, line=mk_line))
+                           write=RP.write_match_kinds, line=mk_line, noun="match kinds", write_strata=RP.write_match_kinds_stratified,
+                           write_boot=RP.write_match_kinds_bootstrap))
+    # --cut-classes: the passes' counts once per stratum and per replicate, behind their counts in the all-reduced vector
+    cuts = []
+    if args.cut_classes:
+        for p in passes:
+            p["cut_ms"] = 0.0
+            if strat is not None:
+                p["strata"] = np.zeros((len(strat["names"]),) + p["counts"].shape, np.int64)
+                cuts.append((p, "strata"))
+            if boot is not None:
+                p["boot"] = np.zeros((boot["n"],) + p["counts"].shape, np.int64)
+                cuts.append((p, "boot"))
     empty = dict(pos=np.zeros(0, np.int32), rlen=np.zeros(0, np.int32), type=np.zeros(0, np.uint8), var_qual=np.zeros(0, np.float32),
                  phase_set=np.zeros(0, np.int32), ref_len=np.zeros(0, np.int32), alt_len=np.zeros(0, np.int32),
                  ref_off=np.zeros(0, np.int64), alt_off=np.zeros(0, np.int64), pool=np.zeros(1, np.uint8))
@@ -632,7 +673,7 @@ def main(argv=None):
         tail = [] if strat is None else [strat["counts"].ravel(), np.asarray([strat["vars"], strat["none"]], np.int64), strat["vs_members"].ravel()]
         if boot is not None:
             tail += [boot["counts"].ravel()] + ([] if strat is None else [boot["strat"].ravel()])
-        tail += [p["counts"].ravel() for p in passes]
+        tail += [p["counts"].ravel() for p in passes] + [p[key].ravel() for p, key in cuts]
         summed = shard.allreduce_tally(np.concatenate([total.ravel()] + tail), device=cdev)
         total = summed[:total.size].reshape(total.shape)
         at = total.size
@@ -652,6 +693,9 @@ def main(argv=None):
         for p in passes:
             p["counts"] = summed[at:at + p["counts"].size].reshape(p["counts"].shape)
             at += p["counts"].size
+        for p, key in cuts:
+            p[key] = summed[at:at + p[key].size].reshape(p[key].shape)
+            at += p[key].size
         if not by_sc:       # (by superclusters every rank already holds every contig's gathered tables)
             gathered = [None] * world
             dist.all_gather_object(gathered, reports)
@@ -666,6 +710,9 @@ def main(argv=None):
             for p in passes:
                 dist.all_gather_object(gathered, p["ms"])
                 p["ms"] = sum(gathered)
+                if args.cut_classes:
+                    dist.all_gather_object(gathered, p["cut_ms"])
+                    p["cut_ms"] = sum(gathered)
     rows = S.pr_summary(total, args.min_qual, args.max_qual)
     if dist_sets is not None:       # write_distance (printed even with -n) and write_edits, edit.cpp:134-280
         text = RP.write_distance(args.prefix, dist_sets, args.min_qual, args.max_qual, args.eval_sub, args.eval_open, args.eval_extend,
@@ -690,6 +737,11 @@ def main(argv=None):
                 if strat is not None:
                     RP.write_bootstrap_stratified(args.prefix, strat["names"], strat["counts"], boot["strat"], boot["seed"], args.min_qual,
                                                   args.max_qual)
+            for p, key in cuts:
+                if key == "strata":
+                    p["write_strata"](args.prefix, strat["names"], p["strata"], strat["counts"], args.min_qual, args.max_qual)
+                else:
+                    p["write_boot"](args.prefix, p["counts"], total, p["boot"], args.min_qual, args.max_qual)
             ctgs = [RP.Contig(c, ln, pl, fasta[c], sl, *tb) for c, ln, pl, sl, tb in (reports[k] for k in sorted(reports))]
             RP.write_results(args.prefix, ctgs, cmd=cmd, credit_threshold=args.credit_threshold)
             if args.realign_query:
@@ -707,6 +759,10 @@ def main(argv=None):
                 print(f"[vcfdist_amd] variant strata: {len(strat['vs'])} strata, {strat['vs_ms']:.3f} ms on the device", file=sys.stderr)
         for p in passes:
             print(p["line"](p), file=sys.stderr)
+        if args.cut_classes:
+            for p in passes:
+                what = ([f"{len(strat['names'])} strata"] if strat is not None else []) + ([f"{boot['n']} replicates"] if boot is not None else [])
+                print(f"[vcfdist_amd] {p['noun']} cut: {', '.join(what)}, {p['cut_ms']:.3f} ms on the device", file=sys.stderr)
         if boot is not None:
             print(f"[vcfdist_amd] bootstrap: {boot['n']} replicates, seed {boot['seed']}, {boot['ms']:.3f} ms on the device", file=sys.stderr)
         print("PRECISION-RECALL SUMMARY\n")

@@ -106,6 +106,14 @@ def lib():
         getattr(L, f"vpr_{name}_timing").argtypes = [H, C.POINTER(C.c_double)]
         getattr(L, f"vpr_{name}_names").restype = C.POINTER(C.c_char_p)
         getattr(L, f"vpr_{name}_names").argtypes = []
+        # the pass's counts cut by stratum and resampled (pr_labelcut.hip)
+        getattr(L, f"vpr_{name}_strata").argtypes = [H, C.c_int32, C.c_int32, A.P_i64]
+        getattr(L, f"vpr_allreduce_{name}_strata").argtypes = [H, C.c_void_p, C.c_int32, C.c_int32, A.P_i64]
+        cut_boot = [C.c_int32, C.c_int32, P_u64, C.c_uint64, C.c_int32, C.c_int32, A.P_i64]
+        getattr(L, f"vpr_{name}_boot").argtypes = [H] + cut_boot
+        getattr(L, f"vpr_allreduce_{name}_boot").argtypes = [H, C.c_void_p] + cut_boot
+        getattr(L, f"vpr_{name}_cut_timing").argtypes = [H, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        getattr(L, f"vpr_{name}_cut_info").argtypes = [H, C.POINTER(C.c_int32 * 6)]
     boot = [C.c_void_p, A.P_i32, C.c_int32, C.c_int32, P_u64, C.c_uint64, C.c_int32, C.c_int32, A.P_i64]
     L.vpr_pr_counts_boot.argtypes = [H] + boot
     L.vpr_allreduce_counts_boot.argtypes = [H, C.c_void_p] + boot
@@ -142,6 +150,10 @@ ERRCLASS_EXPORTED = ["vpr_errclass", "vpr_allreduce_errclass", "vpr_errclass_dow
 # include/vcfdist_matchkind.h
 MATCHKIND_EXPORTED = ["vpr_matchkind", "vpr_allreduce_matchkind", "vpr_matchkind_download", "vpr_matchkind_timing", "vpr_matchkind_names",
                       "vrp_write_match_kinds"]
+# include/vcfdist_errclass.h and include/vcfdist_matchkind.h: the label counts cut by stratum and resampled
+LABELCUT_EXPORTED = [f"vpr_{a}{p}_{c}" for p in ("errclass", "matchkind") for a in ("", "allreduce_") for c in ("strata", "boot")] + \
+                    [f"vpr_{p}_cut_{c}" for p in ("errclass", "matchkind") for c in ("timing", "info")] + \
+                    [f"vrp_write_{n}_{c}" for n in ("error_classes", "match_kinds") for c in ("stratified", "bootstrap")]
 # include/vcfdist_bootstrap.h
 BOOT_EXPORTED = ["vpr_pr_counts_boot", "vpr_allreduce_counts_boot", "vpr_boot_info", "vrp_write_bootstrap", "vrp_write_bootstrap_stratified"]
 # include/vcfdist_realign.h
@@ -569,6 +581,85 @@ class PrecisionRecall:
     def matchkind_timing(self):
         """ms of the last matchkind's kernel launches, from HIP events on the handle's stream"""
         return self._timing("vpr_matchkind_timing")
+
+    def _label_strata(self, name, n_labels, min_qual, max_qual, comm):
+        """vpr_<name>_strata (or its all-reduce with comm) -> int64 [n_strata][2][4][n_labels][nq]"""
+        n_strata = (getattr(self, "_strata", None) or (1, None))[0]      # (without words the call refuses: VPR_ERR_STATE)
+        out = np.zeros((n_strata, 2, 4, n_labels, max(max_qual - min_qual + 1, 1)), np.int64)
+        args = (min_qual, max_qual, A._ptr(out, C.c_int64))
+        if comm is None:
+            rc = getattr(lib(), f"vpr_{name}_strata")(self._h, *args)
+        else:
+            rc = getattr(lib(), f"vpr_allreduce_{name}_strata")(self._h, comm if isinstance(comm, C.c_void_p) else C.c_void_p(comm), *args)
+        self._chk(rc, f"vpr_{name}_strata")
+        return out
+
+    def _label_boot(self, name, n_labels, sc_key, n_rep, seed, min_qual, max_qual, stratum, comm):
+        """vpr_<name>_boot (or its all-reduce with comm) -> int64 [n_rep][2][4][n_labels][nq]"""
+        kp = None                                                        # (a null sc_key: the call refuses)
+        if sc_key is not None:
+            keys = np.ascontiguousarray(sc_key, np.uint64)
+            n_sc = self._batch.n_sc if self._batch is not None else 0
+            if keys.shape != (n_sc,):
+                raise VprError(f"vpr_{name}_boot: {keys.shape} keys for {n_sc} superclusters")
+            keys = keys if keys.size else np.zeros(1, np.uint64)
+            kp = A._ptr(keys, C.c_uint64)
+        n_rep = int(n_rep)
+        out = np.zeros((n_rep if 1 <= n_rep <= A.BOOT_MAX_REPLICATES else 1, 2, 4, n_labels, max(max_qual - min_qual + 1, 1)), np.int64)
+        args = (min_qual, max_qual, kp, int(seed) & (2 ** 64 - 1), n_rep, int(stratum), A._ptr(out, C.c_int64))
+        if comm is None:
+            rc = getattr(lib(), f"vpr_{name}_boot")(self._h, *args)
+        else:
+            rc = getattr(lib(), f"vpr_allreduce_{name}_boot")(self._h, comm if isinstance(comm, C.c_void_p) else C.c_void_p(comm), *args)
+        self._chk(rc, f"vpr_{name}_boot")
+        return out
+
+    def _label_cut_timing(self, name):
+        a, b = C.c_double(), C.c_double()
+        self._chk(getattr(lib(), f"vpr_{name}_cut_timing")(self._h, C.byref(a), C.byref(b)), f"vpr_{name}_cut_timing")
+        return a.value, b.value
+
+    def _label_cut_info(self, name):
+        g = (C.c_int32 * 6)()
+        self._chk(getattr(lib(), f"vpr_{name}_cut_info")(self._h, C.byref(g)), f"vpr_{name}_cut_info")
+        return dict(zip(("chunk", "chunks", "lds", "spans", "groups", "slices"), (int(x) for x in g)))
+
+    def errclass_strata(self, min_qual=0, max_qual=60, comm=None):
+        """The error-class counts of the last errclass cut by the resident membership words (include/vcfdist_errclass.h): stratum
+        k counts the class bytes of the variants whose bit k is set -> int64 [n_strata][2][4][7][nq].  The phasing and the
+        variant classes are the errclass call's; comm: an ncclComm_t (as an integer) for vpr_allreduce_errclass_strata."""
+        return self._label_strata("errclass", A.EC_CLASSES, min_qual, max_qual, comm)
+
+    def errclass_boot(self, sc_key, n_rep, seed=1, min_qual=0, max_qual=60, stratum=-1, comm=None):
+        """The bootstrap replicates of the error-class counts of the last errclass: replicate r counts every classified variant
+        w(seed, r, sc_key[its supercluster]) times (include/vcfdist_bootstrap.h's weight) -> int64 [n_rep][2][4][7][nq].
+        stratum >= 0: only the variants of that stratum of the resident membership words."""
+        return self._label_boot("errclass", A.EC_CLASSES, sc_key, n_rep, seed, min_qual, max_qual, stratum, comm)
+
+    def errclass_cut_timing(self):
+        """(ms of the last errclass_strata's kernels, ms of the last errclass_boot's) from HIP events on the handle's stream"""
+        return self._label_cut_timing("errclass")
+
+    def errclass_cut_info(self):
+        """the launch shapes of the last errclass_strata (chunk: strata of a workgroup, chunks, lds bytes) and errclass_boot
+        (spans, groups of 64 replicates, quality slices)"""
+        return self._label_cut_info("errclass")
+
+    def matchkind_strata(self, min_qual=0, max_qual=60, comm=None):
+        """errclass_strata for the match kinds of the last matchkind -> int64 [n_strata][2][4][4][nq]"""
+        return self._label_strata("matchkind", A.MK_KINDS, min_qual, max_qual, comm)
+
+    def matchkind_boot(self, sc_key, n_rep, seed=1, min_qual=0, max_qual=60, stratum=-1, comm=None):
+        """errclass_boot for the match kinds of the last matchkind -> int64 [n_rep][2][4][4][nq]"""
+        return self._label_boot("matchkind", A.MK_KINDS, sc_key, n_rep, seed, min_qual, max_qual, stratum, comm)
+
+    def matchkind_cut_timing(self):
+        """(ms of the last matchkind_strata's kernels, ms of the last matchkind_boot's)"""
+        return self._label_cut_timing("matchkind")
+
+    def matchkind_cut_info(self):
+        """errclass_cut_info for the match kinds"""
+        return self._label_cut_info("matchkind")
 
     def pr_counts_boot(self, var_class_per_slot, pb_phase, sc_key, n_rep, seed=1, min_qual=0, max_qual=60, stratum=-1, comm=None):
         """The bootstrap replicates of the counters of the last execute (include/vcfdist_bootstrap.h): replicate r counts every

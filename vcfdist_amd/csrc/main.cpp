@@ -14,6 +14,7 @@
 //               [--bootstrap N] [--bootstrap-seed S]
 //               [--classify-errors] [--error-window N]
 //               [--classify-matches]
+//               [--cut-classes]
 // With -d the distance metrics (edits_wrapper, dist.cpp:1908-2077) run on the GPU after each contig's precision/recall path
 // (include/vcfdist_distance.h), as the reference's main.cpp:223-238 runs them after precision_recall_threads_wrapper.
 // With -rq / -rt a callset is clustered and realigned on the GPU (include/vcfdist_realign.h) before the evaluation, in the order of
@@ -31,6 +32,10 @@
 // With --classify-matches every TP of either callset gets the first match kind that applies (include/vcfdist_matchkind.h: exact --
 // what an allele-for-allele comparison finds --, shifted, regrouped, partial), from the resident sync groups on the GPU:
 // match-kinds.tsv, match-kinds-summary.tsv.
+// With --cut-classes (beside --classify-errors / --classify-matches and a --stratify* option or --bootstrap) the label counts of
+// every active pass are cut by the strata and resampled as well, from the label bytes and the membership words that are resident
+// after the passes (include/vcfdist_labelcut.h): stratified-error-classes.tsv, stratified-error-classes-summary.tsv,
+// bootstrap-error-classes-summary.tsv and their match-kinds counterparts.  Without the option no file changes.
 // With --bootstrap N the counters are resampled N times on the GPU (include/vcfdist_bootstrap.h: a Poisson bootstrap over
 // superclusters, conditional on the phasing): bootstrap-precision-recall-summary.tsv with 95 % percentile intervals,
 // bootstrap-replicates.tsv, and with --stratify stratified-bootstrap-precision-recall-summary.tsv.
@@ -76,6 +81,7 @@ struct Args {
     bool classify_errors = false;      // --classify-errors
     int error_window = -1;             // --error-window: -1 not given (VPR_EC_DEFAULT_WINDOW)
     bool classify_matches = false;     // --classify-matches
+    bool cut_classes = false;          // --cut-classes
     uint64_t bootstrap_seed = 1;
 };
 
@@ -159,6 +165,7 @@ Args parse(int argc, char **argv) {
         else if (o == "--classify-errors") a.classify_errors = true;
         else if (o == "--error-window") a.error_window = error_window(need(i));
         else if (o == "--classify-matches") a.classify_matches = true;
+        else if (o == "--cut-classes") a.cut_classes = true;
         else if (o == "-rq" || o == "--realign-query") a.realign_query = true;
         else if (o == "-rt" || o == "--realign-truth") a.realign_truth = true;
         else if (o == "-ro" || o == "--realign-only") a.realign_only = true;
@@ -174,6 +181,9 @@ Args parse(int argc, char **argv) {
         die("ERROR: Max supercluster size (-s) must be at least two larger than max variant size (-l).");
     if (a.error_window >= 0 && !a.classify_errors) die("ERROR: --error-window needs --classify-errors");
     if (a.error_window < 0) a.error_window = VPR_EC_DEFAULT_WINDOW;
+    if (a.cut_classes && !a.classify_errors && !a.classify_matches) die("ERROR: --cut-classes needs --classify-errors or --classify-matches");
+    if (a.cut_classes && a.stratify.empty() && !a.stratify_context && !a.stratify_variants && !a.bootstrap)
+        die("ERROR: --cut-classes needs --stratify, --stratify-context, --stratify-variants or --bootstrap");
     if ((a.realign_query || a.realign_truth) && (a.sub < 1 || a.extend < 1))
         die("ERROR: realignment needs a mismatch penalty (-x) and a gap-extension penalty (-e) of at least 1");
     return a;
@@ -501,9 +511,30 @@ int main(int argc, char **argv) {
         double ms;
         int (*timing)(const vpr_handle *, double *);
         int (*write)(const char *, const int64_t *, const int64_t *, int32_t, int32_t);
+        // --cut-classes: the same counts [n_strata][...] and [n_rep][...] (empty without it), the entries, the writers, device ms
+        const char *noun;
+        std::vector<int64_t> strata, boot;
+        double cut_ms;
+        int (*cut_strata)(vpr_handle *, int32_t, int32_t, int64_t *);
+        int (*cut_boot)(vpr_handle *, int32_t, int32_t, const uint64_t *, uint64_t, int32_t, int32_t, int64_t *);
+        int (*cut_timing)(const vpr_handle *, double *, double *);
+        int (*write_strata)(const char *, const char *const *, int32_t, const int64_t *, const int64_t *, int32_t, int32_t);
+        int (*write_boot)(const char *, const int64_t *, const int64_t *, const int64_t *, int32_t, int32_t, int32_t);
     };
-    LabelPass ec{std::vector<int64_t>(A.classify_errors ? total.size() / 3 * VPR_EC_CLASSES : 0, 0), 0, vpr_errclass_timing, vrp_write_error_classes};
-    LabelPass mk{std::vector<int64_t>(A.classify_matches ? total.size() / 3 * VPR_MK_KINDS : 0, 0), 0, vpr_matchkind_timing, vrp_write_match_kinds};
+    auto label_pass = [&](bool on, size_t labels) {
+        LabelPass P{};
+        P.total.assign(on ? total.size() / 3 * labels : 0, 0);
+        P.strata.assign(on && A.cut_classes ? P.total.size() * size_t(n_strata) : 0, 0);
+        P.boot.assign(on && A.cut_classes ? P.total.size() * size_t(A.bootstrap) : 0, 0);
+        return P;
+    };
+    LabelPass ec = label_pass(A.classify_errors, VPR_EC_CLASSES), mk = label_pass(A.classify_matches, VPR_MK_KINDS);
+    ec.timing = vpr_errclass_timing; ec.write = vrp_write_error_classes; ec.noun = "error classes";
+    ec.cut_strata = vpr_errclass_strata; ec.cut_boot = vpr_errclass_boot; ec.cut_timing = vpr_errclass_cut_timing;
+    ec.write_strata = vrp_write_error_classes_stratified; ec.write_boot = vrp_write_error_classes_bootstrap;
+    mk.timing = vpr_matchkind_timing; mk.write = vrp_write_match_kinds; mk.noun = "match kinds";
+    mk.cut_strata = vpr_matchkind_strata; mk.cut_boot = vpr_matchkind_boot; mk.cut_timing = vpr_matchkind_cut_timing;
+    mk.write_strata = vrp_write_match_kinds_stratified; mk.write_boot = vrp_write_match_kinds_bootstrap;
     // --bootstrap: counts[n_rep][2][4][3][nq], with --stratify also [n_strata][n_rep][2][4][3][nq]; device ms of the launches
     std::vector<int64_t> boot_total(total.size() * size_t(A.bootstrap), 0), boot_strat(boot_total.size() * size_t(n_strata), 0);
     double boot_ms = 0;
@@ -683,6 +714,29 @@ int main(int argc, char **argv) {
                     boot_ms += ms;
                 }
             }
+            if (A.cut_classes) {   // the labels of the same evaluation cut and resampled: their bytes and the words are both resident now
+                const size_t ordinal = size_t(&ctg - contigs.data());
+                std::vector<uint64_t> keys(static_cast<size_t>(n_sc), 0);
+                for (int k = 0; k < n_sc; k++) keys[size_t(k)] = (uint64_t(ordinal) << 32) | uint64_t(k);
+                for (LabelPass *P : {&ec, &mk}) {
+                    if (P->total.empty()) continue;
+                    double ms_strata = 0, ms_boot = 0;
+                    std::vector<int64_t> c(std::max(P->strata.size(), P->boot.size()), 0);
+                    if (n_strata) {
+                        if (P->cut_strata(h, A.min_qual, A.max_qual, c.data()) || P->cut_timing(h, &ms_strata, &ms_boot))
+                            die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+                        for (size_t k = 0; k < P->strata.size(); k++) P->strata[k] += c[k];
+                        P->cut_ms += ms_strata;
+                    }
+                    if (A.bootstrap) {
+                        if (P->cut_boot(h, A.min_qual, A.max_qual, keys.data(), A.bootstrap_seed, A.bootstrap, -1, c.data()) ||
+                            P->cut_timing(h, &ms_strata, &ms_boot))
+                            die("ERROR: contig '%s': %s", ctg.c_str(), vpr_last_error(h));
+                        for (size_t k = 0; k < P->boot.size(); k++) P->boot[k] += c[k];
+                        P->cut_ms += ms_boot;
+                    }
+                }
+            }
             // the reference's WARN lines (dist.cpp:1203-1223) and -- loudly -- what this implementation did not evaluate
             static const struct { uint32_t bit; const char *text; } W[] = {
                 {VPR_ST_WARN_REF_ED, "Nonzero reference edit distance with no truth variants at ctg %s supercluster %d"},
@@ -770,6 +824,17 @@ int main(int argc, char **argv) {
             if (!P->total.empty() && P->write(A.prefix.c_str(), P->total.data(), total.data(), A.min_qual, A.max_qual)) die("ERROR: %s", vrp_last_error());
         if (A.bootstrap && vrp_write_bootstrap(A.prefix.c_str(), total.data(), boot_total.data(), A.bootstrap, A.bootstrap_seed, A.min_qual, A.max_qual))
             die("ERROR: %s", vrp_last_error());
+        if (A.cut_classes) {
+            std::vector<const char *> names;
+            for (const auto &n : strata.names) names.push_back(n.c_str());
+            for (const LabelPass *P : {&ec, &mk}) {
+                if (P->total.empty()) continue;
+                if (n_strata && P->write_strata(A.prefix.c_str(), names.data(), n_strata, P->strata.data(), strat_total.data(), A.min_qual, A.max_qual))
+                    die("ERROR: %s", vrp_last_error());
+                if (A.bootstrap && P->write_boot(A.prefix.c_str(), P->total.data(), total.data(), P->boot.data(), A.bootstrap, A.min_qual, A.max_qual))
+                    die("ERROR: %s", vrp_last_error());
+            }
+        }
         std::vector<vrp_contig> ctgs(outs.size());
         for (size_t k = 0; k < outs.size(); k++) {
             ContigOut *C = outs[k];
@@ -832,6 +897,14 @@ int main(int argc, char **argv) {
         fprintf(stderr, "[vcfdist_amd] match kinds: query TP %lld exact, %lld shifted, %lld regrouped, %lld partial; truth TP %lld exact, %lld shifted, "
                 "%lld regrouped, %lld partial, %.3f ms on the device\n", n[0][0], n[0][1], n[0][2], n[0][3], n[1][0], n[1][1], n[1][2], n[1][3], mk.ms);
     }
+    if (A.cut_classes)
+        for (const LabelPass *P : {&ec, &mk}) {
+            if (P->total.empty()) continue;
+            std::string what;
+            if (n_strata) what += std::to_string(n_strata) + " strata, ";
+            if (A.bootstrap) what += std::to_string(A.bootstrap) + " replicates, ";
+            fprintf(stderr, "[vcfdist_amd] %s cut: %s%.3f ms on the device\n", P->noun, what.c_str(), P->cut_ms);
+        }
     if (A.bootstrap)
         fprintf(stderr, "[vcfdist_amd] bootstrap: %d replicates, seed %llu, %.3f ms on the device\n", A.bootstrap, (unsigned long long)A.bootstrap_seed, boot_ms);
     printf("PRECISION-RECALL SUMMARY\n\n");

@@ -140,4 +140,27 @@ int vpr_errclass_timing(const vpr_handle *h, double *ms) { return label_timing(h
 
 const char *const *vpr_errclass_names(void) { return EC_NAMES; }
 
+// the counts cut by stratum and resampled (pr_labelcut.hip)
+int vpr_errclass_strata(vpr_handle *h, int32_t min_qual, int32_t max_qual, int64_t *counts) {
+    return labelcut_strata(h, EC, nullptr, min_qual, max_qual, counts);
+}
+
+int vpr_allreduce_errclass_strata(vpr_handle *h, void *nccl_comm, int32_t min_qual, int32_t max_qual, int64_t *counts) {
+    return nccl_comm ? labelcut_strata(h, EC, nccl_comm, min_qual, max_qual, counts) : VPR_ERR_ARG;
+}
+
+int vpr_errclass_boot(vpr_handle *h, int32_t min_qual, int32_t max_qual, const uint64_t *sc_key, uint64_t seed, int32_t n_rep, int32_t stratum,
+                   int64_t *counts) {
+    return labelcut_boot(h, EC, nullptr, min_qual, max_qual, sc_key, seed, n_rep, stratum, counts);
+}
+
+int vpr_allreduce_errclass_boot(vpr_handle *h, void *nccl_comm, int32_t min_qual, int32_t max_qual, const uint64_t *sc_key, uint64_t seed,
+                             int32_t n_rep, int32_t stratum, int64_t *counts) {
+    return nccl_comm ? labelcut_boot(h, EC, nccl_comm, min_qual, max_qual, sc_key, seed, n_rep, stratum, counts) : VPR_ERR_ARG;
+}
+
+int vpr_errclass_cut_timing(const vpr_handle *h, double *ms_strata, double *ms_boot) { return labelcut_timing(h, EC, ms_strata, ms_boot); }
+
+int vpr_errclass_cut_info(const vpr_handle *h, int32_t shape[6]) { return labelcut_info(h, EC, shape); }
+
 }  // extern "C"

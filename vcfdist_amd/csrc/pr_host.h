@@ -13,6 +13,7 @@
 //   pr_matchkind.hip the match kinds (include/vcfdist_matchkind.h): how each TP was matched
 //   pr_vartab.hip   the host check and the one-block upload of the variant tables those two share (pr_vartab.h)
 //   pr_label.hip    the host side those two share (pr_label.h): the front and back of a call, the fold, download, timing, release
+//   pr_labelcut.hip their counts cut by stratum and resampled (k_label_hist_strata, k_label_boot; pr_label.h)
 #ifndef PR_HOST_H_
 #define PR_HOST_H_
 #include <hip/hip_runtime.h>

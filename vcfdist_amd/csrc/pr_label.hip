@@ -28,6 +28,13 @@ int label_begin(vpr_handle *h, const LabelDesc &D, void *comm, const vpr_variant
     if (int rc = vartab_upload(h, D.entry, v, pool_len, &c->T)) return rc;
     HIPCHK(h, hipMemsetAsync(S->hist.p, 0, 2 * c->nb * 8, h->stream));
     if (int rc = pr_counts_inputs(h, D.entry, var_class, pb_phase, &c->d_pb)) return rc;
+    S->has_pb = c->d_pb != nullptr;      // the cuts' copy of the phasing of this call (h->d_pb is the next counters call's)
+    if (S->has_pb) {
+        char nomem_pb[128];
+        snprintf(nomem_pb, sizeof(nomem_pb), "%s: phase-block phasing: cannot allocate %%zu bytes on the device", D.entry);
+        if (int rc = S->pb.reserve(h, size_t(h->n_sc), nomem_pb)) return rc;
+        HIPCHK(h, hipMemcpyAsync(S->pb.p, c->d_pb, size_t(h->n_sc) * 4, hipMemcpyDeviceToDevice, h->stream));
+    }
     HIPCHK(h, hipEventRecord(S->ev[0], h->stream));
     return VPR_OK;
 }
@@ -94,8 +101,9 @@ int label_timing(const vpr_handle *h, const LabelDesc &D, double *ms) {
 void label_free(vpr_handle *h) {
     for (LabelState *&S : h->label) {
         if (!S) continue;
-        dev_release(h, S->bytes[0], S->bytes[1], S->bytes[2], S->bytes[3], S->hist);
+        dev_release(h, S->bytes[0], S->bytes[1], S->bytes[2], S->bytes[3], S->hist, S->pb, S->cut_hist, S->keys);
         for (int k = 0; k < 2; k++) if (S->ev[k]) (void)hipEventDestroy(S->ev[k]);
+        for (int k = 0; k < 2; k++) if (S->cut_ev[k]) (void)hipEventDestroy(S->cut_ev[k]);
         delete S;
         S = nullptr;
     }

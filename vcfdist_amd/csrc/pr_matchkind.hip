@@ -133,4 +133,27 @@ int vpr_matchkind_timing(const vpr_handle *h, double *ms) { return label_timing(
 
 const char *const *vpr_matchkind_names(void) { return MK_NAMES; }
 
+// the counts cut by stratum and resampled (pr_labelcut.hip)
+int vpr_matchkind_strata(vpr_handle *h, int32_t min_qual, int32_t max_qual, int64_t *counts) {
+    return labelcut_strata(h, MK, nullptr, min_qual, max_qual, counts);
+}
+
+int vpr_allreduce_matchkind_strata(vpr_handle *h, void *nccl_comm, int32_t min_qual, int32_t max_qual, int64_t *counts) {
+    return nccl_comm ? labelcut_strata(h, MK, nccl_comm, min_qual, max_qual, counts) : VPR_ERR_ARG;
+}
+
+int vpr_matchkind_boot(vpr_handle *h, int32_t min_qual, int32_t max_qual, const uint64_t *sc_key, uint64_t seed, int32_t n_rep, int32_t stratum,
+                   int64_t *counts) {
+    return labelcut_boot(h, MK, nullptr, min_qual, max_qual, sc_key, seed, n_rep, stratum, counts);
+}
+
+int vpr_allreduce_matchkind_boot(vpr_handle *h, void *nccl_comm, int32_t min_qual, int32_t max_qual, const uint64_t *sc_key, uint64_t seed,
+                             int32_t n_rep, int32_t stratum, int64_t *counts) {
+    return nccl_comm ? labelcut_boot(h, MK, nccl_comm, min_qual, max_qual, sc_key, seed, n_rep, stratum, counts) : VPR_ERR_ARG;
+}
+
+int vpr_matchkind_cut_timing(const vpr_handle *h, double *ms_strata, double *ms_boot) { return labelcut_timing(h, MK, ms_strata, ms_boot); }
+
+int vpr_matchkind_cut_info(const vpr_handle *h, int32_t shape[6]) { return labelcut_info(h, MK, shape); }
+
 }  // extern "C"

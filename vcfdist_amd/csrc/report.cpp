@@ -242,61 +242,156 @@ extern "C" int vrp_write_variant_strata(const char *prefix, const char *const *n
     return VRP_OK;
 }
 
-// The two files of a label pass (a feature that counts a label per variant: include/vcfdist_errclass.h, vcfdist_matchkind.h):
-// <stem>.tsv with a row per (type, threshold) and <stem>-summary.tsv with the NONE and BEST rows of each type.  counts
+// The files of a label pass (a feature that counts a label per variant: include/vcfdist_errclass.h, vcfdist_matchkind.h).  counts
 // [2][VPR_VARTYPES][stride][nq]; a row's cells are each callset's total, then its first n_labels[callset] labels, under `cols`
-static int write_label_counts(const char *entry, const char *prefix, const char *stem, const char *cols, const int n_labels[2], int stride,
-                              const int64_t *counts, const int64_t *pr_counts, int32_t min_qual, int32_t max_qual) {
-    if (!prefix || !counts || !pr_counts || max_qual < min_qual) return fail(VRP_ERR_ARG, std::string(entry) + ": bad argument");
+namespace {
+struct LabelTable { const char *stem, *cols; int n_labels[2]; int stride; };
+const LabelTable EC_TABLE = {"error-classes",
+                             "QUERY_FP\tFP_GT\tFP_SYNC\tFP_PHASE\tFP_SITE\tFP_NEAR\tFP_ALONE\tTRUTH_FN\tFN_GT\tFN_SYNC\tFN_PHASE\tFN_SITE\tFN_NEAR\tFN_ALONE\tFN_LOWQ\n",
+                             {VPR_EC_CLASSES - 1, VPR_EC_CLASSES}, VPR_EC_CLASSES};      // (the query has no LOWQ)
+const LabelTable MK_TABLE = {"match-kinds", "QUERY_TP\tQTP_EXACT\tQTP_SHIFTED\tQTP_REGROUPED\tQTP_PARTIAL\tTRUTH_TP\tTTP_EXACT\tTTP_SHIFTED\tTTP_REGROUPED\tTTP_PARTIAL\n",
+                             {VPR_MK_KINDS, VPR_MK_KINDS}, VPR_MK_KINDS};
+
+// the cells of one row (type, threshold index k), in column order
+void label_cells(const LabelTable &T, const int64_t *counts, int nq, int type, int k, std::vector<long long> *out) {
+    out->clear();
+    for (int cs = 0; cs < 2; cs++) {
+        const int64_t *c = counts + (size_t(cs) * VPR_VARTYPES + type) * T.stride * size_t(nq) + k;
+        long long tot = 0;
+        for (int j = 0; j < T.n_labels[cs]; j++) tot += c[size_t(j) * nq];
+        out->push_back(tot);
+        for (int j = 0; j < T.n_labels[cs]; j++) out->push_back((long long)c[size_t(j) * nq]);
+    }
+}
+
+// the rows of <stem>.tsv (a row per type and threshold) and <stem>-summary.tsv (the NONE and BEST rows of each type, BEST from
+// pr_counts by vpr_pr_summary's rule) for one set of label counts, every line behind `lead`
+void label_rows(FILE *all, FILE *sum, const char *lead, const LabelTable &T, const int64_t *counts, const int64_t *pr_counts, int min_qual,
+                int max_qual) {
     const int nq = max_qual - min_qual + 1;
-    const std::string fn_all = std::string(prefix) + stem + ".tsv", fn_sum = std::string(prefix) + stem + "-summary.tsv";
-    File all(fn_all.c_str());
-    if (!all) return fail(VRP_ERR_OPEN, "cannot create " + fn_all);
-    File sum(fn_sum.c_str());
-    if (!sum) return fail(VRP_ERR_OPEN, "cannot create " + fn_sum);
-    fprintf(all, "VAR_TYPE\tMIN_QUAL\t%s", cols);
-    fprintf(sum, "VAR_TYPE\tTHRESHOLD\tMIN_QUAL\t%s", cols);
+    std::vector<long long> row;
     auto cells = [&](FILE *f, int type, int k) {
-        for (int cs = 0; cs < 2; cs++) {
-            const int64_t *c = counts + (size_t(cs) * VPR_VARTYPES + type) * stride * size_t(nq) + k;
-            long long tot = 0;
-            for (int j = 0; j < n_labels[cs]; j++) tot += c[size_t(j) * nq];
-            fprintf(f, "%s%lld", cs ? "\t" : "", tot);
-            for (int j = 0; j < n_labels[cs]; j++) fprintf(f, "\t%lld", (long long)c[size_t(j) * nq]);
-        }
+        label_cells(T, counts, nq, type, k, &row);
+        for (size_t j = 0; j < row.size(); j++) fprintf(f, "%s%lld", j ? "\t" : "", row[j]);
         fputc('\n', f);
     };
     for (int type = 0; type < VPR_VARTYPES; type++)
         for (int qual = min_qual; qual <= max_qual; qual++) {
-            fprintf(all, "%s\t%d\t", VARTYPE_STR[type], qual);
+            fprintf(all, "%s%s\t%d\t", lead, VARTYPE_STR[type], qual);
             cells(all, type, qual - min_qual);
         }
     for (int type = 0; type < VPR_VARTYPES; type++) {
         const int quals[2] = {min_qual, best_qual_of(pr_counts, type, min_qual, max_qual)};
         const char *const thresh[2] = {"NONE", "BEST"};
         for (int i = 0; i < 2; i++) {
-            fprintf(sum, "%s\t%s\t%d\t", VARTYPE_STR[type], thresh[i], quals[i]);
+            fprintf(sum, "%s%s\t%s\t%d\t", lead, VARTYPE_STR[type], thresh[i], quals[i]);
             cells(sum, type, quals[i] - min_qual);
         }
+    }
+}
+
+// <stem>.tsv and <stem>-summary.tsv (names null), or stratified-<stem>.tsv and stratified-<stem>-summary.tsv: the same two
+// tables once per stratum behind a leading STRATUM column, counts[n_strata][...] and pr_counts[n_strata][...] (vpr_pr_counts_strata)
+int write_label_counts(const char *entry, const char *prefix, const LabelTable &T, const char *const *names, int32_t n_strata,
+                       const int64_t *counts, const int64_t *pr_counts, int32_t min_qual, int32_t max_qual) {
+    if (!prefix || max_qual < min_qual || (names ? n_strata < 0 || (n_strata && (!counts || !pr_counts)) : !counts || !pr_counts))
+        return fail(VRP_ERR_ARG, std::string(entry) + ": bad argument");
+    for (int32_t k = 0; names && k < n_strata; k++) if (!names[k]) return fail(VRP_ERR_ARG, std::string(entry) + ": null stratum name");
+    const int nq = max_qual - min_qual + 1;
+    const std::string head = std::string(prefix) + (names ? "stratified-" : "") + T.stem;
+    const std::string fn_all = head + ".tsv", fn_sum = head + "-summary.tsv";
+    File all(fn_all.c_str());
+    if (!all) return fail(VRP_ERR_OPEN, "cannot create " + fn_all);
+    File sum(fn_sum.c_str());
+    if (!sum) return fail(VRP_ERR_OPEN, "cannot create " + fn_sum);
+    fprintf(all, "%sVAR_TYPE\tMIN_QUAL\t%s", names ? "STRATUM\t" : "", T.cols);
+    fprintf(sum, "%sVAR_TYPE\tTHRESHOLD\tMIN_QUAL\t%s", names ? "STRATUM\t" : "", T.cols);
+    if (!names) {
+        label_rows(all, sum, "", T, counts, pr_counts, min_qual, max_qual);
+    } else {
+        const size_t nl1 = size_t(2) * VPR_VARTYPES * T.stride * size_t(nq), nc1 = size_t(2) * VPR_VARTYPES * 3 * size_t(nq);
+        for (int32_t k = 0; k < n_strata; k++)
+            label_rows(all, sum, (std::string(names[k]) + "\t").c_str(), T, counts + size_t(k) * nl1, pr_counts + size_t(k) * nc1, min_qual, max_qual);
     }
     if (!all.finish() || !sum.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn_all + " / " + fn_sum);
     return VRP_OK;
 }
 
+// bootstrap-<stem>-summary.tsv: the rows of <stem>-summary.tsv, every count column followed by its _LO and _HI -- the replicate
+// counts sorted as integers, x[floor(0.025 n)] and x[ceil(0.975 n) - 1]; BEST's quality is the point estimate's
+int write_label_bootstrap(const char *entry, const char *prefix, const LabelTable &T, const int64_t *counts, const int64_t *pr_counts,
+                          const int64_t *boot, int32_t n_rep, int32_t min_qual, int32_t max_qual) {
+    if (!prefix || !counts || !pr_counts || !boot || n_rep < 1 || max_qual < min_qual) return fail(VRP_ERR_ARG, std::string(entry) + ": bad argument");
+    const int nq = max_qual - min_qual + 1;
+    const size_t nl1 = size_t(2) * VPR_VARTYPES * T.stride * size_t(nq);
+    const std::string fn = std::string(prefix) + "bootstrap-" + T.stem + "-summary.tsv";
+    File sum(fn.c_str());
+    if (!sum) return fail(VRP_ERR_OPEN, "cannot create " + fn);
+    fputs("VAR_TYPE\tTHRESHOLD\tMIN_QUAL", sum);
+    for (const char *p = T.cols; *p && *p != '\n';) {
+        const char *e = p;
+        while (*e != '\t' && *e != '\n') e++;
+        const std::string col(p, e);
+        fprintf(sum, "\t%s\t%s_LO\t%s_HI", col.c_str(), col.c_str(), col.c_str());
+        p = *e == '\t' ? e + 1 : e;
+    }
+    fputc('\n', sum);
+    const size_t lo = size_t(n_rep) / 40, hi = (size_t(39) * size_t(n_rep) + 39) / 40 - 1;
+    std::vector<long long> point, row;
+    std::vector<std::vector<long long>> x;
+    for (int type = 0; type < VPR_VARTYPES; type++) {
+        const int quals[2] = {min_qual, best_qual_of(pr_counts, type, min_qual, max_qual)};
+        const char *const thresh[2] = {"NONE", "BEST"};
+        for (int i = 0; i < 2; i++) {
+            label_cells(T, counts, nq, type, quals[i] - min_qual, &point);
+            x.assign(point.size(), std::vector<long long>(size_t(n_rep)));
+            for (int r = 0; r < n_rep; r++) {
+                label_cells(T, boot + size_t(r) * nl1, nq, type, quals[i] - min_qual, &row);
+                for (size_t j = 0; j < row.size(); j++) x[j][size_t(r)] = row[j];
+            }
+            fprintf(sum, "%s\t%s\t%d", VARTYPE_STR[type], thresh[i], quals[i]);
+            for (size_t j = 0; j < point.size(); j++) {
+                std::sort(x[j].begin(), x[j].end());
+                fprintf(sum, "\t%lld\t%lld\t%lld", point[j], x[j][lo], x[j][hi]);
+            }
+            fputc('\n', sum);
+        }
+    }
+    if (!sum.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn);
+    return VRP_OK;
+}
+}  // namespace
+
 extern "C" int vrp_write_error_classes(const char *prefix, const int64_t *class_counts, const int64_t *pr_counts, int32_t min_qual,
                                        int32_t max_qual) {
-    const int n[2] = {VPR_EC_CLASSES - 1, VPR_EC_CLASSES};      // (the query has no LOWQ)
-    return write_label_counts("vrp_write_error_classes", prefix, "error-classes",
-                              "QUERY_FP\tFP_GT\tFP_SYNC\tFP_PHASE\tFP_SITE\tFP_NEAR\tFP_ALONE\tTRUTH_FN\tFN_GT\tFN_SYNC\tFN_PHASE\tFN_SITE\tFN_NEAR\tFN_ALONE\tFN_LOWQ\n",
-                              n, VPR_EC_CLASSES, class_counts, pr_counts, min_qual, max_qual);
+    return write_label_counts("vrp_write_error_classes", prefix, EC_TABLE, nullptr, 0, class_counts, pr_counts, min_qual, max_qual);
 }
 
 extern "C" int vrp_write_match_kinds(const char *prefix, const int64_t *kind_counts, const int64_t *pr_counts, int32_t min_qual,
                                      int32_t max_qual) {
-    const int n[2] = {VPR_MK_KINDS, VPR_MK_KINDS};
-    return write_label_counts("vrp_write_match_kinds", prefix, "match-kinds",
-                              "QUERY_TP\tQTP_EXACT\tQTP_SHIFTED\tQTP_REGROUPED\tQTP_PARTIAL\tTRUTH_TP\tTTP_EXACT\tTTP_SHIFTED\tTTP_REGROUPED\tTTP_PARTIAL\n",
-                              n, VPR_MK_KINDS, kind_counts, pr_counts, min_qual, max_qual);
+    return write_label_counts("vrp_write_match_kinds", prefix, MK_TABLE, nullptr, 0, kind_counts, pr_counts, min_qual, max_qual);
+}
+
+extern "C" int vrp_write_error_classes_stratified(const char *prefix, const char *const *names, int32_t n_strata, const int64_t *class_counts,
+                                                  const int64_t *pr_counts, int32_t min_qual, int32_t max_qual) {
+    if (!names) return fail(VRP_ERR_ARG, "vrp_write_error_classes_stratified: bad argument");
+    return write_label_counts("vrp_write_error_classes_stratified", prefix, EC_TABLE, names, n_strata, class_counts, pr_counts, min_qual, max_qual);
+}
+
+extern "C" int vrp_write_match_kinds_stratified(const char *prefix, const char *const *names, int32_t n_strata, const int64_t *kind_counts,
+                                                const int64_t *pr_counts, int32_t min_qual, int32_t max_qual) {
+    if (!names) return fail(VRP_ERR_ARG, "vrp_write_match_kinds_stratified: bad argument");
+    return write_label_counts("vrp_write_match_kinds_stratified", prefix, MK_TABLE, names, n_strata, kind_counts, pr_counts, min_qual, max_qual);
+}
+
+extern "C" int vrp_write_error_classes_bootstrap(const char *prefix, const int64_t *class_counts, const int64_t *pr_counts,
+                                                 const int64_t *class_boot, int32_t n_rep, int32_t min_qual, int32_t max_qual) {
+    return write_label_bootstrap("vrp_write_error_classes_bootstrap", prefix, EC_TABLE, class_counts, pr_counts, class_boot, n_rep, min_qual, max_qual);
+}
+
+extern "C" int vrp_write_match_kinds_bootstrap(const char *prefix, const int64_t *kind_counts, const int64_t *pr_counts, const int64_t *kind_boot,
+                                               int32_t n_rep, int32_t min_qual, int32_t max_qual) {
+    return write_label_bootstrap("vrp_write_match_kinds_bootstrap", prefix, MK_TABLE, kind_counts, pr_counts, kind_boot, n_rep, min_qual, max_qual);
 }
 
 extern "C" int vrp_write_bootstrap(const char *prefix, const int64_t *counts, const int64_t *counts_boot, int32_t n_rep, uint64_t seed,

@@ -200,6 +200,57 @@ def write_match_kinds(prefix, kind_counts, counts, min_qual, max_qual):
     _write_label_counts("write_match_kinds", prefix, kind_counts, A.MK_KINDS, counts, min_qual, max_qual)
 
 
+def _write_label_stratified(entry, prefix, names, label_counts, n_labels, counts, min_qual, max_qual):
+    """the two stratified files of a label pass (vrp_<entry>): label_counts int64 [n_strata][2][4][n_labels][nq] beside counts
+    int64 [n_strata][2][4][3][nq] (summary.pr_counts_strata)"""
+    nq, n = max_qual - min_qual + 1, len(names)
+    lc, cnt = np.ascontiguousarray(label_counts, np.int64), np.ascontiguousarray(counts, np.int64)
+    if lc.shape != (n, 2, 4, n_labels, nq) or cnt.shape != (n, 2, 4, 3, nq):
+        raise ReportError(f"{entry}: {n} stratum names, counts of shapes {lc.shape} and {cnt.shape} for {nq} thresholds")
+    fn = getattr(api.lib(), "vrp_" + entry)
+    fn.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, A.P_i64, A.P_i64, C.c_int32, C.c_int32]
+    arr = (C.c_char_p * max(n, 1))(*[x.encode() for x in names])
+    if n == 0:
+        lc = cnt = np.zeros(1, np.int64)
+    _check(fn(prefix.encode(), arr, n, A._ptr(lc, C.c_int64), A._ptr(cnt, C.c_int64), min_qual, max_qual), "vrp_" + entry)
+
+
+def _write_label_bootstrap(entry, prefix, label_counts, n_labels, counts, label_boot, min_qual, max_qual):
+    """the bootstrap file of a label pass (vrp_<entry>): label_boot int64 [n_rep][2][4][n_labels][nq] beside the point counts"""
+    nq = max_qual - min_qual + 1
+    lc, cnt, boot = (np.ascontiguousarray(x, np.int64) for x in (label_counts, counts, label_boot))
+    if lc.shape != (2, 4, n_labels, nq) or cnt.shape != (2, 4, 3, nq) or boot.ndim != 5 or boot.shape[0] < 1 or boot.shape[1:] != lc.shape:
+        raise ReportError(f"{entry}: counts of shapes {lc.shape}, {cnt.shape} and {boot.shape} for {nq} thresholds")
+    fn = getattr(api.lib(), "vrp_" + entry)
+    fn.argtypes = [C.c_char_p, A.P_i64, A.P_i64, A.P_i64, C.c_int32, C.c_int32, C.c_int32]
+    _check(fn(prefix.encode(), A._ptr(lc, C.c_int64), A._ptr(cnt, C.c_int64), A._ptr(boot, C.c_int64), boot.shape[0], min_qual, max_qual),
+           "vrp_" + entry)
+
+
+def write_error_classes_stratified(prefix, names, class_counts, counts, min_qual, max_qual):
+    """stratified-error-classes.tsv and stratified-error-classes-summary.tsv: class_counts int64 [n_strata][2][4][7][nq]
+    (PrecisionRecall.errclass_strata), counts int64 [n_strata][2][4][3][nq] (summary.pr_counts_strata), for BEST per stratum"""
+    _write_label_stratified("write_error_classes_stratified", prefix, names, class_counts, A.EC_CLASSES, counts, min_qual, max_qual)
+
+
+def write_match_kinds_stratified(prefix, names, kind_counts, counts, min_qual, max_qual):
+    """stratified-match-kinds.tsv and stratified-match-kinds-summary.tsv: kind_counts int64 [n_strata][2][4][4][nq]
+    (PrecisionRecall.matchkind_strata), counts int64 [n_strata][2][4][3][nq] (summary.pr_counts_strata)"""
+    _write_label_stratified("write_match_kinds_stratified", prefix, names, kind_counts, A.MK_KINDS, counts, min_qual, max_qual)
+
+
+def write_error_classes_bootstrap(prefix, class_counts, counts, class_boot, min_qual, max_qual):
+    """bootstrap-error-classes-summary.tsv: the point counts of write_error_classes and class_boot int64 [n_rep][2][4][7][nq]
+    (PrecisionRecall.errclass_boot); every count column is followed by its 95 % percentile bounds, integers"""
+    _write_label_bootstrap("write_error_classes_bootstrap", prefix, class_counts, A.EC_CLASSES, counts, class_boot, min_qual, max_qual)
+
+
+def write_match_kinds_bootstrap(prefix, kind_counts, counts, kind_boot, min_qual, max_qual):
+    """bootstrap-match-kinds-summary.tsv: the point counts of write_match_kinds and kind_boot int64 [n_rep][2][4][4][nq]
+    (PrecisionRecall.matchkind_boot)"""
+    _write_label_bootstrap("write_match_kinds_bootstrap", prefix, kind_counts, A.MK_KINDS, counts, kind_boot, min_qual, max_qual)
+
+
 def write_bootstrap(prefix, counts, counts_boot, seed, min_qual, max_qual):
     """bootstrap-precision-recall-summary.tsv and bootstrap-replicates.tsv (include/vcfdist_bootstrap.h): counts int64
     [2][4][3][nq] (summary.pr_counts), counts_boot int64 [n_rep][2][4][3][nq] (summary.pr_counts_boot)"""
