@@ -539,6 +539,23 @@ def ctx_gc(lo, hi, window, slop=0):
     return VprContextStratum(CTX_GC, 0, 0, 0, lo, hi, window, slop)
 
 
+# ---- include/vcfdist_repeats.h
+REP_MIN_K, REP_MAX_K = 4, 32
+REP_MAX_SPEC = 8
+
+
+class VprRepeatStratum(C.Structure):
+    _fields_ = [("k", C.c_int32), ("slop", C.c_int32)]
+
+    def __repr__(self):
+        return f"repeat(k={self.k}, slop={self.slop})"
+
+
+def rep_kmer(k, slop=0):
+    """a repeat stratum: the bases covered by a k-mer that occurs more than once in the genome (either strand), padded by slop"""
+    return VprRepeatStratum(k, slop)
+
+
 # ---- include/vcfdist_varstrata.h
 VS_SIZE, VS_TI, VS_TV, VS_HOM, VS_HET, VS_NEAR = range(6)
 VS_MAX_SPEC = 64

@@ -95,6 +95,13 @@ def lib():
     L.vpr_context_download_intervals.argtypes = [H, A.P_i32, A.P_i32]
     L.vpr_context_info.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.vpr_context_timing.argtypes = [H, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.vpr_repeats_default.argtypes = [C.POINTER(C.POINTER(A.VprRepeatStratum)), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.c_int32)]
+    L.vpr_repeat_intervals.argtypes = [H, C.c_int32, A.P_i64, A.P_u8, C.POINTER(A.VprRepeatStratum), C.c_int32]
+    L.vpr_repeat_interval_counts.argtypes = [H, A.P_i64]
+    L.vpr_repeat_download_intervals.argtypes = [H, A.P_i32, A.P_i32]
+    L.vpr_repeat_stats.argtypes = [H, A.P_i64, A.P_i64]
+    L.vpr_repeat_timing.argtypes = [H] + [C.POINTER(C.c_double)] * 4
+    L.vpr_repeat_sort_floor.argtypes = [H, C.c_int64, C.c_int32, C.c_uint64, C.POINTER(C.c_double)]
     L.vpr_varstrata_default.argtypes = [C.POINTER(C.POINTER(A.VprVariantStratum)), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.c_int32)]
     L.vpr_varstrata_masks.argtypes = [H, C.POINTER(A.VprVariants), C.POINTER(A.VprVariantStratum), C.c_int32, C.c_int32]
     L.vpr_varstrata_timing.argtypes = [H, C.POINTER(C.c_double)]
@@ -142,6 +149,9 @@ STRATA_EXPORTED = ["vpr_strata_masks", "vpr_strata_download_masks", "vpr_strata_
 # include/vcfdist_context.h
 CONTEXT_EXPORTED = ["vpr_context_default", "vpr_context_masks", "vpr_context_interval_counts", "vpr_context_download_intervals",
                     "vpr_context_info", "vpr_context_timing"]
+# include/vcfdist_repeats.h
+REPEATS_EXPORTED = ["vpr_repeats_default", "vpr_repeat_intervals", "vpr_repeat_interval_counts", "vpr_repeat_download_intervals",
+                    "vpr_repeat_stats", "vpr_repeat_timing", "vpr_repeat_sort_floor", "vrp_write_repeat_bed"]
 # include/vcfdist_varstrata.h
 VARSTRATA_EXPORTED = ["vpr_varstrata_default", "vpr_varstrata_masks", "vpr_varstrata_timing", "vrp_write_variant_strata"]
 # include/vcfdist_errclass.h
@@ -214,6 +224,15 @@ def context_default():
     if rc:
         raise VprError(f"vpr_context_default failed ({rc})")
     return [names[k].decode() for k in range(n.value)], [A.VprContextStratum.from_buffer_copy(spec[k]) for k in range(n.value)]
+
+
+def repeats_default():
+    """the command lines' default repeat strata (vpr_repeats_default): (names, [A.VprRepeatStratum])"""
+    spec, names, n = C.POINTER(A.VprRepeatStratum)(), C.POINTER(C.c_char_p)(), C.c_int32()
+    rc = lib().vpr_repeats_default(C.byref(spec), C.byref(names), C.byref(n))
+    if rc:
+        raise VprError(f"vpr_repeats_default failed ({rc})")
+    return [names[k].decode() for k in range(n.value)], [A.VprRepeatStratum.from_buffer_copy(spec[k]) for k in range(n.value)]
 
 
 def varstrata_default():
@@ -503,6 +522,55 @@ class PrecisionRecall:
         a, b = C.c_double(), C.c_double()
         self._chk(lib().vpr_context_timing(self._h, C.byref(a), C.byref(b)), "vpr_context_timing")
         return a.value, b.value
+
+    def repeat_intervals(self, contigs, spec):
+        """The repeat strata (include/vcfdist_repeats.h): the intervals of every entry of `spec` (A.rep_kmer) for the whole genome,
+        built on the device in one call.  contigs: the sequences (bytes or uint8 arrays) in order, or (ctg_off, ctg_seq) as the
+        library takes them.  The handle needs no batch."""
+        if isinstance(contigs, tuple):
+            off, seq = np.ascontiguousarray(contigs[0], np.int64), contigs[1]
+        else:
+            parts = [np.frombuffer(s, np.uint8) if isinstance(s, (bytes, bytearray)) else np.asarray(s, np.uint8) for s in contigs]
+            off = np.concatenate([[0], np.cumsum([len(x) for x in parts])]).astype(np.int64)
+            seq = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+        if seq is not None:
+            seq = np.ascontiguousarray(seq, np.uint8)
+            if seq.size == 0:
+                seq = np.zeros(1, np.uint8)
+        arr = (A.VprRepeatStratum * max(len(spec), 1))(*spec) if spec is not None else None
+        self._repeats = None
+        self._chk(lib().vpr_repeat_intervals(self._h, len(off) - 1, A._ptr(off, C.c_int64), A._ptr(seq, C.c_uint8) if seq is not None else None,
+                                             arr, len(spec) if spec is not None else 1), "vpr_repeat_intervals")
+        self._repeats = (len(spec), len(off) - 1)
+
+    def download_repeat_intervals(self):
+        """the intervals of the last repeat_intervals: rows[spec][contig] = (starts, stops), int32 arrays, 0-based half-open"""
+        n_spec, n_ctg = getattr(self, "_repeats", None) or (0, 1)      # (before a call the library refuses: VPR_ERR_STATE)
+        off = np.zeros(n_spec * n_ctg + 1, np.int64)
+        self._chk(lib().vpr_repeat_interval_counts(self._h, A._ptr(off, C.c_int64)), "vpr_repeat_interval_counts")
+        st, sp = np.zeros(max(int(off[-1]), 1), np.int32), np.zeros(max(int(off[-1]), 1), np.int32)
+        self._chk(lib().vpr_repeat_download_intervals(self._h, A._ptr(st, C.c_int32), A._ptr(sp, C.c_int32)), "vpr_repeat_download_intervals")
+        return [[(st[off[k * n_ctg + c]:off[k * n_ctg + c + 1]], sp[off[k * n_ctg + c]:off[k * n_ctg + c + 1]]) for c in range(n_ctg)]
+                for k in range(n_spec)]
+
+    def repeat_stats(self):
+        """(valid starts, repeated starts) per entry of the last repeat_intervals: two int64 arrays"""
+        n_spec = (getattr(self, "_repeats", None) or (1, 1))[0]
+        a, b = np.zeros(n_spec, np.int64), np.zeros(n_spec, np.int64)
+        self._chk(lib().vpr_repeat_stats(self._h, A._ptr(a, C.c_int64), A._ptr(b, C.c_int64)), "vpr_repeat_stats")
+        return a, b
+
+    def repeat_timing(self):
+        """(ms_pack, ms_sort, ms_mark, ms_intervals) of the last repeat_intervals, from HIP events on the handle's stream"""
+        t = [C.c_double() for _ in range(4)]
+        self._chk(lib().vpr_repeat_timing(self._h, *[C.byref(x) for x in t]), "vpr_repeat_timing")
+        return tuple(x.value for x in t)
+
+    def repeat_sort_floor(self, n, k, seed=1):
+        """ms of the bare sort of repeat_intervals (key bits [0, 2k)) over n random keys: the floor under an entry with n valid starts"""
+        ms = C.c_double()
+        self._chk(lib().vpr_repeat_sort_floor(self._h, int(n), int(k), int(seed), C.byref(ms)), "vpr_repeat_sort_floor")
+        return ms.value
 
     def varstrata_masks(self, variants, spec, append=False):
         """The variant strata (include/vcfdist_varstrata.h): the bits of every entry of `spec` (A.vs_size / A.vs_kind / A.vs_near)

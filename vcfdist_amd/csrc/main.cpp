@@ -9,7 +9,7 @@
 //   vcfdist_gpu <query.vcf[.gz]> <truth.vcf[.gz]> <ref.fasta[.gz]> [-b regions.bed] [-p prefix] [-n] [-c biwfa | gap N | size N]
 //               [-l max variant size] [-s max supercluster size] [-mn / -mx qual] [-f filters] [-i iterations] [-x -o -e penalties]
 //               [-ct credit threshold] [-pt phasing threshold] [-sv threshold] [--reach-min-gap N] [--strict] [--device N]
-//               [-d] [-ex -eo -ee evaluation penalties] [-rq] [-rt] [-ro] [--stratify strata.tsv] [--stratify-context]
+//               [-d] [-ex -eo -ee evaluation penalties] [-rq] [-rt] [-ro] [--stratify strata.tsv] [--stratify-repeats] [--stratify-context]
 //               [--stratify-variants]
 //               [--bootstrap N] [--bootstrap-seed S]
 //               [--classify-errors] [--error-window N]
@@ -23,6 +23,8 @@
 // by region on the GPU (include/vcfdist_strata.h): stratified-precision-recall.tsv and stratified-precision-recall-summary.tsv.
 // With --stratify-context the default sequence-context strata (homopolymers, short tandem repeats, GC bands: intervals built on
 // the GPU from the FASTA, include/vcfdist_context.h) follow the list's strata, or stand alone; context-strata.bed holds them.
+// With --stratify-repeats the default repeat strata (where the FASTA is not unique: include/vcfdist_repeats.h, one genome-wide pass
+// on the GPU before the contig loop) follow the list's strata, in front of the context strata; repeat-strata.bed holds them.
 // With --stratify-variants the default variant strata (transitions / transversions, indel size bins, hom / het, isolated / crowded:
 // bits made on the GPU from the variant tables, include/vcfdist_varstrata.h) follow those, or stand alone; variant-strata.tsv lists
 // them with their numbers of members.
@@ -60,6 +62,7 @@
 #include "../../include/vcfdist_realign.h"
 #include "../../include/vcfdist_report.h"
 #include "../../include/vcfdist_context.h"
+#include "../../include/vcfdist_repeats.h"
 #include "../../include/vcfdist_strata.h"
 #include "../../include/vcfdist_varstrata.h"
 #include "../../include/vcfdist_errclass.h"
@@ -69,7 +72,7 @@ namespace {
 
 struct Args {
     std::string query, truth, fasta, bed, filter, prefix = "./", cluster = "biwfa", stratify;
-    bool stratify_context = false, stratify_variants = false;
+    bool stratify_context = false, stratify_variants = false, stratify_repeats = false;
     int max_size = 5000, min_qual = 0, max_qual = 60, cluster_gap = 50, max_iterations = 4, max_supercluster_size = 10000;
     int sub = 5, open = 6, extend = 2, sv_threshold = 50, reach_min_gap = 10, device = 0;
     int eval_sub = 3, eval_open = 2, eval_extend = 1;      // globals.h:52-55
@@ -159,6 +162,7 @@ Args parse(int argc, char **argv) {
         else if (o == "-d" || o == "--distance") a.distance = true;
         else if (o == "--stratify") a.stratify = need(i);
         else if (o == "--stratify-context") a.stratify_context = true;
+        else if (o == "--stratify-repeats") a.stratify_repeats = true;
         else if (o == "--stratify-variants") a.stratify_variants = true;
         else if (o == "--bootstrap") a.bootstrap = bootstrap_replicates(need(i));
         else if (o == "--bootstrap-seed") a.bootstrap_seed = bootstrap_seed(need(i));
@@ -182,7 +186,7 @@ Args parse(int argc, char **argv) {
     if (a.error_window >= 0 && !a.classify_errors) die("ERROR: --error-window needs --classify-errors");
     if (a.error_window < 0) a.error_window = VPR_EC_DEFAULT_WINDOW;
     if (a.cut_classes && !a.classify_errors && !a.classify_matches) die("ERROR: --cut-classes needs --classify-errors or --classify-matches");
-    if (a.cut_classes && a.stratify.empty() && !a.stratify_context && !a.stratify_variants && !a.bootstrap)
+    if (a.cut_classes && a.stratify.empty() && !a.stratify_repeats && !a.stratify_context && !a.stratify_variants && !a.bootstrap)
         die("ERROR: --cut-classes needs --stratify, --stratify-context, --stratify-variants or --bootstrap");
     if ((a.realign_query || a.realign_truth) && (a.sub < 1 || a.extend < 1))
         die("ERROR: realignment needs a mismatch penalty (-x) and a gap-extension penalty (-e) of at least 1");
@@ -411,7 +415,25 @@ int main(int argc, char **argv) {
     }
     Strata strata;
     if (!A.stratify.empty()) strata = read_strata(A.stratify);
-    // --stratify-context: the default sequence-context strata (include/vcfdist_context.h) behind the list's
+    // --stratify-repeats: the default repeat strata (include/vcfdist_repeats.h) behind the list's; their intervals come from one
+    // genome-wide pass in front of the contig loop and then travel with the list's rows
+    const int n_list = int(strata.names.size());
+    const vpr_repeat_stratum *rep_spec = nullptr;
+    const char *const *rep_names = nullptr;
+    int32_t n_rep = 0;
+    if (A.stratify_repeats) {
+        if (vpr_repeats_default(&rep_spec, &rep_names, &n_rep)) die("ERROR: vpr_repeats_default failed");
+        for (int k = 0; k < n_rep; k++) {
+            if (find(strata.names, rep_names[k]) >= 0)
+                die("ERROR: strata list '%s': duplicate stratum name '%s' (a repeat stratum of --stratify-repeats)", A.stratify.c_str(), rep_names[k]);
+            strata.names.push_back(rep_names[k]);
+        }
+    }
+    std::vector<int64_t> rep_off;                                               // [n_rep * FASTA contigs + 1], row = stratum * contigs + contig
+    std::vector<int32_t> rep_start, rep_stop;
+    std::vector<int64_t> rep_valid(size_t(n_rep), 0), rep_repeated(size_t(n_rep), 0);
+    double rep_ms = 0;
+    // --stratify-context: the default sequence-context strata (include/vcfdist_context.h) behind the list's and the repeat strata
     const int n_bed = int(strata.names.size());
     const vpr_context_stratum *ctx_spec = nullptr;
     const char *const *ctx_names = nullptr;
@@ -542,6 +564,20 @@ int main(int argc, char **argv) {
     memset(&cfg, 0, sizeof(cfg));
     cfg.device = A.device; cfg.max_qual = float(A.max_qual); cfg.credit_threshold = A.credit_threshold; cfg.phase_threshold = A.phase_threshold;
     cfg.band_mode = 1;
+    if (n_rep) {           // the genome-wide pass over all contigs of the FASTA, on a handle of its own: the evaluation has the memory back
+        vpr_handle *hr = nullptr;
+        if (vpr_create(&cfg, &hr)) { fprintf(stderr, "vpr_create: %s\n", vpr_last_error(nullptr)); return 2; }
+        rep_off.assign(size_t(n_rep) * size_t(fa->n_ctg) + 1, 0);
+        if (vpr_repeat_intervals(hr, fa->n_ctg, fa->ctg_off, fa->seq, rep_spec, n_rep) || vpr_repeat_interval_counts(hr, rep_off.data()))
+            die("ERROR: %s", vpr_last_error(hr));
+        rep_start.assign(size_t(rep_off.back()) + 1, 0); rep_stop.assign(size_t(rep_off.back()) + 1, 0);
+        double ms[4] = {0, 0, 0, 0};
+        if (vpr_repeat_download_intervals(hr, rep_start.data(), rep_stop.data()) || vpr_repeat_stats(hr, rep_valid.data(), rep_repeated.data()) ||
+            vpr_repeat_timing(hr, &ms[0], &ms[1], &ms[2], &ms[3]))
+            die("ERROR: %s", vpr_last_error(hr));
+        rep_ms = ms[0] + ms[1] + ms[2] + ms[3];
+        vpr_destroy(hr);
+    }
     vpr_handle *h = nullptr;
     if (vpr_create(&cfg, &h)) { fprintf(stderr, "vpr_create: %s\n", vpr_last_error(nullptr)); return 2; }
 
@@ -659,12 +695,18 @@ int main(int argc, char **argv) {
             if (n_strata) {        // the same evaluation, cut by region: membership words, then the histogram per stratum
                 std::vector<int64_t> iv_off(size_t(n_bed) + 1, 0);
                 std::vector<int32_t> iv_start, iv_stop;
-                for (int k = 0; k < n_bed; k++) {
+                for (int k = 0; k < n_list; k++) {
                     int64_t n = 0;
                     const int32_t *st = nullptr, *sp = nullptr;
                     if (vio_bed_intervals(strata.beds[size_t(k)], ctg.c_str(), &n, &st, &sp)) die("ERROR: %s", vio_last_error());
                     iv_start.insert(iv_start.end(), st, st + n); iv_stop.insert(iv_stop.end(), sp, sp + n);
                     iv_off[size_t(k) + 1] = int64_t(iv_start.size());
+                }
+                for (int k = 0; k < n_rep; k++) {      // the contig's rows of the repeat strata, as ordinary BED rows behind the list's
+                    const size_t r = size_t(k) * size_t(fa->n_ctg) + size_t(fi);
+                    iv_start.insert(iv_start.end(), rep_start.begin() + rep_off[r], rep_start.begin() + rep_off[r + 1]);
+                    iv_stop.insert(iv_stop.end(), rep_stop.begin() + rep_off[r], rep_stop.begin() + rep_off[r + 1]);
+                    iv_off[size_t(n_list + k) + 1] = int64_t(iv_start.size());
                 }
                 const vpr_strata ST = {n_bed, 1, iv_off.data(), iv_start.data(), iv_stop.data()};
                 std::vector<int64_t> sc_counts(strat_total.size(), 0);
@@ -812,6 +854,24 @@ int main(int argc, char **argv) {
             if (A.bootstrap && vrp_write_bootstrap_stratified(A.prefix.c_str(), names.data(), n_strata, strat_total.data(), boot_strat.data(), A.bootstrap,
                                                               A.bootstrap_seed, A.min_qual, A.max_qual))
                 die("ERROR: %s", vrp_last_error());
+            if (n_rep) {           // repeat-strata.bed: the evaluated contigs in evaluation order, rows contig-major
+                std::vector<const char *> cn;
+                std::vector<int64_t> off(1, 0);
+                std::vector<int32_t> st, sp;
+                for (const auto &c : contigs) {
+                    cn.push_back(c.c_str());
+                    const int fi = find(fn, c);
+                    for (int k = 0; k < n_rep; k++) {
+                        const size_t r = size_t(k) * size_t(fa->n_ctg) + size_t(fi);
+                        st.insert(st.end(), rep_start.begin() + rep_off[r], rep_start.begin() + rep_off[r + 1]);
+                        sp.insert(sp.end(), rep_stop.begin() + rep_off[r], rep_stop.begin() + rep_off[r + 1]);
+                        off.push_back(int64_t(st.size()));
+                    }
+                }
+                st.push_back(0); sp.push_back(0);      // (never empty: a pointer is wanted)
+                if (vrp_write_repeat_bed(A.prefix.c_str(), cn.data(), int32_t(cn.size()), rep_names, n_rep, off.data(), st.data(), sp.data()))
+                    die("ERROR: %s", vrp_last_error());
+            }
             if (n_ctx) {
                 std::vector<const char *> cn;
                 for (const auto &c : ctx_contigs) cn.push_back(c.c_str());
@@ -875,6 +935,17 @@ int main(int argc, char **argv) {
     if (n_strata)
         fprintf(stderr, "[vcfdist_amd] stratified: %d strata, %lld of %lld hap-variants in none of them\n", n_strata, (long long)strat_none,
                 (long long)strat_vars);
+    if (n_rep) {
+        std::string starts;
+        for (int k = 0; k < n_rep; k++) {
+            char buf[128];
+            snprintf(buf, sizeof(buf), "%lld valid and %lld repeated starts (k=%d), ", (long long)rep_valid[size_t(k)], (long long)rep_repeated[size_t(k)],
+                     rep_spec[k].k);
+            starts += buf;
+        }
+        fprintf(stderr, "[vcfdist_amd] repeat strata: %lld intervals of %d strata, %s%.3f ms on the device\n", (long long)rep_off.back(), n_rep,
+                starts.c_str(), rep_ms);
+    }
     if (n_ctx)
         fprintf(stderr, "[vcfdist_amd] context strata: %lld intervals of %d strata, %.3f ms on the device\n", (long long)ctx_start.size(), n_ctx, ctx_ms);
     if (n_vs)

@@ -1162,6 +1162,7 @@ void vpr_destroy(vpr_handle *h) {
     (void)hipSetDevice(h->cfg.device);
     dist_free(h);
     context_free(h);
+    repeats_free(h);
     free_batch(h);
     for (auto &b : h->dev_cache) (void)x_free(h, b.p, SITE);
     for (int k = 0; k < 4; k++)

@@ -12,6 +12,7 @@
 //   6. k_ctx_group, a scan, k_ctx_merge         kept tracts have increasing starts and stops, so "starts a new merged interval"
 //                                               is a comparison with the previous kept tract alone
 //   7. k_ctx_rows                               the rows' offsets (one bisection per contig)
+// Passes 2 to 7 are ctx_intervals_from_flags (pr_host.h), which pr_repeats.hip calls with flag bits of its own.
 // No pass compacts with atomics: every output index is a prefix sum, so two calls give identical arrays.  No pass walks a
 // run: a 100 kb homopolymer is 100 k flag bits and one start / end pair.
 //
@@ -21,6 +22,7 @@
 // is not split), which bounds the per-base part; the sequence itself (one byte per base) is resident for the call.
 #include "pr_host.h"
 #include "pr_plan.h"
+#include "pr_ctxdev.h"
 #include "../../include/vcfdist_context.h"
 
 struct ContextState {
@@ -51,38 +53,10 @@ const vpr_context_stratum DEFAULT_SPEC[] = {
 const char *const DEFAULT_NAMES[] = {"hp_4to6", "hp_7to11", "hp_ge12", "tr_di_ge10", "tr_tri_ge14", "tr_quad_ge19",
                                      "gc_lt25", "gc_25to30", "gc_30to55", "gc_55to65", "gc_ge65"};
 
-__device__ inline bool called(unsigned x) { return x == 'A' || x == 'C' || x == 'G' || x == 'T'; }
-
 // 0x01 in every byte of x that equals the byte repeated in c4
 __device__ inline uint32_t eq_bytes(uint32_t x, uint32_t c4) {
     const uint32_t t = x ^ c4;
     return ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t | 0x7F7F7F7Fu) >> 7;
-}
-
-// contig of base G of the concatenation (0 <= G < ctg_off[n_ctg]): the largest c with ctg_off[c] <= G, which is not empty
-__device__ inline int ctg_of(const int64_t *__restrict__ ctg_off, int n_ctg, int64_t G) {
-    int lo = 0, hi = n_ctg;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (ctg_off[mid] <= G) lo = mid; else hi = mid; }
-    return lo;
-}
-
-// exclusive prefix sum of one value per lane over a workgroup of 256; *total: the workgroup's sum
-__device__ inline uint32_t block_scan(uint32_t v, uint32_t *lds /* [4] */, uint32_t *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { const uint32_t s = lds[k]; if (k < wave) before += s; all += s; }
-    __syncthreads();
-    *total = all;
-    return before + inc - v;
 }
 
 }  // namespace
@@ -278,14 +252,14 @@ __device__ inline void run_masks(const uint64_t *__restrict__ words, int64_t nw,
 
 // tract r of the run lists: false when the filter drops it, else its contig and its padded, clipped interval
 __device__ inline bool tract_of(int64_t r, const uint32_t *__restrict__ run_st, const uint32_t *__restrict__ run_en, int64_t T0,
-                                const uint8_t *__restrict__ seq, const int64_t *__restrict__ ctg_off, int n_ctg, int p, int min_len,
+                                const uint8_t *__restrict__ seq, const int64_t *__restrict__ ctg_off, int n_ctg, int p, int prim, int min_len,
                                 int max_len, int slop, int *c_out, int32_t *ps, int32_t *pe) {
     const int64_t a = run_st[r], b = int64_t(run_en[r]) + 1, Ga = T0 + a;
     const int c = ctg_of(ctg_off, n_ctg, Ga);
     const int64_t cs = ctg_off[c], L = ctg_off[c + 1] - cs, ts = Ga - cs - p, len = b - a + p;
     if (len < min_len || (max_len && len > max_len)) return false;
     const uint8_t *__restrict__ s = seq + cs + ts;
-    for (int q = 1; q < p; q++) {
+    for (int q = 1; q < prim; q++) {     // (prim: p for a period stratum, 0 where the primitive test does not apply)
         if (p % q) continue;
         bool rep = true;
         for (int k = q; k < p; k++) rep = rep && s[k] == s[k - q];
@@ -331,23 +305,23 @@ __global__ void __launch_bounds__(256) k_ctx_run_write(const uint64_t *__restric
 
 __global__ void __launch_bounds__(256) k_ctx_keep(int64_t n_run, const uint32_t *__restrict__ run_st, const uint32_t *__restrict__ run_en,
                                                   int64_t T0, const uint8_t *__restrict__ seq, const int64_t *__restrict__ ctg_off, int n_ctg,
-                                                  int p, int min_len, int max_len, int slop, uint32_t *__restrict__ keep /* [n_run + 1] */) {
+                                                  int p, int prim, int min_len, int max_len, int slop, uint32_t *__restrict__ keep /* [n_run + 1] */) {
     const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
     if (r > n_run) return;
     int c; int32_t ps, pe;
-    keep[r] = r < n_run && tract_of(r, run_st, run_en, T0, seq, ctg_off, n_ctg, p, min_len, max_len, slop, &c, &ps, &pe);
+    keep[r] = r < n_run && tract_of(r, run_st, run_en, T0, seq, ctg_off, n_ctg, p, prim, min_len, max_len, slop, &c, &ps, &pe);
 }
 
 __global__ void __launch_bounds__(256) k_ctx_compact(int64_t n_run, const uint32_t *__restrict__ run_st, const uint32_t *__restrict__ run_en,
                                                      int64_t T0, const uint8_t *__restrict__ seq, const int64_t *__restrict__ ctg_off, int n_ctg,
-                                                     int p, int min_len, int max_len, int slop, const uint32_t *__restrict__ keep,
+                                                     int p, int prim, int min_len, int max_len, int slop, const uint32_t *__restrict__ keep,
                                                      const uint32_t *__restrict__ keep_scan, int32_t *__restrict__ k_ctg,
                                                      int32_t *__restrict__ k_ps, int32_t *__restrict__ k_pe, uint32_t *__restrict__ n_kept) {
     const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
     if (r == 0) *n_kept = keep_scan[n_run];
     if (r >= n_run || !keep[r]) return;
     int c; int32_t ps, pe;
-    (void)tract_of(r, run_st, run_en, T0, seq, ctg_off, n_ctg, p, min_len, max_len, slop, &c, &ps, &pe);
+    (void)tract_of(r, run_st, run_en, T0, seq, ctg_off, n_ctg, p, prim, min_len, max_len, slop, &c, &ps, &pe);
     const uint32_t k = keep_scan[r];
     k_ctg[k] = c; k_ps[k] = ps; k_pe[k] = pe;
 }
@@ -388,26 +362,8 @@ __global__ void __launch_bounds__(256) k_ctx_rows(const int32_t *__restrict__ ou
 
 namespace {
 
-// room for `bytes` in a buffer of the call, a quarter more than asked for when it has to grow; keep_bytes of the old content survive
-template <typename T>
-int ctx_need(vpr_handle *h, DevBuf<T> &b, size_t bytes, const char *what, size_t keep_bytes = 0) {
-    if (b.cap * sizeof(T) >= bytes) return VPR_OK;
-    const std::string nomem = std::string("vpr_context_masks: cannot allocate %zu bytes on the device (") + what + ")";
-    return b.reserve(h, std::max<size_t>((bytes + bytes / 4 + 255) & ~size_t(255), 256) / sizeof(T), nomem.c_str(), keep_bytes / sizeof(T));
-}
 template <typename T>
 T *as(const DevBuf<uint8_t> &b) { return reinterpret_cast<T *>(b.p); }
-
-struct Work {
-    vpr_handle *h;
-    DevBuf<uint8_t> seq, ctg_off, bits, cnt, runs, keep, kept, out_ctg, tmp, small;
-    explicit Work(vpr_handle *h_) : h(h_) {}
-    ~Work() {
-        (void)hipStreamSynchronize(h->stream);
-        dev_release(h, seq, ctg_off, bits, cnt, runs, keep, kept, out_ctg, tmp, small);
-    }
-    int need(DevBuf<uint8_t> &b, size_t bytes, const char *what) { return ctx_need(h, b, bytes, what); }
-};
 
 int check_spec(vpr_handle *h, const vpr_context_stratum *spec, int32_t n_spec) {
     for (int k = 0; k < n_spec; k++) {
@@ -429,19 +385,14 @@ int check_spec(vpr_handle *h, const vpr_context_stratum *spec, int32_t n_spec) {
     return VPR_OK;
 }
 
-int64_t piece_bases() {       // (VPR_CONTEXT_PIECE_BASES: a smaller piece, so that a test's few contigs make several)
-    const char *e = getenv("VPR_CONTEXT_PIECE_BASES");
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? int64_t(v) : PIECE_BASES;
-}
-
 unsigned blocks_of(int64_t n) { return unsigned((n + 255) / 256); }
 
-int scan_u32(vpr_handle *h, Work &W, const uint32_t *in, uint32_t *out, size_t n) {
+int scan_u32(CtxWork &W, const uint32_t *in, uint32_t *out, size_t n) {
+    vpr_handle *h = W.h;
     size_t bytes = 0;
-    if (vplan_exclusive_scan_u32(nullptr, &bytes, in, out, n, h->stream) != 0) return fail(h, VPR_ERR_DEVICE, "vpr_context_masks: scan workspace query failed");
+    if (vplan_exclusive_scan_u32(nullptr, &bytes, in, out, n, h->stream) != 0) return fail(h, VPR_ERR_DEVICE, "%s: scan workspace query failed", W.entry);
     if (int rc = W.need(W.tmp, bytes + 256, "scan workspace")) return rc;
-    if (vplan_exclusive_scan_u32(W.tmp.p, &bytes, in, out, n, h->stream) != 0) return fail(h, VPR_ERR_DEVICE, "vpr_context_masks: scan failed");
+    if (vplan_exclusive_scan_u32(W.tmp.p, &bytes, in, out, n, h->stream) != 0) return fail(h, VPR_ERR_DEVICE, "%s: scan failed", W.entry);
     return VPR_OK;
 }
 
@@ -452,6 +403,94 @@ void launch_period(unsigned blocks, hipStream_t st, const uint8_t *seq, const in
 }
 
 }  // namespace
+
+int64_t ctx_piece_bases() {   // (VPR_CONTEXT_PIECE_BASES: a smaller piece, so that a test's few contigs make several)
+    const char *e = getenv("VPR_CONTEXT_PIECE_BASES");
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? int64_t(v) : PIECE_BASES;
+}
+
+int CtxWork::seg_begin() {
+    if (!open) { HIPCHK(h, hipEventRecord(ev[0], h->stream)); open = true; }
+    return VPR_OK;
+}
+int CtxWork::seg_end() {
+    HIPCHK(h, hipEventRecord(ev[1], h->stream));
+    HIPCHK(h, x_sync(h, h->stream, SITE));
+    float t = 0;
+    (void)hipEventElapsedTime(&t, ev[0], ev[1]);
+    *ms += t; open = false;
+    return VPR_OK;
+}
+
+// passes 2 to 7 of the file's header; a timed segment may be under way on entry, and one is on return
+int ctx_intervals_from_flags(CtxWork &W, const uint64_t *words, int64_t nw, int64_t T0, int64_t g0, const uint8_t *d_seq, const int64_t *d_ctg,
+                             int n_ctg, int c0, int c1, const CtxRunRule &rule, int spec_entry, DevBuf<int32_t> &d_start, DevBuf<int32_t> &d_stop,
+                             size_t have, int64_t *row_off, uint32_t *n_out_p) {
+    vpr_handle *h = W.h;
+    const int64_t n_blk = (nw + 255) / 256;
+    const int min_run = rule.min_run, p = rule.p, prim = rule.primitive ? rule.p : 0, min_len = rule.min_len, max_len = rule.max_len;
+    uint32_t *d_nkept = as<uint32_t>(W.small);
+    uint32_t n_run = 0, n_run_en = 0, n_out = 0;
+    *n_out_p = 0;
+    if (int rc = W.seg_begin()) return rc;
+    if (nw) {
+        if (int rc = W.need(W.cnt, size_t(n_blk + 1) * 16, "workgroup counts")) return rc;
+        uint32_t *cnt_st = as<uint32_t>(W.cnt), *cnt_en = cnt_st + (n_blk + 1), *off_st = cnt_en + (n_blk + 1), *off_en = off_st + (n_blk + 1);
+        HIPCHK(h, hipMemsetAsync(cnt_st + n_blk, 0, 4, h->stream));
+        HIPCHK(h, hipMemsetAsync(cnt_en + n_blk, 0, 4, h->stream));
+        hipLaunchKernelGGL(k_ctx_run_count, dim3(unsigned(n_blk)), dim3(256), 0, h->stream, words, nw, T0, d_ctg, n_ctg, g0, min_run, cnt_st, cnt_en);
+        HIPCHK(h, hipGetLastError());
+        if (int rc = scan_u32(W, cnt_st, off_st, size_t(n_blk + 1))) return rc;
+        if (int rc = scan_u32(W, cnt_en, off_en, size_t(n_blk + 1))) return rc;
+        HIPCHK(h, hipMemcpyAsync(&n_run, off_st + n_blk, 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(&n_run_en, off_en + n_blk, 4, hipMemcpyDeviceToHost, h->stream));
+        if (int rc = W.seg_end()) return rc;
+        if (n_run != n_run_en) return fail(h, VPR_ERR_DEVICE, "%s: entry %d: %u run starts and %u run ends", W.entry, spec_entry, n_run, n_run_en);
+        if (n_run) {
+            const size_t n1 = size_t(n_run) + 1;
+            if (int rc = W.need(W.runs, n1 * 8, "run lists")) return rc;
+            if (int rc = W.need(W.keep, n1 * 8, "tract flags")) return rc;
+            if (int rc = W.need(W.kept, n1 * 12, "kept tracts")) return rc;
+            uint32_t *run_st = as<uint32_t>(W.runs), *run_en = run_st + n1;
+            uint32_t *flag = as<uint32_t>(W.keep), *flag_scan = flag + n1;
+            int32_t *k_ctg = as<int32_t>(W.kept), *k_ps = k_ctg + n1, *k_pe = k_ps + n1;
+            if (int rc = W.seg_begin()) return rc;
+            hipLaunchKernelGGL(k_ctx_run_write, dim3(unsigned(n_blk)), dim3(256), 0, h->stream, words, nw, T0, d_ctg, n_ctg, g0, min_run, off_st, off_en,
+                               run_st, run_en);
+            HIPCHK(h, hipGetLastError());
+            hipLaunchKernelGGL(k_ctx_keep, dim3(blocks_of(int64_t(n1))), dim3(256), 0, h->stream, int64_t(n_run), run_st, run_en, T0, d_seq, d_ctg,
+                               n_ctg, p, prim, min_len, max_len, rule.slop, flag);
+            HIPCHK(h, hipGetLastError());
+            if (int rc = scan_u32(W, flag, flag_scan, n1)) return rc;
+            hipLaunchKernelGGL(k_ctx_compact, dim3(blocks_of(n_run)), dim3(256), 0, h->stream, int64_t(n_run), run_st, run_en, T0, d_seq, d_ctg,
+                               n_ctg, p, prim, min_len, max_len, rule.slop, flag, flag_scan, k_ctg, k_ps, k_pe, d_nkept);
+            HIPCHK(h, hipGetLastError());
+            hipLaunchKernelGGL(k_ctx_group, dim3(blocks_of(int64_t(n1))), dim3(256), 0, h->stream, int64_t(n_run), d_nkept, k_ctg, k_ps, k_pe, flag);
+            HIPCHK(h, hipGetLastError());
+            if (int rc = scan_u32(W, flag, flag_scan, n1)) return rc;
+            HIPCHK(h, hipMemcpyAsync(&n_out, flag_scan + n_run, 4, hipMemcpyDeviceToHost, h->stream));
+            if (int rc = W.seg_end()) return rc;
+            const size_t want = have + n_out;
+            if (int rc = ctx_need(h, W.entry, d_start, want * 4, "intervals", have * 4)) return rc;
+            if (int rc = ctx_need(h, W.entry, d_stop, want * 4, "intervals", have * 4)) return rc;
+            if (int rc = W.need(W.out_ctg, (size_t(n_out) + 1) * 4, "interval contigs")) return rc;
+            if (int rc = W.seg_begin()) return rc;
+            if (n_out) {
+                hipLaunchKernelGGL(k_ctx_merge, dim3(blocks_of(n_run)), dim3(256), 0, h->stream, d_nkept, k_ctg, k_ps, k_pe, flag, flag_scan,
+                                   as<int32_t>(W.out_ctg), d_start.p + have, d_stop.p + have);
+                HIPCHK(h, hipGetLastError());
+            }
+        }
+    }
+    if (int rc = W.need(W.out_ctg, 4, "interval contigs")) return rc;
+    if (int rc = W.seg_begin()) return rc;
+    hipLaunchKernelGGL(k_ctx_rows, dim3(blocks_of(c1 - c0 + 1)), dim3(256), 0, h->stream, as<int32_t>(W.out_ctg), int64_t(n_out), c0, c1,
+                       int64_t(have), row_off);
+    HIPCHK(h, hipGetLastError());
+    *n_out_p = n_out;
+    return VPR_OK;
+}
 
 void context_free(vpr_handle *h) {
     ContextState *S = h->context;
@@ -495,10 +534,11 @@ int vpr_context_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *be
     const size_t bed_rows = size_t(n_bed) * size_t(n_ctg), all_rows = bed_rows + size_t(n_spec) * size_t(n_ctg);
     const int64_t n_iv_bed = bed ? bed->iv_off[bed_rows] : 0;
     S->n_spec = n_spec; S->n_ctg = n_ctg; S->n_bed = n_bed; S->n_iv_bed = n_iv_bed;
-    if (int rc = ctx_need(h, S->d_off, 8 * (all_rows + 1), "row offsets")) return rc;
+    const char *const entry = "vpr_context_masks";
+    if (int rc = ctx_need(h, entry, S->d_off, 8 * (all_rows + 1), "row offsets")) return rc;
     const size_t iv0 = size_t(n_iv_bed) + 1024;
-    if (int rc = ctx_need(h, S->d_start, 4 * iv0, "intervals")) return rc;
-    if (int rc = ctx_need(h, S->d_stop, 4 * iv0, "intervals")) return rc;
+    if (int rc = ctx_need(h, entry, S->d_start, 4 * iv0, "intervals")) return rc;
+    if (int rc = ctx_need(h, entry, S->d_stop, 4 * iv0, "intervals")) return rc;
     if (bed) {
         HIPCHK(h, hipMemcpyAsync(S->d_off.p, bed->iv_off, 8 * (bed_rows + 1), hipMemcpyHostToDevice, h->stream));
         if (n_iv_bed) {
@@ -507,7 +547,7 @@ int vpr_context_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *be
         }
     }
 
-    Work W(h);
+    CtxWork W(h, entry);
     // the sequence, padded with zero bytes (not called) to whole tiles plus one, so that every 16-byte load stays inside
     const int64_t n_pad = (N + CTX_TILE - 1) / CTX_TILE * CTX_TILE + CTX_TILE;
     if (int rc = W.need(W.seq, size_t(n_pad), "contig sequences")) return rc;
@@ -518,12 +558,11 @@ int vpr_context_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *be
     HIPCHK(h, hipMemcpyAsync(W.ctg_off.p, v->ctg_off, 8 * (size_t(n_ctg) + 1), hipMemcpyHostToDevice, h->stream));
     const uint8_t *d_seq = as<uint8_t>(W.seq);
     const int64_t *d_ctg = as<int64_t>(W.ctg_off);
-    uint32_t *d_nkept = as<uint32_t>(W.small);
 
     // pieces of whole contigs
     struct Piece { int c0, c1; };       // contigs [c0, c1)
     std::vector<Piece> pieces;
-    const int64_t budget = piece_bases();
+    const int64_t budget = ctx_piece_bases();
     for (int c = 0; c < n_ctg;) {
         int e = c + 1;
         while (e < n_ctg && v->ctg_off[e + 1] - v->ctg_off[c] <= budget) e++;
@@ -532,16 +571,7 @@ int vpr_context_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *be
     }
 
     double ms = 0;
-    bool open = false;                  // a timed segment is under way (it ends with the next wait for a count)
-    auto seg_begin = [&]() -> int { if (!open) { HIPCHK(h, hipEventRecord(S->ev[0], h->stream)); open = true; } return VPR_OK; };
-    auto seg_end = [&]() -> int {
-        HIPCHK(h, hipEventRecord(S->ev[1], h->stream));
-        HIPCHK(h, x_sync(h, h->stream, SITE));
-        float t = 0;
-        (void)hipEventElapsedTime(&t, S->ev[0], S->ev[1]);
-        ms += t; open = false;
-        return VPR_OK;
-    };
+    W.ev[0] = S->ev[0]; W.ev[1] = S->ev[1]; W.ms = &ms;
     HIPCHK(h, x_sync(h, h->stream, SITE));       // (the uploads are not part of the interval kernels' time)
 
     int64_t n_ctx = 0;
@@ -553,15 +583,12 @@ int vpr_context_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *be
         int64_t *row_off = S->d_off.p + bed_rows + size_t(k) * size_t(n_ctg);
         for (const Piece &pc : pieces) {
             const int64_t g0 = v->ctg_off[pc.c0], g1 = v->ctg_off[pc.c1], T0 = g0 / CTX_TILE * CTX_TILE;
-            const int64_t n_tiles = (g1 - T0 + CTX_TILE - 1) / CTX_TILE, nw = n_tiles * (CTX_TILE / 64), n_blk = (nw + 255) / 256;
-            uint32_t n_run = 0, n_run_en = 0, n_out = 0;
-            if (int rc = seg_begin()) return rc;
+            const int64_t n_tiles = (g1 - T0 + CTX_TILE - 1) / CTX_TILE, nw = n_tiles * (CTX_TILE / 64);
+            uint32_t n_out = 0;
+            if (int rc = W.seg_begin()) return rc;
             if (n_tiles) {
                 if (int rc = W.need(W.bits, size_t(nw) * 8, "flag bits")) return rc;
-                if (int rc = W.need(W.cnt, size_t(n_blk + 1) * 16, "workgroup counts")) return rc;
                 uint16_t *bits = as<uint16_t>(W.bits);
-                const uint64_t *words = as<uint64_t>(W.bits);
-                uint32_t *cnt_st = as<uint32_t>(W.cnt), *cnt_en = cnt_st + (n_blk + 1), *off_st = cnt_en + (n_blk + 1), *off_en = off_st + (n_blk + 1);
                 if (gc) {
                     if (sp.window <= GC_LDS_MAX_W)
                         hipLaunchKernelGGL(k_ctx_flags_gc, dim3(unsigned(n_tiles)), dim3(CTX_WG), size_t(4) * size_t(CTX_TILE + sp.window + 48), h->stream,
@@ -580,62 +607,15 @@ int vpr_context_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *be
                     }
                 }
                 HIPCHK(h, hipGetLastError());
-                HIPCHK(h, hipMemsetAsync(cnt_st + n_blk, 0, 4, h->stream));
-                HIPCHK(h, hipMemsetAsync(cnt_en + n_blk, 0, 4, h->stream));
-                hipLaunchKernelGGL(k_ctx_run_count, dim3(unsigned(n_blk)), dim3(256), 0, h->stream, words, nw, T0, d_ctg, n_ctg, g0, min_run, cnt_st, cnt_en);
-                HIPCHK(h, hipGetLastError());
-                if (int rc = scan_u32(h, W, cnt_st, off_st, size_t(n_blk + 1))) return rc;
-                if (int rc = scan_u32(h, W, cnt_en, off_en, size_t(n_blk + 1))) return rc;
-                HIPCHK(h, hipMemcpyAsync(&n_run, off_st + n_blk, 4, hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(h, hipMemcpyAsync(&n_run_en, off_en + n_blk, 4, hipMemcpyDeviceToHost, h->stream));
-                if (int rc = seg_end()) return rc;
-                if (n_run != n_run_en) return fail(h, VPR_ERR_DEVICE, "vpr_context_masks: entry %d: %u run starts and %u run ends", k, n_run, n_run_en);
-                if (n_run) {
-                    const size_t n1 = size_t(n_run) + 1;
-                    if (int rc = W.need(W.runs, n1 * 8, "run lists")) return rc;
-                    if (int rc = W.need(W.keep, n1 * 8, "tract flags")) return rc;
-                    if (int rc = W.need(W.kept, n1 * 12, "kept tracts")) return rc;
-                    uint32_t *run_st = as<uint32_t>(W.runs), *run_en = run_st + n1;
-                    uint32_t *flag = as<uint32_t>(W.keep), *flag_scan = flag + n1;
-                    int32_t *k_ctg = as<int32_t>(W.kept), *k_ps = k_ctg + n1, *k_pe = k_ps + n1;
-                    const int p = gc ? 0 : sp.period, min_len = gc ? 1 : sp.min_len, max_len = gc ? 0 : sp.max_len;
-                    if (int rc = seg_begin()) return rc;
-                    hipLaunchKernelGGL(k_ctx_run_write, dim3(unsigned(n_blk)), dim3(256), 0, h->stream, words, nw, T0, d_ctg, n_ctg, g0, min_run, off_st, off_en,
-                                       run_st, run_en);
-                    HIPCHK(h, hipGetLastError());
-                    hipLaunchKernelGGL(k_ctx_keep, dim3(blocks_of(int64_t(n1))), dim3(256), 0, h->stream, int64_t(n_run), run_st, run_en, T0, d_seq, d_ctg,
-                                       n_ctg, p, min_len, max_len, sp.slop, flag);
-                    HIPCHK(h, hipGetLastError());
-                    if (int rc = scan_u32(h, W, flag, flag_scan, n1)) return rc;
-                    hipLaunchKernelGGL(k_ctx_compact, dim3(blocks_of(n_run)), dim3(256), 0, h->stream, int64_t(n_run), run_st, run_en, T0, d_seq, d_ctg,
-                                       n_ctg, p, min_len, max_len, sp.slop, flag, flag_scan, k_ctg, k_ps, k_pe, d_nkept);
-                    HIPCHK(h, hipGetLastError());
-                    hipLaunchKernelGGL(k_ctx_group, dim3(blocks_of(int64_t(n1))), dim3(256), 0, h->stream, int64_t(n_run), d_nkept, k_ctg, k_ps, k_pe, flag);
-                    HIPCHK(h, hipGetLastError());
-                    if (int rc = scan_u32(h, W, flag, flag_scan, n1)) return rc;
-                    HIPCHK(h, hipMemcpyAsync(&n_out, flag_scan + n_run, 4, hipMemcpyDeviceToHost, h->stream));
-                    if (int rc = seg_end()) return rc;
-                    const size_t have = size_t(n_iv_bed + n_ctx), want = have + n_out;
-                    if (int rc = ctx_need(h, S->d_start, want * 4, "intervals", have * 4)) return rc;
-                    if (int rc = ctx_need(h, S->d_stop, want * 4, "intervals", have * 4)) return rc;
-                    if (int rc = W.need(W.out_ctg, (size_t(n_out) + 1) * 4, "interval contigs")) return rc;
-                    if (int rc = seg_begin()) return rc;
-                    if (n_out) {
-                        hipLaunchKernelGGL(k_ctx_merge, dim3(blocks_of(n_run)), dim3(256), 0, h->stream, d_nkept, k_ctg, k_ps, k_pe, flag, flag_scan,
-                                           as<int32_t>(W.out_ctg), S->d_start.p + have, S->d_stop.p + have);
-                        HIPCHK(h, hipGetLastError());
-                    }
-                }
             }
-            if (int rc = W.need(W.out_ctg, 4, "interval contigs")) return rc;
-            if (int rc = seg_begin()) return rc;
-            hipLaunchKernelGGL(k_ctx_rows, dim3(blocks_of(pc.c1 - pc.c0 + 1)), dim3(256), 0, h->stream, as<int32_t>(W.out_ctg), int64_t(n_out), pc.c0, pc.c1,
-                               n_iv_bed + n_ctx, row_off);
-            HIPCHK(h, hipGetLastError());
+            const CtxRunRule rule = {gc ? 0 : sp.period, gc ? 1 : sp.min_len, gc ? 0 : sp.max_len, sp.slop, min_run, !gc};
+            if (int rc = ctx_intervals_from_flags(W, as<uint64_t>(W.bits), nw, T0, g0, d_seq, d_ctg, n_ctg, pc.c0, pc.c1, rule, k, S->d_start, S->d_stop,
+                                                  size_t(n_iv_bed + n_ctx), row_off, &n_out))
+                return rc;
             n_ctx += n_out;
         }
     }
-    if (open) if (int rc = seg_end()) return rc;
+    if (W.open) if (int rc = W.seg_end()) return rc;
     S->n_iv_ctx = n_ctx;
     S->ms_intervals = ms;
     if (int rc = strata_masks_device(h, v, n_bed + n_spec, S->d_off.p, S->d_start.p, S->d_stop.p)) return rc;

@@ -7,6 +7,7 @@
 //                   the front and back of a counters call that pr_strata.hip and pr_boot.hip share (the bin rule: pr_counts.h)
 //   pr_strata.hip   the region-stratified counters (include/vcfdist_strata.h): membership words, the stratified histogram
 //   pr_context.hip  the sequence-context strata (include/vcfdist_context.h): interval lists built from the contig sequences
+//   pr_repeats.hip  the repeat strata (include/vcfdist_repeats.h): genome-wide repeated k-mers, in front of pr_context.hip's run passes
 //   pr_varstrata.hip the variant strata (include/vcfdist_varstrata.h): bits made from the variant tables themselves
 //   pr_boot.hip     the bootstrap replicates of the counters (include/vcfdist_bootstrap.h): the replicate histogram
 //   pr_errclass.hip the error classes (include/vcfdist_errclass.h): why each FP and FN is wrong
@@ -273,6 +274,7 @@ using namespace vprh;
 struct DistState;                        // the distance step's tables and arena (pr_dist.hip)
 struct StrataState;                      // the membership words and the stratified histogram (pr_strata.hip)
 struct ContextState;                     // the sequence-context intervals (pr_context.hip)
+struct RepeatState;                      // the repeat intervals (pr_repeats.hip)
 struct LabelState;                       // the label bytes and the label histogram of a label pass (pr_label.h)
 enum { LABEL_ERRCLASS, LABEL_MATCHKIND, LABEL_PASSES };     // the label passes: pr_errclass.hip, pr_matchkind.hip
 struct BootState;                        // the replicate histogram and the supercluster keys (pr_boot.hip)
@@ -425,6 +427,7 @@ struct vpr_handle {
     DistState *dist = nullptr;           // vpr_distance (pr_dist.hip), created by its first call
     StrataState *strata = nullptr;       // vpr_strata_masks / vpr_strata_upload_masks (pr_strata.hip), released with the batch
     ContextState *context = nullptr;     // vpr_context_masks (pr_context.hip), released by the next one or vpr_destroy
+    RepeatState *repeats = nullptr;      // vpr_repeat_intervals (pr_repeats.hip), released by the next one or vpr_destroy
     BootState *boot = nullptr;           // vpr_pr_counts_boot (pr_boot.hip), created by its first call, released with the batch
     LabelState *label[LABEL_PASSES] = {nullptr, nullptr};   // vpr_errclass / vpr_matchkind (pr_label.hip), created by a pass's first call, released with the batch
     double varstrata_ms = 0;             // device time of the last vpr_varstrata_masks' kernel launches (pr_varstrata.hip)
@@ -480,6 +483,7 @@ int strata_extend(vpr_handle *h, const char *entry, int32_t n_add, const int64_t
                   uint64_t *words[VPR_HAPS], int32_t *n_words);
 void strata_commit(vpr_handle *h);
 void context_free(vpr_handle *h);                                    // pr_context.hip: the resident context intervals
+void repeats_free(vpr_handle *h);                                    // pr_repeats.hip: the resident repeat intervals
 void label_free(vpr_handle *h);                                      // pr_label.hip: the label bytes and histograms of both label passes
 void boot_free(vpr_handle *h);                                       // pr_boot.hip: the replicate histogram and the keys
 // pr_collect.hip, shared by the three counters entries (vpr_pr_counts, _strata, _boot; `entry`: the entry's name, for the
@@ -538,4 +542,41 @@ int dev_upload(vpr_handle *h, const T **dst, const T *src, size_t n) {
     *dst = p;
     return VPR_OK;
 }
+// pr_context.hip, shared with pr_repeats.hip: the run passes behind the flag bits (run starts and ends, tracts, pad, merge, rows).
+// room for `bytes` in a buffer of the call `entry`, a quarter more than asked for when it has to grow; keep_bytes of the old content survive
+template <typename T>
+int ctx_need(vpr_handle *h, const char *entry, DevBuf<T> &b, size_t bytes, const char *what, size_t keep_bytes = 0) {
+    if (b.cap * sizeof(T) >= bytes) return VPR_OK;
+    const std::string nomem = std::string(entry) + ": cannot allocate %zu bytes on the device (" + what + ")";
+    return b.reserve(h, std::max<size_t>((bytes + bytes / 4 + 255) & ~size_t(255), 256) / sizeof(T), nomem.c_str(), keep_bytes / sizeof(T));
+}
+// The workspace of one call (released when it goes), and the clock of its timed segments: a segment runs from seg_begin to the
+// next seg_end, which waits for the stream (the host needs a count then anyway) and adds the events' time to *ms.
+struct CtxWork {
+    vpr_handle *h;
+    const char *entry;                   // the calling entry's name, for the messages
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double *ms = nullptr;
+    bool open = false;
+    DevBuf<uint8_t> seq, ctg_off, bits, cnt, runs, keep, kept, out_ctg, tmp, small;
+    CtxWork(vpr_handle *h_, const char *entry_) : h(h_), entry(entry_) {}
+    ~CtxWork() {
+        (void)hipStreamSynchronize(h->stream);
+        dev_release(h, seq, ctg_off, bits, cnt, runs, keep, kept, out_ctg, tmp, small);
+    }
+    int need(DevBuf<uint8_t> &b, size_t bytes, const char *what) { return ctx_need(h, entry, b, bytes, what); }
+    int seg_begin();
+    int seg_end();
+};
+// What the run passes are told about the flags: a run [a, b) of flags gives the tract [a - p, b); tracts shorter than min_len or
+// (max_len set) longer than max_len are dropped, as are -- with `primitive` -- those whose first p bases repeat a shorter word;
+// min_run: flags a run must have to count at all (1: every run).
+struct CtxRunRule { int p, min_len, max_len, slop, min_run; bool primitive; };
+// The flag words of one piece (contigs [c0, c1) of the concatenation, g0 = ctg_off[c0]; word w holds the bases from T0 + 64 w, nw
+// words; W.bits may be their home) become merged intervals appended to d_start / d_stop behind the `have` already there, and the
+// rows c0..c1 of row_off (entry of contig 0 of the stratum; base `have`).  *n_out: the intervals appended.  W.small holds 256 bytes.
+int ctx_intervals_from_flags(CtxWork &W, const uint64_t *words, int64_t nw, int64_t T0, int64_t g0, const uint8_t *d_seq, const int64_t *d_ctg,
+                             int n_ctg, int c0, int c1, const CtxRunRule &rule, int spec_entry, DevBuf<int32_t> &d_start, DevBuf<int32_t> &d_stop,
+                             size_t have, int64_t *row_off, uint32_t *n_out);
+int64_t ctx_piece_bases();               // bases of a piece of whole contigs (VPR_CONTEXT_PIECE_BASES: a smaller one, for the tests)
 #endif

@@ -15,6 +15,13 @@ int vplan_sort_pairs_desc(void *tmp, size_t *tmp_bytes, const uint16_t *keys, ui
     return int(rocprim::radix_sort_pairs_desc(tmp, *tmp_bytes, keys, keys_out, vals, vals_out, n, 0u, 16u, st));
 }
 
+// stable, ascending by the key's bits [0, bits): (keys, vals) -> (keys_out, vals_out), for pr_repeats.hip (canonical k-mer codes
+// of 2k bits and their global starts).  tmp == nullptr: only *tmp_bytes is set.
+int vplan_sort_pairs_u64(void *tmp, size_t *tmp_bytes, const uint64_t *keys, uint64_t *keys_out, const uint32_t *vals, uint32_t *vals_out,
+                         size_t n, unsigned bits, hipStream_t st) {
+    return int(rocprim::radix_sort_pairs(tmp, *tmp_bytes, keys, keys_out, vals, vals_out, n, 0u, bits, st));
+}
+
 // exclusive prefix sums of uint32 values (workspace offsets in 128-byte units: the caller checked that the total fits)
 int vplan_exclusive_scan_u32(void *tmp, size_t *tmp_bytes, const uint32_t *in, uint32_t *out, size_t n, hipStream_t st) {
     return int(rocprim::exclusive_scan(tmp, *tmp_bytes, in, out, uint32_t(0), n, rocprim::plus<uint32_t>(), st));

@@ -201,14 +201,16 @@ extern "C" int vrp_write_stratified(const char *prefix, const char *const *names
     return VRP_OK;
 }
 
-extern "C" int vrp_write_context_bed(const char *prefix, const char *const *contigs, int32_t n_ctg, const char *const *names, int32_t n_strata,
-                                     const int64_t *iv_off, const int32_t *start, const int32_t *stop) {
-    if (!prefix || !contigs || !names || n_ctg < 0 || n_strata < 0 || !iv_off) return fail(VRP_ERR_ARG, "vrp_write_context_bed: bad argument");
+// context-strata.bed and repeat-strata.bed: one body
+static int write_strata_bed(const char *entry, const char *file, const char *prefix, const char *const *contigs, int32_t n_ctg,
+                            const char *const *names, int32_t n_strata, const int64_t *iv_off, const int32_t *start, const int32_t *stop) {
+    const std::string who = entry;
+    if (!prefix || !contigs || !names || n_ctg < 0 || n_strata < 0 || !iv_off) return fail(VRP_ERR_ARG, who + ": bad argument");
     const size_t n_rows = size_t(n_ctg) * size_t(n_strata);
-    if (iv_off[n_rows] > iv_off[0] && (!start || !stop)) return fail(VRP_ERR_ARG, "vrp_write_context_bed: null interval table");
-    for (int32_t c = 0; c < n_ctg; c++) if (!contigs[c]) return fail(VRP_ERR_ARG, "vrp_write_context_bed: null contig name");
-    for (int32_t k = 0; k < n_strata; k++) if (!names[k]) return fail(VRP_ERR_ARG, "vrp_write_context_bed: null stratum name");
-    const std::string fn = std::string(prefix) + "context-strata.bed";
+    if (iv_off[n_rows] > iv_off[0] && (!start || !stop)) return fail(VRP_ERR_ARG, who + ": null interval table");
+    for (int32_t c = 0; c < n_ctg; c++) if (!contigs[c]) return fail(VRP_ERR_ARG, who + ": null contig name");
+    for (int32_t k = 0; k < n_strata; k++) if (!names[k]) return fail(VRP_ERR_ARG, who + ": null stratum name");
+    const std::string fn = std::string(prefix) + file;
     File bed(fn.c_str());
     if (!bed) return fail(VRP_ERR_OPEN, "cannot create " + fn);
     for (size_t r = 0; r < n_rows; r++)
@@ -216,6 +218,16 @@ extern "C" int vrp_write_context_bed(const char *prefix, const char *const *cont
             fprintf(bed, "%s\t%d\t%d\t%s\n", contigs[r / size_t(n_strata)], start[j], stop[j], names[r % size_t(n_strata)]);
     if (!bed.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn);
     return VRP_OK;
+}
+
+extern "C" int vrp_write_context_bed(const char *prefix, const char *const *contigs, int32_t n_ctg, const char *const *names, int32_t n_strata,
+                                     const int64_t *iv_off, const int32_t *start, const int32_t *stop) {
+    return write_strata_bed("vrp_write_context_bed", "context-strata.bed", prefix, contigs, n_ctg, names, n_strata, iv_off, start, stop);
+}
+
+extern "C" int vrp_write_repeat_bed(const char *prefix, const char *const *contigs, int32_t n_ctg, const char *const *names, int32_t n_strata,
+                                    const int64_t *iv_off, const int32_t *start, const int32_t *stop) {
+    return write_strata_bed("vrp_write_repeat_bed", "repeat-strata.bed", prefix, contigs, n_ctg, names, n_strata, iv_off, start, stop);
 }
 
 extern "C" int vrp_write_variant_strata(const char *prefix, const char *const *names, const vpr_variant_stratum *spec, int32_t n_spec,

@@ -25,7 +25,7 @@ class VrpContig(C.Structure):
                 ("n_flips", C.c_int32), ("switches", A.P_i32), ("flips", A.P_i32)]
 
 
-EXPORTED = ["vrp_phase_blocks", "vrp_write_precision_recall", "vrp_write_stratified", "vrp_write_context_bed", "vrp_write_bootstrap", "vrp_write_bootstrap_stratified", "vrp_write_phase_blocks", "vrp_write_superclusters",
+EXPORTED = ["vrp_phase_blocks", "vrp_write_precision_recall", "vrp_write_stratified", "vrp_write_context_bed", "vrp_write_repeat_bed", "vrp_write_bootstrap", "vrp_write_bootstrap_stratified", "vrp_write_phase_blocks", "vrp_write_superclusters",
             "vrp_write_switchflips", "vrp_write_phasing_summary", "vrp_ng50",
             "vrp_write_variants", "vrp_write_summary_vcf", "vrp_write_distance", "vrp_write_edits", "vrp_write_vcf", "vrp_last_error"]
 
@@ -139,9 +139,7 @@ def write_stratified(prefix, names, counts, min_qual, max_qual):
     _check(L.vrp_write_stratified(prefix.encode(), arr, len(names), A._ptr(cnt, C.c_int64), min_qual, max_qual), "vrp_write_stratified")
 
 
-def write_context_bed(prefix, contigs, names, intervals):
-    """context-strata.bed (include/vcfdist_context.h): contigs in evaluation order, names of the context strata in table order,
-    intervals[contig] = [(starts, stops) per stratum]"""
+def _write_strata_bed(entry, prefix, contigs, names, intervals):
     off, st, sp = [0], [], []
     for c in contigs:
         rows = intervals[c]
@@ -153,12 +151,22 @@ def write_context_bed(prefix, contigs, names, intervals):
     off = np.asarray(off, np.int64)
     st = np.ascontiguousarray(np.concatenate(st + [np.zeros(1, np.int32)]), np.int32)     # (never empty: a pointer is wanted)
     sp = np.ascontiguousarray(np.concatenate(sp + [np.zeros(1, np.int32)]), np.int32)
-    L = api.lib()
+    f = getattr(api.lib(), entry)
     carr = (C.c_char_p * max(len(contigs), 1))(*[c.encode() for c in contigs])
     narr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
-    L.vrp_write_context_bed.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_char_p), C.c_int32, A.P_i64, A.P_i32, A.P_i32]
-    _check(L.vrp_write_context_bed(prefix.encode(), carr, len(contigs), narr, len(names), A._ptr(off, C.c_int64), A._ptr(st, C.c_int32),
-                                   A._ptr(sp, C.c_int32)), "vrp_write_context_bed")
+    f.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_char_p), C.c_int32, A.P_i64, A.P_i32, A.P_i32]
+    _check(f(prefix.encode(), carr, len(contigs), narr, len(names), A._ptr(off, C.c_int64), A._ptr(st, C.c_int32), A._ptr(sp, C.c_int32)), entry)
+
+
+def write_context_bed(prefix, contigs, names, intervals):
+    """context-strata.bed (include/vcfdist_context.h): contigs in evaluation order, names of the context strata in table order,
+    intervals[contig] = [(starts, stops) per stratum]"""
+    _write_strata_bed("vrp_write_context_bed", prefix, contigs, names, intervals)
+
+
+def write_repeat_bed(prefix, contigs, names, intervals):
+    """repeat-strata.bed (include/vcfdist_repeats.h): the same for the repeat strata, in the same format and order"""
+    _write_strata_bed("vrp_write_repeat_bed", prefix, contigs, names, intervals)
 
 
 def write_variant_strata(prefix, names, spec, n_query, n_truth):
