@@ -247,11 +247,16 @@ def test_diagnostic_switches_leave_the_results_unchanged(monkeypatch):
     got, want, _, pr = compare(batch, A.default_config(band_mode=1))
     names = {s.kernel.decode() for s in pr.launch_stats()}
     assert "k_fwd_strip" in names
+    forced = {"VPR_ED_DIAG": "k_ed_diag", "VPR_ED_WF": "k_ed_wf"}
     for var in ("VPR_NO_STRIPS", "VPR_NO_UB", "VPR_NO_ROUND_OVERLAP", "VPR_ED_DIAG", "VPR_ED_WF"):
         monkeypatch.setenv(var, "1")
-        other = api.PrecisionRecall(A.default_config(band_mode=1)).run(batch)
+        pr2 = api.PrecisionRecall(A.default_config(band_mode=1))
+        other = pr2.run(batch)
         monkeypatch.delenv(var)
         assert not got.diff(other), var
+        if var in forced and "k_ed_bits" in names:        # the batch has deferred sections: the forced kernel took them
+            names2 = {s.kernel.decode() for s in pr2.launch_stats()}
+            assert forced[var] in names2 and "k_ed_bits" not in names2, (var, names2)
 
 
 def test_segment_walk_and_row_walk_equal_the_oracle(monkeypatch):

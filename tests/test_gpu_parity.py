@@ -114,7 +114,7 @@ def test_superclusters_at_the_contig_end():
 
 def test_sv_sized_sections_use_deferred_edit_distance():
     """Large indels make sync sections whose ref/truth segments both exceed the inline limit,
-    so K4 (k_ed) computes wf_ed for them."""
+    so K4 (k_ed_bits, pr_ed.hip) computes wf_ed for them."""
     rng = np.random.RandomState(3)
     L = 1500
     ref = "".join(rng.choice(list("ACGT"), L))
@@ -128,7 +128,7 @@ def test_sv_sized_sections_use_deferred_edit_distance():
     batch = api.batch_from_variants(v)
     got, want, ntie, pr = compare(batch)
     names = {s_.kernel.decode() for s_ in pr.launch_stats()}
-    assert any(n.startswith("k_ed") for n in names), names       # the deferred wf_ed kernel ran
+    assert "k_ed_bits" in names, names       # the deferred wf_ed kernel ran
     assert (got.ref_ed[2][0] > 32).any()
 
 
