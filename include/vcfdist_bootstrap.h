@@ -31,7 +31,7 @@
  * quality are each sorted ascending as floats; LO = x[floor(0.025 * n_rep)], HI = x[ceil(0.975 * n_rep) - 1]: the 95 %
  * percentile interval (x[25] and x[974] of 1 000; both x[0] of 1).
  *
- * Device code: pr_boot.hip (k_pr_boot).  No CPU fallback.
+ * Device code: pr_cut.hip (k_pr_boot).  No CPU fallback.
  */
 #ifndef VCFDIST_BOOTSTRAP_H_
 #define VCFDIST_BOOTSTRAP_H_

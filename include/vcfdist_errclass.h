@@ -54,7 +54,7 @@
  *   A cut uses the phasing the bytes were made under: the label call's phase-block words stay on the device, and the cut entries
  *   take no pb_phase and no var_class.
  *
- * Device code: pr_errclass.hip (k_errclass); pr_labelcut.hip for the cuts.  No CPU fallback.
+ * Device code: pr_errclass.hip (k_errclass); pr_cut.hip for the cuts.  No CPU fallback.
  */
 #ifndef VCFDIST_ERRCLASS_H_
 #define VCFDIST_ERRCLASS_H_

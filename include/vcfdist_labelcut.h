@@ -2,7 +2,7 @@
  * this file: the label counts of a label pass (the error classes, the match kinds) cut by stratum and resampled.  The definitions
  * are in vcfdist_errclass.h ("Cut by stratum and resampled"); tests/labelcut_model.py states them in terms of the passes' models.
  *
- * Device code: pr_labelcut.hip (k_label_hist_strata, k_label_boot; both generic over the pass).  No CPU fallback.
+ * Device code: pr_cut.hip (k_label_hist_strata, k_label_boot; both generic over the pass).  No CPU fallback.
  */
 #ifndef VCFDIST_LABELCUT_H_
 #define VCFDIST_LABELCUT_H_

@@ -11,7 +11,7 @@
  * start == stop).  BORDER, OUTSIDE and OFFCTG are all "not a member".  Query and truth variants are each assigned by their
  * own position.
  *
- * Device code: pr_strata.hip (k_strata_mask, k_pr_hist_strata).  No CPU fallback.
+ * Device code: pr_strata.hip (k_strata_mask), pr_cut.hip (k_pr_hist_strata).  No CPU fallback.
  */
 #ifndef VCFDIST_STRATA_H_
 #define VCFDIST_STRATA_H_

@@ -1,4 +1,4 @@
-"""The label cuts' C ABI (include/vcfdist_labelcut.h) and both kernels of pr_labelcut.hip are defined dynamic symbols of the library."""
+"""The label cuts' C ABI (include/vcfdist_labelcut.h) and both label kernels of pr_cut.hip are defined dynamic symbols of the library."""
 import subprocess
 
 from vcfdist_amd import api

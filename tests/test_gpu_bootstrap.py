@@ -1,4 +1,4 @@
-"""Bootstrap replicates of the precision/recall counters on the GPU (include/vcfdist_bootstrap.h, pr_boot.hip): every
+"""Bootstrap replicates of the precision/recall counters on the GPU (include/vcfdist_bootstrap.h, pr_cut.hip): every
 replicate against the numpy definition (tests/bootstrap_model.py), exact integer equality throughout; the launch shapes
 (replicate groups, variant spans, quality slices), the weight algebra (equal keys, split and permuted batches), the stratum
 cut, seeds, the native collective, the state machine of the calls, and both command lines with --bootstrap (one rank and

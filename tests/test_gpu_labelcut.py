@@ -1,4 +1,4 @@
-"""The label counts cut by stratum and resampled on the GPU (include/vcfdist_labelcut.h, pr_labelcut.hip), for both label passes:
+"""The label counts cut by stratum and resampled on the GPU (include/vcfdist_labelcut.h, pr_cut.hip), for both label passes:
 k_label_hist_strata and k_label_boot bit for bit against tests/labelcut_model.py on the downloaded label bytes (hand batches, the
 random shapes under 70 random strata, replicate-group edges, quality slices, a permuted batch), the sums against the stratified
 and the replicate counters, a synthetic batch with the all-reduce entries, the state machine of the calls, and both command lines

@@ -1,4 +1,4 @@
-"""Region-stratified precision/recall counters on the GPU (include/vcfdist_strata.h, pr_strata.hip): the membership words
+"""Region-stratified precision/recall counters on the GPU (include/vcfdist_strata.h, pr_strata.hip, pr_cut.hip): the membership words
 against the host's vio_bed_contains, the stratified counters against the counting oracle, the state machine of the calls,
 the native collective, and both command lines with --stratify (one rank and two)."""
 import os

@@ -113,7 +113,7 @@ def lib():
         getattr(L, f"vpr_{name}_timing").argtypes = [H, C.POINTER(C.c_double)]
         getattr(L, f"vpr_{name}_names").restype = C.POINTER(C.c_char_p)
         getattr(L, f"vpr_{name}_names").argtypes = []
-        # the pass's counts cut by stratum and resampled (pr_labelcut.hip)
+        # the pass's counts cut by stratum and resampled (pr_cut.hip)
         getattr(L, f"vpr_{name}_strata").argtypes = [H, C.c_int32, C.c_int32, A.P_i64]
         getattr(L, f"vpr_allreduce_{name}_strata").argtypes = [H, C.c_void_p, C.c_int32, C.c_int32, A.P_i64]
         cut_boot = [C.c_int32, C.c_int32, P_u64, C.c_uint64, C.c_int32, C.c_int32, A.P_i64]
@@ -131,6 +131,13 @@ def lib():
     L.vrl_result_free.argtypes = [C.POINTER(A.VrlResult)]
     _LIB = L
     return L
+
+
+def call_or_allreduce(h, plain, reduced, comm, *args):
+    """the entry `plain` on handle h, or with a communicator its all-reduce form `reduced` -> the return code"""
+    if comm is None:
+        return getattr(lib(), plain)(h, *args)
+    return getattr(lib(), reduced)(h, comm if isinstance(comm, C.c_void_p) else C.c_void_p(comm), *args)
 
 
 EXPORTED = [
@@ -604,11 +611,7 @@ class PrecisionRecall:
             cls = [np.ascontiguousarray(c, dtype=np.uint8) for c in var_class_per_slot]
             arr = (A.P_u8 * 4)(*[A._ptr(c, C.c_uint8) for c in cls])
         args = (C.byref(vs), arr, None if pb is None else A._ptr(pb, C.c_int32), *own, min_qual, max_qual, A._ptr(out, C.c_int64))
-        L = lib()
-        if comm is None:
-            rc = getattr(L, f"vpr_{name}")(self._h, *args)
-        else:
-            rc = getattr(L, f"vpr_allreduce_{name}")(self._h, comm if isinstance(comm, C.c_void_p) else C.c_void_p(comm), *args)
+        rc = call_or_allreduce(self._h, f"vpr_{name}", f"vpr_allreduce_{name}", comm, *args)
         self._chk(rc, f"vpr_{name}")
         return out
 
@@ -655,10 +658,7 @@ class PrecisionRecall:
         n_strata = (getattr(self, "_strata", None) or (1, None))[0]      # (without words the call refuses: VPR_ERR_STATE)
         out = np.zeros((n_strata, 2, 4, n_labels, max(max_qual - min_qual + 1, 1)), np.int64)
         args = (min_qual, max_qual, A._ptr(out, C.c_int64))
-        if comm is None:
-            rc = getattr(lib(), f"vpr_{name}_strata")(self._h, *args)
-        else:
-            rc = getattr(lib(), f"vpr_allreduce_{name}_strata")(self._h, comm if isinstance(comm, C.c_void_p) else C.c_void_p(comm), *args)
+        rc = call_or_allreduce(self._h, f"vpr_{name}_strata", f"vpr_allreduce_{name}_strata", comm, *args)
         self._chk(rc, f"vpr_{name}_strata")
         return out
 
@@ -675,10 +675,7 @@ class PrecisionRecall:
         n_rep = int(n_rep)
         out = np.zeros((n_rep if 1 <= n_rep <= A.BOOT_MAX_REPLICATES else 1, 2, 4, n_labels, max(max_qual - min_qual + 1, 1)), np.int64)
         args = (min_qual, max_qual, kp, int(seed) & (2 ** 64 - 1), n_rep, int(stratum), A._ptr(out, C.c_int64))
-        if comm is None:
-            rc = getattr(lib(), f"vpr_{name}_boot")(self._h, *args)
-        else:
-            rc = getattr(lib(), f"vpr_allreduce_{name}_boot")(self._h, comm if isinstance(comm, C.c_void_p) else C.c_void_p(comm), *args)
+        rc = call_or_allreduce(self._h, f"vpr_{name}_boot", f"vpr_allreduce_{name}_boot", comm, *args)
         self._chk(rc, f"vpr_{name}_boot")
         return out
 

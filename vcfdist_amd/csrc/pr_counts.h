@@ -1,4 +1,4 @@
-// pr_counts.h -- what the three counter kernels (k_pr_hist, pr_collect.hip; k_pr_hist_strata, pr_strata.hip; k_pr_boot, pr_boot.hip)
+// pr_counts.h -- what the three counter kernels (k_pr_hist, pr_collect.hip; k_pr_hist_strata and k_pr_boot, pr_cut.hip, with their label siblings)
 // and the two join kernels (k_errclass, pr_errclass.hip; k_matchkind, pr_matchkind.hip) decide alike: the supercluster of a variant and the bin the variant counts in (print.cpp:328-438).
 #pragma once
 

@@ -140,7 +140,7 @@ int vpr_errclass_timing(const vpr_handle *h, double *ms) { return label_timing(h
 
 const char *const *vpr_errclass_names(void) { return EC_NAMES; }
 
-// the counts cut by stratum and resampled (pr_labelcut.hip)
+// the counts cut by stratum and resampled (pr_cut.hip)
 int vpr_errclass_strata(vpr_handle *h, int32_t min_qual, int32_t max_qual, int64_t *counts) {
     return labelcut_strata(h, EC, nullptr, min_qual, max_qual, counts);
 }

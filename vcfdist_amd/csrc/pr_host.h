@@ -4,17 +4,18 @@
 //   pr_mem.hip      allocator wrappers, the process-wide books of device memory, block caches (dev_alloc, pin_alloc, exec_alloc)
 //   pr_results.hip  vpr_download, vpr_results_alloc, tallies, timing and launch statistics
 //   pr_collect.hip  the counters histogram, vpr_pr_counts, and the RCCL collectives (vpr_allreduce_counts, vpr_allgather_phase);
-//                   the front and back of a counters call that pr_strata.hip and pr_boot.hip share (the bin rule: pr_counts.h)
-//   pr_strata.hip   the region-stratified counters (include/vcfdist_strata.h): membership words, the stratified histogram
+//                   the front and back of a counters call that pr_cut.hip and pr_label.hip share (the bin rule: pr_counts.h)
+//   pr_strata.hip   the membership words of the region-stratified counters (include/vcfdist_strata.h): k_strata_mask, up- and download
 //   pr_context.hip  the sequence-context strata (include/vcfdist_context.h): interval lists built from the contig sequences
 //   pr_repeats.hip  the repeat strata (include/vcfdist_repeats.h): genome-wide repeated k-mers, in front of pr_context.hip's run passes
 //   pr_varstrata.hip the variant strata (include/vcfdist_varstrata.h): bits made from the variant tables themselves
-//   pr_boot.hip     the bootstrap replicates of the counters (include/vcfdist_bootstrap.h): the replicate histogram
 //   pr_errclass.hip the error classes (include/vcfdist_errclass.h): why each FP and FN is wrong
 //   pr_matchkind.hip the match kinds (include/vcfdist_matchkind.h): how each TP was matched
 //   pr_vartab.hip   the host check and the one-block upload of the variant tables those two share (pr_vartab.h)
 //   pr_label.hip    the host side those two share (pr_label.h): the front and back of a call, the fold, download, timing, release
-//   pr_labelcut.hip their counts cut by stratum and resampled (k_label_hist_strata, k_label_boot; pr_label.h)
+//   pr_cut.hip      the count cuts (pr_cut.h): the counters and those two's label counts, cut by stratum (k_pr_hist_strata,
+//                   k_label_hist_strata; include/vcfdist_strata.h) and resampled (k_pr_boot, k_label_boot; include/vcfdist_bootstrap.h,
+//                   include/vcfdist_labelcut.h) -- one device body and one host driver per cut
 #ifndef PR_HOST_H_
 #define PR_HOST_H_
 #include <hip/hip_runtime.h>
@@ -272,12 +273,12 @@ const int TIE_DEC_SLOTS = 64;     // early-replay launches per execute that can 
 using namespace vprh;
 
 struct DistState;                        // the distance step's tables and arena (pr_dist.hip)
-struct StrataState;                      // the membership words and the stratified histogram (pr_strata.hip)
+struct StrataState;                      // the membership words and the stratified counters' cut state (pr_strata.hip)
 struct ContextState;                     // the sequence-context intervals (pr_context.hip)
 struct RepeatState;                      // the repeat intervals (pr_repeats.hip)
 struct LabelState;                       // the label bytes and the label histogram of a label pass (pr_label.h)
 enum { LABEL_ERRCLASS, LABEL_MATCHKIND, LABEL_PASSES };     // the label passes: pr_errclass.hip, pr_matchkind.hip
-struct BootState;                        // the replicate histogram and the supercluster keys (pr_boot.hip)
+struct CutState;                         // the histogram, keys and device time of a count cut (pr_cut.h)
 
 struct vpr_handle {
     vpr_config cfg;
@@ -428,7 +429,7 @@ struct vpr_handle {
     StrataState *strata = nullptr;       // vpr_strata_masks / vpr_strata_upload_masks (pr_strata.hip), released with the batch
     ContextState *context = nullptr;     // vpr_context_masks (pr_context.hip), released by the next one or vpr_destroy
     RepeatState *repeats = nullptr;      // vpr_repeat_intervals (pr_repeats.hip), released by the next one or vpr_destroy
-    BootState *boot = nullptr;           // vpr_pr_counts_boot (pr_boot.hip), created by its first call, released with the batch
+    CutState *boot = nullptr;            // vpr_pr_counts_boot (pr_cut.hip), created by its first call, released with the batch
     LabelState *label[LABEL_PASSES] = {nullptr, nullptr};   // vpr_errclass / vpr_matchkind (pr_label.hip), created by a pass's first call, released with the batch
     double varstrata_ms = 0;             // device time of the last vpr_varstrata_masks' kernel launches (pr_varstrata.hip)
     vpr_timing timing;
@@ -485,8 +486,8 @@ void strata_commit(vpr_handle *h);
 void context_free(vpr_handle *h);                                    // pr_context.hip: the resident context intervals
 void repeats_free(vpr_handle *h);                                    // pr_repeats.hip: the resident repeat intervals
 void label_free(vpr_handle *h);                                      // pr_label.hip: the label bytes and histograms of both label passes
-void boot_free(vpr_handle *h);                                       // pr_boot.hip: the replicate histogram and the keys
-// pr_collect.hip, shared by the three counters entries (vpr_pr_counts, _strata, _boot; `entry`: the entry's name, for the
+void boot_free(vpr_handle *h);                                       // pr_cut.hip: the replicate histogram and the keys
+// pr_collect.hip, shared by the three counters entries (vpr_pr_counts; _strata, _boot: pr_cut.hip; `entry`: the entry's name, for the
 // messages).  pr_counts_begin: the state checks and the device, before the entry's own buffers; pr_counts_inputs: the caller's
 // phase-block phasing and variant classes on the device (*d_pb stays null without pb_phase), every slot with variants has classes;
 // pr_counts_finish: the all-reduce (comm non-null), the nh histogram words to the host, the wait; then the host fold of one histogram

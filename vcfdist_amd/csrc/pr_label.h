@@ -2,10 +2,11 @@
 // kernel of its own that joins the two callsets inside the supercluster, and counts the labels by callset, type and threshold
 // (vpr_errclass, pr_errclass.hip: the error classes; vpr_matchkind, pr_matchkind.hip: the match kinds).  A pass brings its kernel,
 // its launch loop, its names and a LabelDesc; everything around the launches is here (pr_label.hip), and so are the pass's counts
-// cut by stratum and resampled (pr_labelcut.hip), which need the LabelDesc alone.
+// cut by stratum and resampled (pr_cut.hip), which need the LabelDesc alone.
 #pragma once
 
 #include "pr_host.h"
+#include "pr_cut.h"
 #include "pr_vartab.h"
 
 // What a pass keeps in the handle (vpr_handle::label[LabelDesc::pass]), created by its first call, released with the batch
@@ -15,14 +16,10 @@ struct LabelState {
     hipEvent_t ev[2] = {nullptr, nullptr};
     double ms = 0;
     bool valid = false;
-    // for the cuts (pr_labelcut.hip): a cut must use the phasing the bytes were made under, so the call's phase-block words stay
+    // for the cuts (pr_cut.hip): a cut must use the phasing the bytes were made under, so the call's phase-block words stay
     DevBuf<int32_t> pb;                                          // the last call's pb_phase [n_sc]
     bool has_pb = false;                                         // (false: the call had none)
-    DevBuf<unsigned long long> cut_hist;                         // [n_strata][2][3][labels][nq + 1], or replicate-minor [2][3][labels][nq + 1][groups * 64]
-    DevBuf<uint64_t> keys;                                       // the caller's sc_key
-    hipEvent_t cut_ev[2] = {nullptr, nullptr};
-    double ms_strata = 0, ms_boot = 0;
-    int32_t cut_shape[6] = {0, 0, 0, 0, 0, 0};                   // labelcut_info
+    CutState cut;                                                // labelcut_strata, labelcut_boot; labelcut_timing, labelcut_info
 };
 
 // The thresholds a variant of bin b (pr_count_row, pr_counts.h: bin nq is callq < min_qual) counts at
@@ -64,7 +61,7 @@ void fold_labels(const LabelDesc &D, const unsigned long long *hist, int nq, int
 int label_download(vpr_handle *h, const LabelDesc &D, uint8_t *const bytes[VPR_HAPS]);
 int label_timing(const vpr_handle *h, const LabelDesc &D, double *ms);
 
-// ---- pr_labelcut.hip: the counts of the resident label bytes cut by the resident membership words and resampled; the entries of
+// ---- pr_cut.hip: the counts of the resident label bytes cut by the resident membership words and resampled; the entries of
 // a pass are <D.entry>_strata, <D.entry>_boot, <D.entry>_cut_timing and <D.entry>_cut_info (their names are in the messages)
 // counts[n_strata][2][VPR_VARTYPES][labels][nq]: the bytes masked by stratum k (comm non-null: one all-reduce of the histogram)
 int labelcut_strata(vpr_handle *h, const LabelDesc &D, void *comm, int32_t min_qual, int32_t max_qual, int64_t *counts);

@@ -101,9 +101,9 @@ int label_timing(const vpr_handle *h, const LabelDesc &D, double *ms) {
 void label_free(vpr_handle *h) {
     for (LabelState *&S : h->label) {
         if (!S) continue;
-        dev_release(h, S->bytes[0], S->bytes[1], S->bytes[2], S->bytes[3], S->hist, S->pb, S->cut_hist, S->keys);
+        dev_release(h, S->bytes[0], S->bytes[1], S->bytes[2], S->bytes[3], S->hist, S->pb);
         for (int k = 0; k < 2; k++) if (S->ev[k]) (void)hipEventDestroy(S->ev[k]);
-        for (int k = 0; k < 2; k++) if (S->cut_ev[k]) (void)hipEventDestroy(S->cut_ev[k]);
+        cut_release(h, S->cut);
         delete S;
         S = nullptr;
     }

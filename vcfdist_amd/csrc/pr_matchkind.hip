@@ -133,7 +133,7 @@ int vpr_matchkind_timing(const vpr_handle *h, double *ms) { return label_timing(
 
 const char *const *vpr_matchkind_names(void) { return MK_NAMES; }
 
-// the counts cut by stratum and resampled (pr_labelcut.hip)
+// the counts cut by stratum and resampled (pr_cut.hip)
 int vpr_matchkind_strata(vpr_handle *h, int32_t min_qual, int32_t max_qual, int64_t *counts) {
     return labelcut_strata(h, MK, nullptr, min_qual, max_qual, counts);
 }

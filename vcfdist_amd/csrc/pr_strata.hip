@@ -1,37 +1,26 @@
-// pr_strata.hip -- the region-stratified precision/recall counters (include/vcfdist_strata.h): one evaluation, cut by region
+// pr_strata.hip -- the membership words of the region-stratified counters (include/vcfdist_strata.h): one evaluation, cut by region
 // afterwards.  k_strata_mask gives every variant a bit per stratum (the membership rule is the host's vio_bed_contains ==
-// VIO_BED_INSIDE, vcf_io.cpp, which follows bedData::contains, bed.cpp:73-121); k_pr_hist_strata counts a variant's bin
-// (pr_counts.h) into every stratum whose bit is set.  The host fold of a histogram and the front and back of a counters call
-// are the ones of pr_collect.hip.
+// VIO_BED_INSIDE, vcf_io.cpp, which follows bedData::contains, bed.cpp:73-121).  What counts behind the words -- k_pr_hist_strata
+// and the other cuts -- is pr_cut.hip; its state for the stratified counters lives here, with the words.
 #include "pr_host.h"
 #include "pr_counts.h"
+#include "pr_cut.h"
 #include "../../include/vcfdist_strata.h"
 
 struct StrataState {
     int32_t n_strata = 0, n_words = 0;
     int64_t n_var[VPR_HAPS] = {0, 0, 0, 0};
     DevBuf<uint64_t> words[VPR_HAPS];                                   // word-major: [n_words][n_var[slot]]
-    DevBuf<unsigned long long> hist;                                    // [n_strata][2][3 classes][3][nq + 1]
     bool valid = false;
-    // device time of the last k_strata_mask launches / k_pr_hist_strata launches (vpr_strata_timing)
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    double ms_mask = 0, ms_hist = 0;
+    // the stratified counters' histogram and device time (ms_strata: vpr_strata_timing's ms_hist); its event pair also times
+    // the k_strata_mask launches
+    CutState cut;
+    double ms_mask = 0;
 };
 
 namespace {
 
 const int TYPE_INS = 2;               // VPR_TYPE_INS
-// LDS a workgroup of k_pr_hist_strata may ask for: four of them fit beside each other in a compute unit's 160 KiB
-const size_t HIST_LDS_BUDGET = 40 * 1024;
-
-// strata of one workgroup of k_pr_hist_strata: the largest power of two up to 64 (a chunk then never straddles a
-// membership word) whose privatised bins fit the budget; one stratum when even that does not
-int hist_chunk(int nq) {
-    const size_t per = size_t(9) * size_t(nq + 1) * 4;
-    int c = 64;
-    while (c > 1 && size_t(c) * per > HIST_LDS_BUDGET) c >>= 1;
-    return c;
-}
 
 }  // namespace
 
@@ -74,49 +63,9 @@ __global__ void __launch_bounds__(256) k_strata_mask(const int64_t *__restrict__
     words[size_t(w) * size_t(n_var) + size_t(v)] = word;
 }
 
-// k_pr_hist with a stratum dimension: blockIdx.y is a chunk of n_chunk strata (a power of two up to 64, so the chunk's bits
-// lie in one membership word), whose 9 x (nq + 1) bins per stratum are privatised in LDS and flushed once with 64-bit
-// global atomics.  A lane whose bits of the chunk are all zero does nothing.
-__global__ void __launch_bounds__(256) k_pr_hist_strata(const int64_t *__restrict__ var_off, int n_sc, int64_t n_var,
-                                 const uint8_t *__restrict__ cls, const int32_t *__restrict__ sc_phase,
-                                 const int32_t *__restrict__ pb_phase, VarCols c0, VarCols c1, int callset, int min_qual,
-                                 int max_qual, const uint64_t *__restrict__ words, int n_strata, int n_chunk,
-                                 unsigned long long *__restrict__ hist /* [n_strata][2][3 classes][3][nq + 1] */) {
-    extern __shared__ unsigned int blk[];      // [n_chunk][3][3][nq + 1]
-    const int nq = max_qual - min_qual + 1, nb = 9 * (nq + 1);
-    const int k0 = blockIdx.y * n_chunk, nk = min(n_chunk, n_strata - k0);
-    for (int k = threadIdx.x; k < nk * nb; k += blockDim.x) blk[k] = 0;
-    __syncthreads();
-    const int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (v < n_var) {
-        uint64_t bits = words[size_t(k0 >> 6) * size_t(n_var) + size_t(v)] >> (k0 & 63);
-        if (nk < 64) bits &= (uint64_t(1) << nk) - 1;
-        if (bits) {
-            int b = 0;
-            const int row = pr_count_row(sc_of_var(var_off, n_sc, v), v, sc_phase, pb_phase, c0.errtype, c1.errtype, c0.callq, c1.callq, cls,
-                                         min_qual, nq, &b);
-            const int bin = row * (nq + 1) + b;
-            while (row >= 0 && bits) {
-                const int j = __ffsll((long long)bits) - 1;
-                bits &= bits - 1;
-                atomicAdd(&blk[j * nb + bin], 1u);
-            }
-        }
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < nk * nb; k += blockDim.x)
-        if (blk[k]) atomicAdd(&hist[(size_t(k0 + k / nb) * 2 + size_t(callset)) * nb + size_t(k % nb)], (unsigned long long)blk[k]);
-}
-
 }  // extern "C"
 
 namespace {
-
-double ev_ms(const StrataState *S) {     // (both events have completed: the caller has synchronised the stream)
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, S->ev[0], S->ev[1]);
-    return ms;
-}
 
 void release_words(vpr_handle *h, StrataState *S) {
     for (int s = 0; s < VPR_HAPS; s++) { S->words[s].release(h); S->n_var[s] = 0; }
@@ -127,9 +76,8 @@ void release_words(vpr_handle *h, StrataState *S) {
 int strata_prepare(vpr_handle *h, int32_t n_strata, const int64_t n_var[VPR_HAPS]) {
     if (!h->strata) h->strata = new StrataState();
     StrataState *S = h->strata;
-    for (int k = 0; k < 2; k++) if (!S->ev[k]) HIPCHK(h, hipEventCreate(&S->ev[k]));
     release_words(h, S);
-    S->ms_mask = S->ms_hist = 0;
+    S->ms_mask = S->cut.ms_strata = 0;
     S->n_strata = n_strata; S->n_words = (n_strata + 63) / 64;
     for (int s = 0; s < VPR_HAPS; s++) {
         const size_t n = std::max<size_t>(size_t(S->n_words) * size_t(n_var[s]), 32);
@@ -142,49 +90,13 @@ int strata_prepare(vpr_handle *h, int32_t n_strata, const int64_t n_var[VPR_HAPS
     return VPR_OK;
 }
 
-int strata_counts_impl(vpr_handle *h, void *comm, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase,
-                       int32_t min_qual, int32_t max_qual, int64_t *counts) {
-    if (!h || !counts || max_qual < min_qual) return VPR_ERR_ARG;
-    if (int rc = pr_counts_begin(h, "vpr_pr_counts_strata", comm)) return rc;
-    int32_t n_strata = 0;
-    const uint64_t *words[VPR_HAPS];
-    if (int rc = strata_view(h, "vpr_pr_counts_strata", &n_strata, words)) return rc;
-    StrataState *S = h->strata;
-    const int nq = max_qual - min_qual + 1;
-    const size_t nb = size_t(9) * size_t(nq + 1), nh1 = 2 * nb, nh = size_t(n_strata) * nh1;
-    if (int rc = S->hist.reserve(h, nh, "stratified histogram: cannot allocate %zu bytes on the device")) return rc;
-    HIPCHK(h, hipMemsetAsync(S->hist.p, 0, nh * 8, h->stream));
-    int32_t *d_pb = nullptr;
-    if (int rc = pr_counts_inputs(h, "vpr_pr_counts_strata", var_class, pb_phase, &d_pb)) return rc;
-    const int chunk = hist_chunk(nq);
-    const unsigned n_chunks = unsigned((n_strata + chunk - 1) / chunk);
-    const size_t lds = size_t(std::min(chunk, n_strata)) * nb * 4;
-    HIPCHK(h, hipEventRecord(S->ev[0], h->stream));
-    for (int s = 0; s < VPR_HAPS; s++) {
-        const int64_t nv = h->n_var[s];
-        if (!nv) continue;
-        hipLaunchKernelGGL(k_pr_hist_strata, dim3(unsigned((nv + 255) / 256), n_chunks), dim3(256), lds, h->stream,
-                           h->dB.var_off[s], h->n_sc, nv, h->d_cls[s], h->dR.sc_phase, d_pb, h->dR.v[s][0], h->dR.v[s][1],
-                           s >> 1, min_qual, max_qual, words[s], n_strata, chunk, S->hist.p);
-        HIPCHK(h, hipGetLastError());
-    }
-    HIPCHK(h, hipEventRecord(S->ev[1], h->stream));
-    std::vector<unsigned long long> hist(nh);
-    if (int rc = pr_counts_finish(h, comm, S->hist.p, nh, hist.data())) return rc;
-    S->ms_hist = ev_ms(S);
-    const size_t nc1 = size_t(2) * VPR_VARTYPES * 3 * size_t(nq);
-    for (int k = 0; k < n_strata; k++) pr_fold_counts(hist.data() + size_t(k) * nh1, nq, counts + size_t(k) * nc1);
-    return VPR_OK;
-}
-
 }  // namespace
 
 void strata_free(vpr_handle *h) {
     StrataState *S = h->strata;
     if (!S) return;
     release_words(h, S);
-    S->hist.release(h);
-    for (int k = 0; k < 2; k++) if (S->ev[k]) (void)hipEventDestroy(S->ev[k]);
+    cut_release(h, S->cut);
     delete S;
     h->strata = nullptr;
 }
@@ -261,7 +173,7 @@ int strata_masks_device(vpr_handle *h, const vpr_variants *v, int32_t n_strata, 
     for (const Piece &p : pieces)
         if (p.bytes && p.src) HIPCHK(h, hipMemcpyAsync(blk + p.at, p.src, p.bytes, hipMemcpyHostToDevice, h->stream));
     auto at = [&](size_t i) { return blk + pieces[i].at; };
-    HIPCHK(h, hipEventRecord(S->ev[0], h->stream));
+    if (int rc = cut_mark(h, S->cut, 0)) return rc;
     for (int i = 0; i < VPR_HAPS; i++) {
         if (!n_var[i]) continue;
         hipLaunchKernelGGL(k_strata_mask, dim3(unsigned((n_var[i] + 255) / 256), unsigned(S->n_words)), dim3(256), 0, h->stream,
@@ -270,9 +182,9 @@ int strata_masks_device(vpr_handle *h, const vpr_variants *v, int32_t n_strata, 
                            d_iv_off, d_iv_start, d_iv_stop, n_strata, v->n_ctg, S->words[i].p);
         HIPCHK(h, hipGetLastError());
     }
-    HIPCHK(h, hipEventRecord(S->ev[1], h->stream));
+    if (int rc = cut_mark(h, S->cut, 1)) return rc;
     HIPCHK(h, x_sync(h, h->stream, SITE));
-    S->ms_mask = ev_ms(S);
+    S->ms_mask = cut_elapsed(S->cut);
     S->valid = true;
     return VPR_OK;
 }
@@ -311,6 +223,8 @@ int strata_extend(vpr_handle *h, const char *entry, int32_t n_add, const int64_t
 }
 
 void strata_commit(vpr_handle *h) { h->strata->valid = true; }
+
+CutState &strata_cut(vpr_handle *h) { return h->strata->cut; }
 
 int strata_view(vpr_handle *h, const char *entry, int32_t *n_strata, const uint64_t *words[VPR_HAPS]) {
     const StrataState *S = h->strata;
@@ -354,7 +268,7 @@ int vpr_strata_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *s) 
 
 int vpr_strata_timing(const vpr_handle *h, double *ms_mask, double *ms_hist) {
     if (!h || !h->strata || !ms_mask || !ms_hist) return VPR_ERR_ARG;
-    *ms_mask = h->strata->ms_mask; *ms_hist = h->strata->ms_hist;
+    *ms_mask = h->strata->ms_mask; *ms_hist = h->strata->cut.ms_strata;
     return VPR_OK;
 }
 
@@ -389,17 +303,6 @@ int vpr_strata_upload_masks(vpr_handle *h, int32_t n_strata, const int64_t n_var
     HIPCHK(h, x_sync(h, h->stream, SITE));
     S->valid = true;
     return VPR_OK;
-}
-
-int vpr_pr_counts_strata(vpr_handle *h, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase,
-                         int32_t min_qual, int32_t max_qual, int64_t *counts) {
-    return strata_counts_impl(h, nullptr, var_class, pb_phase, min_qual, max_qual, counts);
-}
-
-int vpr_allreduce_counts_strata(vpr_handle *h, void *nccl_comm, const uint8_t *const var_class[VPR_HAPS], const int32_t *pb_phase,
-                                int32_t min_qual, int32_t max_qual, int64_t *counts) {
-    if (!nccl_comm) return VPR_ERR_ARG;
-    return strata_counts_impl(h, nccl_comm, var_class, pb_phase, min_qual, max_qual, counts);
 }
 
 }  // extern "C"

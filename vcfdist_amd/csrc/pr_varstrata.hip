@@ -1,7 +1,7 @@
 // pr_varstrata.hip -- the variant strata (include/vcfdist_varstrata.h): strata that are a function of the variant tables alone
 // (transition / transversion, insertion and deletion size bins, genotype, crowding).  k_varstrata_mask gives every hap-variant a
 // bit per spec entry and writes them into the membership words of pr_strata.hip, alone or behind the resident ones; everything
-// behind the words (k_pr_hist_strata, the bootstrap's stratum cut) is the code of pr_strata.hip / pr_boot.hip.
+// behind the words (k_pr_hist_strata, the bootstrap's stratum cut) is the code of pr_strata.hip / pr_cut.hip.
 #include "pr_host.h"
 #include "pr_counts.h"
 #include "pr_varscan.h"

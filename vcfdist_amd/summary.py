@@ -88,7 +88,7 @@ def pr_counts_strata(pr, var_class_per_slot, pb_phase=None, min_qual=0, max_qual
         cls = [np.ascontiguousarray(c, dtype=np.uint8) for c in var_class_per_slot]
         arr = (A.P_u8 * 4)(*[A._ptr(c, C.c_uint8) for c in cls])
     args = (arr, None if pb is None else A._ptr(pb, C.c_int32), min_qual, max_qual, A._ptr(out, C.c_int64))
-    rc = L.vpr_pr_counts_strata(pr._h, *args) if comm is None else L.vpr_allreduce_counts_strata(pr._h, comm if isinstance(comm, C.c_void_p) else C.c_void_p(comm), *args)
+    rc = api.call_or_allreduce(pr._h, "vpr_pr_counts_strata", "vpr_allreduce_counts_strata", comm, *args)
     if rc:
         raise api.VprError(f"vpr_pr_counts_strata failed ({rc}): {L.vpr_last_error(pr._h).decode()}")
     return out
@@ -112,7 +112,7 @@ def pr_counts_boot(pr, var_class_per_slot, pb_phase, sc_key, n_rep, seed=1, min_
         arr = (A.P_u8 * 4)(*[A._ptr(c, C.c_uint8) for c in cls])
     args = (arr, None if pb is None else A._ptr(pb, C.c_int32), min_qual, max_qual, None if key is None else A._ptr(key, C.c_uint64),
             int(seed) & (2 ** 64 - 1), n_rep, int(stratum), A._ptr(out, C.c_int64))
-    rc = L.vpr_pr_counts_boot(pr._h, *args) if comm is None else L.vpr_allreduce_counts_boot(pr._h, comm if isinstance(comm, C.c_void_p) else C.c_void_p(comm), *args)
+    rc = api.call_or_allreduce(pr._h, "vpr_pr_counts_boot", "vpr_allreduce_counts_boot", comm, *args)
     if rc:
         raise api.VprError(f"vpr_pr_counts_boot failed ({rc}): {L.vpr_last_error(pr._h).decode()}")
     return out
