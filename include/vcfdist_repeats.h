@@ -24,7 +24,7 @@
  * passed to --stratify.
  *
  * This is in the spirit of k-mer uniqueness / mappability tracks and NOT a reproduction of GIAB's LowMappability or SegDup
- * BEDs: it matches exactly (no mismatches), k <= 32 (k > 32 needs two-word keys), and it compares both strands.
+ * BEDs: it matches exactly (no mismatches), k <= 32 (longer k-mers: vcfdist_longrepeats.h), and it compares both strands.
  *
  * Limits: 4 <= k <= 32; at most 2^32 - 1 bases in total (the sort's values are 32-bit global starts); a contig of at most
  * INT32_MAX bases.  Device memory (the formula is repeated in pr_repeats.hip): 1 byte per base (the sequence) + 1/8 byte per

@@ -7,7 +7,8 @@
  *   vrp_write_stratified         (none: the same tables per stratum, include/vcfdist_strata.h)
  *   vrp_write_context_bed        (none: the intervals of the sequence-context strata, include/vcfdist_context.h)
  *   vrp_write_repeat_bed         (none: the intervals of the repeat strata, include/vcfdist_repeats.h)
- *   vrp_write_phase_blocks       write_results, phase-blocks.tsv                   src/print.cpp:585-609
+ *   vrp_write_long_repeat_bed    (none: the intervals of the long repeat strata, include/vcfdist_longrepeats.h)
+ *   vrp_write_phase_blocks       write_results, phase-blocks.tsv                  src/print.cpp:585-609
  *   vrp_write_superclusters      write_results, superclusters.tsv                  src/print.cpp:611-671
  *   vrp_write_variants           write_results, query.tsv / truth.tsv              src/print.cpp:673-876
  *   vrp_write_switchflips        phaseblockData::write_switchflips                 src/phase.cpp:406-509
@@ -98,6 +99,9 @@ int vrp_write_context_bed(const char *prefix, const char *const *contigs, int32_
 /* <prefix>repeat-strata.bed: the same for the repeat strata (include/vcfdist_repeats.h), in the same format and order. */
 int vrp_write_repeat_bed(const char *prefix, const char *const *contigs, int32_t n_ctg, const char *const *names, int32_t n_strata,
                          const int64_t *iv_off, const int32_t *start, const int32_t *stop);
+/* <prefix>long-repeat-strata.bed: the same for the long repeat strata (include/vcfdist_longrepeats.h). */
+int vrp_write_long_repeat_bed(const char *prefix, const char *const *contigs, int32_t n_ctg, const char *const *names, int32_t n_strata,
+                              const int64_t *iv_off, const int32_t *start, const int32_t *stop);
 
 int vrp_write_phase_blocks(const char *path, const vrp_contig *ctgs, int32_t n_ctg);
 /* switchflips.tsv: where every switch / flip error may have happened; phasing-summary.tsv: block and error totals with

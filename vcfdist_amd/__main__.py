@@ -14,7 +14,9 @@ stratified-precision-recall-summary.tsv; works under several ranks in both --sha
 sequence-context strata (include/vcfdist_context.h: intervals built on the GPU from the FASTA) follow the list's strata, or stand
 alone, and context-strata.bed holds their intervals.  With --stratify-repeats the default repeat strata (include/vcfdist_repeats.h:
 where the FASTA is not unique, found genome-wide on the GPU before the contig loop) follow the list's strata, in front of the context
-strata, and repeat-strata.bed holds their intervals.  With --stratify-variants the default variant strata
+strata, and repeat-strata.bed holds their intervals.  With --stratify-long-repeats the default long repeat strata (repeated 64-, 100-
+and 250-mers, include/vcfdist_longrepeats.h: one more genome-wide pass) follow those, and long-repeat-strata.bed holds their intervals.
+With --stratify-variants the default variant strata
 (include/vcfdist_varstrata.h: transitions / transversions, indel size bins, hom / het, isolated / crowded -- bits made on the GPU from
 the variant tables) follow those, or stand alone, and variant-strata.tsv lists them with their numbers of members.  With --bootstrap N
 the counters are
@@ -145,10 +147,12 @@ def stratify_contig(pr, prep, strat, args, pb, part_idx=None):
     from . import shard
     name, whole = prep["name"], prep["batch"]
     n_strata = len(strat["names"])
-    # the interval table: the rows of --stratify's BEDs, with --stratify-repeats the contig's rows of the genome-wide pass behind them
+    # the interval table: the rows of --stratify's BEDs, with --stratify-repeats and --stratify-long-repeats the contig's rows of the
+    # genome-wide passes behind them
     table = None
-    if strat["beds"] or strat["rep"]:
-        table = A.Strata([[b.intervals(name)] for b in strat["beds"]] + [[row] for row in (strat["rep_rows"][name] if strat["rep"] else ())], 1)
+    if strat["beds"] or strat["rep"] or strat["lrep"]:
+        table = A.Strata([[b.intervals(name)] for b in strat["beds"]] + [[row] for row in (strat["rep_rows"][name] if strat["rep"] else ())] +
+                         [[row] for row in (strat["lrep_rows"][name] if strat["lrep"] else ())], 1)
     if strat["ctx"]:        # --stratify-context: the context intervals are built on the device and go to the same mask kernel
         pr.context_masks(prep["variants"], strat["ctx"], table)
         keep_context_intervals(pr, strat, name)
@@ -189,6 +193,20 @@ def repeat_strata(fasta, strat, args, device=0):
     strat["rep_rows"] = {c: [rows[k][j] for k in range(len(strat["rep"]))] for j, c in enumerate(names)}
     strat["rep_stats"] = pr.repeat_stats()
     strat["rep_ms"] = sum(pr.repeat_timing())
+    pr.close()
+
+
+def long_repeat_strata(fasta, strat, args, device=0):
+    """--stratify-long-repeats: the same for the long repeat strata (include/vcfdist_longrepeats.h), on a handle of its own"""
+    cfg = A.default_config(device=device)
+    cfg.max_qual = float(args.max_qual)
+    pr = api.PrecisionRecall(cfg)
+    names = list(fasta)
+    pr.longrepeat_intervals([fasta[c] for c in names], strat["lrep"])
+    rows = pr.download_longrepeat_intervals()
+    strat["lrep_rows"] = {c: [rows[k][j] for k in range(len(strat["lrep"]))] for j, c in enumerate(names)}
+    strat["lrep_stats"] = pr.longrepeat_stats()
+    strat["lrep_ms"] = sum(pr.longrepeat_timing())
     pr.close()
 
 
@@ -484,6 +502,10 @@ def main(argv=None):
                     help="the default repeat strata (bases covered by a 16-, 24- or 32-mer that occurs more than once in the FASTA, on "
                          "either strand), built on the GPU, behind those of --stratify or alone; their intervals are written to "
                          "repeat-strata.bed")
+    ap.add_argument("--stratify-long-repeats", action="store_true",
+                    help="the default long repeat strata (bases covered by a 64-, 100- or 250-mer that occurs more than once in the FASTA, on "
+                         "either strand), built on the GPU in one more genome-wide pass, behind the strata of --stratify and "
+                         "--stratify-repeats; also writes long-repeat-strata.bed")
     ap.add_argument("--stratify-context", action="store_true",
                     help="the default sequence-context strata (homopolymers, short tandem repeats, GC bands), built on the GPU from the "
                          "FASTA, behind those of --stratify or alone; their intervals are written to context-strata.bed")
@@ -522,7 +544,7 @@ def main(argv=None):
         raise SystemExit("ERROR: --error-window needs --classify-errors")
     if args.cut_classes and not (args.classify_errors or args.classify_matches):
         raise SystemExit("ERROR: --cut-classes needs --classify-errors or --classify-matches")
-    if args.cut_classes and not (args.stratify or args.stratify_repeats or args.stratify_context or args.stratify_variants or args.bootstrap):
+    if args.cut_classes and not (args.stratify or args.stratify_repeats or args.stratify_long_repeats or args.stratify_context or args.stratify_variants or args.bootstrap):
         raise SystemExit("ERROR: --cut-classes needs --stratify, --stratify-context, --stratify-variants or --bootstrap")
     realigning = args.realign_query or args.realign_truth
     if realigning and (args.sub < 1 or args.extend < 1):
@@ -556,7 +578,7 @@ def main(argv=None):
             torch.cuda.set_device(device)
         dist.init_process_group(backend=backend)
     strat = None
-    if args.stratify or args.stratify_repeats or args.stratify_context or args.stratify_variants:       # the strata list and every BED it names are read and checked before anything is evaluated
+    if args.stratify or args.stratify_repeats or args.stratify_long_repeats or args.stratify_context or args.stratify_variants:       # the strata list and every BED it names are read and checked before anything is evaluated
         names, beds = [], []
         if args.stratify:
             try:
@@ -564,7 +586,8 @@ def main(argv=None):
             except IOError as e:
                 raise SystemExit(f"ERROR: {e}")
         strat = dict(names=list(names), beds=beds, counts=None, vars=0, none=0, ctx=None, ctx_names=[], intervals={}, ctx_ms={},
-                     vs=None, vs_names=[], vs_members=np.zeros((2, 0), np.int64), vs_ms=0.0, rep=None, rep_names=[], rep_rows={})
+                     vs=None, vs_names=[], vs_members=np.zeros((2, 0), np.int64), vs_ms=0.0, rep=None, rep_names=[], rep_rows={},
+                     lrep=None, lrep_names=[], lrep_rows={})
         if args.stratify_repeats:       # the default repeat strata (include/vcfdist_repeats.h) behind the list's, in front of the context strata
             strat["rep_names"], strat["rep"] = api.repeats_default()
             for n in strat["rep_names"]:
@@ -572,6 +595,13 @@ def main(argv=None):
                     raise SystemExit(f"ERROR: strata list '{args.stratify}': duplicate stratum name '{n}' (a repeat stratum of "
                                      "--stratify-repeats)")
             strat["names"] += strat["rep_names"]
+        if args.stratify_long_repeats:  # the default long repeat strata (include/vcfdist_longrepeats.h) behind those
+            strat["lrep_names"], strat["lrep"] = api.longrepeats_default()
+            for n in strat["lrep_names"]:
+                if n in strat["names"]:
+                    raise SystemExit(f"ERROR: strata list '{args.stratify}': duplicate stratum name '{n}' (a long repeat stratum of "
+                                     "--stratify-long-repeats)")
+            strat["names"] += strat["lrep_names"]
         if args.stratify_context:       # the default sequence-context strata (include/vcfdist_context.h) behind the list's
             strat["ctx_names"], strat["ctx"] = api.context_default()
             for n in strat["ctx_names"]:
@@ -616,6 +646,11 @@ def main(argv=None):
     if strat is not None and strat["rep"]:      # the genome-wide pass, before the contig loop (not under -ro)
         try:
             repeat_strata(fasta, strat, args, device=device)
+        except api.VprError as e:
+            raise SystemExit(f"ERROR: {e}")
+    if strat is not None and strat["lrep"]:
+        try:
+            long_repeat_strata(fasta, strat, args, device=device)
         except api.VprError as e:
             raise SystemExit(f"ERROR: {e}")
     nq = args.max_qual - args.min_qual + 1
@@ -765,6 +800,8 @@ def main(argv=None):
                 RP.write_stratified(args.prefix, strat["names"], strat["counts"], args.min_qual, args.max_qual)
                 if strat["rep"]:
                     RP.write_repeat_bed(args.prefix, contigs, strat["rep_names"], strat["rep_rows"])
+                if strat["lrep"]:
+                    RP.write_long_repeat_bed(args.prefix, contigs, strat["lrep_names"], strat["lrep_rows"])
                 if strat["ctx"]:
                     RP.write_context_bed(args.prefix, contigs, strat["ctx_names"], strat["intervals"])
                 if strat["vs"]:
@@ -795,6 +832,11 @@ def main(argv=None):
                 starts = ", ".join(f"{int(v)} valid and {int(r)} repeated starts (k={sp.k})" for sp, v, r in zip(strat["rep"], *strat["rep_stats"]))
                 print(f"[vcfdist_amd] repeat strata: {n_iv} intervals of {len(strat['rep'])} strata, {starts}, {strat['rep_ms']:.3f} ms on the device",
                       file=sys.stderr)
+            if strat["lrep"]:
+                n_iv = sum(len(a) for rows in strat["lrep_rows"].values() for a, _ in rows)
+                starts = ", ".join(f"{int(v)} valid and {int(r)} repeated starts (k={sp.k})" for sp, v, r in zip(strat["lrep"], *strat["lrep_stats"]))
+                print(f"[vcfdist_amd] long repeat strata: {n_iv} intervals of {len(strat['lrep'])} strata, {starts}, {strat['lrep_ms']:.3f} ms on "
+                      "the device", file=sys.stderr)
             if strat["ctx"]:
                 n_iv = sum(len(a) for rows in strat["intervals"].values() for a, _ in rows)
                 print(f"[vcfdist_amd] context strata: {n_iv} intervals of {len(strat['ctx'])} strata, {sum(strat['ctx_ms'].values()):.3f} ms "

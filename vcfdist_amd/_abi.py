@@ -542,6 +542,9 @@ def ctx_gc(lo, hi, window, slop=0):
 # ---- include/vcfdist_repeats.h
 REP_MIN_K, REP_MAX_K = 4, 32
 REP_MAX_SPEC = 8
+# ---- include/vcfdist_longrepeats.h (its strata are VprRepeatStratum with 33 <= k <= 256)
+LREP_MIN_K, LREP_MAX_K = 33, 256
+LREP_MAX_SPEC = 8
 
 
 class VprRepeatStratum(C.Structure):

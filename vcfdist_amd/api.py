@@ -102,6 +102,12 @@ def lib():
     L.vpr_repeat_stats.argtypes = [H, A.P_i64, A.P_i64]
     L.vpr_repeat_timing.argtypes = [H] + [C.POINTER(C.c_double)] * 4
     L.vpr_repeat_sort_floor.argtypes = [H, C.c_int64, C.c_int32, C.c_uint64, C.POINTER(C.c_double)]
+    L.vpr_longrepeats_default.argtypes = L.vpr_repeats_default.argtypes
+    L.vpr_longrepeat_intervals.argtypes = L.vpr_repeat_intervals.argtypes
+    L.vpr_longrepeat_interval_counts.argtypes = [H, A.P_i64]
+    L.vpr_longrepeat_download_intervals.argtypes = [H, A.P_i32, A.P_i32]
+    L.vpr_longrepeat_stats.argtypes = [H, A.P_i64, A.P_i64, A.P_i64, A.P_i64]
+    L.vpr_longrepeat_timing.argtypes = [H] + [C.POINTER(C.c_double)] * 4
     L.vpr_varstrata_default.argtypes = [C.POINTER(C.POINTER(A.VprVariantStratum)), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.c_int32)]
     L.vpr_varstrata_masks.argtypes = [H, C.POINTER(A.VprVariants), C.POINTER(A.VprVariantStratum), C.c_int32, C.c_int32]
     L.vpr_varstrata_timing.argtypes = [H, C.POINTER(C.c_double)]
@@ -159,6 +165,9 @@ CONTEXT_EXPORTED = ["vpr_context_default", "vpr_context_masks", "vpr_context_int
 # include/vcfdist_repeats.h
 REPEATS_EXPORTED = ["vpr_repeats_default", "vpr_repeat_intervals", "vpr_repeat_interval_counts", "vpr_repeat_download_intervals",
                     "vpr_repeat_stats", "vpr_repeat_timing", "vpr_repeat_sort_floor", "vrp_write_repeat_bed"]
+# include/vcfdist_longrepeats.h
+LONGREPEATS_EXPORTED = ["vpr_longrepeats_default", "vpr_longrepeat_intervals", "vpr_longrepeat_interval_counts",
+                        "vpr_longrepeat_download_intervals", "vpr_longrepeat_stats", "vpr_longrepeat_timing", "vrp_write_long_repeat_bed"]
 # include/vcfdist_varstrata.h
 VARSTRATA_EXPORTED = ["vpr_varstrata_default", "vpr_varstrata_masks", "vpr_varstrata_timing", "vrp_write_variant_strata"]
 # include/vcfdist_errclass.h
@@ -239,6 +248,15 @@ def repeats_default():
     rc = lib().vpr_repeats_default(C.byref(spec), C.byref(names), C.byref(n))
     if rc:
         raise VprError(f"vpr_repeats_default failed ({rc})")
+    return [names[k].decode() for k in range(n.value)], [A.VprRepeatStratum.from_buffer_copy(spec[k]) for k in range(n.value)]
+
+
+def longrepeats_default():
+    """the command lines' default long repeat strata (vpr_longrepeats_default): (names, [A.VprRepeatStratum])"""
+    spec, names, n = C.POINTER(A.VprRepeatStratum)(), C.POINTER(C.c_char_p)(), C.c_int32()
+    rc = lib().vpr_longrepeats_default(C.byref(spec), C.byref(names), C.byref(n))
+    if rc:
+        raise VprError(f"vpr_longrepeats_default failed ({rc})")
     return [names[k].decode() for k in range(n.value)], [A.VprRepeatStratum.from_buffer_copy(spec[k]) for k in range(n.value)]
 
 
@@ -530,10 +548,9 @@ class PrecisionRecall:
         self._chk(lib().vpr_context_timing(self._h, C.byref(a), C.byref(b)), "vpr_context_timing")
         return a.value, b.value
 
-    def repeat_intervals(self, contigs, spec):
-        """The repeat strata (include/vcfdist_repeats.h): the intervals of every entry of `spec` (A.rep_kmer) for the whole genome,
-        built on the device in one call.  contigs: the sequences (bytes or uint8 arrays) in order, or (ctg_off, ctg_seq) as the
-        library takes them.  The handle needs no batch."""
+    @staticmethod
+    def _genome(contigs):
+        """(ctg_off int64, ctg_seq uint8 or None) of the contigs' sequences, or of (ctg_off, ctg_seq) as the library takes them"""
         if isinstance(contigs, tuple):
             off, seq = np.ascontiguousarray(contigs[0], np.int64), contigs[1]
         else:
@@ -544,21 +561,58 @@ class PrecisionRecall:
             seq = np.ascontiguousarray(seq, np.uint8)
             if seq.size == 0:
                 seq = np.zeros(1, np.uint8)
+        return off, seq
+
+    def _repeat_call(self, entry, attr, contigs, spec):
+        off, seq = self._genome(contigs)
         arr = (A.VprRepeatStratum * max(len(spec), 1))(*spec) if spec is not None else None
-        self._repeats = None
-        self._chk(lib().vpr_repeat_intervals(self._h, len(off) - 1, A._ptr(off, C.c_int64), A._ptr(seq, C.c_uint8) if seq is not None else None,
-                                             arr, len(spec) if spec is not None else 1), "vpr_repeat_intervals")
-        self._repeats = (len(spec), len(off) - 1)
+        setattr(self, attr, None)
+        self._chk(getattr(lib(), entry)(self._h, len(off) - 1, A._ptr(off, C.c_int64), A._ptr(seq, C.c_uint8) if seq is not None else None,
+                                        arr, len(spec) if spec is not None else 1), entry)
+        setattr(self, attr, (len(spec), len(off) - 1))
+
+    def _repeat_rows(self, stem, attr):
+        n_spec, n_ctg = getattr(self, attr, None) or (0, 1)      # (before a call the library refuses: VPR_ERR_STATE)
+        off = np.zeros(n_spec * n_ctg + 1, np.int64)
+        self._chk(getattr(lib(), f"{stem}_interval_counts")(self._h, A._ptr(off, C.c_int64)), f"{stem}_interval_counts")
+        st, sp = np.zeros(max(int(off[-1]), 1), np.int32), np.zeros(max(int(off[-1]), 1), np.int32)
+        self._chk(getattr(lib(), f"{stem}_download_intervals")(self._h, A._ptr(st, C.c_int32), A._ptr(sp, C.c_int32)), f"{stem}_download_intervals")
+        return [[(st[off[k * n_ctg + c]:off[k * n_ctg + c + 1]], sp[off[k * n_ctg + c]:off[k * n_ctg + c + 1]]) for c in range(n_ctg)]
+                for k in range(n_spec)]
+
+    def longrepeat_intervals(self, contigs, spec):
+        """The long repeat strata (include/vcfdist_longrepeats.h): the intervals of every entry of `spec` (A.rep_kmer with 33 <= k <=
+        256) for the whole genome, built on the device in one call.  contigs: as for repeat_intervals.  The handle needs no batch."""
+        self._repeat_call("vpr_longrepeat_intervals", "_longrepeats", contigs, spec)
+
+    def download_longrepeat_intervals(self):
+        """the intervals of the last longrepeat_intervals: rows[spec][contig] = (starts, stops), int32 arrays, 0-based half-open"""
+        return self._repeat_rows("vpr_longrepeat", "_longrepeats")
+
+    def longrepeat_stats(self, levels=False):
+        """(valid starts, repeated starts) per entry of the last longrepeat_intervals: two int64 arrays; with `levels` also the
+        candidates of every entry's last level and (pairs of the base level, candidates of the levels 64 and 128)"""
+        n_spec = (getattr(self, "_longrepeats", None) or (1, 1))[0]
+        a, b, c, lv = np.zeros(n_spec, np.int64), np.zeros(n_spec, np.int64), np.zeros(n_spec, np.int64), np.zeros(3, np.int64)
+        self._chk(lib().vpr_longrepeat_stats(self._h, A._ptr(a, C.c_int64), A._ptr(b, C.c_int64), A._ptr(c, C.c_int64), A._ptr(lv, C.c_int64)),
+                  "vpr_longrepeat_stats")
+        return (a, b, c, lv) if levels else (a, b)
+
+    def longrepeat_timing(self):
+        """(ms_base, ms_levels, ms_last, ms_intervals) of the last longrepeat_intervals, from HIP events on the handle's stream"""
+        t = [C.c_double() for _ in range(4)]
+        self._chk(lib().vpr_longrepeat_timing(self._h, *[C.byref(x) for x in t]), "vpr_longrepeat_timing")
+        return tuple(x.value for x in t)
+
+    def repeat_intervals(self, contigs, spec):
+        """The repeat strata (include/vcfdist_repeats.h): the intervals of every entry of `spec` (A.rep_kmer) for the whole genome,
+        built on the device in one call.  contigs: the sequences (bytes or uint8 arrays) in order, or (ctg_off, ctg_seq) as the
+        library takes them.  The handle needs no batch."""
+        self._repeat_call("vpr_repeat_intervals", "_repeats", contigs, spec)
 
     def download_repeat_intervals(self):
         """the intervals of the last repeat_intervals: rows[spec][contig] = (starts, stops), int32 arrays, 0-based half-open"""
-        n_spec, n_ctg = getattr(self, "_repeats", None) or (0, 1)      # (before a call the library refuses: VPR_ERR_STATE)
-        off = np.zeros(n_spec * n_ctg + 1, np.int64)
-        self._chk(lib().vpr_repeat_interval_counts(self._h, A._ptr(off, C.c_int64)), "vpr_repeat_interval_counts")
-        st, sp = np.zeros(max(int(off[-1]), 1), np.int32), np.zeros(max(int(off[-1]), 1), np.int32)
-        self._chk(lib().vpr_repeat_download_intervals(self._h, A._ptr(st, C.c_int32), A._ptr(sp, C.c_int32)), "vpr_repeat_download_intervals")
-        return [[(st[off[k * n_ctg + c]:off[k * n_ctg + c + 1]], sp[off[k * n_ctg + c]:off[k * n_ctg + c + 1]]) for c in range(n_ctg)]
-                for k in range(n_spec)]
+        return self._repeat_rows("vpr_repeat", "_repeats")
 
     def repeat_stats(self):
         """(valid starts, repeated starts) per entry of the last repeat_intervals: two int64 arrays"""

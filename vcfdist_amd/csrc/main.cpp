@@ -9,7 +9,7 @@
 //   vcfdist_gpu <query.vcf[.gz]> <truth.vcf[.gz]> <ref.fasta[.gz]> [-b regions.bed] [-p prefix] [-n] [-c biwfa | gap N | size N]
 //               [-l max variant size] [-s max supercluster size] [-mn / -mx qual] [-f filters] [-i iterations] [-x -o -e penalties]
 //               [-ct credit threshold] [-pt phasing threshold] [-sv threshold] [--reach-min-gap N] [--strict] [--device N]
-//               [-d] [-ex -eo -ee evaluation penalties] [-rq] [-rt] [-ro] [--stratify strata.tsv] [--stratify-repeats] [--stratify-context]
+//               [-d] [-ex -eo -ee evaluation penalties] [-rq] [-rt] [-ro] [--stratify strata.tsv] [--stratify-repeats] [--stratify-long-repeats] [--stratify-context]
 //               [--stratify-variants]
 //               [--bootstrap N] [--bootstrap-seed S]
 //               [--classify-errors] [--error-window N]
@@ -25,6 +25,8 @@
 // the GPU from the FASTA, include/vcfdist_context.h) follow the list's strata, or stand alone; context-strata.bed holds them.
 // With --stratify-repeats the default repeat strata (where the FASTA is not unique: include/vcfdist_repeats.h, one genome-wide pass
 // on the GPU before the contig loop) follow the list's strata, in front of the context strata; repeat-strata.bed holds them.
+// With --stratify-long-repeats the default long repeat strata (repeated 64-, 100- and 250-mers: include/vcfdist_longrepeats.h, one
+// more genome-wide pass) follow those, in front of the context strata; long-repeat-strata.bed holds them.
 // With --stratify-variants the default variant strata (transitions / transversions, indel size bins, hom / het, isolated / crowded:
 // bits made on the GPU from the variant tables, include/vcfdist_varstrata.h) follow those, or stand alone; variant-strata.tsv lists
 // them with their numbers of members.
@@ -63,6 +65,7 @@
 #include "../../include/vcfdist_report.h"
 #include "../../include/vcfdist_context.h"
 #include "../../include/vcfdist_repeats.h"
+#include "../../include/vcfdist_longrepeats.h"
 #include "../../include/vcfdist_strata.h"
 #include "../../include/vcfdist_varstrata.h"
 #include "../../include/vcfdist_errclass.h"
@@ -72,7 +75,7 @@ namespace {
 
 struct Args {
     std::string query, truth, fasta, bed, filter, prefix = "./", cluster = "biwfa", stratify;
-    bool stratify_context = false, stratify_variants = false, stratify_repeats = false;
+    bool stratify_context = false, stratify_variants = false, stratify_repeats = false, stratify_long_repeats = false;
     int max_size = 5000, min_qual = 0, max_qual = 60, cluster_gap = 50, max_iterations = 4, max_supercluster_size = 10000;
     int sub = 5, open = 6, extend = 2, sv_threshold = 50, reach_min_gap = 10, device = 0;
     int eval_sub = 3, eval_open = 2, eval_extend = 1;      // globals.h:52-55
@@ -163,6 +166,7 @@ Args parse(int argc, char **argv) {
         else if (o == "--stratify") a.stratify = need(i);
         else if (o == "--stratify-context") a.stratify_context = true;
         else if (o == "--stratify-repeats") a.stratify_repeats = true;
+        else if (o == "--stratify-long-repeats") a.stratify_long_repeats = true;
         else if (o == "--stratify-variants") a.stratify_variants = true;
         else if (o == "--bootstrap") a.bootstrap = bootstrap_replicates(need(i));
         else if (o == "--bootstrap-seed") a.bootstrap_seed = bootstrap_seed(need(i));
@@ -186,7 +190,7 @@ Args parse(int argc, char **argv) {
     if (a.error_window >= 0 && !a.classify_errors) die("ERROR: --error-window needs --classify-errors");
     if (a.error_window < 0) a.error_window = VPR_EC_DEFAULT_WINDOW;
     if (a.cut_classes && !a.classify_errors && !a.classify_matches) die("ERROR: --cut-classes needs --classify-errors or --classify-matches");
-    if (a.cut_classes && a.stratify.empty() && !a.stratify_repeats && !a.stratify_context && !a.stratify_variants && !a.bootstrap)
+    if (a.cut_classes && a.stratify.empty() && !a.stratify_repeats && !a.stratify_long_repeats && !a.stratify_context && !a.stratify_variants && !a.bootstrap)
         die("ERROR: --cut-classes needs --stratify, --stratify-context, --stratify-variants or --bootstrap");
     if ((a.realign_query || a.realign_truth) && (a.sub < 1 || a.extend < 1))
         die("ERROR: realignment needs a mismatch penalty (-x) and a gap-extension penalty (-e) of at least 1");
@@ -433,6 +437,24 @@ int main(int argc, char **argv) {
     std::vector<int32_t> rep_start, rep_stop;
     std::vector<int64_t> rep_valid(size_t(n_rep), 0), rep_repeated(size_t(n_rep), 0);
     double rep_ms = 0;
+    // --stratify-long-repeats: the default long repeat strata (include/vcfdist_longrepeats.h) behind the list's and the repeat strata,
+    // from a genome-wide pass of their own; their rows travel the same way
+    const vpr_repeat_stratum *lrep_spec = nullptr;
+    const char *const *lrep_names = nullptr;
+    int32_t n_lrep = 0;
+    if (A.stratify_long_repeats) {
+        if (vpr_longrepeats_default(&lrep_spec, &lrep_names, &n_lrep)) die("ERROR: vpr_longrepeats_default failed");
+        for (int k = 0; k < n_lrep; k++) {
+            if (find(strata.names, lrep_names[k]) >= 0)
+                die("ERROR: strata list '%s': duplicate stratum name '%s' (a long repeat stratum of --stratify-long-repeats)", A.stratify.c_str(),
+                    lrep_names[k]);
+            strata.names.push_back(lrep_names[k]);
+        }
+    }
+    std::vector<int64_t> lrep_off;                                              // [n_lrep * FASTA contigs + 1], row = stratum * contigs + contig
+    std::vector<int32_t> lrep_start, lrep_stop;
+    std::vector<int64_t> lrep_valid(size_t(n_lrep), 0), lrep_repeated(size_t(n_lrep), 0);
+    double lrep_ms = 0;
     // --stratify-context: the default sequence-context strata (include/vcfdist_context.h) behind the list's and the repeat strata
     const int n_bed = int(strata.names.size());
     const vpr_context_stratum *ctx_spec = nullptr;
@@ -578,6 +600,22 @@ int main(int argc, char **argv) {
         rep_ms = ms[0] + ms[1] + ms[2] + ms[3];
         vpr_destroy(hr);
     }
+    if (n_lrep) {          // the same for the long repeat strata
+        vpr_handle *hr = nullptr;
+        if (vpr_create(&cfg, &hr)) { fprintf(stderr, "vpr_create: %s\n", vpr_last_error(nullptr)); return 2; }
+        lrep_off.assign(size_t(n_lrep) * size_t(fa->n_ctg) + 1, 0);
+        if (vpr_longrepeat_intervals(hr, fa->n_ctg, fa->ctg_off, fa->seq, lrep_spec, n_lrep) || vpr_longrepeat_interval_counts(hr, lrep_off.data()))
+            die("ERROR: %s", vpr_last_error(hr));
+        lrep_start.assign(size_t(lrep_off.back()) + 1, 0); lrep_stop.assign(size_t(lrep_off.back()) + 1, 0);
+        std::vector<int64_t> n_last(size_t(n_lrep), 0);
+        double ms[4] = {0, 0, 0, 0};
+        if (vpr_longrepeat_download_intervals(hr, lrep_start.data(), lrep_stop.data()) ||
+            vpr_longrepeat_stats(hr, lrep_valid.data(), lrep_repeated.data(), n_last.data(), nullptr) ||
+            vpr_longrepeat_timing(hr, &ms[0], &ms[1], &ms[2], &ms[3]))
+            die("ERROR: %s", vpr_last_error(hr));
+        lrep_ms = ms[0] + ms[1] + ms[2] + ms[3];
+        vpr_destroy(hr);
+    }
     vpr_handle *h = nullptr;
     if (vpr_create(&cfg, &h)) { fprintf(stderr, "vpr_create: %s\n", vpr_last_error(nullptr)); return 2; }
 
@@ -707,6 +745,12 @@ int main(int argc, char **argv) {
                     iv_start.insert(iv_start.end(), rep_start.begin() + rep_off[r], rep_start.begin() + rep_off[r + 1]);
                     iv_stop.insert(iv_stop.end(), rep_stop.begin() + rep_off[r], rep_stop.begin() + rep_off[r + 1]);
                     iv_off[size_t(n_list + k) + 1] = int64_t(iv_start.size());
+                }
+                for (int k = 0; k < n_lrep; k++) {     // and those of the long repeat strata behind them
+                    const size_t r = size_t(k) * size_t(fa->n_ctg) + size_t(fi);
+                    iv_start.insert(iv_start.end(), lrep_start.begin() + lrep_off[r], lrep_start.begin() + lrep_off[r + 1]);
+                    iv_stop.insert(iv_stop.end(), lrep_stop.begin() + lrep_off[r], lrep_stop.begin() + lrep_off[r + 1]);
+                    iv_off[size_t(n_list + n_rep + k) + 1] = int64_t(iv_start.size());
                 }
                 const vpr_strata ST = {n_bed, 1, iv_off.data(), iv_start.data(), iv_stop.data()};
                 std::vector<int64_t> sc_counts(strat_total.size(), 0);
@@ -854,24 +898,27 @@ int main(int argc, char **argv) {
             if (A.bootstrap && vrp_write_bootstrap_stratified(A.prefix.c_str(), names.data(), n_strata, strat_total.data(), boot_strat.data(), A.bootstrap,
                                                               A.bootstrap_seed, A.min_qual, A.max_qual))
                 die("ERROR: %s", vrp_last_error());
-            if (n_rep) {           // repeat-strata.bed: the evaluated contigs in evaluation order, rows contig-major
+            // repeat-strata.bed and long-repeat-strata.bed: the evaluated contigs in evaluation order, rows contig-major
+            auto repeat_bed = [&](int32_t n, const char *const *rnames, const std::vector<int64_t> &roff, const std::vector<int32_t> &rstart,
+                                  const std::vector<int32_t> &rstop, decltype(&vrp_write_repeat_bed) write) {
                 std::vector<const char *> cn;
                 std::vector<int64_t> off(1, 0);
                 std::vector<int32_t> st, sp;
                 for (const auto &c : contigs) {
                     cn.push_back(c.c_str());
                     const int fi = find(fn, c);
-                    for (int k = 0; k < n_rep; k++) {
+                    for (int k = 0; k < n; k++) {
                         const size_t r = size_t(k) * size_t(fa->n_ctg) + size_t(fi);
-                        st.insert(st.end(), rep_start.begin() + rep_off[r], rep_start.begin() + rep_off[r + 1]);
-                        sp.insert(sp.end(), rep_stop.begin() + rep_off[r], rep_stop.begin() + rep_off[r + 1]);
+                        st.insert(st.end(), rstart.begin() + roff[r], rstart.begin() + roff[r + 1]);
+                        sp.insert(sp.end(), rstop.begin() + roff[r], rstop.begin() + roff[r + 1]);
                         off.push_back(int64_t(st.size()));
                     }
                 }
                 st.push_back(0); sp.push_back(0);      // (never empty: a pointer is wanted)
-                if (vrp_write_repeat_bed(A.prefix.c_str(), cn.data(), int32_t(cn.size()), rep_names, n_rep, off.data(), st.data(), sp.data()))
-                    die("ERROR: %s", vrp_last_error());
-            }
+                if (write(A.prefix.c_str(), cn.data(), int32_t(cn.size()), rnames, n, off.data(), st.data(), sp.data())) die("ERROR: %s", vrp_last_error());
+            };
+            if (n_rep) repeat_bed(n_rep, rep_names, rep_off, rep_start, rep_stop, vrp_write_repeat_bed);
+            if (n_lrep) repeat_bed(n_lrep, lrep_names, lrep_off, lrep_start, lrep_stop, vrp_write_long_repeat_bed);
             if (n_ctx) {
                 std::vector<const char *> cn;
                 for (const auto &c : ctx_contigs) cn.push_back(c.c_str());
@@ -945,6 +992,17 @@ int main(int argc, char **argv) {
         }
         fprintf(stderr, "[vcfdist_amd] repeat strata: %lld intervals of %d strata, %s%.3f ms on the device\n", (long long)rep_off.back(), n_rep,
                 starts.c_str(), rep_ms);
+    }
+    if (n_lrep) {
+        std::string starts;
+        for (int k = 0; k < n_lrep; k++) {
+            char buf[128];
+            snprintf(buf, sizeof(buf), "%lld valid and %lld repeated starts (k=%d), ", (long long)lrep_valid[size_t(k)], (long long)lrep_repeated[size_t(k)],
+                     lrep_spec[k].k);
+            starts += buf;
+        }
+        fprintf(stderr, "[vcfdist_amd] long repeat strata: %lld intervals of %d strata, %s%.3f ms on the device\n", (long long)lrep_off.back(), n_lrep,
+                starts.c_str(), lrep_ms);
     }
     if (n_ctx)
         fprintf(stderr, "[vcfdist_amd] context strata: %lld intervals of %d strata, %.3f ms on the device\n", (long long)ctx_start.size(), n_ctx, ctx_ms);

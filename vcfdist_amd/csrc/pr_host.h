@@ -8,6 +8,7 @@
 //   pr_strata.hip   the membership words of the region-stratified counters (include/vcfdist_strata.h): k_strata_mask, up- and download
 //   pr_context.hip  the sequence-context strata (include/vcfdist_context.h): interval lists built from the contig sequences
 //   pr_repeats.hip  the repeat strata (include/vcfdist_repeats.h): genome-wide repeated k-mers, in front of pr_context.hip's run passes
+//   pr_longrepeats.hip the long repeat strata (include/vcfdist_longrepeats.h): repeated k-mers of 33..256 bases by rank doubling
 //   pr_varstrata.hip the variant strata (include/vcfdist_varstrata.h): bits made from the variant tables themselves
 //   pr_errclass.hip the error classes (include/vcfdist_errclass.h): why each FP and FN is wrong
 //   pr_matchkind.hip the match kinds (include/vcfdist_matchkind.h): how each TP was matched
@@ -276,6 +277,7 @@ struct DistState;                        // the distance step's tables and arena
 struct StrataState;                      // the membership words and the stratified counters' cut state (pr_strata.hip)
 struct ContextState;                     // the sequence-context intervals (pr_context.hip)
 struct RepeatState;                      // the repeat intervals (pr_repeats.hip)
+struct LongRepeatState;                  // the long repeat intervals (pr_longrepeats.hip)
 struct LabelState;                       // the label bytes and the label histogram of a label pass (pr_label.h)
 enum { LABEL_ERRCLASS, LABEL_MATCHKIND, LABEL_PASSES };     // the label passes: pr_errclass.hip, pr_matchkind.hip
 struct CutState;                         // the histogram, keys and device time of a count cut (pr_cut.h)
@@ -429,6 +431,7 @@ struct vpr_handle {
     StrataState *strata = nullptr;       // vpr_strata_masks / vpr_strata_upload_masks (pr_strata.hip), released with the batch
     ContextState *context = nullptr;     // vpr_context_masks (pr_context.hip), released by the next one or vpr_destroy
     RepeatState *repeats = nullptr;      // vpr_repeat_intervals (pr_repeats.hip), released by the next one or vpr_destroy
+    LongRepeatState *longrepeats = nullptr;   // vpr_longrepeat_intervals (pr_longrepeats.hip), released by the next one or vpr_destroy
     CutState *boot = nullptr;            // vpr_pr_counts_boot (pr_cut.hip), created by its first call, released with the batch
     LabelState *label[LABEL_PASSES] = {nullptr, nullptr};   // vpr_errclass / vpr_matchkind (pr_label.hip), created by a pass's first call, released with the batch
     double varstrata_ms = 0;             // device time of the last vpr_varstrata_masks' kernel launches (pr_varstrata.hip)
@@ -485,7 +488,15 @@ int strata_extend(vpr_handle *h, const char *entry, int32_t n_add, const int64_t
 void strata_commit(vpr_handle *h);
 void context_free(vpr_handle *h);                                    // pr_context.hip: the resident context intervals
 void repeats_free(vpr_handle *h);                                    // pr_repeats.hip: the resident repeat intervals
-void label_free(vpr_handle *h);                                      // pr_label.hip: the label bytes and histograms of both label passes
+// pr_repeats.hip, for pr_longrepeats.hip (a kernel is launched from the unit that holds it): the pack over tiles of REP_PACK_TILE
+// starts (write false: the tiles' counts into out; true: the pairs behind the scanned counts), the mark and a piece's flag words
+constexpr int REP_PACK_TILE = 4096;
+void rep_launch_pack(hipStream_t st, bool write, unsigned n_tiles, const uint8_t *seq, const int64_t *ctg_off, int n_ctg, int64_t N, int k,
+                     uint32_t *out, uint64_t *keys, uint32_t *vals);
+void rep_launch_mark(hipStream_t st, const uint64_t *keys, const uint32_t *vals, uint64_t n, int k, uint32_t *flags32, unsigned long long *n_rep);
+void rep_launch_piece_words(hipStream_t st, const uint64_t *all, int64_t nw, int64_t T0, int64_t g0, int64_t g1, uint64_t *words);
+void longrepeats_free(vpr_handle *h);                              // pr_longrepeats.hip: the resident long repeat intervals
+void label_free(vpr_handle *h);                                    // pr_label.hip: the label bytes and histograms of both label passes
 void boot_free(vpr_handle *h);                                       // pr_cut.hip: the replicate histogram and the keys
 // pr_collect.hip, shared by the three counters entries (vpr_pr_counts; _strata, _boot: pr_cut.hip; `entry`: the entry's name, for the
 // messages).  pr_counts_begin: the state checks and the device, before the entry's own buffers; pr_counts_inputs: the caller's

@@ -434,3 +434,20 @@ int vpr_repeat_timing(const vpr_handle *h, double *ms_pack, double *ms_sort, dou
 }
 
 }  // extern "C"
+
+// the launches pr_longrepeats.hip borrows for its base level (k = 32) and its last level (pr_host.h)
+static_assert(REP_TILE == REP_PACK_TILE, "pr_host.h names the pack's tile");
+
+void rep_launch_pack(hipStream_t st, bool write, unsigned n_tiles, const uint8_t *seq, const int64_t *ctg_off, int n_ctg, int64_t N, int k,
+                     uint32_t *out, uint64_t *keys, uint32_t *vals) {
+    if (write) hipLaunchKernelGGL(k_rep_pack<true>, dim3(n_tiles), dim3(REP_WG), 0, st, seq, ctg_off, n_ctg, N, k, out, keys, vals);
+    else hipLaunchKernelGGL(k_rep_pack<false>, dim3(n_tiles), dim3(REP_WG), 0, st, seq, ctg_off, n_ctg, N, k, out, keys, vals);
+}
+
+void rep_launch_mark(hipStream_t st, const uint64_t *keys, const uint32_t *vals, uint64_t n, int k, uint32_t *flags32, unsigned long long *n_rep) {
+    hipLaunchKernelGGL(k_rep_mark, dim3(std::min(blocks_of(int64_t(n)), MARK_MAX_WG)), dim3(256), 0, st, keys, vals, n, k, flags32, n_rep);
+}
+
+void rep_launch_piece_words(hipStream_t st, const uint64_t *all, int64_t nw, int64_t T0, int64_t g0, int64_t g1, uint64_t *words) {
+    hipLaunchKernelGGL(k_rep_piece_words, dim3(blocks_of(nw)), dim3(256), 0, st, all, nw, T0, g0, g1, words);
+}
