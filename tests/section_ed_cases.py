@@ -98,6 +98,17 @@ def _mutate(rng, X, n):
     return y
 
 
+def _plant(rng, X, n):
+    """X with n edits planted: n // 2 substitutions, then n // 4 one-base deletions and as many one-base insertions (same length)"""
+    y = bytearray(X)
+    for i in rng.choice(np.arange(1, len(y) - 1), n // 2, replace=False):
+        y[int(i)] = _other(rng, y[int(i)])
+    for _ in range(n // 4):
+        del y[int(rng.randint(1, len(y) - 1))]
+        y.insert(int(rng.randint(1, len(y) - 1)), int(rng.choice(_BASES)))
+    return y
+
+
 def _differ_at_the_ends(rng, X, y):
     """first and last base of y made unlike X's, so that nothing is trimmed"""
     if X and y:
@@ -114,6 +125,7 @@ def _differ_at_the_ends(rng, X, y):
 def make_pair(xspec, yspec, rng):
     """X-spec: ("rand", n) | ("rand_n", n): with 40 N and a lower-case base | ("homo", n): A^n | ("none",)
     Y-spec: ("rand", n) | ("mut", n) | ("mut_n", n): X mutated to length n (then N and lower case); all three unlike X at both ends
+            | ("planted", n, k): X with k planted edits, unlike X at both ends | ("x-bases", (i, ...)) / ("x+bases", (i, ...)): X less / plus one base at each i
             | ("x+tail", k): X + k bases | ("x-tail", k): X without its last k | ("homo", n) | ("sub_mid",) | ("sub_ends",) | ("none",)"""
     kx = xspec[0]
     if kx == "rand":
@@ -133,6 +145,19 @@ def make_pair(xspec, yspec, rng):
         Y = _differ_at_the_ends(rng, X, _mutate(rng, X, yspec[1]))
     elif ky == "mut_n":
         Y = _differ_at_the_ends(rng, X, _sprinkle(rng, _mutate(rng, X, yspec[1])))
+    elif ky == "planted":           # ("planted", n, k): length n == len(X), at most k + 2 edits away from X
+        assert yspec[1] == len(X)
+        Y = _differ_at_the_ends(rng, X, _plant(rng, X, yspec[2]))
+    elif ky == "x-bases":           # ("x-bases", (i, ...)): X without its bases i, ..., each made unlike both neighbours (the gap cannot move)
+        for i in yspec[1]:
+            X[i] = _other(rng, X[i - 1], X[i + 1])
+        Y = bytearray(c for i, c in enumerate(X) if i not in yspec[1])
+    elif ky == "x+bases":           # ("x+bases", (i, ...)): X with one more base in front of its bases i, ..., unlike both neighbours
+        Y = bytearray()
+        for i, c in enumerate(X):
+            if i in yspec[1]:
+                Y.append(_other(rng, X[i - 1], c))
+            Y.append(c)
     elif ky == "x+tail":
         Y = X + _rand(rng, yspec[1])
     elif ky == "x-tail":
@@ -169,7 +194,8 @@ TYPE_INS, TYPE_DEL = 2, 3       # include/vcfdist_pr.h (asserted against the ABI
 def build(case, ctg=0):
     """-> Built: the contig (str), the supercluster dict for Variants.from_sites, the (X, Y) pairs and the truth variants' pairs.
     Mode `same`: the query equals the truth (distance 0: the lane levels emit the jobs); `near`: the query's deletion lacks a few
-    bases at either end and its insertion a few at the end (the window or dense levels emit them)."""
+    bases at either end and its insertion a few at the end (the window or dense levels emit them); `fn`: the query has no variant
+    at all (its haplotypes are the reference; every truth variant is a false negative)."""
     rng = np.random.RandomState(case.seed)
     pairs = [make_pair(xs, ys, rng) for xs, ys in case.pairs]
     homo = any(xs[0] == "homo" for xs, _ in case.pairs)
@@ -188,11 +214,13 @@ def build(case, ctg=0):
         short = min(20, ny // 4) if case.mode == "near" else 0
         if nx:
             t.append((p, TYPE_DEL, X.decode(), "", 40.0))
-            q.append((p + cut, TYPE_DEL, X[cut:nx - cut].decode(), "", 30.0))
+            if case.mode != "fn":
+                q.append((p + cut, TYPE_DEL, X[cut:nx - cut].decode(), "", 30.0))
             var_pair.append(k)
         if ny:
             t.append((p + nx, TYPE_INS, "", Y.decode(), 40.0))
-            q.append((p + nx, TYPE_INS, "", Y[:ny - short].decode(), 30.0))
+            if case.mode != "fn":
+                q.append((p + nx, TYPE_INS, "", Y[:ny - short].decode(), 30.0))
             var_pair.append(k)
     end = len(contig)
     contig += right

@@ -3,8 +3,8 @@ that one launch carries many jobs of very different lengths.  Every array agains
 test_gpu_parity.py), and -- independently of the oracle -- ref_ed of every truth variant against the plain DP lev(X, Y).  By
 default the deferred sections go through k_ed_bits (pr_ed.hip); VPR_ED_WF / VPR_ED_DIAG force k_ed_wf / k_ed_diag
 (pr_kernels.hip), which must have run and must give the same arrays.  The inline sections (small_ed in credit_walk) are the
-group inline_borders' first half.  Not reached here: the row sweep k_ed and the kernel selection for batches with a haplotype
-above 65 536 bases (the CPU oracle needs most of a minute and tens of GB for such a section)."""
+group inline_borders' first half.  The row sweep k_ed and the kernel selection for batches with a haplotype above 65 536 bases are
+in tests/test_gpu_long_haplotype.py (the table of tests/long_haplotype_cases.py, behind a ballast supercluster)."""
 import functools
 import time
 
