@@ -1,7 +1,7 @@
 """Regenerates tests/golden/ref/: cases and what the REFERENCE's own functions answer for them (oracle/_ref/ref_harness, built by
 `make -C oracle ref` where the reference's sources are at hand).  Seeded and deterministic; refuses to run without the
 harness.  tests/ref_pins.py describes the files; tests/golden/README.md the case sets.  Run from the repository's root:
-    python tests/golden/make_ref_goldens.py [set ...]          (sets: swg ed cluster chain demo realign; default: all)"""
+    python tests/golden/make_ref_goldens.py [set ...]          (sets: swg ed cluster chain demo realign window_edges; default: all)"""
 import os
 import sys
 import time
@@ -263,6 +263,43 @@ def make_chain():
         save(name, "chain", case, 60)
 
 
+def window_edge_cases():
+    """the subset of tests/window_edge_cases.py's table behind chain_window_edges: the two cases on either side of every border
+    of the 16- and the 64-cell level (shift at distance 0, priced with one mutation; both signs), the priced ties, and two cases
+    each whose paths need the 256-cell, the 1024-cell and the dense level (deletion forms at 1024: haplotypes below 2 000 bases)"""
+    import window_edge_cases as WE
+    needs = WE.needs(WE.TABLE)
+    sweep = {}
+    for c in WE.TABLE:
+        if (c.family == "shift" and c.snp == 0 and c.form == "ins") or (c.family == "priced" and c.k == 1):
+            sweep[(c.family, c.sign, c.u)] = c
+    out = []
+    for (fam, sign, u), c in sweep.items():
+        up = sweep.get((fam, sign, u + 1))
+        lv = needs[c.name][0].level
+        if up is not None and lv in (16, 64) and needs[up.name][0].level == WE.next_level(lv):
+            out += [c, up]
+    assert len(out) == 2 * 2 * 2 * 2, len(out)
+    out += [c for c in WE.TABLE if c.tie]
+    for lv in (256, 1024, WE.DENSE):
+        fit = [c for c in WE.TABLE if c.family == "shift" and c.W == 1024 // (4 if lv == 256 else 1) and c.snp < 2 and
+               (c.form == "del" or lv == 256) and needs[c.name][0].level == lv]
+        out += fit[:2] if lv == WE.DENSE else fit[-2:]          # (the ones next to the border)
+    assert len(out) == 16 + 6 + 6 and len({c.name for c in out}) == len(out), [c.name for c in out]
+    assert all(max(needs[c.name][0].lens) < 2000 for c in out)
+    return out
+
+
+def make_window_edges():
+    """paths along the edge of a window level (tests/window_edge_cases.py).  `-c gap 2000` keeps a case's two variants, a whole
+    tract apart, in one supercluster; every case is a contig of its own"""
+    import window_edge_cases as WE
+    cases = window_edge_cases()
+    v, _, _ = WE.batch_of(cases)
+    save("chain_window_edges", "chain", variants_to_case(v, ["-c", "gap", "2000"] + BASE, per_sc=True), 600,
+         extra=dict(case_names=np.frombuffer("\n".join(c.name for c in cases).encode(), np.uint8)))
+
+
 def make_cluster():
     """clustering alone, on whole synthetic contigs (no precision/recall behind it, so the clusters may grow large): the size
     method, and wf_swg_cluster at other penalties and iteration limits"""
@@ -349,7 +386,8 @@ def make_realign():
         save(name, "realign", R.chain_case([("chr1", seq.encode())], [R.slot_from_sites(sites)] + [R.empty_slot()] * 3, GAP50 + base), 60)
 
 
-SETS = {"swg": make_swg, "ed": make_ed, "cluster": make_cluster, "chain": make_chain, "demo": make_demo, "realign": make_realign}
+SETS = {"swg": make_swg, "ed": make_ed, "cluster": make_cluster, "chain": make_chain, "demo": make_demo, "realign": make_realign,
+        "window_edges": make_window_edges}          # (chain_window_edges: a set of its own, it computes needed_level for the whole table)
 
 
 def main(argv):

@@ -21,7 +21,9 @@ Cases
              -> c<s>_{off, start, left, right}: clusters per slot (off: per contig);  out_ctgs, sc_off, sc_beg, sc_end, brk<s> +
              brk_off, sc_phase, sc_orig_dist, sc_swap_dist, sc_phase_set, pb_phase, phase_blocks / switches / flips with offsets;
              p<s>_<w>_{errtype, sync_group, callq, ref_ed, query_ed, credit} per variant (rows as the input's) and phasing w;
-             with -d ed_{ctg, pos, hap, type, len, sc, min_qual, max_qual}; realign: r<s>_* the realigned tables."""
+             with -d ed_{ctg, pos, hap, type, len, sc, min_qual, max_qual}; realign: r<s>_* the realigned tables.
+  chain_window_edges also stores x_case_names: the names of its cases in tests/window_edge_cases.py's table, one per line, in the
+             order of its contigs (a contig and, with `-c gap 2000`, a supercluster per case)."""
 import os
 import re
 import subprocess
