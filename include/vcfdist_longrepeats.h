@@ -36,7 +36,7 @@
  *
  * Limits: 33 <= k <= 256; at most 2^32 - 1 bases in total (the sort's values are 32-bit global starts); a contig of at most
  * INT32_MAX bases; fewer than 2^31 - 1 kept classes at a level (checked when it runs; real genomes are nowhere near).  Device memory
- * (the formula is repeated in pr_longrepeats.hip), with N the bases padded to whole tiles of 4096 plus one tile: N bytes (the
+ * (pr_longrepeats.hip has it as csrc/pr_kmer.h's plus the ids), with N the bases padded to whole tiles of 4096 plus one tile: N bytes (the
  * sequence) + N / 8 (the flag bits) + 16 N (four id arrays: F and R of the level read and of the level written) + per valid
  * 32-mer start 2 x 12 bytes (the base level's key and value, double-buffered for the sort) and 8 bytes (class heads and their
  * scan); the upper levels use the same buffers for their candidates only, which are fewer; + rocPRIM's temporary + what the run

@@ -27,7 +27,7 @@
  * BEDs: it matches exactly (no mismatches), k <= 32 (longer k-mers: vcfdist_longrepeats.h), and it compares both strands.
  *
  * Limits: 4 <= k <= 32; at most 2^32 - 1 bases in total (the sort's values are 32-bit global starts); a contig of at most
- * INT32_MAX bases.  Device memory (the formula is repeated in pr_repeats.hip): 1 byte per base (the sequence) + 1/8 byte per
+ * INT32_MAX bases.  Device memory (the formula is repeated in csrc/pr_kmer.h): 1 byte per base (the sequence) + 1/8 byte per
  * base (the flag bits) + per valid start 2 x 12 bytes (key and value, double-buffered for the sort) + rocPRIM's temporary.
  *
  * Device code: pr_repeats.hip (pack, mark), pr_plan.hip (the sort), pr_context.hip (the run passes).  No CPU fallback.

@@ -59,6 +59,43 @@ def test_cases_equal_the_model(k):
     assert not failed, failed
 
 
+def edge_inputs(name):
+    """(contigs, short specs, long specs) at the edges of what the two entries share: an entry without a valid start between two that
+    have some, a genome without a called base, a genome of whole tiles"""
+    rng = np.random.RandomState(11)
+    if name == "no valid start":         # three contigs of 20 called bases, the third the first one's reverse complement
+        a = LC.rand(rng, 20)
+        return [a, LC.rand(rng, 20), LC.revcomp(a)], [A.rep_kmer(16), A.rep_kmer(24), A.rep_kmer(16, 3)], [A.rep_kmer(33)]
+    if name == "all N":                  # (and an empty contig between the two)
+        return [b"N" * 5000, b"", b"N" * 4096], api.repeats_default()[1], api.longrepeats_default()[1]
+    s = bytearray(LC.rand(rng, 8192))    # "whole tiles": 8192 called bases, 2 tiles of the pack and 4 of the pair kernel, one 300-base copy
+    s[5000:5300] = s[1000:1300]
+    return [bytes(s)], [A.rep_kmer(32)], api.longrepeats_default()[1]
+
+
+@pytest.mark.parametrize("name", ["no valid start", "all N", "whole tiles"])
+def test_edges_of_the_shared_tail_equal_the_models(name):
+    contigs, short, long_ = edge_inputs(name)
+    want_short, want_long = RM.all_intervals(contigs, short), LM.all_intervals(contigs, long_)
+    empty = lambda rows: all(len(r[0]) == 0 and len(r[1]) == 0 for r in rows)
+    # (what the inputs are about, on the model)
+    if name == "no valid start":
+        assert want_short[1].tolist() == [15, 0, 15] and want_short[2].tolist() == [10, 0, 10] and empty(want_short[0][1])
+        assert not empty(want_short[0][0]) and not empty(want_short[0][2]) and want_long[1].tolist() == [0] and empty(want_long[0][0])
+    elif name == "all N":
+        for want in (want_short, want_long):
+            assert not want[1].any() and not want[2].any() and all(empty(rows) for rows in want[0])
+    else:
+        assert len(contigs[0]) == 8192 and all(n > 0 for n in want_long[2]) and want_short[2][0] >= 2 * (300 - 31)
+    pr = api.PrecisionRecall()
+    for _ in range(2):                   # (the second round meets the first one's buffers)
+        pr.repeat_intervals(contigs, short)
+        check_rows(pr.download_repeat_intervals(), want_short[0], (name, "short"))
+        got = pr.repeat_stats()
+        assert np.array_equal(got[0], want_short[1]) and np.array_equal(got[1], want_short[2]), (name, got, want_short[1:])
+        check_call(pr, contigs, long_, (name, "long"), want_long)
+
+
 # ---- 2. determinism
 
 def snapshot(pr):

@@ -151,8 +151,8 @@ def stratify_contig(pr, prep, strat, args, pb, part_idx=None):
     # genome-wide passes behind them
     table = None
     if strat["beds"] or strat["rep"] or strat["lrep"]:
-        table = A.Strata([[b.intervals(name)] for b in strat["beds"]] + [[row] for row in (strat["rep_rows"][name] if strat["rep"] else ())] +
-                         [[row] for row in (strat["lrep_rows"][name] if strat["lrep"] else ())], 1)
+        table = A.Strata([[b.intervals(name)] for b in strat["beds"]] +
+                         [[row] for fam in KMER_FAMILIES if strat[fam["key"]] for row in strat[fam["key"] + "_rows"][name]], 1)
     if strat["ctx"]:        # --stratify-context: the context intervals are built on the device and go to the same mask kernel
         pr.context_masks(prep["variants"], strat["ctx"], table)
         keep_context_intervals(pr, strat, name)
@@ -181,32 +181,31 @@ def keep_context_intervals(pr, strat, name):
     strat["ctx_ms"][name] = pr.context_timing()[0]
 
 
-def repeat_strata(fasta, strat, args, device=0):
-    """--stratify-repeats: the genome-wide pass (include/vcfdist_repeats.h) over all contigs of the FASTA, those without a variant
-    included, on a handle of its own that is gone before the evaluation starts.  Every rank computes the same arrays."""
+# The families of genome-wide k-mer strata, in the order of their strata (include/vcfdist_repeats.h, include/vcfdist_longrepeats.h): the
+# prefix of their keys in strat, their option and their word in the messages, the names of api.PrecisionRecall's methods, the defaults
+# and the writer of their BED
+KMER_FAMILIES = (
+    dict(key="rep", option="--stratify-repeats", word="repeat", intervals="repeat_intervals", download="download_repeat_intervals",
+         stats="repeat_stats", timing="repeat_timing", defaults=api.repeats_default, write=RP.write_repeat_bed),
+    dict(key="lrep", option="--stratify-long-repeats", word="long repeat", intervals="longrepeat_intervals",
+         download="download_longrepeat_intervals", stats="longrepeat_stats", timing="longrepeat_timing", defaults=api.longrepeats_default,
+         write=RP.write_long_repeat_bed),
+)
+
+
+def kmer_strata(fam, fasta, strat, args, device=0):
+    """--stratify-repeats, --stratify-long-repeats: the family's genome-wide pass over all contigs of the FASTA, those without a
+    variant included, on a handle of its own that is gone before the evaluation starts.  Every rank computes the same arrays."""
+    key = fam["key"]
     cfg = A.default_config(device=device)
     cfg.max_qual = float(args.max_qual)
     pr = api.PrecisionRecall(cfg)
     names = list(fasta)
-    pr.repeat_intervals([fasta[c] for c in names], strat["rep"])
-    rows = pr.download_repeat_intervals()
-    strat["rep_rows"] = {c: [rows[k][j] for k in range(len(strat["rep"]))] for j, c in enumerate(names)}
-    strat["rep_stats"] = pr.repeat_stats()
-    strat["rep_ms"] = sum(pr.repeat_timing())
-    pr.close()
-
-
-def long_repeat_strata(fasta, strat, args, device=0):
-    """--stratify-long-repeats: the same for the long repeat strata (include/vcfdist_longrepeats.h), on a handle of its own"""
-    cfg = A.default_config(device=device)
-    cfg.max_qual = float(args.max_qual)
-    pr = api.PrecisionRecall(cfg)
-    names = list(fasta)
-    pr.longrepeat_intervals([fasta[c] for c in names], strat["lrep"])
-    rows = pr.download_longrepeat_intervals()
-    strat["lrep_rows"] = {c: [rows[k][j] for k in range(len(strat["lrep"]))] for j, c in enumerate(names)}
-    strat["lrep_stats"] = pr.longrepeat_stats()
-    strat["lrep_ms"] = sum(pr.longrepeat_timing())
+    getattr(pr, fam["intervals"])([fasta[c] for c in names], strat[key])
+    rows = getattr(pr, fam["download"])()
+    strat[key + "_rows"] = {c: [rows[k][j] for k in range(len(strat[key]))] for j, c in enumerate(names)}
+    strat[key + "_stats"] = getattr(pr, fam["stats"])()
+    strat[key + "_ms"] = sum(getattr(pr, fam["timing"])())
     pr.close()
 
 
@@ -588,20 +587,16 @@ def main(argv=None):
         strat = dict(names=list(names), beds=beds, counts=None, vars=0, none=0, ctx=None, ctx_names=[], intervals={}, ctx_ms={},
                      vs=None, vs_names=[], vs_members=np.zeros((2, 0), np.int64), vs_ms=0.0, rep=None, rep_names=[], rep_rows={},
                      lrep=None, lrep_names=[], lrep_rows={})
-        if args.stratify_repeats:       # the default repeat strata (include/vcfdist_repeats.h) behind the list's, in front of the context strata
-            strat["rep_names"], strat["rep"] = api.repeats_default()
-            for n in strat["rep_names"]:
-                if n in names:
-                    raise SystemExit(f"ERROR: strata list '{args.stratify}': duplicate stratum name '{n}' (a repeat stratum of "
-                                     "--stratify-repeats)")
-            strat["names"] += strat["rep_names"]
-        if args.stratify_long_repeats:  # the default long repeat strata (include/vcfdist_longrepeats.h) behind those
-            strat["lrep_names"], strat["lrep"] = api.longrepeats_default()
-            for n in strat["lrep_names"]:
+        for fam in KMER_FAMILIES:       # the default repeat strata behind the list's, the long ones behind those, in front of the context strata
+            key = fam["key"]
+            if not getattr(args, fam["option"][2:].replace("-", "_")):
+                continue
+            strat[key + "_names"], strat[key] = fam["defaults"]()
+            for n in strat[key + "_names"]:
                 if n in strat["names"]:
-                    raise SystemExit(f"ERROR: strata list '{args.stratify}': duplicate stratum name '{n}' (a long repeat stratum of "
-                                     "--stratify-long-repeats)")
-            strat["names"] += strat["lrep_names"]
+                    raise SystemExit(f"ERROR: strata list '{args.stratify}': duplicate stratum name '{n}' (a {fam['word']} stratum of "
+                                     f"{fam['option']})")
+            strat["names"] += strat[key + "_names"]
         if args.stratify_context:       # the default sequence-context strata (include/vcfdist_context.h) behind the list's
             strat["ctx_names"], strat["ctx"] = api.context_default()
             for n in strat["ctx_names"]:
@@ -643,16 +638,12 @@ def main(argv=None):
         if write:
             RP.write_parameters(args.prefix, args, cmd)
         return []
-    if strat is not None and strat["rep"]:      # the genome-wide pass, before the contig loop (not under -ro)
-        try:
-            repeat_strata(fasta, strat, args, device=device)
-        except api.VprError as e:
-            raise SystemExit(f"ERROR: {e}")
-    if strat is not None and strat["lrep"]:
-        try:
-            long_repeat_strata(fasta, strat, args, device=device)
-        except api.VprError as e:
-            raise SystemExit(f"ERROR: {e}")
+    for fam in KMER_FAMILIES:       # the genome-wide passes, before the contig loop (not under -ro)
+        if strat is not None and strat[fam["key"]]:
+            try:
+                kmer_strata(fam, fasta, strat, args, device=device)
+            except api.VprError as e:
+                raise SystemExit(f"ERROR: {e}")
     nq = args.max_qual - args.min_qual + 1
     total = np.zeros((2, 4, 3, nq), np.int64)
     if strat is not None:
@@ -798,10 +789,9 @@ def main(argv=None):
             RP.write_parameters(args.prefix, args, cmd)
             if strat is not None:
                 RP.write_stratified(args.prefix, strat["names"], strat["counts"], args.min_qual, args.max_qual)
-                if strat["rep"]:
-                    RP.write_repeat_bed(args.prefix, contigs, strat["rep_names"], strat["rep_rows"])
-                if strat["lrep"]:
-                    RP.write_long_repeat_bed(args.prefix, contigs, strat["lrep_names"], strat["lrep_rows"])
+                for fam in KMER_FAMILIES:
+                    if strat[fam["key"]]:
+                        fam["write"](args.prefix, contigs, strat[fam["key"] + "_names"], strat[fam["key"] + "_rows"])
                 if strat["ctx"]:
                     RP.write_context_bed(args.prefix, contigs, strat["ctx_names"], strat["intervals"])
                 if strat["vs"]:
@@ -827,16 +817,13 @@ def main(argv=None):
         if strat is not None:
             print(f"[vcfdist_amd] stratified: {len(strat['names'])} strata, {strat['none']} of {strat['vars']} hap-variants in none of them",
                   file=sys.stderr)
-            if strat["rep"]:
-                n_iv = sum(len(a) for rows in strat["rep_rows"].values() for a, _ in rows)
-                starts = ", ".join(f"{int(v)} valid and {int(r)} repeated starts (k={sp.k})" for sp, v, r in zip(strat["rep"], *strat["rep_stats"]))
-                print(f"[vcfdist_amd] repeat strata: {n_iv} intervals of {len(strat['rep'])} strata, {starts}, {strat['rep_ms']:.3f} ms on the device",
-                      file=sys.stderr)
-            if strat["lrep"]:
-                n_iv = sum(len(a) for rows in strat["lrep_rows"].values() for a, _ in rows)
-                starts = ", ".join(f"{int(v)} valid and {int(r)} repeated starts (k={sp.k})" for sp, v, r in zip(strat["lrep"], *strat["lrep_stats"]))
-                print(f"[vcfdist_amd] long repeat strata: {n_iv} intervals of {len(strat['lrep'])} strata, {starts}, {strat['lrep_ms']:.3f} ms on "
-                      "the device", file=sys.stderr)
+            for fam in KMER_FAMILIES:
+                key = fam["key"]
+                if strat[key]:
+                    n_iv = sum(len(a) for rows in strat[key + "_rows"].values() for a, _ in rows)
+                    starts = ", ".join(f"{int(v)} valid and {int(r)} repeated starts (k={sp.k})" for sp, v, r in zip(strat[key], *strat[key + "_stats"]))
+                    print(f"[vcfdist_amd] {fam['word']} strata: {n_iv} intervals of {len(strat[key])} strata, {starts}, {strat[key + '_ms']:.3f} ms on "
+                          "the device", file=sys.stderr)
             if strat["ctx"]:
                 n_iv = sum(len(a) for rows in strat["intervals"].values() for a, _ in rows)
                 print(f"[vcfdist_amd] context strata: {n_iv} intervals of {len(strat['ctx'])} strata, {sum(strat['ctx_ms'].values()):.3f} ms "

@@ -247,6 +247,66 @@ int find(const std::vector<std::string> &v, const std::string &s) {
     return -1;
 }
 
+// A family of genome-wide k-mer strata (--stratify-repeats: include/vcfdist_repeats.h, --stratify-long-repeats:
+// include/vcfdist_longrepeats.h): its option and its word in the messages, its entries and writer, and what its pass gave.
+struct KmerFamily {
+    bool on;
+    const char *option, *word, *defaults_name;
+    int (*defaults)(const vpr_repeat_stratum **, const char *const **, int32_t *);
+    int (*intervals)(vpr_handle *, int32_t, const int64_t *, const uint8_t *, const vpr_repeat_stratum *, int32_t);
+    int (*counts)(vpr_handle *, int64_t *);
+    int (*download)(vpr_handle *, int32_t *, int32_t *);
+    int (*stats)(vpr_handle *, int64_t *, int64_t *);
+    int (*timing)(const vpr_handle *, double *, double *, double *, double *);
+    decltype(&vrp_write_repeat_bed) write_bed;
+    const vpr_repeat_stratum *spec = nullptr;
+    const char *const *names = nullptr;
+    int32_t n = 0;                                       // strata (0 without the option)
+    std::vector<int64_t> off;                            // [n * FASTA contigs + 1], row = stratum * contigs + contig
+    std::vector<int32_t> start, stop;
+    std::vector<int64_t> valid, repeated;                // [n] starts
+    double ms = 0;                                       // device ms of the pass
+};
+int long_repeat_stats(vpr_handle *h, int64_t *n_valid, int64_t *n_repeated) {
+    int64_t n_last[VPR_LREP_MAX_SPEC];
+    return vpr_longrepeat_stats(h, n_valid, n_repeated, n_last, nullptr);
+}
+// the family's default strata behind the names there are; a name that is there already ends the run
+void kmer_register(KmerFamily &F, const std::string &list, std::vector<std::string> &names) {
+    if (!F.on) return;
+    if (F.defaults(&F.spec, &F.names, &F.n)) die("ERROR: %s failed", F.defaults_name);
+    for (int k = 0; k < F.n; k++) {
+        if (find(names, F.names[k]) >= 0)
+            die("ERROR: strata list '%s': duplicate stratum name '%s' (a %s stratum of %s)", list.c_str(), F.names[k], F.word, F.option);
+        names.push_back(F.names[k]);
+    }
+}
+// the genome-wide pass over all contigs of the FASTA, on a handle of its own: the evaluation has the memory back
+void kmer_pass(KmerFamily &F, const vpr_config &cfg, const vio_fasta *fa) {
+    if (!F.n) return;
+    vpr_handle *hr = nullptr;
+    if (vpr_create(&cfg, &hr)) { fprintf(stderr, "vpr_create: %s\n", vpr_last_error(nullptr)); exit(2); }
+    F.off.assign(size_t(F.n) * size_t(fa->n_ctg) + 1, 0);
+    if (F.intervals(hr, fa->n_ctg, fa->ctg_off, fa->seq, F.spec, F.n) || F.counts(hr, F.off.data())) die("ERROR: %s", vpr_last_error(hr));
+    F.start.assign(size_t(F.off.back()) + 1, 0); F.stop.assign(size_t(F.off.back()) + 1, 0);
+    F.valid.assign(size_t(F.n), 0); F.repeated.assign(size_t(F.n), 0);
+    double ms[4] = {0, 0, 0, 0};
+    if (F.download(hr, F.start.data(), F.stop.data()) || F.stats(hr, F.valid.data(), F.repeated.data()) || F.timing(hr, &ms[0], &ms[1], &ms[2], &ms[3]))
+        die("ERROR: %s", vpr_last_error(hr));
+    F.ms = ms[0] + ms[1] + ms[2] + ms[3];
+    vpr_destroy(hr);
+}
+void kmer_report(const KmerFamily &F) {
+    if (!F.n) return;
+    std::string starts;
+    for (int k = 0; k < F.n; k++) {
+        char buf[128];
+        snprintf(buf, sizeof(buf), "%lld valid and %lld repeated starts (k=%d), ", (long long)F.valid[size_t(k)], (long long)F.repeated[size_t(k)], F.spec[k].k);
+        starts += buf;
+    }
+    fprintf(stderr, "[vcfdist_amd] %s strata: %lld intervals of %d strata, %s%.3f ms on the device\n", F.word, (long long)F.off.back(), F.n, starts.c_str(), F.ms);
+}
+
 // check_contigs (bed.cpp:135-284): the contigs to evaluate, in the order the reference's superclusterData walks them
 std::vector<std::string> check_contigs(const std::vector<std::string> &q_in, const std::vector<std::string> &t_in,
                                        const std::vector<std::string> &fa, const std::vector<std::string> *bed) {
@@ -421,40 +481,19 @@ int main(int argc, char **argv) {
     if (!A.stratify.empty()) strata = read_strata(A.stratify);
     // --stratify-repeats: the default repeat strata (include/vcfdist_repeats.h) behind the list's; their intervals come from one
     // genome-wide pass in front of the contig loop and then travel with the list's rows
+    // --stratify-long-repeats: the default long repeat strata (include/vcfdist_longrepeats.h) behind those, from a genome-wide pass
+    // of their own; their rows travel the same way
     const int n_list = int(strata.names.size());
-    const vpr_repeat_stratum *rep_spec = nullptr;
-    const char *const *rep_names = nullptr;
-    int32_t n_rep = 0;
-    if (A.stratify_repeats) {
-        if (vpr_repeats_default(&rep_spec, &rep_names, &n_rep)) die("ERROR: vpr_repeats_default failed");
-        for (int k = 0; k < n_rep; k++) {
-            if (find(strata.names, rep_names[k]) >= 0)
-                die("ERROR: strata list '%s': duplicate stratum name '%s' (a repeat stratum of --stratify-repeats)", A.stratify.c_str(), rep_names[k]);
-            strata.names.push_back(rep_names[k]);
-        }
-    }
-    std::vector<int64_t> rep_off;                                               // [n_rep * FASTA contigs + 1], row = stratum * contigs + contig
-    std::vector<int32_t> rep_start, rep_stop;
-    std::vector<int64_t> rep_valid(size_t(n_rep), 0), rep_repeated(size_t(n_rep), 0);
-    double rep_ms = 0;
-    // --stratify-long-repeats: the default long repeat strata (include/vcfdist_longrepeats.h) behind the list's and the repeat strata,
-    // from a genome-wide pass of their own; their rows travel the same way
-    const vpr_repeat_stratum *lrep_spec = nullptr;
-    const char *const *lrep_names = nullptr;
-    int32_t n_lrep = 0;
-    if (A.stratify_long_repeats) {
-        if (vpr_longrepeats_default(&lrep_spec, &lrep_names, &n_lrep)) die("ERROR: vpr_longrepeats_default failed");
-        for (int k = 0; k < n_lrep; k++) {
-            if (find(strata.names, lrep_names[k]) >= 0)
-                die("ERROR: strata list '%s': duplicate stratum name '%s' (a long repeat stratum of --stratify-long-repeats)", A.stratify.c_str(),
-                    lrep_names[k]);
-            strata.names.push_back(lrep_names[k]);
-        }
-    }
-    std::vector<int64_t> lrep_off;                                              // [n_lrep * FASTA contigs + 1], row = stratum * contigs + contig
-    std::vector<int32_t> lrep_start, lrep_stop;
-    std::vector<int64_t> lrep_valid(size_t(n_lrep), 0), lrep_repeated(size_t(n_lrep), 0);
-    double lrep_ms = 0;
+    KmerFamily kmer[2] = {};
+    kmer[0].on = A.stratify_repeats; kmer[0].option = "--stratify-repeats"; kmer[0].word = "repeat";
+    kmer[0].defaults_name = "vpr_repeats_default"; kmer[0].defaults = vpr_repeats_default; kmer[0].intervals = vpr_repeat_intervals;
+    kmer[0].counts = vpr_repeat_interval_counts; kmer[0].download = vpr_repeat_download_intervals; kmer[0].stats = vpr_repeat_stats;
+    kmer[0].timing = vpr_repeat_timing; kmer[0].write_bed = vrp_write_repeat_bed;
+    kmer[1].on = A.stratify_long_repeats; kmer[1].option = "--stratify-long-repeats"; kmer[1].word = "long repeat";
+    kmer[1].defaults_name = "vpr_longrepeats_default"; kmer[1].defaults = vpr_longrepeats_default; kmer[1].intervals = vpr_longrepeat_intervals;
+    kmer[1].counts = vpr_longrepeat_interval_counts; kmer[1].download = vpr_longrepeat_download_intervals; kmer[1].stats = long_repeat_stats;
+    kmer[1].timing = vpr_longrepeat_timing; kmer[1].write_bed = vrp_write_long_repeat_bed;
+    for (KmerFamily &F : kmer) kmer_register(F, A.stratify, strata.names);
     // --stratify-context: the default sequence-context strata (include/vcfdist_context.h) behind the list's and the repeat strata
     const int n_bed = int(strata.names.size());
     const vpr_context_stratum *ctx_spec = nullptr;
@@ -586,36 +625,7 @@ int main(int argc, char **argv) {
     memset(&cfg, 0, sizeof(cfg));
     cfg.device = A.device; cfg.max_qual = float(A.max_qual); cfg.credit_threshold = A.credit_threshold; cfg.phase_threshold = A.phase_threshold;
     cfg.band_mode = 1;
-    if (n_rep) {           // the genome-wide pass over all contigs of the FASTA, on a handle of its own: the evaluation has the memory back
-        vpr_handle *hr = nullptr;
-        if (vpr_create(&cfg, &hr)) { fprintf(stderr, "vpr_create: %s\n", vpr_last_error(nullptr)); return 2; }
-        rep_off.assign(size_t(n_rep) * size_t(fa->n_ctg) + 1, 0);
-        if (vpr_repeat_intervals(hr, fa->n_ctg, fa->ctg_off, fa->seq, rep_spec, n_rep) || vpr_repeat_interval_counts(hr, rep_off.data()))
-            die("ERROR: %s", vpr_last_error(hr));
-        rep_start.assign(size_t(rep_off.back()) + 1, 0); rep_stop.assign(size_t(rep_off.back()) + 1, 0);
-        double ms[4] = {0, 0, 0, 0};
-        if (vpr_repeat_download_intervals(hr, rep_start.data(), rep_stop.data()) || vpr_repeat_stats(hr, rep_valid.data(), rep_repeated.data()) ||
-            vpr_repeat_timing(hr, &ms[0], &ms[1], &ms[2], &ms[3]))
-            die("ERROR: %s", vpr_last_error(hr));
-        rep_ms = ms[0] + ms[1] + ms[2] + ms[3];
-        vpr_destroy(hr);
-    }
-    if (n_lrep) {          // the same for the long repeat strata
-        vpr_handle *hr = nullptr;
-        if (vpr_create(&cfg, &hr)) { fprintf(stderr, "vpr_create: %s\n", vpr_last_error(nullptr)); return 2; }
-        lrep_off.assign(size_t(n_lrep) * size_t(fa->n_ctg) + 1, 0);
-        if (vpr_longrepeat_intervals(hr, fa->n_ctg, fa->ctg_off, fa->seq, lrep_spec, n_lrep) || vpr_longrepeat_interval_counts(hr, lrep_off.data()))
-            die("ERROR: %s", vpr_last_error(hr));
-        lrep_start.assign(size_t(lrep_off.back()) + 1, 0); lrep_stop.assign(size_t(lrep_off.back()) + 1, 0);
-        std::vector<int64_t> n_last(size_t(n_lrep), 0);
-        double ms[4] = {0, 0, 0, 0};
-        if (vpr_longrepeat_download_intervals(hr, lrep_start.data(), lrep_stop.data()) ||
-            vpr_longrepeat_stats(hr, lrep_valid.data(), lrep_repeated.data(), n_last.data(), nullptr) ||
-            vpr_longrepeat_timing(hr, &ms[0], &ms[1], &ms[2], &ms[3]))
-            die("ERROR: %s", vpr_last_error(hr));
-        lrep_ms = ms[0] + ms[1] + ms[2] + ms[3];
-        vpr_destroy(hr);
-    }
+    for (KmerFamily &F : kmer) kmer_pass(F, cfg, fa);
     vpr_handle *h = nullptr;
     if (vpr_create(&cfg, &h)) { fprintf(stderr, "vpr_create: %s\n", vpr_last_error(nullptr)); return 2; }
 
@@ -740,18 +750,14 @@ int main(int argc, char **argv) {
                     iv_start.insert(iv_start.end(), st, st + n); iv_stop.insert(iv_stop.end(), sp, sp + n);
                     iv_off[size_t(k) + 1] = int64_t(iv_start.size());
                 }
-                for (int k = 0; k < n_rep; k++) {      // the contig's rows of the repeat strata, as ordinary BED rows behind the list's
-                    const size_t r = size_t(k) * size_t(fa->n_ctg) + size_t(fi);
-                    iv_start.insert(iv_start.end(), rep_start.begin() + rep_off[r], rep_start.begin() + rep_off[r + 1]);
-                    iv_stop.insert(iv_stop.end(), rep_stop.begin() + rep_off[r], rep_stop.begin() + rep_off[r + 1]);
-                    iv_off[size_t(n_list + k) + 1] = int64_t(iv_start.size());
-                }
-                for (int k = 0; k < n_lrep; k++) {     // and those of the long repeat strata behind them
-                    const size_t r = size_t(k) * size_t(fa->n_ctg) + size_t(fi);
-                    iv_start.insert(iv_start.end(), lrep_start.begin() + lrep_off[r], lrep_start.begin() + lrep_off[r + 1]);
-                    iv_stop.insert(iv_stop.end(), lrep_stop.begin() + lrep_off[r], lrep_stop.begin() + lrep_off[r + 1]);
-                    iv_off[size_t(n_list + n_rep + k) + 1] = int64_t(iv_start.size());
-                }
+                size_t row = size_t(n_list);
+                for (const KmerFamily &F : kmer)       // the contig's rows of the repeat strata, then of the long ones, as ordinary BED rows behind the list's
+                    for (int k = 0; k < F.n; k++) {
+                        const size_t r = size_t(k) * size_t(fa->n_ctg) + size_t(fi);
+                        iv_start.insert(iv_start.end(), F.start.begin() + F.off[r], F.start.begin() + F.off[r + 1]);
+                        iv_stop.insert(iv_stop.end(), F.stop.begin() + F.off[r], F.stop.begin() + F.off[r + 1]);
+                        iv_off[++row] = int64_t(iv_start.size());
+                    }
                 const vpr_strata ST = {n_bed, 1, iv_off.data(), iv_start.data(), iv_stop.data()};
                 std::vector<int64_t> sc_counts(strat_total.size(), 0);
                 // (with --stratify-context the context intervals are built on the device and go to the same mask kernel)
@@ -899,26 +905,24 @@ int main(int argc, char **argv) {
                                                               A.bootstrap_seed, A.min_qual, A.max_qual))
                 die("ERROR: %s", vrp_last_error());
             // repeat-strata.bed and long-repeat-strata.bed: the evaluated contigs in evaluation order, rows contig-major
-            auto repeat_bed = [&](int32_t n, const char *const *rnames, const std::vector<int64_t> &roff, const std::vector<int32_t> &rstart,
-                                  const std::vector<int32_t> &rstop, decltype(&vrp_write_repeat_bed) write) {
+            for (const KmerFamily &F : kmer) {
+                if (!F.n) continue;
                 std::vector<const char *> cn;
                 std::vector<int64_t> off(1, 0);
                 std::vector<int32_t> st, sp;
                 for (const auto &c : contigs) {
                     cn.push_back(c.c_str());
                     const int fi = find(fn, c);
-                    for (int k = 0; k < n; k++) {
+                    for (int k = 0; k < F.n; k++) {
                         const size_t r = size_t(k) * size_t(fa->n_ctg) + size_t(fi);
-                        st.insert(st.end(), rstart.begin() + roff[r], rstart.begin() + roff[r + 1]);
-                        sp.insert(sp.end(), rstop.begin() + roff[r], rstop.begin() + roff[r + 1]);
+                        st.insert(st.end(), F.start.begin() + F.off[r], F.start.begin() + F.off[r + 1]);
+                        sp.insert(sp.end(), F.stop.begin() + F.off[r], F.stop.begin() + F.off[r + 1]);
                         off.push_back(int64_t(st.size()));
                     }
                 }
                 st.push_back(0); sp.push_back(0);      // (never empty: a pointer is wanted)
-                if (write(A.prefix.c_str(), cn.data(), int32_t(cn.size()), rnames, n, off.data(), st.data(), sp.data())) die("ERROR: %s", vrp_last_error());
-            };
-            if (n_rep) repeat_bed(n_rep, rep_names, rep_off, rep_start, rep_stop, vrp_write_repeat_bed);
-            if (n_lrep) repeat_bed(n_lrep, lrep_names, lrep_off, lrep_start, lrep_stop, vrp_write_long_repeat_bed);
+                if (F.write_bed(A.prefix.c_str(), cn.data(), int32_t(cn.size()), F.names, F.n, off.data(), st.data(), sp.data())) die("ERROR: %s", vrp_last_error());
+            }
             if (n_ctx) {
                 std::vector<const char *> cn;
                 for (const auto &c : ctx_contigs) cn.push_back(c.c_str());
@@ -982,28 +986,7 @@ int main(int argc, char **argv) {
     if (n_strata)
         fprintf(stderr, "[vcfdist_amd] stratified: %d strata, %lld of %lld hap-variants in none of them\n", n_strata, (long long)strat_none,
                 (long long)strat_vars);
-    if (n_rep) {
-        std::string starts;
-        for (int k = 0; k < n_rep; k++) {
-            char buf[128];
-            snprintf(buf, sizeof(buf), "%lld valid and %lld repeated starts (k=%d), ", (long long)rep_valid[size_t(k)], (long long)rep_repeated[size_t(k)],
-                     rep_spec[k].k);
-            starts += buf;
-        }
-        fprintf(stderr, "[vcfdist_amd] repeat strata: %lld intervals of %d strata, %s%.3f ms on the device\n", (long long)rep_off.back(), n_rep,
-                starts.c_str(), rep_ms);
-    }
-    if (n_lrep) {
-        std::string starts;
-        for (int k = 0; k < n_lrep; k++) {
-            char buf[128];
-            snprintf(buf, sizeof(buf), "%lld valid and %lld repeated starts (k=%d), ", (long long)lrep_valid[size_t(k)], (long long)lrep_repeated[size_t(k)],
-                     lrep_spec[k].k);
-            starts += buf;
-        }
-        fprintf(stderr, "[vcfdist_amd] long repeat strata: %lld intervals of %d strata, %s%.3f ms on the device\n", (long long)lrep_off.back(), n_lrep,
-                starts.c_str(), lrep_ms);
-    }
+    for (const KmerFamily &F : kmer) kmer_report(F);
     if (n_ctx)
         fprintf(stderr, "[vcfdist_amd] context strata: %lld intervals of %d strata, %.3f ms on the device\n", (long long)ctx_start.size(), n_ctx, ctx_ms);
     if (n_vs)

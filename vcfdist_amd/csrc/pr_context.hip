@@ -362,9 +362,6 @@ __global__ void __launch_bounds__(256) k_ctx_rows(const int32_t *__restrict__ ou
 
 namespace {
 
-template <typename T>
-T *as(const DevBuf<uint8_t> &b) { return reinterpret_cast<T *>(b.p); }
-
 int check_spec(vpr_handle *h, const vpr_context_stratum *spec, int32_t n_spec) {
     for (int k = 0; k < n_spec; k++) {
         const vpr_context_stratum &s = spec[k];
@@ -384,8 +381,6 @@ int check_spec(vpr_handle *h, const vpr_context_stratum *spec, int32_t n_spec) {
     }
     return VPR_OK;
 }
-
-unsigned blocks_of(int64_t n) { return unsigned((n + 255) / 256); }
 
 int scan_u32(CtxWork &W, const uint32_t *in, uint32_t *out, size_t n) {
     vpr_handle *h = W.h;
@@ -408,6 +403,18 @@ int64_t ctx_piece_bases() {   // (VPR_CONTEXT_PIECE_BASES: a smaller piece, so t
     const char *e = getenv("VPR_CONTEXT_PIECE_BASES");
     const long long v = e ? atoll(e) : 0;
     return v > 0 ? int64_t(v) : PIECE_BASES;
+}
+
+std::vector<CtxPiece> ctx_pieces(const int64_t *ctg_off, int n_ctg) {   // (a longer contig is a piece of its own)
+    std::vector<CtxPiece> pieces;
+    const int64_t budget = ctx_piece_bases();
+    for (int c = 0; c < n_ctg;) {
+        int e = c + 1;
+        while (e < n_ctg && ctg_off[e + 1] - ctg_off[c] <= budget) e++;
+        pieces.push_back({c, e});
+        c = e;
+    }
+    return pieces;
 }
 
 int CtxWork::seg_begin() {
@@ -559,16 +566,7 @@ int vpr_context_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *be
     const uint8_t *d_seq = as<uint8_t>(W.seq);
     const int64_t *d_ctg = as<int64_t>(W.ctg_off);
 
-    // pieces of whole contigs
-    struct Piece { int c0, c1; };       // contigs [c0, c1)
-    std::vector<Piece> pieces;
-    const int64_t budget = ctx_piece_bases();
-    for (int c = 0; c < n_ctg;) {
-        int e = c + 1;
-        while (e < n_ctg && v->ctg_off[e + 1] - v->ctg_off[c] <= budget) e++;
-        pieces.push_back({c, e});
-        c = e;
-    }
+    const std::vector<CtxPiece> pieces = ctx_pieces(v->ctg_off, n_ctg);
 
     double ms = 0;
     W.ev[0] = S->ev[0]; W.ev[1] = S->ev[1]; W.ms = &ms;
@@ -581,7 +579,7 @@ int vpr_context_masks(vpr_handle *h, const vpr_variants *v, const vpr_strata *be
         // flags a run must have for its tract to reach min_len, where the run passes can apply that themselves (run_masks)
         const int min_run = (!gc && sp.min_len - sp.period <= 64) ? sp.min_len - sp.period : 1;
         int64_t *row_off = S->d_off.p + bed_rows + size_t(k) * size_t(n_ctg);
-        for (const Piece &pc : pieces) {
+        for (const CtxPiece &pc : pieces) {
             const int64_t g0 = v->ctg_off[pc.c0], g1 = v->ctg_off[pc.c1], T0 = g0 / CTX_TILE * CTX_TILE;
             const int64_t n_tiles = (g1 - T0 + CTX_TILE - 1) / CTX_TILE, nw = n_tiles * (CTX_TILE / 64);
             uint32_t n_out = 0;

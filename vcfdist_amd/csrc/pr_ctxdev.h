@@ -1,5 +1,5 @@
 // pr_ctxdev.h -- device helpers shared by the kernels that walk the concatenated contig sequences: pr_context.hip (the context
-// strata's flag and run kernels) and pr_repeats.hip (the repeat strata's pack and mark kernels).
+// strata's flag and run kernels), pr_repeats.hip (the pack and mark kernels) and pr_longrepeats.hip (the pair and valid kernels).
 #ifndef PR_CTXDEV_H_
 #define PR_CTXDEV_H_
 #include <hip/hip_runtime.h>

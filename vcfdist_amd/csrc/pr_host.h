@@ -7,7 +7,8 @@
 //                   the front and back of a counters call that pr_cut.hip and pr_label.hip share (the bin rule: pr_counts.h)
 //   pr_strata.hip   the membership words of the region-stratified counters (include/vcfdist_strata.h): k_strata_mask, up- and download
 //   pr_context.hip  the sequence-context strata (include/vcfdist_context.h): interval lists built from the contig sequences
-//   pr_repeats.hip  the repeat strata (include/vcfdist_repeats.h): genome-wide repeated k-mers, in front of pr_context.hip's run passes
+//   pr_repeats.hip  the repeat strata (include/vcfdist_repeats.h): genome-wide repeated k-mers, in front of pr_context.hip's run passes;
+//                   the host scaffold of a genome-wide k-mer call and the rows' state that pr_longrepeats.hip shares (pr_kmer.h)
 //   pr_longrepeats.hip the long repeat strata (include/vcfdist_longrepeats.h): repeated k-mers of 33..256 bases by rank doubling
 //   pr_varstrata.hip the variant strata (include/vcfdist_varstrata.h): bits made from the variant tables themselves
 //   pr_errclass.hip the error classes (include/vcfdist_errclass.h): why each FP and FN is wrong
@@ -276,8 +277,8 @@ using namespace vprh;
 struct DistState;                        // the distance step's tables and arena (pr_dist.hip)
 struct StrataState;                      // the membership words and the stratified counters' cut state (pr_strata.hip)
 struct ContextState;                     // the sequence-context intervals (pr_context.hip)
-struct RepeatState;                      // the repeat intervals (pr_repeats.hip)
-struct LongRepeatState;                  // the long repeat intervals (pr_longrepeats.hip)
+struct KmerState;                        // the rows of a genome-wide k-mer call (pr_kmer.h): the repeat intervals (pr_repeats.hip)
+struct LongRepeatState;                  // the same with the levels' counts: the long repeat intervals (pr_longrepeats.hip)
 struct LabelState;                       // the label bytes and the label histogram of a label pass (pr_label.h)
 enum { LABEL_ERRCLASS, LABEL_MATCHKIND, LABEL_PASSES };     // the label passes: pr_errclass.hip, pr_matchkind.hip
 struct CutState;                         // the histogram, keys and device time of a count cut (pr_cut.h)
@@ -430,7 +431,7 @@ struct vpr_handle {
     DistState *dist = nullptr;           // vpr_distance (pr_dist.hip), created by its first call
     StrataState *strata = nullptr;       // vpr_strata_masks / vpr_strata_upload_masks (pr_strata.hip), released with the batch
     ContextState *context = nullptr;     // vpr_context_masks (pr_context.hip), released by the next one or vpr_destroy
-    RepeatState *repeats = nullptr;      // vpr_repeat_intervals (pr_repeats.hip), released by the next one or vpr_destroy
+    KmerState *repeats = nullptr;        // vpr_repeat_intervals (pr_repeats.hip), released by the next one or vpr_destroy
     LongRepeatState *longrepeats = nullptr;   // vpr_longrepeat_intervals (pr_longrepeats.hip), released by the next one or vpr_destroy
     CutState *boot = nullptr;            // vpr_pr_counts_boot (pr_cut.hip), created by its first call, released with the batch
     LabelState *label[LABEL_PASSES] = {nullptr, nullptr};   // vpr_errclass / vpr_matchkind (pr_label.hip), created by a pass's first call, released with the batch
@@ -487,15 +488,8 @@ int strata_extend(vpr_handle *h, const char *entry, int32_t n_add, const int64_t
                   uint64_t *words[VPR_HAPS], int32_t *n_words);
 void strata_commit(vpr_handle *h);
 void context_free(vpr_handle *h);                                    // pr_context.hip: the resident context intervals
-void repeats_free(vpr_handle *h);                                    // pr_repeats.hip: the resident repeat intervals
-// pr_repeats.hip, for pr_longrepeats.hip (a kernel is launched from the unit that holds it): the pack over tiles of REP_PACK_TILE
-// starts (write false: the tiles' counts into out; true: the pairs behind the scanned counts), the mark and a piece's flag words
-constexpr int REP_PACK_TILE = 4096;
-void rep_launch_pack(hipStream_t st, bool write, unsigned n_tiles, const uint8_t *seq, const int64_t *ctg_off, int n_ctg, int64_t N, int k,
-                     uint32_t *out, uint64_t *keys, uint32_t *vals);
-void rep_launch_mark(hipStream_t st, const uint64_t *keys, const uint32_t *vals, uint64_t n, int k, uint32_t *flags32, unsigned long long *n_rep);
-void rep_launch_piece_words(hipStream_t st, const uint64_t *all, int64_t nw, int64_t T0, int64_t g0, int64_t g1, uint64_t *words);
-void longrepeats_free(vpr_handle *h);                              // pr_longrepeats.hip: the resident long repeat intervals
+void repeats_free(vpr_handle *h);                                    // pr_repeats.hip: the repeat intervals (host memory: pr_kmer.h)
+void longrepeats_free(vpr_handle *h);                              // pr_longrepeats.hip: the long repeat intervals (the same)
 void label_free(vpr_handle *h);                                    // pr_label.hip: the label bytes and histograms of both label passes
 void boot_free(vpr_handle *h);                                       // pr_cut.hip: the replicate histogram and the keys
 // pr_collect.hip, shared by the three counters entries (vpr_pr_counts; _strata, _boot: pr_cut.hip; `entry`: the entry's name, for the
@@ -554,6 +548,10 @@ int dev_upload(vpr_handle *h, const T **dst, const T *src, size_t n) {
     *dst = p;
     return VPR_OK;
 }
+// the bytes of a call's workspace as an array of T, and workgroups of 256 for n elements
+template <typename T>
+T *as(const DevBuf<uint8_t> &b) { return reinterpret_cast<T *>(b.p); }
+inline unsigned blocks_of(int64_t n) { return unsigned((n + 255) / 256); }
 // pr_context.hip, shared with pr_repeats.hip: the run passes behind the flag bits (run starts and ends, tracts, pad, merge, rows).
 // room for `bytes` in a buffer of the call `entry`, a quarter more than asked for when it has to grow; keep_bytes of the old content survive
 template <typename T>
@@ -591,4 +589,6 @@ int ctx_intervals_from_flags(CtxWork &W, const uint64_t *words, int64_t nw, int6
                              int n_ctg, int c0, int c1, const CtxRunRule &rule, int spec_entry, DevBuf<int32_t> &d_start, DevBuf<int32_t> &d_stop,
                              size_t have, int64_t *row_off, uint32_t *n_out);
 int64_t ctx_piece_bases();               // bases of a piece of whole contigs (VPR_CONTEXT_PIECE_BASES: a smaller one, for the tests)
+struct CtxPiece { int c0, c1; };         // contigs [c0, c1)
+std::vector<CtxPiece> ctx_pieces(const int64_t *ctg_off, int n_ctg);   // the genome as pieces of whole contigs of at most that many bases
 #endif

@@ -18,24 +18,12 @@
 //                                                    p = k - 1, is the tract [a, b - 1 + k) of the header; min_len 1, no primitive
 //                                                    test (that is a rule of the period strata); pad, merge and rows as there
 //
-// Device memory: 1 byte per base (the sequence, resident for the call) + 1/8 byte per base (the flag bits) + 1/8 byte per base of
-// the largest piece (its masked copy) + per valid start of the entry with the most 2 x 12 bytes (key and value, double-buffered
-// for the sort) + rocPRIM's temporary + what the run passes take (pr_context.hip).  At most 2^32 - 1 bases: values are 32-bit.
-#include "pr_host.h"
+// The host side of these steps is KmerWork (pr_kmer.h, defined at the end of this file beside the kernels it launches), which
+// pr_longrepeats.hip uses too; the rows end in a KmerState.  Device memory: the formula of pr_kmer.h, the pairs being the valid
+// starts of the entry with the most.  The buckets KmerState::ms[0..3] are pack, sort, mark, intervals.
+#include "pr_kmer.h"
 #include "pr_plan.h"
 #include "pr_ctxdev.h"
-#include "../../include/vcfdist_repeats.h"
-
-struct RepeatState {
-    int32_t n_spec = 0, n_ctg = 0;
-    int64_t n_iv = 0;
-    DevBuf<int64_t> d_off;                             // [n_spec * n_ctg + 1]
-    DevBuf<int32_t> d_start, d_stop;                   // [n_iv]
-    std::vector<int64_t> n_valid, n_repeated;          // [n_spec]
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    double ms_pack = 0, ms_sort = 0, ms_mark = 0, ms_intervals = 0;
-    bool valid = false;
-};
 
 namespace {
 
@@ -168,41 +156,189 @@ __global__ void __launch_bounds__(256) k_rep_random_keys(uint64_t n, uint64_t se
 
 }  // extern "C"
 
-namespace {
+// ---- KmerWork and KmerState (pr_kmer.h)
 
-template <typename T>
-T *as(const DevBuf<uint8_t> &b) { return reinterpret_cast<T *>(b.p); }
+int KmerWork::check_args(vpr_handle *h, const char *entry, int min_k, int max_k, int max_spec, int32_t n_ctg, const int64_t *ctg_off,
+                         const uint8_t *ctg_seq, const vpr_repeat_stratum *spec, int32_t n_spec) {
+    if (!spec) return fail(h, VPR_ERR_ARG, "%s: null spec", entry);
+    if (n_spec < 1 || n_spec > max_spec) return fail(h, VPR_ERR_ARG, "%s: n_spec %d is not in 1..%d", entry, n_spec, max_spec);
+    for (int e = 0; e < n_spec; e++) {
+        if (spec[e].k < min_k || spec[e].k > max_k)
+            return fail(h, VPR_ERR_ARG, "%s: entry %d: k %d is not in %d..%d", entry, e, spec[e].k, min_k, max_k);
+        if (spec[e].slop < 0) return fail(h, VPR_ERR_ARG, "%s: entry %d: slop %d is negative", entry, e, spec[e].slop);
+    }
+    if (n_ctg < 1 || !ctg_off) return fail(h, VPR_ERR_ARG, "%s: no contig", entry);
+    if (ctg_off[0] != 0) return fail(h, VPR_ERR_ARG, "%s: ctg_off[0] is not 0", entry);
+    for (int c = 0; c < n_ctg; c++) {
+        const int64_t L = ctg_off[c + 1] - ctg_off[c];
+        if (L < 0 || L > INT32_MAX) return fail(h, VPR_ERR_ARG, "%s: contig %d has %lld bases", entry, c, (long long)L);
+    }
+    const int64_t N = ctg_off[n_ctg];
+    if (N > int64_t(UINT32_MAX))
+        return fail(h, VPR_ERR_ARG, "%s: %lld bases in total, above the %u that 32-bit starts can name", entry, (long long)N, UINT32_MAX);
+    if (N && !ctg_seq) return fail(h, VPR_ERR_ARG, "%s: null ctg_seq", entry);
+    return VPR_OK;
+}
 
-// room for exactly `bytes` (the arrays that scale with the genome are not given the quarter more of ctx_need)
-int rep_need(vpr_handle *h, DevBuf<uint8_t> &b, size_t bytes, const char *what) {
+int KmerWork::need(DevBuf<uint8_t> &b, size_t bytes, const char *what) {
     if (b.cap >= bytes) return VPR_OK;
-    const std::string nomem = std::string(ENTRY) + ": cannot allocate %zu bytes on the device (" + what + ")";
+    const std::string nomem = std::string(room_entry) + ": cannot allocate %zu bytes on the device (" + what + ")";
     return b.reserve(h, (bytes + 255) & ~size_t(255), nomem.c_str());
 }
 
-struct RepBufs {                         // the genome-wide arrays of the call, released when it goes
-    vpr_handle *h;
-    DevBuf<uint8_t> flags, cnt, keys, vals, sort_tmp;
-    explicit RepBufs(vpr_handle *h_) : h(h_) {}
-    ~RepBufs() {
-        (void)hipStreamSynchronize(h->stream);
-        dev_release(h, flags, cnt, keys, vals, sort_tmp);
-    }
-};
-
-unsigned blocks_of(int64_t n) { return unsigned((n + 255) / 256); }
-
-}  // namespace
-
-void repeats_free(vpr_handle *h) {
-    RepeatState *S = h->repeats;
-    if (!S) return;
-    (void)hipStreamSynchronize(h->stream);
-    dev_release(h, S->d_off, S->d_start, S->d_stop);
-    for (int k = 0; k < 2; k++) if (S->ev[k]) (void)hipEventDestroy(S->ev[k]);
-    delete S;
-    h->repeats = nullptr;
+int KmerWork::upload(int32_t n_ctg_, const int64_t *ctg_off_, const uint8_t *ctg_seq, size_t n_rows_, int other_tile) {
+    n_ctg = n_ctg_; ctg_off = ctg_off_; N = ctg_off[n_ctg]; n_rows = n_rows_;
+    if (int rc = ctx_need(h, W.entry, d_off, 8 * (n_rows + 1), "row offsets")) return rc;
+    if (int rc = ctx_need(h, W.entry, d_start, 4 * 1024, "intervals")) return rc;
+    if (int rc = ctx_need(h, W.entry, d_stop, 4 * 1024, "intervals")) return rc;
+    // the sequence, padded with zero bytes (not called) to whole tiles plus one, so that every 16-byte load of the pack stays inside
+    n_tiles = (N + REP_TILE - 1) / REP_TILE; n_pad = n_tiles * REP_TILE + REP_TILE;
+    nw = n_tiles * (REP_TILE / 64);
+    const int64_t n_tiles_max = other_tile ? std::max(n_tiles, (N + other_tile - 1) / other_tile) : n_tiles;
+    if (int rc = need(W.seq, size_t(n_pad), "contig sequences")) return rc;
+    if (int rc = W.need(W.ctg_off, 8 * (size_t(n_ctg) + 1), "contig offsets")) return rc;
+    if (int rc = W.need(W.small, 256, "counters")) return rc;
+    if (int rc = need(flags, size_t(nw) * 8 + 8, "flag bits")) return rc;
+    if (int rc = W.need(cnt, size_t(n_tiles_max + 1) * 8, "workgroup counts")) return rc;
+    if (N) HIPCHK(h, hipMemcpyAsync(W.seq.p, ctg_seq, size_t(N), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(as<uint8_t>(W.seq) + N, 0, size_t(n_pad - N), h->stream));
+    HIPCHK(h, hipMemcpyAsync(W.ctg_off.p, ctg_off, 8 * (size_t(n_ctg) + 1), hipMemcpyHostToDevice, h->stream));
+    d_seq = as<uint8_t>(W.seq); d_ctg = as<int64_t>(W.ctg_off);
+    d_count = reinterpret_cast<unsigned long long *>(as<uint8_t>(W.small) + 128);   // (the run passes use the first word)
+    pieces = ctx_pieces(ctg_off, n_ctg);                                            // for the run passes, as in vpr_context_masks
+    return VPR_OK;
 }
+
+int KmerWork::begin_timing(KmerState *S) {
+    W.ev[0] = S->ev[0]; W.ev[1] = S->ev[1];
+    HIPCHK(h, x_sync(h, h->stream, SITE));       // (the uploads and what the allocations left behind are not part of the passes' time)
+    return VPR_OK;
+}
+
+int KmerWork::scan(const uint32_t *in, uint32_t *out, size_t n) {
+    size_t bytes = 0;
+    if (vplan_exclusive_scan_u32(nullptr, &bytes, in, out, n, h->stream) != 0) return fail(h, VPR_ERR_DEVICE, "%s: scan workspace query failed", W.entry);
+    if (int rc = W.need(W.tmp, bytes + 256, "scan workspace")) return rc;
+    if (vplan_exclusive_scan_u32(W.tmp.p, &bytes, in, out, n, h->stream) != 0) return fail(h, VPR_ERR_DEVICE, "%s: scan failed", W.entry);
+    return VPR_OK;
+}
+
+int KmerWork::pair_room(size_t n) {
+    if (int rc = need(keys, n * 16, "sort keys, two buffers")) return rc;
+    return need(vals, n * 8, "sort values, two buffers");
+}
+
+int KmerWork::sort_room(size_t n, unsigned bits, size_t *bytes_out) {
+    uint64_t *k = as<uint64_t>(keys);
+    uint32_t *v = as<uint32_t>(vals);
+    size_t bytes = 0;
+    if (vplan_sort_pairs_u64(nullptr, &bytes, k, k + n, v, v + n, n, bits, h->stream) != 0)
+        return fail(h, VPR_ERR_DEVICE, "%s: sort workspace query failed", W.entry);
+    if (bytes_out) *bytes_out = bytes;
+    return need(sort_tmp, bytes + 256, "sort workspace");
+}
+
+int KmerWork::sort(size_t n, unsigned bits) {
+    size_t bytes = 0;
+    if (int rc = sort_room(n, bits, &bytes)) return rc;
+    uint64_t *k = as<uint64_t>(keys);
+    uint32_t *v = as<uint32_t>(vals);
+    keys_out = k + n; vals_out = v + n;
+    if (vplan_sort_pairs_u64(sort_tmp.p, &bytes, k, keys_out, v, vals_out, n, bits, h->stream) != 0) return fail(h, VPR_ERR_DEVICE, "%s: sort failed", W.entry);
+    return VPR_OK;
+}
+
+int KmerWork::pack(int k, uint32_t *n) {
+    return compact(n_tiles, [&](bool write, uint32_t *out, uint64_t *ks, uint32_t *vs) {
+        const auto kernel = write ? k_rep_pack<true> : k_rep_pack<false>;
+        hipLaunchKernelGGL(kernel, dim3(unsigned(n_tiles)), dim3(REP_WG), 0, h->stream, d_seq, d_ctg, n_ctg, N, k, out, ks, vs);
+    }, n);
+}
+
+int KmerWork::mark(uint32_t n, int k, unsigned long long *n_rep) {
+    *n_rep = 0;
+    HIPCHK(h, hipMemsetAsync(flags.p, 0, size_t(nw) * 8 + 8, h->stream));
+    if (!n) return VPR_OK;
+    HIPCHK(h, hipMemsetAsync(d_count + 1, 0, 8, h->stream));
+    hipLaunchKernelGGL(k_rep_mark, dim3(std::min(blocks_of(int64_t(n)), MARK_MAX_WG)), dim3(256), 0, h->stream, keys_out, vals_out, uint64_t(n), k,
+                       as<uint32_t>(flags), d_count + 1);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(n_rep, d_count + 1, 8, hipMemcpyDeviceToHost, h->stream));
+    return VPR_OK;
+}
+
+int KmerWork::rows_of_entry(int k, int slop, int spec_entry, int slot, int64_t *n_iv) {
+    int64_t *row_off = d_off.p + size_t(slot) * size_t(n_ctg);
+    const CtxRunRule rule = {k - 1, 1, 0, slop, 1, false};
+    for (const CtxPiece &pc : pieces) {
+        const int64_t g0 = ctg_off[pc.c0], g1 = ctg_off[pc.c1], T0 = g0 / REP_TILE * REP_TILE;
+        const int64_t nw_pc = (g1 - T0 + REP_TILE - 1) / REP_TILE * (REP_TILE / 64);
+        uint32_t n_out = 0;
+        if (int rc = W.seg_begin()) return rc;
+        if (nw_pc) {
+            if (int rc = W.need(W.bits, size_t(nw_pc) * 8, "flag bits of a piece")) return rc;
+            hipLaunchKernelGGL(k_rep_piece_words, dim3(blocks_of(nw_pc)), dim3(256), 0, h->stream, as<uint64_t>(flags), nw_pc, T0, g0, g1, as<uint64_t>(W.bits));
+            HIPCHK(h, hipGetLastError());
+        }
+        if (int rc = ctx_intervals_from_flags(W, as<uint64_t>(W.bits), nw_pc, T0, g0, d_seq, d_ctg, n_ctg, pc.c0, pc.c1, rule, spec_entry, d_start, d_stop,
+                                              size_t(*n_iv), row_off, &n_out))
+            return rc;
+        *n_iv += n_out;
+    }
+    return W.open ? W.seg_end() : VPR_OK;
+}
+
+int KmerWork::download_rows(int64_t n_iv, std::vector<int64_t> &off, std::vector<int32_t> &start, std::vector<int32_t> &stop) {
+    off.assign(n_rows + 1, 0); start.assign(size_t(n_iv), 0); stop.assign(size_t(n_iv), 0);
+    HIPCHK(h, hipMemcpyAsync(off.data(), d_off.p, 8 * (n_rows + 1), hipMemcpyDeviceToHost, h->stream));
+    if (n_iv) {
+        HIPCHK(h, hipMemcpyAsync(start.data(), d_start.p, 4 * size_t(n_iv), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(stop.data(), d_stop.p, 4 * size_t(n_iv), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, x_sync(h, h->stream, SITE));
+    off[n_rows] = n_iv;
+    return VPR_OK;
+}
+
+int KmerState::init(vpr_handle *h, int32_t n_spec_, int32_t n_ctg_) {
+    for (int k = 0; k < 2; k++) HIPCHK(h, hipEventCreate(&ev[k]));
+    n_spec = n_spec_; n_ctg = n_ctg_;
+    n_valid.assign(size_t(n_spec), 0); n_repeated.assign(size_t(n_spec), 0);
+    return VPR_OK;
+}
+
+int kmer_interval_counts(vpr_handle *h, const KmerState *S, const char *self, const char *entry, int64_t *iv_off) {
+    if (!iv_off) return VPR_ERR_ARG;
+    if (!S || !S->valid) return fail(h, VPR_ERR_STATE, "%s before %s", self, entry);
+    std::copy(S->off.begin(), S->off.end(), iv_off);
+    return VPR_OK;
+}
+
+int kmer_download_intervals(vpr_handle *h, const KmerState *S, const char *self, const char *entry, int32_t *start, int32_t *stop) {
+    if (!S || !S->valid) return fail(h, VPR_ERR_STATE, "%s before %s", self, entry);
+    if (S->start.empty()) return VPR_OK;
+    if (!start || !stop) return fail(h, VPR_ERR_ARG, "%s: null buffer", self);
+    std::copy(S->start.begin(), S->start.end(), start);
+    std::copy(S->stop.begin(), S->stop.end(), stop);
+    return VPR_OK;
+}
+
+int kmer_stats(vpr_handle *h, const KmerState *S, const char *self, const char *entry, bool bufs, int64_t *n_valid, int64_t *n_repeated) {
+    if (!S || !S->valid) return fail(h, VPR_ERR_STATE, "%s before %s", self, entry);
+    if (!bufs || !n_valid || !n_repeated) return fail(h, VPR_ERR_ARG, "%s: null buffer", self);
+    std::copy(S->n_valid.begin(), S->n_valid.end(), n_valid);
+    std::copy(S->n_repeated.begin(), S->n_repeated.end(), n_repeated);
+    return VPR_OK;
+}
+
+int kmer_timing(const KmerState *S, double *ms0, double *ms1, double *ms2, double *ms3) {
+    if (!ms0 || !ms1 || !ms2 || !ms3) return VPR_ERR_ARG;
+    const bool on = S && S->valid;
+    *ms0 = on ? S->ms[0] : 0; *ms1 = on ? S->ms[1] : 0; *ms2 = on ? S->ms[2] : 0; *ms3 = on ? S->ms[3] : 0;
+    return VPR_OK;
+}
+
+void repeats_free(vpr_handle *h) { kmer_free(h, &vpr_handle::repeats); }
 
 extern "C" {
 
@@ -217,181 +353,56 @@ int vpr_repeat_intervals(vpr_handle *h, int32_t n_ctg, const int64_t *ctg_off, c
     if (!h) return VPR_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     repeats_free(h);                     // the intervals of the last call end with this one, whatever becomes of it
-    // every check comes before a byte of ctg_seq is read
-    if (!spec) return fail(h, VPR_ERR_ARG, "%s: null spec", ENTRY);
-    if (n_spec < 1 || n_spec > VPR_REP_MAX_SPEC) return fail(h, VPR_ERR_ARG, "%s: n_spec %d is not in 1..%d", ENTRY, n_spec, VPR_REP_MAX_SPEC);
-    for (int e = 0; e < n_spec; e++) {
-        if (spec[e].k < VPR_REP_MIN_K || spec[e].k > VPR_REP_MAX_K)
-            return fail(h, VPR_ERR_ARG, "%s: entry %d: k %d is not in %d..%d", ENTRY, e, spec[e].k, VPR_REP_MIN_K, VPR_REP_MAX_K);
-        if (spec[e].slop < 0) return fail(h, VPR_ERR_ARG, "%s: entry %d: slop %d is negative", ENTRY, e, spec[e].slop);
-    }
-    if (n_ctg < 1 || !ctg_off) return fail(h, VPR_ERR_ARG, "%s: no contig", ENTRY);
-    if (ctg_off[0] != 0) return fail(h, VPR_ERR_ARG, "%s: ctg_off[0] is not 0", ENTRY);
-    for (int c = 0; c < n_ctg; c++) {
-        const int64_t L = ctg_off[c + 1] - ctg_off[c];
-        if (L < 0 || L > INT32_MAX) return fail(h, VPR_ERR_ARG, "%s: contig %d has %lld bases", ENTRY, c, (long long)L);
-    }
-    const int64_t N = ctg_off[n_ctg];
-    if (N > int64_t(UINT32_MAX))
-        return fail(h, VPR_ERR_ARG, "%s: %lld bases in total, above the %u that 32-bit starts can name", ENTRY, (long long)N, UINT32_MAX);
-    if (N && !ctg_seq) return fail(h, VPR_ERR_ARG, "%s: null ctg_seq", ENTRY);
-
-    RepeatState *S = h->repeats = new RepeatState();
-    for (int k = 0; k < 2; k++) HIPCHK(h, hipEventCreate(&S->ev[k]));
-    S->n_spec = n_spec; S->n_ctg = n_ctg;
-    S->n_valid.assign(size_t(n_spec), 0); S->n_repeated.assign(size_t(n_spec), 0);
-    const size_t rows = size_t(n_spec) * size_t(n_ctg);
-    if (int rc = ctx_need(h, ENTRY, S->d_off, 8 * (rows + 1), "row offsets")) return rc;
-    if (int rc = ctx_need(h, ENTRY, S->d_start, 4 * 1024, "intervals")) return rc;
-    if (int rc = ctx_need(h, ENTRY, S->d_stop, 4 * 1024, "intervals")) return rc;
-
-    CtxWork W(h, ENTRY);
-    RepBufs R(h);
-    // the sequence, padded with zero bytes (not called) to whole tiles plus one, so that every 16-byte load stays inside
-    const int64_t n_tiles_all = (N + REP_TILE - 1) / REP_TILE, n_pad = n_tiles_all * REP_TILE + REP_TILE;
-    const int64_t nw_all = n_tiles_all * (REP_TILE / 64);                   // 64-bit flag words of the genome
-    if (int rc = rep_need(h, W.seq, size_t(n_pad), "contig sequences")) return rc;
-    if (int rc = W.need(W.ctg_off, 8 * (size_t(n_ctg) + 1), "contig offsets")) return rc;
-    if (int rc = W.need(W.small, 256, "counters")) return rc;
-    if (int rc = rep_need(h, R.flags, size_t(nw_all) * 8 + 8, "flag bits")) return rc;
-    if (int rc = W.need(R.cnt, size_t(n_tiles_all + 1) * 8, "workgroup counts")) return rc;
-    if (N) HIPCHK(h, hipMemcpyAsync(W.seq.p, ctg_seq, size_t(N), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemsetAsync(as<uint8_t>(W.seq) + N, 0, size_t(n_pad - N), h->stream));
-    HIPCHK(h, hipMemcpyAsync(W.ctg_off.p, ctg_off, 8 * (size_t(n_ctg) + 1), hipMemcpyHostToDevice, h->stream));
-    const uint8_t *d_seq = as<uint8_t>(W.seq);
-    const int64_t *d_ctg = as<int64_t>(W.ctg_off);
-    uint32_t *cnt = as<uint32_t>(R.cnt), *off = cnt + (n_tiles_all + 1);
-    unsigned long long *d_nrep = reinterpret_cast<unsigned long long *>(as<uint8_t>(W.small) + 128);   // (the run passes use the first word)
-
-    // pieces of whole contigs for the run passes, as in vpr_context_masks
-    struct Piece { int c0, c1; };       // contigs [c0, c1)
-    std::vector<Piece> pieces;
-    const int64_t budget = ctx_piece_bases();
-    for (int c = 0; c < n_ctg;) {
-        int e = c + 1;
-        while (e < n_ctg && ctg_off[e + 1] - ctg_off[c] <= budget) e++;
-        pieces.push_back({c, e});
-        c = e;
-    }
-
-    W.ev[0] = S->ev[0]; W.ev[1] = S->ev[1];
-    HIPCHK(h, x_sync(h, h->stream, SITE));       // (the uploads are not part of the passes' time)
+    if (int rc = KmerWork::check_args(h, ENTRY, VPR_REP_MIN_K, VPR_REP_MAX_K, VPR_REP_MAX_SPEC, n_ctg, ctg_off, ctg_seq, spec, n_spec)) return rc;
+    KmerState *S = h->repeats = new KmerState();
+    if (int rc = S->init(h, n_spec, n_ctg)) return rc;
+    KmerWork K(h, ENTRY);
+    CtxWork &W = K.W;
+    if (int rc = K.upload(n_ctg, ctg_off, ctg_seq, size_t(n_spec) * size_t(n_ctg))) return rc;
+    if (int rc = K.begin_timing(S)) return rc;
 
     int64_t n_iv = 0;
     for (int e = 0; e < n_spec; e++) {
         const int k = spec[e].k;
         uint32_t n = 0;                  // valid starts (at most N <= UINT32_MAX)
-        if (n_tiles_all) {
-            W.ms = &S->ms_pack;
+        unsigned long long n_rep = 0;
+        if (K.n_tiles) {
+            W.ms = &S->ms[0];
             if (int rc = W.seg_begin()) return rc;
-            HIPCHK(h, hipMemsetAsync(cnt + n_tiles_all, 0, 4, h->stream));
-            hipLaunchKernelGGL(k_rep_pack<false>, dim3(unsigned(n_tiles_all)), dim3(REP_WG), 0, h->stream, d_seq, d_ctg, n_ctg, N, k, cnt,
-                               (uint64_t *)nullptr, (uint32_t *)nullptr);
-            HIPCHK(h, hipGetLastError());
-            {
-                size_t bytes = 0;
-                if (vplan_exclusive_scan_u32(nullptr, &bytes, cnt, off, size_t(n_tiles_all + 1), h->stream) != 0)
-                    return fail(h, VPR_ERR_DEVICE, "%s: scan workspace query failed", ENTRY);
-                if (int rc = W.need(W.tmp, bytes + 256, "scan workspace")) return rc;
-                if (vplan_exclusive_scan_u32(W.tmp.p, &bytes, cnt, off, size_t(n_tiles_all + 1), h->stream) != 0)
-                    return fail(h, VPR_ERR_DEVICE, "%s: scan failed", ENTRY);
-            }
-            HIPCHK(h, hipMemcpyAsync(&n, off + n_tiles_all, 4, hipMemcpyDeviceToHost, h->stream));
+            if (int rc = K.pack(k, &n)) return rc;
             if (int rc = W.seg_end()) return rc;
         }
         S->n_valid[size_t(e)] = int64_t(n);
         if (n) {
-            if (int rc = rep_need(h, R.keys, size_t(n) * 16, "sort keys, two buffers")) return rc;
-            if (int rc = rep_need(h, R.vals, size_t(n) * 8, "sort values, two buffers")) return rc;
-            uint64_t *keys = as<uint64_t>(R.keys), *keys_out = keys + n;
-            uint32_t *vals = as<uint32_t>(R.vals), *vals_out = vals + n;
+            W.ms = &S->ms[1];
+            if (int rc = K.sort_room(n, unsigned(2 * k))) return rc;     // (not under the sort's clock)
             if (int rc = W.seg_begin()) return rc;
-            hipLaunchKernelGGL(k_rep_pack<true>, dim3(unsigned(n_tiles_all)), dim3(REP_WG), 0, h->stream, d_seq, d_ctg, n_ctg, N, k, off, keys, vals);
-            HIPCHK(h, hipGetLastError());
+            if (int rc = K.sort(n, unsigned(2 * k))) return rc;
             if (int rc = W.seg_end()) return rc;
-
-            W.ms = &S->ms_sort;
-            size_t bytes = 0;
-            if (vplan_sort_pairs_u64(nullptr, &bytes, keys, keys_out, vals, vals_out, size_t(n), unsigned(2 * k), h->stream) != 0)
-                return fail(h, VPR_ERR_DEVICE, "%s: sort workspace query failed", ENTRY);
-            if (int rc = rep_need(h, R.sort_tmp, bytes + 256, "sort workspace")) return rc;
+            W.ms = &S->ms[2];
             if (int rc = W.seg_begin()) return rc;
-            if (vplan_sort_pairs_u64(R.sort_tmp.p, &bytes, keys, keys_out, vals, vals_out, size_t(n), unsigned(2 * k), h->stream) != 0)
-                return fail(h, VPR_ERR_DEVICE, "%s: sort failed", ENTRY);
-            if (int rc = W.seg_end()) return rc;
-
-            W.ms = &S->ms_mark;
-            unsigned long long n_rep = 0;
-            if (int rc = W.seg_begin()) return rc;
-            HIPCHK(h, hipMemsetAsync(R.flags.p, 0, size_t(nw_all) * 8 + 8, h->stream));
-            HIPCHK(h, hipMemsetAsync(d_nrep, 0, 8, h->stream));
-            hipLaunchKernelGGL(k_rep_mark, dim3(std::min(blocks_of(int64_t(n)), MARK_MAX_WG)), dim3(256), 0, h->stream, keys_out, vals_out, uint64_t(n), k,
-                               as<uint32_t>(R.flags), d_nrep);
-            HIPCHK(h, hipGetLastError());
-            HIPCHK(h, hipMemcpyAsync(&n_rep, d_nrep, 8, hipMemcpyDeviceToHost, h->stream));
-            if (int rc = W.seg_end()) return rc;
-            S->n_repeated[size_t(e)] = int64_t(n_rep);
-        } else {
-            HIPCHK(h, hipMemsetAsync(R.flags.p, 0, size_t(nw_all) * 8 + 8, h->stream));
         }
-
-        W.ms = &S->ms_intervals;
-        int64_t *row_off = S->d_off.p + size_t(e) * size_t(n_ctg);
-        const CtxRunRule rule = {k - 1, 1, 0, spec[e].slop, 1, false};
-        for (const Piece &pc : pieces) {
-            const int64_t g0 = ctg_off[pc.c0], g1 = ctg_off[pc.c1], T0 = g0 / REP_TILE * REP_TILE;
-            const int64_t n_tiles = (g1 - T0 + REP_TILE - 1) / REP_TILE, nw = n_tiles * (REP_TILE / 64);
-            uint32_t n_out = 0;
-            if (int rc = W.seg_begin()) return rc;
-            if (nw) {
-                if (int rc = W.need(W.bits, size_t(nw) * 8, "flag bits of a piece")) return rc;
-                hipLaunchKernelGGL(k_rep_piece_words, dim3(blocks_of(nw)), dim3(256), 0, h->stream, as<uint64_t>(R.flags), nw, T0, g0, g1,
-                                   as<uint64_t>(W.bits));
-                HIPCHK(h, hipGetLastError());
-            }
-            if (int rc = ctx_intervals_from_flags(W, as<uint64_t>(W.bits), nw, T0, g0, d_seq, d_ctg, n_ctg, pc.c0, pc.c1, rule, e, S->d_start, S->d_stop,
-                                                  size_t(n_iv), row_off, &n_out))
-                return rc;
-            n_iv += n_out;
-        }
+        if (int rc = K.mark(n, k, &n_rep)) return rc;                    // (without a valid start: the flags are cleared, untimed)
         if (W.open) if (int rc = W.seg_end()) return rc;
+        S->n_repeated[size_t(e)] = int64_t(n_rep);
+        W.ms = &S->ms[3];
+        if (int rc = K.rows_of_entry(k, spec[e].slop, e, e, &n_iv)) return rc;
     }
-    S->n_iv = n_iv;
+    if (int rc = K.download_rows(n_iv, S->off, S->start, S->stop)) return rc;
     S->valid = true;
     return VPR_OK;
 }
 
 int vpr_repeat_interval_counts(vpr_handle *h, int64_t *iv_off) {
-    if (!h || !iv_off) return VPR_ERR_ARG;
-    const RepeatState *S = h->repeats;
-    if (!S || !S->valid) return fail(h, VPR_ERR_STATE, "vpr_repeat_interval_counts before vpr_repeat_intervals");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t rows = size_t(S->n_spec) * size_t(S->n_ctg);
-    HIPCHK(h, hipMemcpyAsync(iv_off, S->d_off.p, 8 * (rows + 1), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, x_sync(h, h->stream, SITE));
-    return VPR_OK;
+    return h ? kmer_interval_counts(h, h->repeats, "vpr_repeat_interval_counts", ENTRY, iv_off) : VPR_ERR_ARG;
 }
 
 int vpr_repeat_download_intervals(vpr_handle *h, int32_t *start, int32_t *stop) {
-    if (!h) return VPR_ERR_ARG;
-    const RepeatState *S = h->repeats;
-    if (!S || !S->valid) return fail(h, VPR_ERR_STATE, "vpr_repeat_download_intervals before vpr_repeat_intervals");
-    if (!S->n_iv) return VPR_OK;
-    if (!start || !stop) return fail(h, VPR_ERR_ARG, "vpr_repeat_download_intervals: null buffer");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipMemcpyAsync(start, S->d_start.p, 4 * size_t(S->n_iv), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(stop, S->d_stop.p, 4 * size_t(S->n_iv), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, x_sync(h, h->stream, SITE));
-    return VPR_OK;
+    return h ? kmer_download_intervals(h, h->repeats, "vpr_repeat_download_intervals", ENTRY, start, stop) : VPR_ERR_ARG;
 }
 
 int vpr_repeat_stats(vpr_handle *h, int64_t *n_valid, int64_t *n_repeated) {
-    if (!h) return VPR_ERR_ARG;
-    const RepeatState *S = h->repeats;
-    if (!S || !S->valid) return fail(h, VPR_ERR_STATE, "vpr_repeat_stats before vpr_repeat_intervals");
-    if (!n_valid || !n_repeated) return fail(h, VPR_ERR_ARG, "vpr_repeat_stats: null buffer");
-    for (int e = 0; e < S->n_spec; e++) { n_valid[e] = S->n_valid[size_t(e)]; n_repeated[e] = S->n_repeated[size_t(e)]; }
-    return VPR_OK;
+    return h ? kmer_stats(h, h->repeats, "vpr_repeat_stats", ENTRY, true, n_valid, n_repeated) : VPR_ERR_ARG;
 }
 
 int vpr_repeat_sort_floor(vpr_handle *h, int64_t n, int32_t k, uint64_t seed, double *ms) {
@@ -399,55 +410,28 @@ int vpr_repeat_sort_floor(vpr_handle *h, int64_t n, int32_t k, uint64_t seed, do
     if (n < 1 || n > int64_t(UINT32_MAX) || k < VPR_REP_MIN_K || k > VPR_REP_MAX_K)
         return fail(h, VPR_ERR_ARG, "vpr_repeat_sort_floor: n %lld or k %d outside the limits of vpr_repeat_intervals", (long long)n, k);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    RepBufs R(h);
-    if (int rc = rep_need(h, R.keys, size_t(n) * 16, "sort keys, two buffers")) return rc;
-    if (int rc = rep_need(h, R.vals, size_t(n) * 8, "sort values, two buffers")) return rc;
-    uint64_t *keys = as<uint64_t>(R.keys), *keys_out = keys + n;
-    uint32_t *vals = as<uint32_t>(R.vals), *vals_out = vals + n;
-    size_t bytes = 0;
-    if (vplan_sort_pairs_u64(nullptr, &bytes, keys, keys_out, vals, vals_out, size_t(n), unsigned(2 * k), h->stream) != 0)
-        return fail(h, VPR_ERR_DEVICE, "vpr_repeat_sort_floor: sort workspace query failed");
-    if (int rc = rep_need(h, R.sort_tmp, bytes + 256, "sort workspace")) return rc;
+    KmerWork K(h, "vpr_repeat_sort_floor", ENTRY);       // (its arrays have always been refused under the name of the entry it measures)
+    if (int rc = K.pair_room(size_t(n))) return rc;
+    if (int rc = K.sort_room(size_t(n), unsigned(2 * k))) return rc;
     hipEvent_t ev[2];
     for (int i = 0; i < 2; i++) HIPCHK(h, hipEventCreate(&ev[i]));
-    hipLaunchKernelGGL(k_rep_random_keys, dim3(blocks_of(n)), dim3(256), 0, h->stream, uint64_t(n), seed, keys, vals);
+    hipLaunchKernelGGL(k_rep_random_keys, dim3(blocks_of(n)), dim3(256), 0, h->stream, uint64_t(n), seed, as<uint64_t>(K.keys), as<uint32_t>(K.vals));
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipEventRecord(ev[0], h->stream);
-    const int rc = e == hipSuccess ? vplan_sort_pairs_u64(R.sort_tmp.p, &bytes, keys, keys_out, vals, vals_out, size_t(n), unsigned(2 * k), h->stream) : 0;
+    const int rc = e == hipSuccess ? K.sort(size_t(n), unsigned(2 * k)) : VPR_OK;
     if (e == hipSuccess) e = hipEventRecord(ev[1], h->stream);
     if (e == hipSuccess) e = x_sync(h, h->stream, SITE);
     float t = 0;
     if (e == hipSuccess) e = hipEventElapsedTime(&t, ev[0], ev[1]);
     for (int i = 0; i < 2; i++) (void)hipEventDestroy(ev[i]);
     if (e != hipSuccess) return fail(h, VPR_ERR_DEVICE, "vpr_repeat_sort_floor: %s", hipGetErrorString(e));
-    if (rc != 0) return fail(h, VPR_ERR_DEVICE, "vpr_repeat_sort_floor: sort failed");
+    if (rc) return rc;                   // ("vpr_repeat_sort_floor: sort failed")
     *ms = t;
     return VPR_OK;
 }
 
 int vpr_repeat_timing(const vpr_handle *h, double *ms_pack, double *ms_sort, double *ms_mark, double *ms_intervals) {
-    if (!h || !ms_pack || !ms_sort || !ms_mark || !ms_intervals) return VPR_ERR_ARG;
-    const RepeatState *S = h->repeats;
-    if (!S || !S->valid) { *ms_pack = *ms_sort = *ms_mark = *ms_intervals = 0; return VPR_OK; }
-    *ms_pack = S->ms_pack; *ms_sort = S->ms_sort; *ms_mark = S->ms_mark; *ms_intervals = S->ms_intervals;
-    return VPR_OK;
+    return h ? kmer_timing(h->repeats, ms_pack, ms_sort, ms_mark, ms_intervals) : VPR_ERR_ARG;
 }
 
 }  // extern "C"
-
-// the launches pr_longrepeats.hip borrows for its base level (k = 32) and its last level (pr_host.h)
-static_assert(REP_TILE == REP_PACK_TILE, "pr_host.h names the pack's tile");
-
-void rep_launch_pack(hipStream_t st, bool write, unsigned n_tiles, const uint8_t *seq, const int64_t *ctg_off, int n_ctg, int64_t N, int k,
-                     uint32_t *out, uint64_t *keys, uint32_t *vals) {
-    if (write) hipLaunchKernelGGL(k_rep_pack<true>, dim3(n_tiles), dim3(REP_WG), 0, st, seq, ctg_off, n_ctg, N, k, out, keys, vals);
-    else hipLaunchKernelGGL(k_rep_pack<false>, dim3(n_tiles), dim3(REP_WG), 0, st, seq, ctg_off, n_ctg, N, k, out, keys, vals);
-}
-
-void rep_launch_mark(hipStream_t st, const uint64_t *keys, const uint32_t *vals, uint64_t n, int k, uint32_t *flags32, unsigned long long *n_rep) {
-    hipLaunchKernelGGL(k_rep_mark, dim3(std::min(blocks_of(int64_t(n)), MARK_MAX_WG)), dim3(256), 0, st, keys, vals, n, k, flags32, n_rep);
-}
-
-void rep_launch_piece_words(hipStream_t st, const uint64_t *all, int64_t nw, int64_t T0, int64_t g0, int64_t g1, uint64_t *words) {
-    hipLaunchKernelGGL(k_rep_piece_words, dim3(blocks_of(nw)), dim3(256), 0, st, all, nw, T0, g0, g1, words);
-}
