@@ -173,6 +173,11 @@ typedef struct vpr_config {
 #define VPR_CFG_KEEP_PATHS 8    /* the zero-distance lane kernel (most alignments of whole-genome input end there) keeps its walk in a
                                    compact form only its own credit kernel reads; with this flag it also writes the 16-byte path
                                    entries vpr_download_path returns (tests, callers who want the alignment path itself) */
+#define VPR_CFG_KEEP_STRIP_PLAN 32 /* test aid: the dense level cuts alignments of more than 2 048 columns into column strips, one
+                                   workgroup each, where a planner kernel finds cuts (k_strip_plan, pr_strip.hip), and leaves the
+                                   others to the one-workgroup kernels.  With this flag vpr_execute also brings every planner call's
+                                   decisions to the host, behind the wait it has anyway (vpr_strip_plan_count / _record); without
+                                   it nothing is copied or allocated */
 
 /* Results: the fields precision_recall_wrapper writes in place
    (ctgVariants::{errtypes,sync_group,credit,ref_ed,query_ed,callq}, src/variant.h:49-60;
@@ -284,6 +289,22 @@ int vpr_get_timing(const vpr_handle *h, vpr_timing *t);
    use `cpu_quota` CPUs (cgroup quota / local ranks): 0 for a quota of 1 - 3, never more than the quota */
 int32_t vpr_test_pool_workers(int32_t cpu_quota);
 int vpr_get_launch_stats(const vpr_handle *h, vpr_launch_stat *out, int32_t cap);  /* returns #launches */
+/* test aid (VPR_CFG_KEEP_STRIP_PLAN): what the strip planner decided in the last vpr_execute.  One record per planner call and
+   alignment of that call, in call order: the round-0 dense plan (band_mode 0), the dense rounds behind the window ladders
+   (from_window: the alignment failed a window level's exit test, its distance there bounds the strips' sweep from above) and
+   the dense tie rounds (tie_round). */
+typedef struct vpr_strip_plan_rec {
+    int32_t sc, aln;       /* supercluster, alignment 0..3 */
+    int32_t from_window;   /* 1: the call came behind a window level */
+    int32_t tie_round;     /* 1: the call belongs to a tie round */
+    int32_t call;          /* index of the planner call inside the execute */
+    int32_t ok;            /* 1 = the strips took it, 0 = left to the one-workgroup kernels, 2 = neither can (VPR_ST_ERR_LIMIT) */
+    int32_t n_strips;      /* 0 unless ok == 1 */
+} vpr_strip_plan_rec;
+int vpr_strip_plan_count(const vpr_handle *h);     /* records kept by the last vpr_execute (0 without the flag), or < 0 */
+/* record k; lohi (may be NULL) receives {lo_q, lo_r, hi_q, hi_r} of its first min(n_strips, cap) strips: strip j holds the
+   columns [lo, hi) of the QUERY and of the REF plane */
+int vpr_strip_plan_record(const vpr_handle *h, int32_t k, vpr_strip_plan_rec *rec, int32_t *lohi, int32_t cap);
 /* TP/FP/FN counts [callset QUERY,TRUTH][TP,FP,FN] of the phasing each supercluster's distances select
    (sc_phase SWAP -> swap slot 1, else slot 0), accumulated on the device by the last vpr_execute: the
    per-rank input of the final tally all-reduce */

@@ -202,7 +202,7 @@ def test_sv_sized_indels_long_alignments_against_the_oracle(seed):
     import fuzz_parity
     shape, kw, band_mode = fuzz_parity.random_workload(seed, 6)
     batch = api.Synth(**kw).batch()
-    got, want, n_nonmax, pr = compare(batch, A.default_config(band_mode=band_mode))
+    got, want, n_nonmax, pr = compare(batch, A.default_config(band_mode=band_mode, flags=A.CFG_KEEP_STRIP_PLAN))
     t = pr.timing()
     big = max(max(batch.lens(k)[q] for q in (0, 1)) + batch.lens(k)[4] for k in range(batch.n_sc))
     print(f"seed {seed}: {batch.n_sc} superclusters, largest Lq + Lr {big}, {batch.dense_cells():.2e} dense cells, "
@@ -210,6 +210,9 @@ def test_sv_sized_indels_long_alignments_against_the_oracle(seed):
     names = {s.kernel.decode() for s in pr.launch_stats()}
     assert t.ms_ed > 0 and t.n_band_retries > 0 and any(n.startswith("k_fwd<") for n in names)
     assert "k_fwd_strip" in names and "k_bwd_strip" in names        # the wide alignments of the dense level: over column strips
+    cut = [r for r in pr.strip_plan() if r["ok"] == 1 and len(r["strips"]) >= 2]
+    print(f"seed {seed}: {len(cut)} of {len(pr.strip_plan())} planned alignments cut, up to {max(len(r['strips']) for r in cut)} strips")
+    assert cut                                                       # ... and not only launched: the planner cut at least one
     if seed == 64017:
         assert any("s16" in n for n in names)
 
@@ -231,10 +234,12 @@ def test_dense_strips_and_what_the_strip_planner_cannot_cut():
     t2 = [(2000, D, ref[2000:2040], "", 40.0), (4500, I, "", ins[:90], 40.0)]
     v = A.Variants.from_sites([ref], [dict(ctg=0, beg=100, end=8900, vars=[q1, q2, t1, t2])])
     batch = api.batch_from_variants(v)
-    got, want, _, pr = compare(batch, A.default_config(band_mode=0))
+    got, want, _, pr = compare(batch, A.default_config(band_mode=0, flags=A.CFG_KEEP_STRIP_PLAN))
     names = {s.kernel.decode() for s in pr.launch_stats()}
     assert "k_fwd_strip" in names and "k_bwd_strip" in names and any(n.startswith("k_fwd<1024") for n in names)
     assert want.aln_dist[0] <= 2 and want.aln_dist[3] >= 90
+    plan = {(r["sc"], r["aln"]): (r["ok"], len(r["strips"])) for r in pr.strip_plan()}      # what the planner decided
+    assert plan == {(0, 0): (0, 0), (0, 1): (0, 0), (0, 2): (1, 3), (0, 3): (1, 3)}, plan
 
 
 def test_diagnostic_switches_leave_the_results_unchanged(monkeypatch):

@@ -77,6 +77,7 @@ CFG_TIE_SMALL_LOGS = 2   # VPR_CFG_TIE_SMALL_LOGS
 CFG_GUARD_ALLOC = 4      # VPR_CFG_GUARD_ALLOC
 CFG_KEEP_PATHS = 8       # VPR_CFG_KEEP_PATHS
 CFG_HAP_DEDUP = 16       # VPR_CFG_HAP_DEDUP
+CFG_KEEP_STRIP_PLAN = 32  # VPR_CFG_KEEP_STRIP_PLAN
 
 
 class VprTiming(C.Structure):
@@ -90,6 +91,10 @@ class VprTiming(C.Structure):
         ("ms_host_blocked", C.c_double), ("n_alignments_computed", C.c_int64), ("n_device_allocs", C.c_int64), ("n_device_frees", C.c_int64),
         ("n_host_allocs", C.c_int64), ("n_lane1_seen", C.c_int64), ("n_lane1_finished", C.c_int64), ("n_lane1_waves_dropped", C.c_int64),
     ]
+
+
+class VprStripPlanRec(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("sc", "aln", "from_window", "tie_round", "call", "ok", "n_strips")]
 
 
 class VprLaunchStat(C.Structure):

@@ -66,6 +66,8 @@ def lib():
     L.vpr_get_timing.argtypes = [H, C.POINTER(A.VprTiming)]
     L.vpr_get_launch_stats.argtypes = [H, C.POINTER(A.VprLaunchStat), C.c_int32]
     L.vpr_get_tally.argtypes = [H, C.POINTER(C.c_int64)]
+    L.vpr_strip_plan_count.argtypes = [H]
+    L.vpr_strip_plan_record.argtypes = [H, C.c_int32, C.POINTER(A.VprStripPlanRec), A.P_i32, C.c_int32]
     L.vpr_download_path.restype = C.c_int64
     L.vpr_download_path.argtypes = [H, C.c_int32, C.c_int32, C.c_int64, A.P_u8, A.P_i32, A.P_i32, A.P_u8, A.P_u8]
     L.vpr_store_phase.restype = C.c_int32
@@ -149,7 +151,7 @@ def call_or_allreduce(h, plain, reduced, comm, *args):
 EXPORTED = [
     "vpr_create", "vpr_destroy", "vpr_last_error", "vpr_version", "vpr_run", "vpr_upload",
     "vpr_upload_variants", "vpr_download_level_a", "vpr_select_device", "vpr_execute", "vpr_download", "vpr_host_alloc", "vpr_host_free", "vpr_get_timing", "vpr_get_launch_stats",
-    "vpr_get_tally",
+    "vpr_get_tally", "vpr_strip_plan_count", "vpr_strip_plan_record",
     "vpr_download_path", "vpr_phase", "vpr_var_class", "vpr_upload_var_class", "vpr_results_alloc", "vpr_pr_counts", "vpr_pr_summary",
     "vpr_store_phase", "vpr_batch_from_variants", "vpr_owned_batch_view", "vpr_owned_batch_free",
     "vpr_synth_default_params", "vpr_synth_create", "vpr_synth_variants", "vpr_synth_destroy",
@@ -810,6 +812,24 @@ class PrecisionRecall:
         arr = (A.VprLaunchStat * max(n, 1))()
         L.vpr_get_launch_stats(self._h, arr, n)
         return [arr[i] for i in range(n)]
+
+    def strip_plan(self):
+        """test aid (A.CFG_KEEP_STRIP_PLAN): what the strip planner (k_strip_plan) decided in the last execute -> one dict per
+        planner call and alignment, in call order: sc, aln, from_window, tie_round, call, ok (1 strips, 0 one-workgroup kernels,
+        2 neither) and strips, the list of (lo_q, lo_r, hi_q, hi_r).  Empty without the flag."""
+        L = lib()
+        n = L.vpr_strip_plan_count(self._h)
+        self._chk(min(n, 0), "vpr_strip_plan_count")
+        out = []
+        for k in range(n):
+            rec = A.VprStripPlanRec()
+            self._chk(L.vpr_strip_plan_record(self._h, k, C.byref(rec), None, 0), "vpr_strip_plan_record")
+            lohi = np.zeros((max(rec.n_strips, 1), 4), np.int32)
+            self._chk(L.vpr_strip_plan_record(self._h, k, C.byref(rec), lohi.ctypes.data_as(A.P_i32), rec.n_strips), "vpr_strip_plan_record")
+            d = {f: int(getattr(rec, f)) for f, _ in A.VprStripPlanRec._fields_ if f != "n_strips"}
+            d["strips"] = [tuple(int(x) for x in row) for row in lohi[:rec.n_strips]]
+            out.append(d)
+        return out
 
     def upload_variants(self, variants_struct, batch_for_results):
         """Upload a vpr_variants struct (e.g. Synth.struct): the host sizes and checks the regions, the device writes the

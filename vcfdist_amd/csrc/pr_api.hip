@@ -2147,7 +2147,17 @@ struct Exec {
         StripTab *d_tab = nullptr;
         int2 *d_bnd = nullptr; int4 *d_bbnd = nullptr;
     };
-    int strip_plan(const Plan &P, const int32_t *d_work, int64_t off, int32_t cnt, hipStream_t ks, StripGroup &G) {
+    // VPR_CFG_KEEP_STRIP_PLAN: the tables of every strip_plan call of this execute, fetched by finish() behind the execute's
+    // one wait (the blocks -- device and page-locked -- belong to the execute: nothing hands them out again before the next one)
+    struct KeptPlan {
+        const int32_t *d_n, *d_ok, *h_base; const StripTab *d_tab; int32_t cnt;
+        std::vector<std::pair<int32_t, int32_t>> who;       // (supercluster, alignment) of each entry
+        bool from_window, tie_round;
+    };
+    std::vector<KeptPlan> kept_plans;
+
+    int strip_plan(const Plan &P, const int32_t *d_work, int64_t off, int32_t cnt, hipStream_t ks, StripGroup &G, bool from_window,
+                   bool tie_round) {
         G.off = off; G.cnt = cnt;
         // slots per alignment: twice what the longer plane needs (a cut may have to move far back to a clean column)
         auto slots_of = [](const AlnDesc &d) { return 2 * ((std::max(d.Lq, d.Lr) + ST_CAP - 1) / ST_CAP) + 2; };
@@ -2211,6 +2221,40 @@ struct Exec {
         HIPCHK(h, hipMemsetAsync(G.d_prog, 0, size_t(slots) * 8 + 8, ks));
         hipLaunchKernelGGL(k_strip_plan, dim3((cnt + 63) / 64), dim3(64), 0, ks, h->dB, h->d_descs, d_work + off, cnt, G.d_base, G.d_tab,
                            G.d_n, G.d_ok, d_fits, h->d_err, h->d_outs);
+        if (h->cfg.flags & VPR_CFG_KEEP_STRIP_PLAN) {
+            KeptPlan K{G.d_n, G.d_ok, h_base, G.d_tab, cnt, {}, from_window, tie_round};
+            for (int32_t k = 0; k < cnt; k++) { const AlnDesc &d = P.descs[size_t(off) + k]; K.who.emplace_back(d.sc, d.aln); }
+            kept_plans.push_back(std::move(K));
+        }
+        return VPR_OK;
+    }
+
+    // the kept strip plans -> the handle (vpr_strip_plan_count / vpr_strip_plan_record); the stream has been waited for
+    int fetch_strip_plans() {
+        std::vector<int32_t> nk;
+        std::vector<StripTab> tab;
+        for (size_t c = 0; c < kept_plans.size(); c++) {
+            const KeptPlan &K = kept_plans[c];
+            nk.resize(size_t(K.cnt) * 2);       // (d_n and d_ok lie side by side: strip_plan)
+            HIPCHK(h, hipMemcpyAsync(nk.data(), K.d_n, size_t(K.cnt) * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(h, hipStreamSynchronize(st));
+            int64_t used = 0;                   // slots up to the last one the planner filled
+            for (int32_t k = 0; k < K.cnt; k++) if (nk[size_t(k)] > 0) used = int64_t(K.h_base[k]) + nk[size_t(k)];
+            tab.resize(size_t(used));
+            if (used) {
+                HIPCHK(h, hipMemcpyAsync(tab.data(), K.d_tab, size_t(used) * sizeof(StripTab), hipMemcpyDeviceToHost, st));
+                HIPCHK(h, hipStreamSynchronize(st));
+            }
+            for (int32_t k = 0; k < K.cnt; k++) {
+                vpr_handle::StripPlanRec R{K.who[size_t(k)].first, K.who[size_t(k)].second, K.from_window ? 1 : 0, K.tie_round ? 1 : 0,
+                                           int32_t(c), nk[size_t(K.cnt) + size_t(k)], nk[size_t(k)], int64_t(h->strip_lohi.size() / 4)};
+                for (int32_t j = 0; j < R.n_strips; j++) {
+                    const StripTab &T = tab[size_t(K.h_base[k]) + size_t(j)];
+                    h->strip_lohi.insert(h->strip_lohi.end(), {T.lo[0], T.lo[1], T.hi[0], T.hi[1]});
+                }
+                h->strip_recs.push_back(R);
+            }
+        }
         return VPR_OK;
     }
 
@@ -2304,7 +2348,7 @@ struct Exec {
             if (strips) {
                 hipStream_t ks = one_stream ? base : h->cls_stream[STRIP_CLS];
                 if (!one_stream) HIPCHK(h, hipStreamWaitEvent(ks, h->ev_fork, 0));
-                int rc = strip_plan(P, d_work, g_off, g_cnt, ks, G);
+                int rc = strip_plan(P, d_work, g_off, g_cnt, ks, G, from_window, tag_or != 0);
                 if (rc) return rc;
                 if (tag_or && (rc = tie_replay(P, G.off, G.cnt, ks, true))) return rc;
                 vpr_launch_stat ls;
@@ -3517,6 +3561,7 @@ struct Exec {
         phase(5);
         lapx("done");
         HIPCHK(h, hipGetLastError());
+        if (!kept_plans.empty()) { const int rk = fetch_strip_plans(); if (rk) return rk; }
         (void)need_err_check;      // (an alignment neither the strips nor one workgroup can take carries VPR_ST_ERR_LIMIT: k_strip_plan)
         float ms = 0;
         (void)hipEventElapsedTime(&ms, t0, t1);
@@ -3661,6 +3706,7 @@ int vpr_execute(vpr_handle *h) {
     dist_free(h);           // distance results of an earlier execute are no longer this execute's
     for (auto &b : h->exec_blks) b.used = false;
     for (auto &b : h->exec_pins) b.used = false;
+    h->strip_recs.clear(); h->strip_lohi.clear();
     h->hs = vpr_handle::HostStat();
     Exec x(h);
     const int rc = x.run();

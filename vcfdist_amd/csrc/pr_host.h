@@ -423,6 +423,11 @@ struct vpr_handle {
     int32_t *d_ed_scratch = nullptr; size_t ed_scratch_ints = 0;
     int64_t ed_max_len = -1;                               // longest ref / truth string of the batch (-1: not looked at yet)
     std::vector<EvPair> events;
+    // VPR_CFG_KEEP_STRIP_PLAN: what k_strip_plan decided in every strip_plan call of the last execute, one record per (call,
+    // alignment) in call order; lohi: {lo_q, lo_r, hi_q, hi_r} of the record's strips from strip_off (vpr_strip_plan_record)
+    struct StripPlanRec { int32_t sc, aln, from_window, tie_round, call, ok, n_strips; int64_t strip_off; };
+    std::vector<StripPlanRec> strip_recs;
+    std::vector<int32_t> strip_lohi;
     std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;   // timing events, reused by every execute
     std::vector<hipStream_t> pad_streams;                  // (diagnostic, VPR_STREAM_PAD)
     int zl_lds_bytes = 0;                // (diagnostic, VPR_ZL_LDS_KB) LDS the zero level's waves ask for and never touch: caps how many of them a compute unit holds

@@ -19,6 +19,21 @@ int vpr_get_launch_stats(const vpr_handle *h, vpr_launch_stat *out, int32_t cap)
     return n;
 }
 
+int vpr_strip_plan_count(const vpr_handle *h) {
+    if (!h) return VPR_ERR_ARG;
+    return int(h->strip_recs.size());
+}
+
+int vpr_strip_plan_record(const vpr_handle *h, int32_t k, vpr_strip_plan_rec *rec, int32_t *lohi, int32_t cap) {
+    if (!h || !rec || k < 0 || size_t(k) >= h->strip_recs.size()) return VPR_ERR_ARG;
+    const vpr_handle::StripPlanRec &R = h->strip_recs[size_t(k)];
+    rec->sc = R.sc; rec->aln = R.aln; rec->from_window = R.from_window; rec->tie_round = R.tie_round; rec->call = R.call;
+    rec->ok = R.ok; rec->n_strips = R.n_strips;
+    for (int32_t j = 0; lohi && j < R.n_strips && j < cap; j++)
+        for (int w = 0; w < 4; w++) lohi[4 * j + w] = h->strip_lohi[size_t(R.strip_off + j) * 4 + size_t(w)];
+    return VPR_OK;
+}
+
 int vpr_get_timing(const vpr_handle *h, vpr_timing *t) {
     if (!h || !t) return VPR_ERR_ARG;
     *t = h->timing;
