@@ -3,6 +3,7 @@ three small contigs of tests/cli_paths_cases.py: a contig only the truth VCF has
 superclusters: the context intervals alone), -n, and realignment with distance clustering.  Both drivers write the same bytes."""
 import os
 import re
+import socket
 import subprocess
 import sys
 
@@ -21,11 +22,15 @@ pytestmark = pytest.mark.gpu
 REPLICATES = 4
 
 
+def every_option(w):
+    return ["-d", "--stratify", w["list"], "--stratify-repeats", "--stratify-long-repeats", "--stratify-context", "--stratify-variants",
+            "--bootstrap", str(REPLICATES), "--classify-errors", "--classify-matches", "--cut-classes"]
+
+
 def test_every_option_on_three_contigs(tmp_path):
     w = PC.write(tmp_path)
     cli, py = [os.path.join(ROOT, "vcfdist_amd", "lib", "vcfdist_gpu")], [sys.executable, "-m", "vcfdist_amd"]
-    every = ["-d", "--stratify", w["list"], "--stratify-repeats", "--stratify-long-repeats", "--stratify-context", "--stratify-variants",
-             "--bootstrap", str(REPLICATES), "--classify-errors", "--classify-matches", "--cut-classes"]
+    every = every_option(w)
     runs = {}
     for name, cmd, extra in (("c", cli, every), ("py", py, every), ("c-n", cli, every + ["-n"]), ("c-r", cli, ["-rq", "-rt", "-c", "gap", "50"])):
         pre = str(tmp_path / name) + "/"
@@ -85,3 +90,46 @@ def test_every_option_on_three_contigs(tmp_path):
     assert len(hom_het) == 2
     assert sum(int(r[8]) for r in hom_het) == PC.hap_variants(PC.CHR_A, True)
     assert sum(int(r[9]) for r in hom_het) == PC.hap_variants(PC.CHR_A, False) + PC.hap_variants(PC.CHR_B, False)
+
+
+@pytest.fixture(scope="module")
+def one_rank(tmp_path_factory):
+    """the three contigs and the Python driver's one-rank run with every option but -d (distance is refused on several ranks)
+    -> (directory, the arguments without the prefix, the environment, the one-rank run's stdout)"""
+    tmp = tmp_path_factory.mktemp("cli_paths_ranks")
+    w = PC.write(tmp)
+    base = w["inputs"] + every_option(w)[1:]
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), VCFDIST_ONE_GPU="1")
+    (tmp / "one").mkdir()
+    r = subprocess.run(["timeout", "-k", "10", "120", sys.executable, "-m", "vcfdist_amd"] + base + ["-p", str(tmp / "one") + "/"],
+                       capture_output=True, text=True, env=env, cwd=ROOT, timeout=150)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return tmp, base, env, r.stdout
+
+
+@pytest.mark.parametrize("how", ["superclusters", "contigs"])
+def test_two_ranks_every_option(one_rank, how):
+    """every section of the vector the ranks sum at once (strata, variant members, replicates, both label passes and their cuts),
+    with a contig of which a rank's share is empty: the files and the summary are the one-rank run's"""
+    tmp, base, env, summary = one_rank
+    out = tmp / how
+    out.mkdir()
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    # (the child runs under its own time limit: a rank that hangs in a collective is ended, not waited for)
+    r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
+                        "--master-addr", "127.0.0.1", "--master-port", str(port), "-m", "vcfdist_amd"] + base +
+                       ["-p", str(out) + "/", "--shard", how], capture_output=True, text=True, env=env, cwd=ROOT, timeout=330)
+    assert r.returncode == 0, r.stderr[-2000:]
+    files = sorted(os.listdir(tmp / "one"))
+    assert files == sorted(os.listdir(out)) and len(files) > 25, (files, sorted(os.listdir(out)))
+    for f in files:
+        assert _without_command(str(tmp / "one" / f)) == _without_command(str(out / f)), f
+    # stdout ends with the summary, and in front of it stands nothing but what gloo announces there when the group comes up, long
+    # before: "[Gloo] Rank 0 is connected to 1 peer ranks. Expected number of connected peer ranks is : 1" once per rank, each written
+    # in pieces that the two ranks' lines interleave -- so the head is to consist of that line's words, numbers and blanks alone
+    assert r.stdout.endswith(summary) and "PRECISION-RECALL SUMMARY" in summary
+    head = r.stdout[:len(r.stdout) - len(summary)]
+    words = r"\[Gloo\]|Rank|is|connected|to|peer|ranks\.|Expected|number|of|ranks|:|[0-9]+|\s+"
+    assert re.sub(words, "", head) == "", r.stdout[:400]

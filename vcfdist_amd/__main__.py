@@ -34,7 +34,9 @@ every TP of either callset gets the first match kind that applies (include/vcfdi
 comparison finds --, shifted, regrouped, partial), from the resident sync groups on the GPU: match-kinds.tsv and
 match-kinds-summary.tsv; works under several ranks in both --shard modes."""
 import argparse
+import os
 import sys
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -114,21 +116,22 @@ def print_warnings(name, aln_status, strict=False):
     return len(bad_sc)
 
 
+def cluster_hap(s, seq, args, device):
+    """a hap's columns as a K.HapSeq, and its clusters as the run clusters: biWFA on the GPU, or by gap / size"""
+    h = K.HapSeq.__new__(K.HapSeq)
+    K.Hap.__init__(h, s["pos"], s["rlen"], s["type"], s["ref_len"], s["alt_len"])
+    h.ref_off, h.alt_off, h.pool = s["ref_off"], s["alt_off"], s["pool"]
+    if args.cluster == "biwfa":
+        return h, K.wfa_cluster(h, bytes(seq), sub=args.sub, open=args.open, extend=args.extend, max_cluster_itrs=args.max_iterations,
+                                reach_min_gap=args.reach_min_gap, device=device)[0]
+    return h, K.simple_cluster(h, 1 if args.cluster == "size" else 0, args.cluster_gap, args.reach_min_gap)
+
+
 def prepare_contig(name, seq, slots, args, device=0):
     """everything in front of the precision/recall path for one contig: clustering, superclustering and the host
     marshalling (generate_ptrs_strs).  A contig the library cannot marshal (vpr_batch_from_variants, include/vcfdist_pr.h)
     raises here, before any contig has been evaluated."""
-    haps = []
-    for s in slots:
-        h = K.HapSeq.__new__(K.HapSeq)
-        K.Hap.__init__(h, s["pos"], s["rlen"], s["type"], s["ref_len"], s["alt_len"])
-        h.ref_off, h.alt_off, h.pool = s["ref_off"], s["alt_off"], s["pool"]
-        haps.append(h)
-    if args.cluster == "biwfa":
-        cl = [K.wfa_cluster(h, bytes(seq), sub=args.sub, open=args.open, extend=args.extend, max_cluster_itrs=args.max_iterations,
-                            reach_min_gap=args.reach_min_gap, device=device)[0] for h in haps]
-    else:
-        cl = [K.simple_cluster(h, 1 if args.cluster == "size" else 0, args.cluster_gap, args.reach_min_gap) for h in haps]
+    haps, cl = map(list, zip(*(cluster_hap(s, seq, args, device) for s in slots)))
     sc = K.supercluster(haps, cl, args.max_supercluster_size)
     batch = None
     if sc.n:
@@ -140,76 +143,175 @@ def prepare_contig(name, seq, slots, args, device=0):
     return dict(name=name, haps=haps, cl=cl, sc=sc, batch=batch, slots=slots, variants=v if sc.n else None)
 
 
-def stratify_contig(pr, prep, strat, args, pb, part_idx=None):
-    """--stratify: the contig's membership words on the device (every hap-variant against every stratum), then the counters of the
-    executed batch cut by them, added to strat['counts'].  part_idx: this rank holds the superclusters part_idx of the contig -- the
+# The families of default strata, in the order of their strata behind the list's: their option, their word in the messages and their
+# defaults; the genome-wide k-mer families (include/vcfdist_repeats.h, include/vcfdist_longrepeats.h) also name api.PrecisionRecall's
+# methods for their pass and report's writer of their BED
+FAMILIES = (
+    dict(option="--stratify-repeats", word="repeat", defaults=api.repeats_default, intervals="repeat_intervals",
+         download="download_repeat_intervals", stats_call="repeat_stats", timing="repeat_timing", write="write_repeat_bed"),
+    dict(option="--stratify-long-repeats", word="long repeat", defaults=api.longrepeats_default, intervals="longrepeat_intervals",
+         download="download_longrepeat_intervals", stats_call="longrepeat_stats", timing="longrepeat_timing", write="write_long_repeat_bed"),
+    dict(option="--stratify-context", word="sequence-context", defaults=api.context_default),
+    dict(option="--stratify-variants", word="variant", defaults=api.varstrata_default),
+)
+
+
+def option_on(args, option):
+    return getattr(args, option[2:].replace("-", "_"))
+
+
+def stratifying(args):
+    return bool(args.stratify) or any(option_on(args, row["option"]) for row in FAMILIES)
+
+
+@dataclass
+class Family:
+    """a row of FAMILIES in a StrataPlan, and what the run makes of it"""
+    option: str; word: str; defaults: object
+    intervals: str = None; download: str = None; stats_call: str = None; timing: str = None; write: str = None
+    specs: object = None                            # the strata's parameters; None: the option is off
+    names: list = field(default_factory=list)
+    rows: dict = field(default_factory=dict)        # k-mer families, context: per contig, every stratum's intervals
+    stats: object = None                            # k-mer families: the valid and the repeated starts of every stratum
+    ms: float = 0.0                                 # on the device
+
+
+@dataclass
+class StrataPlan:
+    """which strata, in which order (StrataPlan in main.cpp): every stratum's name in table order, the list's BEDs, the families"""
+    names: list = field(default_factory=list)
+    beds: list = field(default_factory=list)
+    families: list = field(default_factory=lambda: [Family(**row) for row in FAMILIES])
+    kmer = property(lambda self: [fam for fam in self.families[:2] if fam.specs])       # the genome-wide families that are on
+    ctx = property(lambda self: self.families[2])
+    vs = property(lambda self: self.families[3])
+
+
+@dataclass
+class LabelPass:
+    """--classify-errors / --classify-matches (LabelPass in main.cpp): the names of api.PrecisionRecall's methods and of report's
+    writers (looked up when they are called), the pass's stderr line, and its sums over the contigs"""
+    noun: str; labels: int; label: str; timing: str; cut_strata: str; cut_boot: str; cut_timing: str
+    write: str; write_strata: str; write_boot: str; line: object
+    extra: tuple = ()                               # arguments of `label` behind the phasing
+    counts: object = None; strata: object = None; boot: object = None      # [2][4][labels][nq]; --cut-classes: per stratum, per replicate
+    ms: float = 0.0; cut_ms: float = 0.0
+
+
+def errclass_line(p):
+    return (f"[vcfdist_amd] error classes: window {p.extra[0]}, {int(p.counts[0, 3, :, 0].sum())} query FP and "
+            f"{int(p.counts[1, 3, :, 0].sum())} truth FN classified, {p.ms:.3f} ms on the device")
+
+
+def matchkind_line(p):
+    qk, tk = p.counts[0, 3, :, 0], p.counts[1, 3, :, 0]
+    return (f"[vcfdist_amd] match kinds: query TP {int(qk[0])} exact, {int(qk[1])} shifted, {int(qk[2])} regrouped, {int(qk[3])} partial; "
+            f"truth TP {int(tk[0])} exact, {int(tk[1])} shifted, {int(tk[2])} regrouped, {int(tk[3])} partial, {p.ms:.3f} ms on the device")
+
+
+class Totals:
+    """the sums over the contigs (Totals in main.cpp): counts[2][4][3][nq], with strata the stratified ones, the hap-variants seen
+    and in no stratum and the variant strata's members per callset, with --bootstrap the replicates' (and per stratum), the label
+    passes with their cuts.  tally lists the int64 arrays that are summed over the ranks, in the order of the vector (pack, unpack):
+    every sum is added in place, so the list made here stays the owners'."""
+    def __init__(self, args, plan):
+        nq = args.max_qual - args.min_qual + 1
+        n_strata, n_rep = len(plan.names) if plan else 0, args.bootstrap
+        zeros = lambda *shape: np.zeros(shape, np.int64)
+        self.total = zeros(2, 4, 3, nq)
+        self.strat = zeros(n_strata, 2, 4, 3, nq) if plan else None
+        self.seen_none = zeros(2) if plan else None
+        self.vs_members = zeros(2, len(plan.vs.specs or ())) if plan else None
+        self.boot = zeros(n_rep, 2, 4, 3, nq) if n_rep else None
+        self.boot_strat = zeros(n_strata, n_rep, 2, 4, 3, nq) if n_rep and plan else None
+        self.boot_ms = 0.0
+        self.passes = []        # in the order of their counts in the vector, of their files and of their stderr lines
+        if args.classify_errors:
+            window = A.EC_DEFAULT_WINDOW if args.error_window is None else args.error_window
+            self.passes.append(LabelPass("error classes", A.EC_CLASSES, "errclass", "errclass_timing", "errclass_strata", "errclass_boot",
+                                         "errclass_cut_timing", "write_error_classes", "write_error_classes_stratified",
+                                         "write_error_classes_bootstrap", errclass_line, (window,)))
+        if args.classify_matches:
+            self.passes.append(LabelPass("match kinds", A.MK_KINDS, "matchkind", "matchkind_timing", "matchkind_strata", "matchkind_boot",
+                                         "matchkind_cut_timing", "write_match_kinds", "write_match_kinds_stratified",
+                                         "write_match_kinds_bootstrap", matchkind_line))
+        for p in self.passes:
+            p.counts = zeros(2, 4, p.labels, nq)
+            if args.cut_classes:
+                p.strata = zeros(n_strata, 2, 4, p.labels, nq) if plan else None
+                p.boot = zeros(n_rep, 2, 4, p.labels, nq) if n_rep else None
+        tally = [self.total, self.strat, self.seen_none, self.vs_members, self.boot, self.boot_strat] + [p.counts for p in self.passes]
+        self.tally = [a for a in tally + [cut for p in self.passes for cut in (p.strata, p.boot)] if a is not None]
+
+
+def pack(arrays):
+    """the vector the ranks sum: the arrays of a tally one behind the other"""
+    return np.concatenate([a.ravel() for a in arrays])
+
+
+def unpack(arrays, vector):
+    """the summed vector back into the arrays it was packed from"""
+    at = 0
+    for a in arrays:
+        a[...] = vector[at:at + a.size].reshape(a.shape)
+        at += a.size
+
+
+def stratify_contig(pr, prep, plan, tot, args, pb, part_idx=None):
+    """--stratify*: the contig's membership words on the device (every hap-variant against every stratum), then the counters of the
+    executed batch cut by them, added to tot.strat.  part_idx: this rank holds the superclusters part_idx of the contig -- the
     words are computed for the whole contig and the rank keeps its share's."""
     from . import shard
     name, whole = prep["name"], prep["batch"]
-    n_strata = len(strat["names"])
+    n_strata = len(plan.names)
     # the interval table: the rows of --stratify's BEDs, with --stratify-repeats and --stratify-long-repeats the contig's rows of the
     # genome-wide passes behind them
     table = None
-    if strat["beds"] or strat["rep"] or strat["lrep"]:
-        table = A.Strata([[b.intervals(name)] for b in strat["beds"]] +
-                         [[row] for fam in KMER_FAMILIES if strat[fam["key"]] for row in strat[fam["key"] + "_rows"][name]], 1)
-    if strat["ctx"]:        # --stratify-context: the context intervals are built on the device and go to the same mask kernel
-        pr.context_masks(prep["variants"], strat["ctx"], table)
-        keep_context_intervals(pr, strat, name)
+    if plan.beds or plan.kmer:
+        table = A.Strata([[b.intervals(name)] for b in plan.beds] + [[row] for fam in plan.kmer for row in fam.rows[name]], 1)
+    if plan.ctx.specs:      # --stratify-context: the context intervals are built on the device and go to the same mask kernel
+        pr.context_masks(prep["variants"], plan.ctx.specs, table)
+        keep_context_intervals(pr, plan.ctx, name)
     elif table is not None:
         pr.strata_masks(prep["variants"], table)
-    n_pre = n_strata - len(strat["vs"] or ())
-    if strat["vs"]:         # --stratify-variants: the bits made from the variant tables follow in the same words
-        pr.varstrata_masks(prep["variants"], strat["vs"], append=n_pre > 0)
-        strat["vs_ms"] += pr.varstrata_timing()
+    n_pre = n_strata - len(plan.vs.specs or ())
+    if plan.vs.specs:       # --stratify-variants: the bits made from the variant tables follow in the same words
+        pr.varstrata_masks(prep["variants"], plan.vs.specs, append=n_pre > 0)
+        plan.vs.ms += pr.varstrata_timing()
     words = pr.download_strata_masks()
     if part_idx is not None:
         words = [np.stack([shard.subset_per_variant(w, whole.var_off[s], part_idx) for w in words[s]]) for s in range(4)]
         pr.upload_strata_masks(n_strata, words)
-    strat["counts"] += S.pr_counts_strata(pr, None, pb, args.min_qual, args.max_qual)     # (the classes are resident: pr_counts)
+    tot.strat += S.pr_counts_strata(pr, None, pb, args.min_qual, args.max_qual)     # (the classes are resident: pr_counts)
     for w in words:
-        strat["vars"] += w.shape[1]
-        strat["none"] += int((np.bitwise_or.reduce(w, axis=0) == 0).sum())
+        tot.seen_none += (w.shape[1], int((np.bitwise_or.reduce(w, axis=0) == 0).sum()))
     for k in range(n_pre, n_strata):      # variant-strata.tsv: the members of every variant stratum, per callset
         for s, w in enumerate(words):
-            strat["vs_members"][s >> 1, k - n_pre] += int(((w[k >> 6] >> np.uint64(k & 63)) & np.uint64(1)).sum())
+            tot.vs_members[s >> 1, k - n_pre] += int(((w[k >> 6] >> np.uint64(k & 63)) & np.uint64(1)).sum())
 
 
-def keep_context_intervals(pr, strat, name):
+def keep_context_intervals(pr, ctx, name):
     """the context intervals of the contig the last context_masks saw, for context-strata.bed and the stderr line"""
-    strat["intervals"][name] = [row[0] for row in pr.download_context_intervals()]
-    strat["ctx_ms"][name] = pr.context_timing()[0]
+    ctx.rows[name] = [row[0] for row in pr.download_context_intervals()]
+    ctx.ms += pr.context_timing()[0]
 
 
-# The families of genome-wide k-mer strata, in the order of their strata (include/vcfdist_repeats.h, include/vcfdist_longrepeats.h): the
-# prefix of their keys in strat, their option and their word in the messages, the names of api.PrecisionRecall's methods, the defaults
-# and the writer of their BED
-KMER_FAMILIES = (
-    dict(key="rep", option="--stratify-repeats", word="repeat", intervals="repeat_intervals", download="download_repeat_intervals",
-         stats="repeat_stats", timing="repeat_timing", defaults=api.repeats_default, write=RP.write_repeat_bed),
-    dict(key="lrep", option="--stratify-long-repeats", word="long repeat", intervals="longrepeat_intervals",
-         download="download_longrepeat_intervals", stats="longrepeat_stats", timing="longrepeat_timing", defaults=api.longrepeats_default,
-         write=RP.write_long_repeat_bed),
-)
-
-
-def kmer_strata(fam, fasta, strat, args, device=0):
+def kmer_strata(fam, fasta, args, device=0):
     """--stratify-repeats, --stratify-long-repeats: the family's genome-wide pass over all contigs of the FASTA, those without a
     variant included, on a handle of its own that is gone before the evaluation starts.  Every rank computes the same arrays."""
-    key = fam["key"]
     cfg = A.default_config(device=device)
     cfg.max_qual = float(args.max_qual)
     pr = api.PrecisionRecall(cfg)
     names = list(fasta)
-    getattr(pr, fam["intervals"])([fasta[c] for c in names], strat[key])
-    rows = getattr(pr, fam["download"])()
-    strat[key + "_rows"] = {c: [rows[k][j] for k in range(len(strat[key]))] for j, c in enumerate(names)}
-    strat[key + "_stats"] = getattr(pr, fam["stats"])()
-    strat[key + "_ms"] = sum(getattr(pr, fam["timing"])())
+    getattr(pr, fam.intervals)([fasta[c] for c in names], fam.specs)
+    rows = getattr(pr, fam.download)()
+    fam.rows = {c: [rows[k][j] for k in range(len(fam.specs))] for j, c in enumerate(names)}
+    fam.stats = getattr(pr, fam.stats_call)()
+    fam.ms = sum(getattr(pr, fam.timing)())
     pr.close()
 
 
-def context_only(name, seq, strat, args, device=0):
+def context_only(name, seq, ctx, args, device=0):
     """--stratify-context for a contig (or a rank's share of one) without a supercluster: the intervals alone, for no variant"""
     cfg = A.default_config(device=device)
     cfg.max_qual = float(args.max_qual)
@@ -218,95 +320,119 @@ def context_only(name, seq, strat, args, device=0):
     seq = np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else np.asarray(seq, np.uint8)
     v = A.Variants(np.array([0, len(seq)], np.int64), seq, z32, z32, z32, [z64] * 4, [z32] * 4, [z8] * 4, [np.zeros(0, np.float32)] * 4,
                    [np.zeros(0, np.int64)] * 4, [z32] * 4, [np.zeros(0, np.int64)] * 4, [z32] * 4, [z8] * 4)
-    pr.context_masks(v, strat["ctx"])
-    keep_context_intervals(pr, strat, name)
+    pr.context_masks(v, ctx.specs)
+    keep_context_intervals(pr, ctx, name)
     pr.close()
 
 
-def bootstrap_contig(pr, boot, strat, args, pb, keys):
-    """--bootstrap: the replicate counters of the executed batch, added to boot['counts']; with --stratify one pass per stratum
-    of the resident membership words, added to boot['strat']"""
-    kw = dict(n_rep=boot["n"], seed=boot["seed"], min_qual=args.min_qual, max_qual=args.max_qual)
-    boot["counts"] += pr.pr_counts_boot(None, pb, keys, **kw)        # (the classes are resident: pr_counts)
-    boot["ms"] += pr.boot_info()[1]
-    if strat is not None:
-        for k in range(len(strat["names"])):
-            boot["strat"][k] += pr.pr_counts_boot(None, pb, keys, stratum=k, **kw)
-            boot["ms"] += pr.boot_info()[1]
+def bootstrap_contig(pr, tot, plan, args, pb, keys):
+    """--bootstrap: the replicate counters of the executed batch, added to tot.boot; with strata one pass per stratum of the
+    resident membership words, added to tot.boot_strat"""
+    kw = dict(n_rep=args.bootstrap, seed=args.bootstrap_seed, min_qual=args.min_qual, max_qual=args.max_qual)
+    tot.boot += pr.pr_counts_boot(None, pb, keys, **kw)        # (the classes are resident: pr_counts)
+    tot.boot_ms += pr.boot_info()[1]
+    if plan is not None:
+        for k in range(len(plan.names)):
+            tot.boot_strat[k] += pr.pr_counts_boot(None, pb, keys, stratum=k, **kw)
+            tot.boot_ms += pr.boot_info()[1]
 
 
 def label_contig(pr, variants, passes, args, pb):
-    """--classify-errors / --classify-matches: the labels of the executed batch by each of `passes` (main's list), added to its
-    counts (the variant classes are resident: pr_counts)"""
+    """--classify-errors / --classify-matches: the labels of the executed batch by each of `passes`, added to its counts (the variant
+    classes are resident: pr_counts)"""
     for p in passes:
-        p["counts"] += getattr(pr, p["call"])(variants, None, pb, *p["extra"], args.min_qual, args.max_qual)
-        p["ms"] += getattr(pr, p["call"] + "_timing")()
+        p.counts += getattr(pr, p.label)(variants, None, pb, *p.extra, args.min_qual, args.max_qual)
+        p.ms += getattr(pr, p.timing)()
 
 
-def cut_contig(pr, passes, strat, boot, args, keys):
+def cut_contig(pr, passes, plan, args, keys):
     """--cut-classes: the label counts of every pass cut by the strata and resampled (include/vcfdist_labelcut.h), behind
     stratify_contig and bootstrap_contig: the label bytes and the share's membership words are both resident.  Added to the
-    pass's 'strata' / 'boot'."""
+    pass's strata / boot."""
     for p in passes:
-        if strat is not None:
-            p["strata"] += getattr(pr, p["call"] + "_strata")(args.min_qual, args.max_qual)
-            p["cut_ms"] += getattr(pr, p["call"] + "_cut_timing")()[0]
-        if boot is not None:
-            p["boot"] += getattr(pr, p["call"] + "_boot")(keys, boot["n"], boot["seed"], args.min_qual, args.max_qual)
-            p["cut_ms"] += getattr(pr, p["call"] + "_cut_timing")()[1]
+        if plan is not None:
+            p.strata += getattr(pr, p.cut_strata)(args.min_qual, args.max_qual)
+            p.cut_ms += getattr(pr, p.cut_timing)()[0]
+        if args.bootstrap:
+            p.boot += getattr(pr, p.cut_boot)(keys, args.bootstrap, args.bootstrap_seed, args.min_qual, args.max_qual)
+            p.cut_ms += getattr(pr, p.cut_timing)()[1]
 
 
-def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None, boot=None, ordinal=0, passes=()):
-    """the precision/recall path on the GPU, phasing and counters for a prepared contig.  -> int64 counters [2][4][3][nq],
-    n_sc, and what the writers need: (clusters after splitting, superclusters, results, phase sets, pb_phase, switches, flips).
-    part = (rank, world, collective device): this rank evaluates its share of the contig's SUPERCLUSTERS -- dealt by the
+@dataclass
+class Ranks:
+    """this process among the run's: under torch.distributed.run one process per GPU; dist is torch.distributed with its group up, or
+    None on one rank; cdev is where the collectives' tensors live (None: the host, gloo); by_sc: --shard superclusters on several ranks"""
+    rank: int; world: int; device: int; dist: object = None; cdev: object = None; by_sc: bool = False
+
+
+def count_contig(pr, prep, args, plan, tot, cls, pb, variants, keys, idx=None):
+    """the one counting sequence behind an executed batch: counters, labels, strata, replicates, cuts, each reading what the one
+    before left resident.  idx: the superclusters of the contig the handle holds (None: all of them); cls, pb, variants and keys
+    are the caller's for that set.  -> counts[2][4][3][nq], everything else added to tot"""
+    counts = S.pr_counts(pr, cls, pb, args.min_qual, args.max_qual)
+    label_contig(pr, variants, tot.passes, args, pb)
+    if plan is not None:
+        stratify_contig(pr, prep, plan, tot, args, pb, part_idx=idx)
+    if args.bootstrap:
+        bootstrap_contig(pr, tot, plan, args, pb, keys)
+    if args.cut_classes:
+        cut_contig(pr, tot.passes, plan, args, keys)
+    return counts
+
+
+def distance_contig(pr, prep, args, dist_sets):
+    """-d: edits_wrapper behind the precision/recall path (main.cpp:223-238), from what it left on the device"""
+    d = pr.distance(prep["variants"], eval_sub=args.eval_sub, eval_open=args.eval_open, eval_extend=args.eval_extend,
+                    min_qual=args.min_qual, max_qual=args.max_qual)
+    info = d["info"]
+    if info.n_limit or info.n_error:
+        print(f"[WARN  vcfdist_amd] contig '{prep['name']}': {info.n_limit} distance alignment(s) beyond the device's memory plan and "
+              f"{info.n_error} that failed: NOT EVALUATED -- left out of the distance metrics", file=sys.stderr)
+    print(f"[vcfdist_amd] {prep['name']}: {info.n_jobs} distance alignments, {info.n_edits} edits, edit distance {int(d['qual_dists'].min())}",
+          file=sys.stderr)
+    dist_sets.append((prep["name"], d))
+
+
+NOT_EVALUATED = np.uint32(A.ST_ERR_LIMIT | A.ST_ERR_NO_PTR | A.ST_ERR_UNFINISHED)
+
+
+def mask_unevaluated(r):
+    """a supercluster with an alignment the GPU path did not evaluate (VPR_ST_ERR_*): its phase distances come from alignments
+    that were cut short -- it takes no side in the contig's phasing (print_warnings reports it)"""
+    bad = np.unique(np.nonzero(r.aln_status & NOT_EVALUATED)[0] // 4)
+    if len(bad):
+        r.sc_phase[bad] = A.PHASE_NONE
+
+
+def evaluate_contig(prep, args, ranks, plan, tot, dist_sets=None, ordinal=0):
+    """the precision/recall path on the GPU, phasing and counters for a prepared contig.  -> int64 counters [2][4][3][nq] and what
+    the writers need: (clusters after splitting, superclusters, results, phase sets, pb_phase, switches, flips).
+    With ranks.by_sc this rank evaluates its share of the contig's SUPERCLUSTERS -- dealt by the
     reference's own size estimate (shard.deal: LPT + snake, as precision_recall_threads_wrapper spreads superclusters over its
     threads, dist.cpp:1670-1726) -- the per-supercluster phasing is all-gathered (the contig's phasing needs all of it and
     every rank then runs it), the counters returned are this rank's share (the caller all-reduces the sum over the contigs),
     and the result records are gathered (every rank gets the contig's full tables; rank 0 writes them)."""
     name, haps, cl, sc, slots = prep["name"], prep["haps"], prep["cl"], prep["sc"], prep["slots"]
-    nq = args.max_qual - args.min_qual + 1
+    counts = np.zeros_like(tot.total)
     if sc.n == 0:
         z = np.zeros(0, np.int32)
-        return np.zeros((2, 4, 3, nq), np.int64), 0, (sc.clusters, sc, A.Results(0, [len(h.pos) for h in haps]), z, z, z, z)
-    cfg = A.default_config(device=device)
+        return counts, (sc.clusters, sc, A.Results(0, [len(h.pos) for h in haps]), z, z, z, z)
+    cfg = A.default_config(device=ranks.device)
     cfg.max_qual = float(args.max_qual); cfg.credit_threshold = args.credit_threshold; cfg.phase_threshold = args.phase_threshold
     pr = api.PrecisionRecall(cfg)
     phase_sets = transfer_phase_sets(slots, cl, sc)
     cls = [S.var_class(h.type, h.ref_len, h.alt_len, args.sv_threshold) for h in haps]
-    def mask_unevaluated(r):
-        """a supercluster with an alignment the GPU path did not evaluate (VPR_ST_ERR_*): its phase distances come from alignments
-        that were cut short -- it takes no side in the contig's phasing (print_warnings reports it)"""
-        bad = np.unique(np.nonzero(r.aln_status & np.uint32(A.ST_ERR_LIMIT | A.ST_ERR_NO_PTR | A.ST_ERR_UNFINISHED))[0] // 4)
-        if len(bad):
-            r.sc_phase[bad] = A.PHASE_NONE
-    if part is None:
+    if not ranks.by_sc:
         res = pr.run(prep["batch"])
-        if dist_sets is not None:      # -d: edits_wrapper behind the precision/recall path (main.cpp:223-238), from what it left on the device
-            d = pr.distance(prep["variants"], eval_sub=args.eval_sub, eval_open=args.eval_open, eval_extend=args.eval_extend,
-                            min_qual=args.min_qual, max_qual=args.max_qual)
-            info = d["info"]
-            if info.n_limit or info.n_error:
-                print(f"[WARN  vcfdist_amd] contig '{name}': {info.n_limit} distance alignment(s) beyond the device's memory plan and "
-                      f"{info.n_error} that failed: NOT EVALUATED -- left out of the distance metrics", file=sys.stderr)
-            print(f"[vcfdist_amd] {name}: {info.n_jobs} distance alignments, {info.n_edits} edits, edit distance {int(d['qual_dists'].min())}",
-                  file=sys.stderr)
-            dist_sets.append((name, d))
+        if dist_sets is not None:
+            distance_contig(pr, prep, args, dist_sets)
         mask_unevaluated(res)
         pb, sw, fl = S.phase(res.sc_phase, phase_sets)
-        counts = S.pr_counts(pr, cls, pb, args.min_qual, args.max_qual)
-        label_contig(pr, prep["variants"], passes, args, pb)
-        if strat is not None:
-            stratify_contig(pr, prep, strat, args, pb)
-        if boot is not None:
-            bootstrap_contig(pr, boot, strat, args, pb, A.boot_keys(ordinal, np.arange(sc.n)))
-        if args.cut_classes:
-            cut_contig(pr, passes, strat, boot, args, A.boot_keys(ordinal, np.arange(sc.n)))
+        counts = count_contig(pr, prep, args, plan, tot, cls, pb, prep["variants"], A.boot_keys(ordinal, np.arange(sc.n)))
     else:
         from . import shard
-        rank, world, cdev = part
         whole = prep["batch"]
-        idx = shard.deal(shard.estimate_cells(whole), world)[rank]
+        idx = shard.deal(shard.estimate_cells(whole), ranks.world)[ranks.rank]
         mine = whole.subset(idx)
         # (every rank enters the collectives below: a rank whose share fails tells the others first, and all end together --
         # a lone SystemExit would leave the rest waiting in all_gather for ever)
@@ -315,35 +441,26 @@ def evaluate_contig(prep, args, device=0, part=None, dist_sets=None, strat=None,
             local = pr.run(mine) if len(idx) else A.Results(0, [0, 0, 0, 0])
         except Exception as e:      # noqa: BLE001 -- whatever it is (VprError, MemoryError, OSError ...), the other ranks must hear of it
             err, local = e, None
-        if shard.any_rank(err is not None, device=cdev):
+        if shard.any_rank(err is not None, device=ranks.cdev):
             raise api.VprError(str(err) if err is not None else "another rank's share of the contig failed")
         mask_unevaluated(local)
-        sc_phase, _, _ = shard.allgather_phase(local, idx, sc.n, device=cdev)
+        sc_phase, _, _ = shard.allgather_phase(local, idx, sc.n, device=ranks.cdev)
         pb, sw, fl = S.phase(sc_phase, phase_sets)
-        if len(idx):
+        if len(idx):    # (everything is local to the supercluster, sync groups too: the rank labels its share from its share's tables)
             cls_mine = [shard.subset_per_variant(cls[s], whole.var_off[s], idx) for s in range(4)]
-            counts = S.pr_counts(pr, cls_mine, pb[idx], args.min_qual, args.max_qual)
-            if passes:      # (everything is local to the supercluster, sync groups too: the rank labels its share from its share's tables)
-                label_contig(pr, shard.subset_variants(prep["variants"], idx), passes, args, pb[idx])
-            if strat is not None:
-                stratify_contig(pr, prep, strat, args, pb[idx], part_idx=idx)
-            if boot is not None:
-                bootstrap_contig(pr, boot, strat, args, pb[idx], A.boot_keys(ordinal, idx))
-            if args.cut_classes:
-                cut_contig(pr, passes, strat, boot, args, A.boot_keys(ordinal, idx))
-        else:
-            counts = np.zeros((2, 4, 3, nq), np.int64)
-        res = shard.gather_results(local, idx, whole.var_off, device=cdev)
-        if rank != 0:
+            variants = shard.subset_variants(prep["variants"], idx) if tot.passes else None
+            counts = count_contig(pr, prep, args, plan, tot, cls_mine, pb[idx], variants, A.boot_keys(ordinal, idx), idx)
+        res = shard.gather_results(local, idx, whole.var_off, device=ranks.cdev)
+        if ranks.rank != 0:
             # (--strict ends the run on EVERY rank: the gathered status column is the same everywhere, rank 0 prints the report
             # below and the others leave with it instead of waiting in the next contig's collective -- ADVICE r5)
-            if getattr(args, "strict", False) and (res.aln_status & np.uint32(A.ST_ERR_LIMIT | A.ST_ERR_NO_PTR | A.ST_ERR_UNFINISHED)).any():
+            if args.strict and (res.aln_status & NOT_EVALUATED).any():
                 raise SystemExit(1)
-            return counts, sc.n, (sc.clusters, sc, res, phase_sets, pb, sw, fl)
-    print_warnings(name, res.aln_status, strict=getattr(args, "strict", False))
+            return counts, (sc.clusters, sc, res, phase_sets, pb, sw, fl)
+    print_warnings(name, res.aln_status, strict=args.strict)
     print(f"[vcfdist_amd] {name}: {sum(len(h.pos) for h in haps)} hap-variants, {sum(c.n for c in cl)} clusters, {sc.n} superclusters, "
           f"{len(sw)} switch / {len(fl)} flip errors", file=sys.stderr)
-    return counts, sc.n, (sc.clusters, sc, res, phase_sets, pb, sw, fl)
+    return counts, (sc.clusters, sc, res, phase_sets, pb, sw, fl)
 
 
 def check_contigs(q, t, fasta, bed):
@@ -392,14 +509,7 @@ def realign_callset(which, cs, fasta, args, device=0):
         seq = fasta[ctg]
         per = []
         for s in cs["vars"][k]:
-            h = K.HapSeq.__new__(K.HapSeq)
-            K.Hap.__init__(h, s["pos"], s["rlen"], s["type"], s["ref_len"], s["alt_len"])
-            h.ref_off, h.alt_off, h.pool = s["ref_off"], s["alt_off"], s["pool"]
-            if args.cluster == "biwfa":
-                cl = K.wfa_cluster(h, bytes(seq), sub=args.sub, open=args.open, extend=args.extend, max_cluster_itrs=args.max_iterations,
-                                   reach_min_gap=args.reach_min_gap, device=device)[0]
-            else:
-                cl = K.simple_cluster(h, 1 if args.cluster == "size" else 0, args.cluster_gap, args.reach_min_gap)
+            cl = cluster_hap(s, seq, args, device)[1]
             try:
                 cols, _, info = api.realign(s, cl, seq, sub=args.sub, open=args.open, extend=args.extend, max_qual=args.max_qual, device=device)
             except api.VprError as e:
@@ -419,50 +529,31 @@ def realign_callset(which, cs, fasta, args, device=0):
     return dict(cs, vars=out)
 
 
-def eval_penalty(what):
-    """an evaluation penalty as globals.cpp:274-335 reads it: an integer, non-negative"""
+def integer(lo, hi, invalid, outside):
+    """an option's integer within lo..hi (hi None: unbounded), read with the messages given; `invalid` is formatted with the text"""
     def parse(v):
         try:
             x = int(v)
         except ValueError:
-            raise argparse.ArgumentTypeError(f"Invalid {what} provided")
-        if x < 0:
-            raise argparse.ArgumentTypeError(f"Must provide non-negative {what}")
+            raise argparse.ArgumentTypeError(invalid.format(v))
+        if x < lo or (hi is not None and x > hi):
+            raise argparse.ArgumentTypeError(outside)
         return x
     return parse
 
 
-def bootstrap_replicates(v):
-    try:
-        n = int(v)
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"Invalid number of bootstrap replicates '{v}'")
-    if not 1 <= n <= A.BOOT_MAX_REPLICATES:
-        raise argparse.ArgumentTypeError(f"Must provide 1 to {A.BOOT_MAX_REPLICATES} bootstrap replicates")
-    return n
+def eval_penalty(what):
+    """an evaluation penalty as globals.cpp:274-335 reads it: an integer, non-negative"""
+    return integer(0, None, f"Invalid {what} provided", f"Must provide non-negative {what}")
 
 
-def bootstrap_seed(v):
-    try:
-        s = int(v)
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"Invalid bootstrap seed '{v}'")
-    if not 0 <= s < 2 ** 64:
-        raise argparse.ArgumentTypeError("Must provide a bootstrap seed of 0 to 2^64 - 1")
-    return s
+bootstrap_replicates = integer(1, A.BOOT_MAX_REPLICATES, "Invalid number of bootstrap replicates '{}'",
+                               f"Must provide 1 to {A.BOOT_MAX_REPLICATES} bootstrap replicates")
+bootstrap_seed = integer(0, 2 ** 64 - 1, "Invalid bootstrap seed '{}'", "Must provide a bootstrap seed of 0 to 2^64 - 1")
+error_window = integer(0, 2 ** 31 - 1, "Invalid error window '{}'", "Must provide an error window of 0 to 2147483647 bases")
 
 
-def error_window(v):
-    try:
-        n = int(v)
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"Invalid error window '{v}'")
-    if not 0 <= n < 2 ** 31:
-        raise argparse.ArgumentTypeError("Must provide an error window of 0 to 2147483647 bases")
-    return n
-
-
-def main(argv=None):
+def argument_parser():
     ap = argparse.ArgumentParser(prog="python -m vcfdist_amd", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("query"); ap.add_argument("truth"); ap.add_argument("fasta")
     ap.add_argument("-b", "--bed")
@@ -532,7 +623,12 @@ def main(argv=None):
     ap.add_argument("--shard", default="superclusters", choices=["superclusters", "contigs"],
                     help="several ranks (torch.distributed.run, one per GPU): deal every contig's superclusters over the ranks "
                          "(default; balanced whatever the contigs' sizes) or whole contigs")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def parse(argv=None):
+    """the arguments, checked against each other: every error an option can be without a file having been opened"""
+    args = argument_parser().parse_args(argv)
     args.cluster_gap = 50
     if args.cluster[0] in ("gap", "size") and len(args.cluster) > 1:
         args.cluster_gap = int(args.cluster[1])
@@ -543,20 +639,22 @@ def main(argv=None):
         raise SystemExit("ERROR: --error-window needs --classify-errors")
     if args.cut_classes and not (args.classify_errors or args.classify_matches):
         raise SystemExit("ERROR: --cut-classes needs --classify-errors or --classify-matches")
-    if args.cut_classes and not (args.stratify or args.stratify_repeats or args.stratify_long_repeats or args.stratify_context or args.stratify_variants or args.bootstrap):
+    if args.cut_classes and not (stratifying(args) or args.bootstrap):
         raise SystemExit("ERROR: --cut-classes needs --stratify, --stratify-context, --stratify-variants or --bootstrap")
-    realigning = args.realign_query or args.realign_truth
-    if realigning and (args.sub < 1 or args.extend < 1):
+    if (args.realign_query or args.realign_truth) and (args.sub < 1 or args.extend < 1):
         raise SystemExit("ERROR: realignment needs a mismatch penalty (-x) and a gap-extension penalty (-e) of at least 1")
-    # one process per GPU under torch.distributed.run: every contig's superclusters are dealt over the ranks (--shard; the
-    # per-supercluster phasing is all-gathered, a contig's phasing needs all of it), the counters are summed with one all-reduce
-    # (RCCL), the result records are gathered, and rank 0 writes the files
-    import os
+    return args
+
+
+def setup_ranks(args):
+    """one process per GPU under torch.distributed.run: every contig's superclusters are dealt over the ranks (--shard; the
+    per-supercluster phasing is all-gathered, a contig's phasing needs all of it), the counters are summed with one all-reduce
+    (RCCL), the result records are gathered, and rank 0 writes the files.  Selects this process's GPU and brings the group up."""
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     if args.distance and world > 1:
         raise SystemExit("ERROR: -d/--distance runs on one rank only (its edit records are not gathered over ranks): "
                          "run it without torch.distributed.run")
-    if realigning and world > 1:
+    if (args.realign_query or args.realign_truth) and world > 1:
         raise SystemExit("ERROR: -rq/-rt realignment runs on one rank only (the realigned callsets are not sharded): "
                          "run it without torch.distributed.run")
     device = args.device if args.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
@@ -567,7 +665,7 @@ def main(argv=None):
         api.lib().vpr_select_device(int(device))
     except api.VprError:
         pass
-    dist = None
+    ranks = Ranks(rank, world, device)
     if world > 1:
         import torch
         import torch.distributed as dist
@@ -576,278 +674,242 @@ def main(argv=None):
         if backend == "nccl":
             torch.cuda.set_device(device)
         dist.init_process_group(backend=backend)
-    strat = None
-    if args.stratify or args.stratify_repeats or args.stratify_long_repeats or args.stratify_context or args.stratify_variants:       # the strata list and every BED it names are read and checked before anything is evaluated
-        names, beds = [], []
-        if args.stratify:
-            try:
-                names, beds = IO.read_strata(args.stratify)
-            except IOError as e:
-                raise SystemExit(f"ERROR: {e}")
-        strat = dict(names=list(names), beds=beds, counts=None, vars=0, none=0, ctx=None, ctx_names=[], intervals={}, ctx_ms={},
-                     vs=None, vs_names=[], vs_members=np.zeros((2, 0), np.int64), vs_ms=0.0, rep=None, rep_names=[], rep_rows={},
-                     lrep=None, lrep_names=[], lrep_rows={})
-        for fam in KMER_FAMILIES:       # the default repeat strata behind the list's, the long ones behind those, in front of the context strata
-            key = fam["key"]
-            if not getattr(args, fam["option"][2:].replace("-", "_")):
-                continue
-            strat[key + "_names"], strat[key] = fam["defaults"]()
-            for n in strat[key + "_names"]:
-                if n in strat["names"]:
-                    raise SystemExit(f"ERROR: strata list '{args.stratify}': duplicate stratum name '{n}' (a {fam['word']} stratum of "
-                                     f"{fam['option']})")
-            strat["names"] += strat[key + "_names"]
-        if args.stratify_context:       # the default sequence-context strata (include/vcfdist_context.h) behind the list's
-            strat["ctx_names"], strat["ctx"] = api.context_default()
-            for n in strat["ctx_names"]:
-                if n in names:
-                    raise SystemExit(f"ERROR: strata list '{args.stratify}': duplicate stratum name '{n}' (a sequence-context stratum of "
-                                     "--stratify-context)")
-            strat["names"] += strat["ctx_names"]
-        if args.stratify_variants:      # the default variant strata (include/vcfdist_varstrata.h) behind the list's and the context strata
-            strat["vs_names"], strat["vs"] = api.varstrata_default()
-            for n in strat["vs_names"]:
-                if n in names:
-                    raise SystemExit(f"ERROR: strata list '{args.stratify}': duplicate stratum name '{n}' (a variant stratum of "
-                                     "--stratify-variants)")
-            strat["names"] += strat["vs_names"]
-            strat["vs_members"] = np.zeros((2, len(strat["vs"])), np.int64)
+        ranks.dist, ranks.cdev, ranks.by_sc = dist, None if backend == "gloo" else f"cuda:{device}", args.shard == "superclusters"
+    return ranks
+
+
+def plan_strata(args):
+    """--stratify*: the strata list and every BED it names, read and checked before any input is opened, and behind the list's strata
+    the defaults of every family that is on.  -> StrataPlan, or None without such an option"""
+    if not stratifying(args):
+        return None
+    plan = StrataPlan()
+    if args.stratify:
+        try:
+            names, plan.beds = IO.read_strata(args.stratify)
+        except IOError as e:
+            raise SystemExit(f"ERROR: {e}")
+        plan.names = list(names)
+    for fam in plan.families:
+        if not option_on(args, fam.option):
+            continue
+        fam.names, fam.specs = fam.defaults()
+        for n in fam.names:
+            if n in plan.names:
+                raise SystemExit(f"ERROR: strata list '{args.stratify}': duplicate stratum name '{n}' (a {fam.word} stratum of {fam.option})")
+        plan.names += fam.names
+    return plan
+
+
+EMPTY_SLOT = dict(pos=np.zeros(0, np.int32), rlen=np.zeros(0, np.int32), type=np.zeros(0, np.uint8), var_qual=np.zeros(0, np.float32),
+                  phase_set=np.zeros(0, np.int32), ref_len=np.zeros(0, np.int32), alt_len=np.zeros(0, np.int32),
+                  ref_off=np.zeros(0, np.int64), alt_off=np.zeros(0, np.int64), pool=np.zeros(1, np.uint8))
+
+
+@dataclass
+class Inputs:
+    """what the run reads (Inputs in main.cpp): the callsets inside the -b BED, the FASTA, the contigs to evaluate in the reference's
+    order, and the command line as the files record it"""
+    q: dict; t: dict; fasta: dict; bed: object; contigs: list; cmd: str
+
+    def slots_of(self, ctg):
+        qs = self.q["vars"][self.q["contigs"].index(ctg)] if ctg in self.q["contigs"] else [EMPTY_SLOT, EMPTY_SLOT]
+        ts = self.t["vars"][self.t["contigs"].index(ctg)] if ctg in self.t["contigs"] else [EMPTY_SLOT, EMPTY_SLOT]
+        return [qs[0], qs[1], ts[0], ts[1]]
+
+    def header_of(self, ctg):
+        """a contig's length and ploidy (superclusterData ctor, cluster.cpp:134-157): the query's header wins, then the truth's"""
+        src = self.q if ctg in self.q["contigs"] else self.t
+        if ctg in src["contigs"]:
+            j = src["contigs"].index(ctg)
+            return src["lengths"][j], src["ploidy"][j]
+        return len(self.fasta[ctg]), 0      # a BED contig neither callset lists (check_contigs appends it, ploidy 0)
+
+
+def read_inputs(args, argv):
+    """both callsets, the FASTA, with -rq / -rt the callsets as read (orig-query.vcf, orig-truth.vcf, main.cpp:50-180), and the contigs"""
     filters = tuple(f for f in args.filter.split(",") if f)
     bed = IO.Bed(args.bed) if args.bed else None
     kw = dict(min_qual=args.min_qual, max_qual=args.max_qual, max_size=args.max_size, cluster_min_gap=args.cluster_gap, filters=filters)
     q = IO.read_vcf(args.query, bed, **kw)
     t = IO.read_vcf(args.truth, bed, **kw)
     fasta = IO.read_fasta(args.fasta)
-    write = not args.no_output_files
-    # realignment (main.cpp:50-180): the callsets as read, then each realigned in place of its columns; -ro stops there
-    if write and args.realign_query:
+    if not args.no_output_files and args.realign_query:
         RP.write_vcf(args.prefix + "orig-query.vcf", q, fasta)
-    if write and args.realign_truth:
+    if not args.no_output_files and args.realign_truth:
         RP.write_vcf(args.prefix + "orig-truth.vcf", t, fasta)
     contigs = check_contigs(q, t, fasta, bed)
-    cmd = " ".join(["vcfdist"] + list(sys.argv[1:] if argv is None else argv))
+    return Inputs(q, t, fasta, bed, contigs, " ".join(["vcfdist"] + list(sys.argv[1:] if argv is None else argv)))
+
+
+def realign_inputs(inp, args, device):
+    """-rq / -rt: each callset realigned in place of its columns.  -> True when -ro ends the run here, behind the realigned VCFs
+    and the parameters (written first by the reference, main.cpp:35)"""
+    write = not args.no_output_files
     if args.realign_query:
-        q = realign_callset("query", q, fasta, args, device=device)
+        inp.q = realign_callset("query", inp.q, inp.fasta, args, device=device)
         if args.realign_only and write:
-            RP.write_vcf(args.prefix + "query.vcf", q, fasta)
+            RP.write_vcf(args.prefix + "query.vcf", inp.q, inp.fasta)
     if args.realign_truth:
-        t = realign_callset("truth", t, fasta, args, device=device)
-    if args.realign_only:       # the parameters (written first by the reference, main.cpp:35) and stop
+        inp.t = realign_callset("truth", inp.t, inp.fasta, args, device=device)
+    if args.realign_only:
         if args.realign_truth and write:
-            RP.write_vcf(args.prefix + "truth.vcf", t, fasta)
+            RP.write_vcf(args.prefix + "truth.vcf", inp.t, inp.fasta)
         if write:
-            RP.write_parameters(args.prefix, args, cmd)
-        return []
-    for fam in KMER_FAMILIES:       # the genome-wide passes, before the contig loop (not under -ro)
-        if strat is not None and strat[fam["key"]]:
-            try:
-                kmer_strata(fam, fasta, strat, args, device=device)
-            except api.VprError as e:
-                raise SystemExit(f"ERROR: {e}")
-    nq = args.max_qual - args.min_qual + 1
-    total = np.zeros((2, 4, 3, nq), np.int64)
-    if strat is not None:
-        strat["counts"] = np.zeros((len(strat["names"]), 2, 4, 3, nq), np.int64)
-    boot = None
-    if args.bootstrap:
-        boot = dict(n=args.bootstrap, seed=args.bootstrap_seed, ms=0.0, counts=np.zeros((args.bootstrap, 2, 4, 3, nq), np.int64),
-                    strat=None if strat is None else np.zeros((len(strat["names"]), args.bootstrap, 2, 4, 3, nq), np.int64))
-    # the label passes, in the order of their counts behind the all-reduced vector, of their files and of their stderr lines
-    passes = []
-    if args.classify_errors:
-        window = A.EC_DEFAULT_WINDOW if args.error_window is None else args.error_window
+            RP.write_parameters(args.prefix, args, inp.cmd)
+    return args.realign_only
 
-        def ec_line(p):
-            return (f"[vcfdist_amd] error classes: window {window}, {int(p['counts'][0, 3, :, 0].sum())} query FP and "
-                    f"{int(p['counts'][1, 3, :, 0].sum())} truth FN classified, {p['ms']:.3f} ms on the device")
-        passes.append(dict(call="errclass", extra=(window,), counts=np.zeros((2, 4, A.EC_CLASSES, nq), np.int64), ms=0.0,
-                           write=RP.write_error_classes, line=ec_line, noun="error classes", write_strata=RP.write_error_classes_stratified,
-                           write_boot=RP.write_error_classes_bootstrap))
-    if args.classify_matches:
-        def mk_line(p):
-            qk, tk = p["counts"][0, 3, :, 0], p["counts"][1, 3, :, 0]
-            return (f"[vcfdist_amd] match kinds: query TP {int(qk[0])} exact, {int(qk[1])} shifted, {int(qk[2])} regrouped, {int(qk[3])} partial; "
-                    f"truth TP {int(tk[0])} exact, {int(tk[1])} shifted, {int(tk[2])} regrouped, {int(tk[3])} partial, {p['ms']:.3f} ms on the device")
-        passes.append(dict(call="matchkind", extra=(), counts=np.zeros((2, 4, A.MK_KINDS, nq), np.int64), ms=0.0,
-                           write=RP.write_match_kinds, line=mk_line, noun="match kinds", write_strata=RP.write_match_kinds_stratified,
-                           write_boot=RP.write_match_kinds_bootstrap))
-    # --cut-classes: the passes' counts once per stratum and per replicate, behind their counts in the all-reduced vector
-    cuts = []
-    if args.cut_classes:
-        for p in passes:
-            p["cut_ms"] = 0.0
-            if strat is not None:
-                p["strata"] = np.zeros((len(strat["names"]),) + p["counts"].shape, np.int64)
-                cuts.append((p, "strata"))
-            if boot is not None:
-                p["boot"] = np.zeros((boot["n"],) + p["counts"].shape, np.int64)
-                cuts.append((p, "boot"))
-    empty = dict(pos=np.zeros(0, np.int32), rlen=np.zeros(0, np.int32), type=np.zeros(0, np.uint8), var_qual=np.zeros(0, np.float32),
-                 phase_set=np.zeros(0, np.int32), ref_len=np.zeros(0, np.int32), alt_len=np.zeros(0, np.int32),
-                 ref_off=np.zeros(0, np.int64), alt_off=np.zeros(0, np.int64), pool=np.zeros(1, np.uint8))
 
-    def slots_of(ctg):
-        qs = q["vars"][q["contigs"].index(ctg)] if ctg in q["contigs"] else [empty, empty]
-        ts = t["vars"][t["contigs"].index(ctg)] if ctg in t["contigs"] else [empty, empty]
-        return [qs[0], qs[1], ts[0], ts[1]]
-
+def evaluate_contigs(inp, args, ranks, plan, tot):
+    """the contig loop: all of this rank's contigs prepared, then evaluated, their counts added to tot.  By superclusters every rank
+    clusters and marshals every contig (host work and the biWFA clustering, done redundantly) and evaluates its share of each; by
+    contigs a rank does everything for the contigs dealt to it.  -> what the writers need per contig ordinal, and -d's edit sets"""
     from . import shard
-    weights = [sum(len(s["pos"]) for s in slots_of(c)) + 1 for c in contigs]
-    by_sc = dist is not None and args.shard == "superclusters"
-    # by superclusters: every rank clusters and marshals every contig (host work and the biWFA clustering, done redundantly)
-    # and evaluates its share of each; by contigs: a rank does everything for the contigs dealt to it
-    mine = list(range(len(contigs))) if by_sc else shard.deal_contigs(weights, world)[rank]
-    cdev = None if dist is None or dist.get_backend() == "gloo" else f"cuda:{device}"
+    contigs, fasta = inp.contigs, inp.fasta
+    weights = [sum(len(s["pos"]) for s in inp.slots_of(c)) + 1 for c in contigs]
+    mine = list(range(len(contigs))) if ranks.by_sc else shard.deal_contigs(weights, ranks.world)[ranks.rank]
     # everything in front of the path for all of this rank's contigs first: input the library refuses ends the run here,
     # like the reference's ERROR(), before anything has been evaluated or written
     prepared = {}
     for k in mine:
-        ctg = contigs[k]
         try:
-            prepared[k] = prepare_contig(ctg, fasta[ctg], slots_of(ctg), args, device=device)
+            prepared[k] = prepare_contig(contigs[k], fasta[contigs[k]], inp.slots_of(contigs[k]), args, device=ranks.device)
         except api.VprError as e:
-            raise SystemExit(f"ERROR: contig '{ctg}': {e}")
+            raise SystemExit(f"ERROR: contig '{contigs[k]}': {e}")
     reports = {}
     dist_sets = [] if args.distance else None
     for k in mine:
         ctg = contigs[k]
-        try:
-            counts, n_sc, tables = evaluate_contig(prepared.pop(k), args, device=device, part=(rank, world, cdev) if by_sc else None,
-                                                   dist_sets=dist_sets, strat=strat, boot=boot, ordinal=k, passes=passes)
-        except api.VprError as e:     # the library's explicit refusals end the run like the reference's ERROR()
+        try:      # the library's explicit refusals (DESIGN.md section 4) end the run like the reference's ERROR()
+            counts, tables = evaluate_contig(prepared.pop(k), args, ranks, plan, tot, dist_sets=dist_sets, ordinal=k)
+            tot.total += counts
+            if plan is not None and plan.ctx.specs and ctg not in plan.ctx.rows and (ranks.rank == 0 or not ranks.by_sc):
+                context_only(ctg, fasta[ctg], plan.ctx, args, device=ranks.device)
+        except api.VprError as e:
             raise SystemExit(f"ERROR: contig '{ctg}': {e}")
-        total += counts
-        if strat is not None and strat["ctx"] and ctg not in strat["intervals"] and (rank == 0 or not by_sc):
-            try:
-                context_only(ctg, fasta[ctg], strat, args, device=device)
-            except api.VprError as e:
-                raise SystemExit(f"ERROR: contig '{ctg}': {e}")
         if not args.no_output_files:
-            src = q if ctg in q["contigs"] else t     # superclusterData ctor, cluster.cpp:134-157: query's header wins
-            if ctg in src["contigs"]:
-                j = src["contigs"].index(ctg)
-                length, ploidy = src["lengths"][j], src["ploidy"][j]
-            else:                                     # a BED contig neither callset lists (check_contigs appends it, ploidy 0)
-                length, ploidy = len(fasta[ctg]), 0
-            reports[k] = (ctg, length, ploidy, slots_of(ctg), tables)
-    if dist is not None:
-        # the one all-reduce: counts[2][4][3][nq] summed over the ranks, with --stratify the stratified ones behind them
-        # and with --bootstrap the replicate ones behind those
-        tail = [] if strat is None else [strat["counts"].ravel(), np.asarray([strat["vars"], strat["none"]], np.int64), strat["vs_members"].ravel()]
-        if boot is not None:
-            tail += [boot["counts"].ravel()] + ([] if strat is None else [boot["strat"].ravel()])
-        tail += [p["counts"].ravel() for p in passes] + [p[key].ravel() for p, key in cuts]
-        summed = shard.allreduce_tally(np.concatenate([total.ravel()] + tail), device=cdev)
-        total = summed[:total.size].reshape(total.shape)
-        at = total.size
-        if strat is not None:
-            strat["counts"] = summed[at:at + strat["counts"].size].reshape(strat["counts"].shape)
-            at += strat["counts"].size
-            strat["vars"], strat["none"] = int(summed[at]), int(summed[at + 1])
-            at += 2
-            strat["vs_members"] = summed[at:at + strat["vs_members"].size].reshape(strat["vs_members"].shape)
-            at += strat["vs_members"].size
-        if boot is not None:
-            boot["counts"] = summed[at:at + boot["counts"].size].reshape(boot["counts"].shape)
-            at += boot["counts"].size
-            if strat is not None:
-                boot["strat"] = summed[at:at + boot["strat"].size].reshape(boot["strat"].shape)
-                at += boot["strat"].size
-        for p in passes:
-            p["counts"] = summed[at:at + p["counts"].size].reshape(p["counts"].shape)
-            at += p["counts"].size
-        for p, key in cuts:
-            p[key] = summed[at:at + p[key].size].reshape(p[key].shape)
-            at += p[key].size
-        if not by_sc:       # (by superclusters every rank already holds every contig's gathered tables)
-            gathered = [None] * world
-            dist.all_gather_object(gathered, reports)
-            reports = {k: v for part in gathered for k, v in part.items()}
-            if strat is not None and strat["ctx"]:
-                dist.all_gather_object(gathered, (strat["intervals"], strat["ctx_ms"]))
-                strat["intervals"] = {k: v for part in gathered for k, v in part[0].items()}
-                strat["ctx_ms"] = {k: v for part in gathered for k, v in part[1].items()}
-            if strat is not None and strat["vs"]:
-                dist.all_gather_object(gathered, strat["vs_ms"])
-                strat["vs_ms"] = sum(gathered)
-            for p in passes:
-                dist.all_gather_object(gathered, p["ms"])
-                p["ms"] = sum(gathered)
-                if args.cut_classes:
-                    dist.all_gather_object(gathered, p["cut_ms"])
-                    p["cut_ms"] = sum(gathered)
-    rows = S.pr_summary(total, args.min_qual, args.max_qual)
+            reports[k] = (ctg, *inp.header_of(ctg), inp.slots_of(ctg), tables)
+    return reports, dist_sets
+
+
+def reduce_ranks(args, ranks, plan, tot, reports):
+    """the one all-reduce: every array of tot.tally summed over the ranks.  By contigs the ranks also exchange what only the
+    contig's rank has: the writers' tables, the context intervals, and the device times (summed).  -> the reports of all contigs"""
+    from . import shard
+    dist = ranks.dist
+    if dist is None:
+        return reports
+    unpack(tot.tally, shard.allreduce_tally(pack(tot.tally), device=ranks.cdev))
+    if ranks.by_sc:         # (by superclusters every rank already holds every contig's gathered tables)
+        return reports
+    gathered = [None] * ranks.world
+    dist.all_gather_object(gathered, reports)
+    reports = {k: v for part in gathered for k, v in part.items()}
+    if plan is not None and plan.ctx.specs:
+        dist.all_gather_object(gathered, plan.ctx.rows)
+        plan.ctx.rows = {k: v for part in gathered for k, v in part.items()}
+    # the device times that are summed over the ranks, as (owner, attribute): one list, gathered once
+    times = [(fam, "ms") for fam in ((plan.ctx, plan.vs) if plan is not None else ()) if fam.specs]
+    times += [(p, "ms") for p in tot.passes] + [(p, "cut_ms") for p in tot.passes if args.cut_classes]
+    dist.all_gather_object(gathered, tuple(getattr(owner, name) for owner, name in times))
+    for i, (owner, name) in enumerate(times):
+        setattr(owner, name, sum(part[i] for part in gathered))
+    return reports
+
+
+def write_outputs(args, inp, plan, tot, reports):
+    """every file of the evaluation (rank 0); the writers are looked up in report when they are called"""
+    mn, mx, prefix = args.min_qual, args.max_qual, args.prefix
+    RP.write_precision_recall(prefix, tot.total, mn, mx)
+    RP.write_parameters(prefix, args, inp.cmd)
+    if plan is not None:
+        RP.write_stratified(prefix, plan.names, tot.strat, mn, mx)
+        for fam in plan.kmer:
+            getattr(RP, fam.write)(prefix, inp.contigs, fam.names, fam.rows)
+        if plan.ctx.specs:
+            RP.write_context_bed(prefix, inp.contigs, plan.ctx.names, plan.ctx.rows)
+        if plan.vs.specs:
+            RP.write_variant_strata(prefix, plan.vs.names, plan.vs.specs, tot.vs_members[0], tot.vs_members[1])
+    for p in tot.passes:
+        getattr(RP, p.write)(prefix, p.counts, tot.total, mn, mx)
+    if tot.boot is not None:
+        RP.write_bootstrap(prefix, tot.total, tot.boot, args.bootstrap_seed, mn, mx)
+        if plan is not None:
+            RP.write_bootstrap_stratified(prefix, plan.names, tot.strat, tot.boot_strat, args.bootstrap_seed, mn, mx)
+    for p in tot.passes:
+        if p.strata is not None:
+            getattr(RP, p.write_strata)(prefix, plan.names, p.strata, tot.strat, mn, mx)
+        if p.boot is not None:
+            getattr(RP, p.write_boot)(prefix, p.counts, tot.total, p.boot, mn, mx)
+    ctgs = [RP.Contig(c, ln, pl, inp.fasta[c], sl, *tb) for c, ln, pl, sl, tb in (reports[k] for k in sorted(reports))]
+    RP.write_results(prefix, ctgs, cmd=inp.cmd, credit_threshold=args.credit_threshold)
+    if args.realign_query:
+        RP.write_vcf(prefix + "query.vcf", inp.q, inp.fasta)
+    if args.realign_truth:
+        RP.write_vcf(prefix + "truth.vcf", inp.t, inp.fasta)
+
+
+def report(args, plan, tot, rows):
+    """rank 0's closing lines on stderr, one per option, then the PRECISION-RECALL SUMMARY on stdout"""
+    say = lambda line: print("[vcfdist_amd] " + line, file=sys.stderr)
+    if plan is not None:
+        say(f"stratified: {len(plan.names)} strata, {int(tot.seen_none[1])} of {int(tot.seen_none[0])} hap-variants in none of them")
+        for fam in plan.kmer:
+            n_iv = sum(len(a) for per in fam.rows.values() for a, _ in per)
+            starts = ", ".join(f"{int(v)} valid and {int(r)} repeated starts (k={sp.k})" for sp, v, r in zip(fam.specs, *fam.stats))
+            say(f"{fam.word} strata: {n_iv} intervals of {len(fam.specs)} strata, {starts}, {fam.ms:.3f} ms on the device")
+        if plan.ctx.specs:
+            n_iv = sum(len(a) for per in plan.ctx.rows.values() for a, _ in per)
+            say(f"context strata: {n_iv} intervals of {len(plan.ctx.specs)} strata, {plan.ctx.ms:.3f} ms on the device")
+        if plan.vs.specs:
+            say(f"variant strata: {len(plan.vs.specs)} strata, {plan.vs.ms:.3f} ms on the device")
+    for p in tot.passes:
+        print(p.line(p), file=sys.stderr)
+    if args.cut_classes:
+        what = ([f"{len(plan.names)} strata"] if plan is not None else []) + ([f"{args.bootstrap} replicates"] if args.bootstrap else [])
+        for p in tot.passes:
+            say(f"{p.noun} cut: {', '.join(what)}, {p.cut_ms:.3f} ms on the device")
+    if args.bootstrap:
+        say(f"bootstrap: {args.bootstrap} replicates, seed {args.bootstrap_seed}, {tot.boot_ms:.3f} ms on the device")
+    print("PRECISION-RECALL SUMMARY\n")
+    print("TYPE\tTHRESHOLD\tTRUTH_TP\tQUERY_TP\tTRUTH_FN\tQUERY_FP\tPREC\t\tRECALL\t\tF1_SCORE\tF1_QSCORE")
+    for r in rows:
+        print("%s\t%s Q >= %-2d\t%-16d%-16d%-16d%-16d%f\t%f\t%f\t%f" % (S.NAMES[r.vartype], "BEST" if r.best else "NONE", r.qual,
+              r.truth_tp, r.query_tp, r.truth_fn, r.query_fp, r.precision, r.recall, r.f1_score, r.f1_qscore))
+        if r.best:
+            print()
+
+
+def main(argv=None):
+    """the stages, in the order and under the names of main.cpp's -> the summary's rows ([] under -ro)"""
+    args = parse(argv)
+    ranks = setup_ranks(args)
+    plan = plan_strata(args)        # (before any input is opened)
+    inp = read_inputs(args, argv)
+    if realign_inputs(inp, args, ranks.device):
+        return []
+    try:        # the genome-wide k-mer passes, before the contig loop
+        for fam in plan.kmer if plan is not None else ():
+            kmer_strata(fam, inp.fasta, args, device=ranks.device)
+    except api.VprError as e:
+        raise SystemExit(f"ERROR: {e}")
+    tot = Totals(args, plan)
+    reports, dist_sets = evaluate_contigs(inp, args, ranks, plan, tot)
+    reports = reduce_ranks(args, ranks, plan, tot, reports)
+    rows = S.pr_summary(tot.total, args.min_qual, args.max_qual)
     if dist_sets is not None:       # write_distance (printed even with -n) and write_edits, edit.cpp:134-280
         text = RP.write_distance(args.prefix, dist_sets, args.min_qual, args.max_qual, args.eval_sub, args.eval_open, args.eval_extend,
                                  verbosity=1, write_files=not args.no_output_files)
         if not args.no_output_files:
             RP.write_edits(args.prefix + "edits.tsv", dist_sets)
         print(text)
-    if rank == 0:
+    if ranks.rank == 0:
         if not args.no_output_files:
-            RP.write_precision_recall(args.prefix, total, args.min_qual, args.max_qual)
-            RP.write_parameters(args.prefix, args, cmd)
-            if strat is not None:
-                RP.write_stratified(args.prefix, strat["names"], strat["counts"], args.min_qual, args.max_qual)
-                for fam in KMER_FAMILIES:
-                    if strat[fam["key"]]:
-                        fam["write"](args.prefix, contigs, strat[fam["key"] + "_names"], strat[fam["key"] + "_rows"])
-                if strat["ctx"]:
-                    RP.write_context_bed(args.prefix, contigs, strat["ctx_names"], strat["intervals"])
-                if strat["vs"]:
-                    RP.write_variant_strata(args.prefix, strat["vs_names"], strat["vs"], strat["vs_members"][0], strat["vs_members"][1])
-            for p in passes:
-                p["write"](args.prefix, p["counts"], total, args.min_qual, args.max_qual)
-            if boot is not None:
-                RP.write_bootstrap(args.prefix, total, boot["counts"], boot["seed"], args.min_qual, args.max_qual)
-                if strat is not None:
-                    RP.write_bootstrap_stratified(args.prefix, strat["names"], strat["counts"], boot["strat"], boot["seed"], args.min_qual,
-                                                  args.max_qual)
-            for p, key in cuts:
-                if key == "strata":
-                    p["write_strata"](args.prefix, strat["names"], p["strata"], strat["counts"], args.min_qual, args.max_qual)
-                else:
-                    p["write_boot"](args.prefix, p["counts"], total, p["boot"], args.min_qual, args.max_qual)
-            ctgs = [RP.Contig(c, ln, pl, fasta[c], sl, *tb) for c, ln, pl, sl, tb in (reports[k] for k in sorted(reports))]
-            RP.write_results(args.prefix, ctgs, cmd=cmd, credit_threshold=args.credit_threshold)
-            if args.realign_query:
-                RP.write_vcf(args.prefix + "query.vcf", q, fasta)
-            if args.realign_truth:
-                RP.write_vcf(args.prefix + "truth.vcf", t, fasta)
-        if strat is not None:
-            print(f"[vcfdist_amd] stratified: {len(strat['names'])} strata, {strat['none']} of {strat['vars']} hap-variants in none of them",
-                  file=sys.stderr)
-            for fam in KMER_FAMILIES:
-                key = fam["key"]
-                if strat[key]:
-                    n_iv = sum(len(a) for rows in strat[key + "_rows"].values() for a, _ in rows)
-                    starts = ", ".join(f"{int(v)} valid and {int(r)} repeated starts (k={sp.k})" for sp, v, r in zip(strat[key], *strat[key + "_stats"]))
-                    print(f"[vcfdist_amd] {fam['word']} strata: {n_iv} intervals of {len(strat[key])} strata, {starts}, {strat[key + '_ms']:.3f} ms on "
-                          "the device", file=sys.stderr)
-            if strat["ctx"]:
-                n_iv = sum(len(a) for rows in strat["intervals"].values() for a, _ in rows)
-                print(f"[vcfdist_amd] context strata: {n_iv} intervals of {len(strat['ctx'])} strata, {sum(strat['ctx_ms'].values()):.3f} ms "
-                      "on the device", file=sys.stderr)
-            if strat["vs"]:
-                print(f"[vcfdist_amd] variant strata: {len(strat['vs'])} strata, {strat['vs_ms']:.3f} ms on the device", file=sys.stderr)
-        for p in passes:
-            print(p["line"](p), file=sys.stderr)
-        if args.cut_classes:
-            for p in passes:
-                what = ([f"{len(strat['names'])} strata"] if strat is not None else []) + ([f"{boot['n']} replicates"] if boot is not None else [])
-                print(f"[vcfdist_amd] {p['noun']} cut: {', '.join(what)}, {p['cut_ms']:.3f} ms on the device", file=sys.stderr)
-        if boot is not None:
-            print(f"[vcfdist_amd] bootstrap: {boot['n']} replicates, seed {boot['seed']}, {boot['ms']:.3f} ms on the device", file=sys.stderr)
-        print("PRECISION-RECALL SUMMARY\n")
-        print("TYPE\tTHRESHOLD\tTRUTH_TP\tQUERY_TP\tTRUTH_FN\tQUERY_FP\tPREC\t\tRECALL\t\tF1_SCORE\tF1_QSCORE")
-        for r in rows:
-            print("%s\t%s Q >= %-2d\t%-16d%-16d%-16d%-16d%f\t%f\t%f\t%f" % (S.NAMES[r.vartype], "BEST" if r.best else "NONE", r.qual,
-                  r.truth_tp, r.query_tp, r.truth_fn, r.query_fp, r.precision, r.recall, r.f1_score, r.f1_qscore))
-            if r.best:
-                print()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+            write_outputs(args, inp, plan, tot, reports)
+        report(args, plan, tot, rows)
+    if ranks.dist is not None:
+        ranks.dist.barrier()
+        ranks.dist.destroy_process_group()
     return rows
 
 
