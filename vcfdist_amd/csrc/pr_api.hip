@@ -51,6 +51,8 @@ extern "C" int vpr_batch_skeleton_from_variants(const vpr_variants *v, vpr_owned
 
 namespace {
 
+// the grid of a launch with a thread of a 256-thread workgroup per element
+dim3 blocks(int64_t n_) { return dim3(unsigned((n_ + 255) / 256)); }
 
 // window level an alignment has in a plan of level lv (a 16-cell plan holds its long alignments at LONG_LV)
 inline int plan_level_of(int lv, int long_lt, int Lt) { return (lv <= LV_Q16 && Lt >= long_lt) ? LONG_LV : lv; }
@@ -832,8 +834,7 @@ int prep_zero_lane(vpr_handle *h) {
         in_chunk_max = std::max(in_chunk_max, in_words - in_words0);
     }
     if (hdr.empty()) return VPR_OK;
-    int rc;
-    if ((rc = dev_alloc(h, &h->d_zl_hdr, hdr.size()))) return rc;
+    VPRCHK(dev_alloc(h, &h->d_zl_hdr, hdr.size()));
     HIPCHK(h, hipMemcpyAsync(h->d_zl_hdr, hdr.data(), hdr.size() * sizeof(ZlWave), hipMemcpyHostToDevice, h->stream));
     return zl_finish(h, hdr.size(), in_words, log_max, in_chunk_max, n_short_max, len_max);
 }
@@ -842,9 +843,8 @@ int prep_zero_lane(vpr_handle *h) {
 // distance-1 level's blocks; then the position words are written (k_prep_zl, on the upload stream)
 int zl_finish(vpr_handle *h, size_t n_waves, int64_t in_words, int64_t log_max, int64_t in_chunk_max, int64_t n_short_max, int32_t len_max) {
     const Plan &P = h->plan0;
-    int rc;
-    if ((rc = dev_alloc(h, &h->d_zl_in, size_t(in_words)))) return rc;
-    if ((rc = dev_alloc(h, &h->d_zl_log, size_t(log_max)))) return rc;
+    VPRCHK(dev_alloc(h, &h->d_zl_in, size_t(in_words)));
+    VPRCHK(dev_alloc(h, &h->d_zl_log, size_t(log_max)));
     // The distance-1 lane level works on the zero level's rejects (pr_d1.hip): its blocks hold D1_SHARE of what the largest
     // chunk would need if EVERY alignment were rejected (two words per QUERY / REF position instead of one, 40 B of log per
     // row instead of 20), at least D1_FLOOR -- small batches then fit whole --; waves that do not fit stay with the
@@ -863,7 +863,7 @@ int zl_finish(vpr_handle *h, size_t n_waves, int64_t in_words, int64_t log_max, 
         // (the level is optional -- VPR_NO_D1 gives the same results --, so its blocks, several GB on a million superclusters, are
         // optional growth: where the device has no room for them the upload goes on without the level.  ADVICE r5)
         h->soft_alloc = true;
-        rc = dev_alloc(h, &h->d_d1_hdr, size_t(h->d1_wave_cap));
+        int rc = dev_alloc(h, &h->d_d1_hdr, size_t(h->d1_wave_cap));
         if (!rc) rc = dev_alloc(h, &h->d_d1_in, size_t(h->d1_in_cap));
         if (!rc) rc = dev_alloc(h, &h->d_d1_log, size_t(h->d1_log_cap));
         if (!rc) rc = dev_alloc(h, &h->d_d1_fail, size_t(h->d1_fail_cap));
@@ -896,6 +896,40 @@ int zl_finish(vpr_handle *h, size_t n_waves, int64_t in_words, int64_t log_max, 
 }  // namespace
 
 namespace {
+// the offsets of the resident batch, as the planning kernels take them
+BatchOffsets batch_offsets(const DevBatch &D) {
+    BatchOffsets O;
+    for (int s = 0; s < 4; s++) { O.hap_off[s] = D.hap_off[s]; O.var_off[s] = D.var_off[s]; }
+    O.ref_off = D.ref_off;
+    return O;
+}
+
+// the fields of round 0's plan when it is made on the device: one chunk of all n alignments, the n_big long ones in front, the
+// parts' sums from the upload's pass over the superclusters (vpr_handle::Plan0Pass)
+void plan0_fields(vpr_handle *h, int lv0, size_t n, size_t n_big) {
+    Plan &P = h->plan0;
+    const vpr_handle::Plan0Pass &S0 = h->p0;
+    {
+        std::vector<int32_t> kw; std::vector<uint32_t> ko;
+        kw.swap(P.work); ko.swap(P.off128);
+        P = Plan();
+        P.work.swap(kw); P.off128.swap(ko);
+    }
+    P.lv = lv0; P.arena = h->d_arena; P.tag_or = 0; P.long_lt = h->long_lt; P.lazy = true;
+    P.total_need = S0.need128 * 128; P.arena_used = S0.need128 * 128;
+    Chunk ch;
+    ch.work_off = 0; ch.count = int32_t(n);
+    ch.n_long = int32_t(std::min<size_t>(n_big, n));
+    const bool no_long = ch.n_long == 0;
+    for (int q = 0; q < 2; q++) {
+        const int part = no_long ? 1 : q;
+        ch.part_cells[part] += S0.part_cells[q]; ch.part_in[part] += S0.part_in[q];
+        ch.part_dense[part] += S0.part_dense[q]; ch.part_rows[part] += S0.part_rows[q];
+        ch.cells += S0.part_cells[q]; ch.in_bytes += S0.part_in[q];
+    }
+    P.chunks.push_back(std::move(ch));
+}
+
 // ---------------------------------------------------------------------------
 // Round 0's plan of a whole batch built ON THE DEVICE (the usual case: every alignment of the batch, in input order, 16-cell
 // layout for the short part, everything in one chunk).  What make_plan does on the host for four million alignments -- a
@@ -925,63 +959,37 @@ int plan0_device(vpr_handle *h, int lv0, hipEvent_t ev_off, bool *done) {
     std::vector<std::pair<int64_t, int32_t>> big = S0.big;
     std::sort(big.begin(), big.end());
     const size_t n = na, n_big = big.size(), n_short = n - n_big;
-    // ---- the plan's fields
-    {
-        std::vector<int32_t> kw; std::vector<uint32_t> ko;
-        kw.swap(P.work); ko.swap(P.off128);
-        P = Plan();
-        P.work.swap(kw); P.off128.swap(ko);
-    }
-    P.lv = lv0; P.arena = h->d_arena; P.tag_or = 0; P.long_lt = LLT; P.lazy = true;
-    P.total_need = total * 128; P.arena_used = total * 128;
-    {
-        Chunk ch;
-        ch.work_off = 0; ch.count = int32_t(n);
-        ch.n_long = int32_t(std::min<size_t>(n_big, n));
-        const bool no_long = ch.n_long == 0;
-        for (int q = 0; q < 2; q++) {
-            const int part = no_long ? 1 : q;
-            ch.part_cells[part] += S0.part_cells[q]; ch.part_in[part] += S0.part_in[q];
-            ch.part_dense[part] += S0.part_dense[q]; ch.part_rows[part] += S0.part_rows[q];
-            ch.cells += S0.part_cells[q]; ch.in_bytes += S0.part_in[q];
-        }
-        P.chunks.push_back(std::move(ch));
-    }
+    plan0_fields(h, lv0, n, n_big);
     // ---- device: keys -> order -> offsets -> inverse -> wave headers
-    int rc;
     hipStream_t ps = h->cls_stream[0];          // (the class streams are idle during an upload)
     uint16_t *d_key = nullptr, *d_key2 = nullptr;
     int32_t *d_val = nullptr, *d_pos = nullptr;
     uint32_t *d_need = nullptr, *d_need2 = nullptr, *d_off = nullptr;
     int64_t *d_tot = nullptr;
-    if ((rc = dev_alloc(h, &P.d_descs, n))) return rc;
-    if ((rc = dev_alloc(h, &P.d_work, n))) return rc;
-    if ((rc = dev_alloc(h, &d_key, n))) return rc;
-    if ((rc = dev_alloc(h, &d_key2, n))) return rc;
-    if ((rc = dev_alloc(h, &d_val, n))) return rc;
-    if ((rc = dev_alloc(h, &d_pos, n))) return rc;
-    if ((rc = dev_alloc(h, &d_need, n))) return rc;
-    if ((rc = dev_alloc(h, &d_need2, n))) return rc;
-    if ((rc = dev_alloc(h, &d_off, n))) return rc;
-    if ((rc = dev_alloc(h, &d_tot, 4))) return rc;
+    VPRCHK(dev_alloc(h, &P.d_descs, n));
+    VPRCHK(dev_alloc(h, &P.d_work, n));
+    VPRCHK(dev_alloc(h, &d_key, n));
+    VPRCHK(dev_alloc(h, &d_key2, n));
+    VPRCHK(dev_alloc(h, &d_val, n));
+    VPRCHK(dev_alloc(h, &d_pos, n));
+    VPRCHK(dev_alloc(h, &d_need, n));
+    VPRCHK(dev_alloc(h, &d_need2, n));
+    VPRCHK(dev_alloc(h, &d_off, n));
+    VPRCHK(dev_alloc(h, &d_tot, 4));
     size_t tmp_sort = 0, tmp_scan = 0;
     if (vplan_sort_pairs_desc(nullptr, &tmp_sort, d_key, d_key2, d_val, P.d_work, n, ps) != 0 ||
         vplan_exclusive_scan_u32(nullptr, &tmp_scan, d_need2, d_off, n, ps) != 0)
         return fail(h, VPR_ERR_DEVICE, "device planner: workspace query failed");
     uint8_t *d_tmp = nullptr;
-    if ((rc = dev_alloc(h, &d_tmp, std::max(tmp_sort, tmp_scan) + 256))) return rc;
-    void *pin = nullptr;
-    { int rc_pin = pin_alloc(h, &pin, n * 12 + n_big * 4 + 64); if (rc_pin) return rc_pin; }
-    int32_t *hp_work = static_cast<int32_t *>(pin);
+    VPRCHK(dev_alloc(h, &d_tmp, std::max(tmp_sort, tmp_scan) + 256));
+    int32_t *hp_work = nullptr;                 // one page-locked block: work list, offsets, inverse, the long part, the totals
+    VPRCHK(pin_array(h, &hp_work, n * 3 + n_big + 16));
     uint32_t *hp_off = reinterpret_cast<uint32_t *>(hp_work + n);
     int32_t *hp_pos = reinterpret_cast<int32_t *>(hp_off + n);
     int32_t *hp_big = hp_pos + n;
     int64_t *hp_tot = reinterpret_cast<int64_t *>((reinterpret_cast<uintptr_t>(hp_big + n_big) + 15) & ~uintptr_t(15));
     for (size_t k = 0; k < n_big; k++) hp_big[k] = big[k].second;
-    BatchOffsets DO;
-    for (int s_ = 0; s_ < 4; s_++) { DO.hap_off[s_] = h->dB.hap_off[s_]; DO.var_off[s_] = h->dB.var_off[s_]; }
-    DO.ref_off = h->dB.ref_off;
-    auto blocks = [](int64_t n_) { return dim3(unsigned((n_ + 255) / 256)); };
+    const BatchOffsets DO = batch_offsets(h->dB);
     HIPCHK(h, hipStreamWaitEvent(ps, ev_off, 0));
     hipLaunchKernelGGL(k_plan_keys, blocks(int64_t(n)), dim3(256), 0, ps, DO, int(n), lv0, LLT, d_key, d_val, d_need);
     if (vplan_sort_pairs_desc(d_tmp, &tmp_sort, d_key, d_key2, d_val, P.d_work, n, ps) != 0) return fail(h, VPR_ERR_DEVICE, "device planner: sort failed");
@@ -993,7 +1001,7 @@ int plan0_device(vpr_handle *h, int lv0, hipEvent_t ev_off, bool *done) {
     HIPCHK(h, hipMemcpyAsync(hp_pos, d_pos, n * 4, hipMemcpyDeviceToHost, ps));
     const size_t nw = lv0 == LV_Z ? (n_short + 63) / 64 : 0;
     if (nw) {
-        if ((rc = dev_alloc(h, &h->d_zl_hdr, nw))) return rc;
+        VPRCHK(dev_alloc(h, &h->d_zl_hdr, nw));
         hipLaunchKernelGGL(k_zl_hdr, dim3(unsigned(nw)), dim3(64), 0, ps, DO, P.d_work + n_big, int(n_short), h->d_zl_hdr);
         hipLaunchKernelGGL(k_zl_scan, dim3(1), dim3(1024), 0, ps, h->d_zl_hdr, int(nw), d_tot);
         HIPCHK(h, hipMemcpyAsync(hp_tot, d_tot, 32, hipMemcpyDeviceToHost, ps));
@@ -1014,11 +1022,592 @@ int plan0_device(vpr_handle *h, int lv0, hipEvent_t ev_off, bool *done) {
     if (nw) {
         h->zl_wave0.assign(1, 0);
         const int64_t in_words = hp_tot[0], log_max = hp_tot[1];
-        if ((rc = zl_finish(h, nw, in_words, log_max, in_words, int64_t(n_short), int32_t(hp_tot[2])))) return rc;
+        VPRCHK(zl_finish(h, nw, in_words, log_max, in_words, int64_t(n_short), int32_t(hp_tot[2])));
     }
     *done = true;
     return VPR_OK;
 }
+
+// ---------------------------------------------------------------------------
+// The batch's memory plan as a value (what it means: vpr_handle::mem_reserve).  mem_plan() computes it from the device's free
+// memory -- read behind the upload's result and auxiliary allocations, which the figure has to see --, what the handle has
+// kept and what the batch pass found (vpr_handle::p0); it allocates nothing.  Upload::workspaces allocates from it.
+// ---------------------------------------------------------------------------
+struct MemPlan {
+    int64_t free_driver = 0, free = 0;       // free device memory as the driver reports it / as the process's books correct it
+    int64_t kept_blocks = 0;                 // blocks kept from the previous batch: the allocations take them first
+    int64_t kept_scratch = 0;                // the replay scratches (the handle's lifetime: part of the plan, and taken already)
+    int64_t reserve = 0;                     // what the library leaves alone
+    int64_t lane_est = 0;                    // what the upload allocates BEHIND the plan (the lane levels, the device planner)
+    int64_t avail = 0;                       // what there is to plan
+    int64_t want = 0, budget = 0;            // round 0's workspace: what its plan will ask for / what it gets
+    int64_t lad_half = 0, tie_half = 0;      // the rest: the ladders' workspaces / the replay scratches
+    int64_t first[4] = {0, 0, 0, 0};         // the ladders' first workspaces before they are scaled down together by `shrink` ...
+    double shrink = 1.0;
+    int64_t lad_arena[4] = {0, 0, 0, 0};     // ... and as allocated (cfg.workspace_bytes bounds each instead; at least 8 MB)
+    void print() const {
+        fprintf(stderr, "[vpr] memory plan: free %.1f GB + kept blocks %.1f + scratches %.1f, reserve %.1f, lane levels %.1f -> %.1f to plan; round 0 wants %.1f, gets %.1f; "
+                        "ladders' half %.1f (first workspaces %.1f %.1f %.1f %.1f), replays' half %.1f\n",
+                double(free) / 1e9, double(kept_blocks) / 1e9, double(kept_scratch) / 1e9, double(reserve) / 1e9, double(lane_est) / 1e9, double(avail) / 1e9,
+                double(want) / 1e9, double(budget) / 1e9, double(lad_half) / 1e9, double(first[0]) * shrink / 1e9, double(first[1]) * shrink / 1e9,
+                double(first[2]) * shrink / 1e9, double(first[3]) * shrink / 1e9, double(tie_half) / 1e9);
+    }
+};
+
+int mem_plan(vpr_handle *h, MemPlan &M) {
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
+    M.free_driver = int64_t(free_b);
+    M.free = books_free(int64_t(free_b), int64_t(total_b));     // (the driver's figure lags behind this process's own large frees: dev_books)
+    if (h->debug && M.free != M.free_driver) fprintf(stderr, "[vpr] memory plan: the driver reports %.1f GB free, the books %.1f\n", double(M.free_driver) / 1e9, double(M.free) / 1e9);
+    // what the batch may take: the free memory (the blocks kept from the previous batch count: the allocations take them first)
+    // less the tenth of the device the library leaves alone; on a device mostly taken by others, half of what is free
+    for (const auto &c : h->dev_cache) M.kept_blocks += int64_t(c.bytes);
+    for (int k = 0; k < 4; k++) for (int e = 0; e < 2; e++) M.kept_scratch += h->lad[k].tie_scratch_bytes[e];
+    M.reserve = int64_t(double(total_b) * free_share());
+    int64_t avail = M.free + M.kept_blocks + M.kept_scratch;
+    avail = std::max<int64_t>(avail - M.reserve, avail / 2);
+    // What the upload allocates BEHIND this plan comes off first (ADVICE r5: the ladders' and replays' halves were promised memory
+    // the lane levels then took): the lane levels' interleaved position words (4 B per position of the short part) and logs
+    // (20 B per truth row), padded to the waves' longest alignments (measured: < 15 %), the distance-1 level's blocks (0.8 of
+    // both, zl_finish), the device planner's temporaries (28 B per alignment) and the saved forward flags of the long part.
+    const int bm = h->cfg.band_mode;
+    if (h->p0.valid && bm != 0 && bm != 2) {
+        const double zl = 1.15 * (double(h->p0.part_in[1]) / 6.0 * 4.0 + 20.0 * double(h->p0.part_rows[1]));
+        M.lane_est = int64_t(zl * (getenv("VPR_NO_D1") ? 1.0 : 1.8)) + 28 * int64_t(h->descs.size());
+        avail = std::max<int64_t>(avail - M.lane_est, avail / 2);
+    }
+    M.avail = avail;
+    int64_t budget = h->cfg.workspace_bytes > 0 ? h->cfg.workspace_bytes : int64_t(double(avail) * arena_share());
+    if (budget < (8 << 20)) budget = 8 << 20;
+    // do not allocate more than round 0 can use (its layout per alignment: make_plan)
+    const bool q16ok = (bm == 1 || bm == 3);
+    std::vector<int64_t> wants(PAR_MAX, 0);
+    if (h->p0.valid) wants[0] = h->p0.need128 * 128 + 4096;       // (exactly what round 0's plan will ask for)
+    else
+        par_for(h->descs.size(), [&](size_t b0, size_t e0, int tid) {
+            int64_t w = 0;
+            for (size_t k = b0; k < e0; k++) {
+                const AlnDesc &d = h->descs[k];
+                int64_t flags;
+                if (bm != 0 && q16ok && d.Lt < h->long_lt) {
+                    const int64_t nstr = (int64_t(d.Lt) + 3) / 4;
+                    flags = nstr * 128 + round_up(nstr * 8, 64);
+                } else if (bm != 0) {
+                    const int W = (q16ok && bm != 2) ? LV_WINDOW[LONG_LV] : 64;
+                    flags = round_up(round_up(std::min(W, d.Lq), 16) * int64_t(d.Lt), 64) +
+                            round_up(round_up(std::min(W, d.Lr), 16) * int64_t(d.Lt), 64) + round_up(8 * int64_t(d.Lt), 64);
+                } else {
+                    flags = round_up(round_up(d.Lq, 32) * int64_t(d.Lt), 64) + round_up(round_up(d.Lr, 32) * int64_t(d.Lt), 64);
+                }
+                w += flags + round_up(int64_t(d.path_cap) * int64_t(sizeof(PathEnt)) + 128, 128) + 256;
+            }
+            wants[size_t(tid)] = w;
+        });
+    for (int64_t w : wants) M.want += w;
+    if (h->cfg.workspace_bytes <= 0) budget = std::min(budget, std::max<int64_t>(M.want, 256 << 20));
+    M.budget = budget;
+    // What round 0 left is split between the ladders' workspaces and the replay scratches.  The ladders (two retry ladders
+    // beside round 0, two for the tie rounds) start with a sixteenth of round 0's need each -- the short part's with at most
+    // 2 GB -- and grow on demand inside their half (lad_grow); the replay scratches are allocated by the first tie round
+    // (cfg.workspace_bytes bounds each workspace instead).
+    const int64_t rest = std::max<int64_t>(avail - budget, 0);
+    M.lad_half = rest / 2; M.tie_half = rest - rest / 2;
+    // (a handle that has released a batch knows what its ladders grew to: the same fraction of this batch's round-0 need,
+    // all four scaled down together if that is more than the ladders' half)
+    int64_t first_sum = 0;
+    for (int k = 0; k < 4; k++) {
+        int64_t b2 = std::min<int64_t>(M.lad_half / 4, int64_t(ladder_share() * double(std::max<int64_t>(M.want / 16, int64_t(1) << 30))));
+        if (k & 1) b2 = std::min<int64_t>(b2, int64_t(2) << 30);
+        M.first[k] = std::max<int64_t>(b2, std::min<int64_t>(int64_t(h->lad_hw[k] * double(M.want)), h->lad_arena_max));
+        first_sum += M.first[k];
+    }
+    M.shrink = first_sum > M.lad_half && first_sum > 0 ? double(M.lad_half) / double(first_sum) : 1.0;
+    for (int k = 0; k < 4; k++) {
+        int64_t b2 = h->cfg.workspace_bytes;
+        if (b2 <= 0) b2 = int64_t(double(M.first[k]) * M.shrink);
+        M.lad_arena[k] = std::max<int64_t>(b2, 8 << 20);
+    }
+    return VPR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// One vpr_upload call: what its stages share, and the stages.  Everything is enqueued on the upload stream (the device planner
+// on a class stream, behind ev_offsets); nothing waits between the stages but what a stage says.  dev_alloc carves the batch's
+// pool blocks in call order, so the order of the allocations -- inside a stage and across them -- decides addresses and block
+// sizes, and the memory plan has to see exactly what stands in front of it.  run() is the sequence.
+// ---------------------------------------------------------------------------
+struct Upload {
+    vpr_handle *h;
+    const vpr_batch *b;
+    const int n;                                   // superclusters
+    DevBatch &D;
+    int64_t hap_len[4], ref_len;                   // positions of the batch's four haplotype planes / its reference plane
+    const int lv0;                                 // round 0's window level
+    size_t na = 0;                                 // alignments
+    int64_t sec_total = 0, jobs_total = 0, cells = 0, bytes_alg = 0;   // the batch's sums (batch_pass): sections, deferred edit distances, ...
+    MemPlan M;
+    std::vector<int32_t> &all;                     // the work list: the alignments that are computed ...
+    size_t np = 0;                                 // ... and how many they are
+    bool dev_plan = false;                         // round 0's plan was made on the device (plan0_device)
+    hipEvent_t ev_prep[2] = {nullptr, nullptr};    // bracket the K0 prep kernels (vpr_timing::ms_prep); released with the call, however it ends
+
+    static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    const double T0 = now();
+    const bool tim = getenv("VPR_TIMING") != nullptr;       // host-side laps without device synchronisation
+    void lap(const char *what) {
+        if (h->debug) { (void)hipDeviceSynchronize(); fprintf(stderr, "[vpr] upload %-28s %.3f s\n", what, now() - T0); }
+        else if (tim) fprintf(stderr, "[vpr] upload (host) %-28s %.3f s\n", what, now() - T0);
+    }
+
+    Upload(vpr_handle *h_, const vpr_batch *b_)
+        : h(h_), b(b_), n(b_->n_sc), D(h_->dB), ref_len(b_->ref_off[b_->n_sc]),
+          lv0(h_->cfg.band_mode == 0 ? LV_DENSE : h_->cfg.band_mode == 2 ? LV_C1 : h_->cfg.band_mode == 3 ? LV_Q16 : LV_Z),
+          all(h_->scratch_i32[1]) {
+        for (int s = 0; s < 4; s++) hap_len[s] = b->hap_off[s][n];
+    }
+    ~Upload() { for (hipEvent_t e : ev_prep) if (e) (void)hipEventDestroy(e); }
+
+    int run() {
+        lap("previous batch released");
+        VPRCHK(inputs());
+        VPRCHK(generate());
+        lap("inputs copied");
+        VPRCHK(prep_kernels());
+        lap("prep kernels");
+        VPRCHK(batch_pass());
+        lap("descriptors");
+        VPRCHK(result_blocks());
+        lap("result/aux allocations");
+        VPRCHK(mem_plan(h, M));
+        VPRCHK(workspaces());
+        lap("arena allocation");
+        VPRCHK(work_list());
+        VPRCHK(plan_round0());
+        lap("plan0_pos");
+        VPRCHK(round0_descs());
+        return finish();
+    }
+
+    // ---- the Level A arrays and the per-position blocks of K0, their presets, the error word; ev_offsets
+    int inputs() {
+        h->n_sc = n;
+        memset(&D, 0, sizeof(D));
+        D.n_sc = n;
+        for (int s = 0; s < 4; s++) {
+            h->n_var[s] = b->var_off[s][n];
+            VPRCHK(dev_upload(h, &D.hap_off[s], b->hap_off[s], n + 1));
+            VPRCHK(dev_upload(h, &D.hap_seq[s], b->hap_seq[s], hap_len[s]));
+            VPRCHK(dev_upload(h, &D.hap_ptr[s], b->hap_ptr[s], hap_len[s]));
+            VPRCHK(dev_upload(h, &D.hap_flag[s], b->hap_flag[s], hap_len[s]));
+            VPRCHK(dev_upload(h, &D.var_off[s], b->var_off[s], n + 1));
+            VPRCHK(dev_upload(h, &D.var_pos[s], b->var_pos[s], h->n_var[s]));
+            h->var_off[s].assign(b->var_off[s], b->var_off[s] + n + 1);
+            h->var_qual[s].assign(b->var_qual[s], b->var_qual[s] + h->n_var[s]);
+            VPRCHK(dev_alloc(h, &D.has_ins[s], ref_len));
+            VPRCHK(dev_alloc(h, &D.vs_hap[s], hap_len[s]));
+            VPRCHK(dev_alloc(h, &D.dspan[s], size_t(n)));
+            VPRCHK(dev_alloc(h, &D.sc_hap[s], hap_len[s]));
+            HIPCHK(h, hipMemsetAsync(D.has_ins[s], 0, std::max<int64_t>(ref_len, 1), h->stream));
+            if (s == 0) {
+                VPRCHK(dev_alloc(h, &D.sc_limit, size_t(std::max(n, 1))));
+                HIPCHK(h, hipMemsetAsync(D.sc_limit, 0, size_t(std::max(n, 1)), h->stream));
+            }
+        }
+        lap("  inputs: haplotype arrays");
+        VPRCHK(dev_upload(h, &D.ref_off, b->ref_off, n + 1));
+        VPRCHK(dev_upload(h, &D.ref_seq, b->ref_seq, ref_len));
+        VPRCHK(dev_alloc(h, &D.sc_ref, ref_len));
+        for (int q = 0; q < 2; q++) {
+            VPRCHK(dev_upload(h, &D.ref_ptr[q], b->ref_ptr[q], ref_len));
+            VPRCHK(dev_upload(h, &D.ref_flag[q], b->ref_flag[q], ref_len));
+            VPRCHK(dev_alloc(h, &D.cand_q[q], hap_len[q]));
+            VPRCHK(dev_alloc(h, &D.cand_r[q], ref_len));
+            VPRCHK(dev_alloc(h, &D.cand2_q[q], hap_len[q]));
+            VPRCHK(dev_alloc(h, &D.cand2_r[q], ref_len));
+            VPRCHK(dev_alloc(h, &D.fk_q[q], hap_len[q]));
+            VPRCHK(dev_alloc(h, &D.fk_r[q], ref_len));
+            VPRCHK(dev_alloc(h, &D.bk_q[q], hap_len[q]));
+            VPRCHK(dev_alloc(h, &D.bk_r[q], ref_len));
+            VPRCHK(dev_alloc(h, &D.vs_ref[q], ref_len));
+            VPRCHK(dev_alloc(h, &D.fk4_q[q], hap_len[q]));
+            VPRCHK(dev_alloc(h, &D.fk4_r[q], ref_len));
+            VPRCHK(dev_alloc(h, &D.tk[q], hap_len[2 + q]));
+            VPRCHK(dev_alloc(h, &D.tj[q], hap_len[2 + q] + 8));
+            VPRCHK(dev_alloc(h, &D.wk_q[q], hap_len[q]));
+            VPRCHK(dev_alloc(h, &D.wk_r[q], ref_len));
+            VPRCHK(dev_alloc(h, &D.wk_t[q], hap_len[2 + q]));
+            VPRCHK(dev_alloc(h, &D.xb_q[q], hap_len[q]));
+            VPRCHK(dev_alloc(h, &D.xb_r[q], ref_len));
+            HIPCHK(h, hipMemsetAsync(D.cand_q[q], 0xff, std::max<int64_t>(hap_len[q], 1) * sizeof(int4), h->stream));
+            HIPCHK(h, hipMemsetAsync(D.cand_r[q], 0xff, std::max<int64_t>(ref_len, 1) * sizeof(int4), h->stream));
+            HIPCHK(h, hipMemsetAsync(D.cand2_q[q], 0xff, std::max<int64_t>(hap_len[q], 1) * sizeof(int4), h->stream));
+            HIPCHK(h, hipMemsetAsync(D.cand2_r[q], 0xff, std::max<int64_t>(ref_len, 1) * sizeof(int4), h->stream));
+        }
+        lap("  inputs: reference arrays, constants' blocks");
+        VPRCHK(dev_alloc(h, &h->d_err, 1));
+        HIPCHK(h, hipMemsetAsync(h->d_err, 0, 4, h->stream));
+        if (!h->ev_offsets) HIPCHK(h, hipEventCreateWithFlags(&h->ev_offsets, hipEventDisableTiming));
+        HIPCHK(h, hipEventRecord(h->ev_offsets, h->stream));       // the batch's offsets are on the device: what the device planner reads
+        return VPR_OK;
+    }
+
+    // ---- vpr_upload_variants: the strings, pointers and flags are written on the device from the variant tables (pr_gen.hip)
+    int generate() {
+        if (!h->gen_src) return VPR_OK;
+        const vpr_variants *v = h->gen_src;
+        GenTables G;
+        GenOut O;
+        memset(&G, 0, sizeof(G));
+        const int64_t ctg_total = v->ctg_off[v->n_ctg];
+        if (ctg_total > h->ctg_bytes) {
+            if (h->d_ctg_seq) (void)x_free(h, h->d_ctg_seq, SITE);
+            h->d_ctg_seq = nullptr; h->ctg_bytes = 0;
+            void *q = nullptr;
+            if (x_malloc(h, &q, size_t(ctg_total) + 256, SITE) != hipSuccess) return fail(h, VPR_ERR_NOMEM, "contig sequence (%lld bytes)", (long long)ctg_total);
+            h->d_ctg_seq = static_cast<uint8_t *>(q);
+            h->ctg_bytes = ctg_total;
+        }
+        if (ctg_total) HIPCHK(h, hipMemcpyAsync(h->d_ctg_seq, v->ctg_seq, size_t(ctg_total), hipMemcpyHostToDevice, h->stream));
+        G.ctg_seq = h->d_ctg_seq;
+        VPRCHK(dev_upload(h, &G.ctg_off, v->ctg_off, size_t(v->n_ctg) + 1));
+        VPRCHK(dev_upload(h, &G.sc_ctg, v->sc_ctg, size_t(n)));
+        VPRCHK(dev_upload(h, &G.sc_beg, v->sc_beg, size_t(n)));
+        VPRCHK(dev_upload(h, &G.sc_end, v->sc_end, size_t(n)));
+        for (int s = 0; s < 4; s++) {
+            const size_t nv = size_t(h->n_var[s]);
+            std::vector<int64_t> pl(PAR_MAX, 1);
+            par_for(nv, [&](size_t b0, size_t e0, int tid) {
+                int64_t m = 1;
+                for (size_t k = b0; k < e0; k++)
+                    m = std::max(m, std::max(v->var_ref_off[s][k] + v->var_ref_len[s][k], v->var_alt_off[s][k] + v->var_alt_len[s][k]));
+                pl[size_t(tid)] = m;
+            });
+            int64_t pool_len = 1;
+            for (int64_t m : pl) pool_len = std::max(pool_len, m);
+            G.var_pos_rel[s] = D.var_pos[s];
+            VPRCHK(dev_upload(h, &G.var_type[s], v->var_type[s], nv));
+            VPRCHK(dev_upload(h, &G.ref_off[s], v->var_ref_off[s], nv));
+            VPRCHK(dev_upload(h, &G.alt_off[s], v->var_alt_off[s], nv));
+            VPRCHK(dev_upload(h, &G.ref_len[s], v->var_ref_len[s], nv));
+            VPRCHK(dev_upload(h, &G.alt_len[s], v->var_alt_len[s], nv));
+            VPRCHK(dev_upload(h, &G.pool[s], v->allele_pool[s], size_t(pool_len)));
+            O.hap_seq[s] = const_cast<uint8_t *>(D.hap_seq[s]); O.hap_ptr[s] = const_cast<int32_t *>(D.hap_ptr[s]);
+            O.hap_flag[s] = const_cast<uint8_t *>(D.hap_flag[s]);
+        }
+        O.ref_seq = const_cast<uint8_t *>(D.ref_seq);
+        for (int q = 0; q < 2; q++) { O.ref_ptr[q] = const_cast<int32_t *>(D.ref_ptr[q]); O.ref_flag[q] = const_cast<uint8_t *>(D.ref_flag[q]); }
+        if (n > 0) hipLaunchKernelGGL(k_generate, dim3(unsigned((n + 4 * GEN_SC_PER_WAVE - 1) / (4 * GEN_SC_PER_WAVE)), 4), dim3(256), 0, h->stream, D, G, O);
+        HIPCHK(h, hipGetLastError());
+        return VPR_OK;
+    }
+
+    // one launch of a K0 kernel over the haplotype plane and one over the reference plane of each query haplotype
+    template <typename K, typename... A>
+    void query_planes(K kernel, A... tail) {
+        for (int q = 0; q < 2; q++) {
+            if (hap_len[q] > 0) hipLaunchKernelGGL(kernel, blocks(hap_len[q]), dim3(256), 0, h->stream, D, q, 0, hap_len[q], tail...);
+            if (ref_len > 0) hipLaunchKernelGGL(kernel, blocks(ref_len), dim3(256), 0, h->stream, D, q, 1, ref_len, tail...);
+        }
+    }
+
+    // ---- K0: position attributes, between the call's pair of timing events; the variants' spans come back to the host
+    int prep_kernels() {
+        for (hipEvent_t &e : ev_prep) HIPCHK(h, hipEventCreate(&e));
+        HIPCHK(h, hipEventRecord(ev_prep[0], h->stream));
+        if (n > 0) hipLaunchKernelGGL(k_prep_scof, dim3(unsigned((n + 255) / 256), 5), dim3(256), 0, h->stream, D);
+        query_planes(k_prep_cand, h->d_err);
+        query_planes(k_prep_pack);
+        lap("  prep: scof, cand, pack");
+        for (int s = 0; s < 4; s++)
+            if (hap_len[s] > 0)
+                hipLaunchKernelGGL(k_prep_ins, blocks(hap_len[s]), dim3(256), 0, h->stream, D, s, hap_len[s]);
+        if (n > 0) hipLaunchKernelGGL(k_prep_suffix, dim3((n + 4 * SUFFIX_SC_PER_WAVE - 1) / (4 * SUFFIX_SC_PER_WAVE), 6), dim3(256), 0, h->stream, D);
+        int2 *pd = nullptr;
+        VPRCHK(pin_array(h, &pd, size_t(std::max(n, 1)) * 4));
+        for (int s = 0; s < 4; s++) {
+            h->hp_dspan[s] = pd + size_t(s) * size_t(n);
+            if (n > 0) HIPCHK(h, hipMemcpyAsync(h->hp_dspan[s], D.dspan[s], size_t(n) * sizeof(int2), hipMemcpyDeviceToHost, h->stream));
+        }
+        lap("  prep: ins, suffix, spans");
+        query_planes(k_prep_xb);
+        for (int s = 0; s < 2; s++)
+            if (hap_len[2 + s] > 0) hipLaunchKernelGGL(k_prep_tj, blocks(hap_len[2 + s]), dim3(256), 0, h->stream, D, s, hap_len[2 + s]);
+        for (int w = 0; w < 6; w++) {
+            const int64_t npos = w < 2 ? hap_len[w] : (w < 4 ? ref_len : hap_len[w - 2]);
+            if (npos > 0) hipLaunchKernelGGL(k_prep_q16, blocks(npos), dim3(256), 0, h->stream, D, w, npos);
+            if (npos > 0) hipLaunchKernelGGL(k_prep_wk, blocks(npos), dim3(256), 0, h->stream, D, w, npos);
+        }
+        HIPCHK(h, hipEventRecord(ev_prep[1], h->stream));
+        return VPR_OK;
+    }
+
+    // ---- base descriptors: a function of the offsets (BaseDescs); here only the sums and the checks.
+    // ONE pass over the superclusters: the checks and sums of the batch and -- for a windowed round 0 over all alignments, the
+    // usual case -- everything the host contributes to round 0's plan (plan0_device): the level of every alignment, the
+    // parts' sums, the total workspace need (which is also what the arena has to hold), the long alignments.  (Three
+    // passes over four million alignments until round 4, two of them through the full descriptors.)
+    int batch_pass() {
+        h->descs.set(b, h->var_off);
+        h->ed_max_len = -1;
+        na = h->descs.size();
+        for (int s = 0; s < 4; s++) sec_total += 2 * b->var_off[s][n];
+        sec_total += 16 * int64_t(n);
+        const bool plan_pass = lv0 <= LV_Q16 && !(h->cfg.flags & VPR_CFG_HAP_DEDUP) && n > 0;
+        const int LLT = h->long_lt;
+        h->p0 = vpr_handle::Plan0Pass();
+        if (plan_pass) h->level.resize(size_t(n) * 4);
+        struct Acc { int64_t jobs = 0, cells = 0, bytes = 0; int bad = -1; vpr_handle::Plan0Pass P; };
+        std::vector<Acc> acc(PAR_MAX);
+        par_for(size_t(n), [&](size_t b0, size_t e0, int tid) {
+            Acc &A = acc[size_t(tid)];
+            AlnDesc d{};
+            for (size_t scu = b0; scu < e0; scu++) {
+                const int sc = int(scu);
+                const int64_t Lr = b->ref_off[sc + 1] - b->ref_off[sc];
+                int64_t Lh[4];
+                for (int s = 0; s < 4; s++) Lh[s] = b->hap_off[s][sc + 1] - b->hap_off[s][sc];
+                int64_t nv = 0;
+                for (int s = 0; s < 4; s++) nv += b->var_off[s][sc + 1] - b->var_off[s][sc];
+                A.bytes += 6 * (Lh[0] + Lh[1] + Lh[2] + Lh[3]) + 11 * Lr + 26 * nv;
+                if ((Lh[0] < 1 || Lh[1] < 1 || Lh[2] < 1 || Lh[3] < 1 || Lr < 1) && A.bad < 0) A.bad = sc;
+                for (int i = 0; i < 4; i++) {
+                    const int64_t Lq = Lh[i >> 1], Lt = Lh[2 + (i & 1)];
+                    // (deferred sections: both segments longer than 32, or one longer than ED_INLINE_LONG -- segments are disjoint)
+                    A.jobs += std::min(Lr, Lt) / 33 + Lr / (ED_INLINE_LONG + 1) + Lt / (ED_INLINE_LONG + 1);
+                    A.cells += (Lq + Lr) * Lt;
+                    if (!plan_pass) continue;
+                    d.Lq = int32_t(Lq); d.Lr = int32_t(Lr); d.Lt = int32_t(Lt);
+                    d.path_cap = d.Lq + d.Lr + d.Lt + 4;
+                    const int dl = plan_level_of(lv0, LLT, d.Lt);
+                    const int W = LV_WINDOW[dl], part = d.Lt >= LLT ? 0 : 1;
+                    A.P.part_cells[part] += int64_t(std::min(W, d.Lq) + std::min(W, d.Lr)) * d.Lt;
+                    A.P.part_in[part] += 6 * int64_t(d.Lq) + 6 * int64_t(d.Lt) + 6 * int64_t(d.Lr);
+                    A.P.part_dense[part] += int64_t(d.Lq + d.Lr) * d.Lt;
+                    A.P.part_rows[part] += d.Lt;
+                    h->level[size_t(sc) * 4 + size_t(i)] = uint8_t(dl);
+                    if (d.Lt >= LLT)
+                        A.P.big.emplace_back(-(int64_t(round_up(std::min(W, d.Lq), 16) + round_up(std::min(W, d.Lr), 16)) * d.Lt), int32_t(sc * 4 + i));
+                    const int64_t need = window_layout(d, dl, 0, 0);
+                    A.P.need128 += need / 128;
+                    A.P.need_max = std::max(A.P.need_max, need);
+                    if ((d.Lt < LLT && d.Lt > 0xfffe) || d.Lq < 1 || d.Lr < 1 || d.Lt < 1) A.P.bad = true;
+                }
+            }
+        });
+        int bad = -1;
+        for (const Acc &A : acc) {
+            jobs_total += A.jobs; cells += A.cells; bytes_alg += A.bytes;
+            if (A.bad >= 0 && (bad < 0 || A.bad < bad)) bad = A.bad;
+            for (int q = 0; q < 2; q++) {
+                h->p0.part_cells[q] += A.P.part_cells[q]; h->p0.part_in[q] += A.P.part_in[q];
+                h->p0.part_dense[q] += A.P.part_dense[q]; h->p0.part_rows[q] += A.P.part_rows[q];
+            }
+            h->p0.need128 += A.P.need128; h->p0.need_max = std::max(h->p0.need_max, A.P.need_max);
+            h->p0.bad = h->p0.bad || A.P.bad;
+            h->p0.big.insert(h->p0.big.end(), A.P.big.begin(), A.P.big.end());
+        }
+        h->p0.valid = plan_pass;
+        if (bad >= 0) return fail(h, VPR_ERR_ARG, "supercluster %d has an empty string", bad);
+        bytes_alg += 2 * cells;
+        h->timing.cells_dense = cells;
+        h->timing.bytes_algorithmic = bytes_alg;
+        return VPR_OK;
+    }
+
+    // ---- descriptors, outs, sections, false-positive lists, jobs; the result columns; tie and fail lists with their pinned mirrors
+    int result_blocks() {
+        VPRCHK(dev_alloc(h, &h->d_descs, na));
+        VPRCHK(dev_alloc(h, &h->d_outs, na));
+        h->n_secs_cap = sec_total;
+        VPRCHK(dev_alloc(h, &h->d_secs, size_t(sec_total)));
+        for (int q = 0; q < 4; q++) VPRCHK(dev_alloc(h, &h->d_fp[q], size_t(h->n_var[q >> 1])));
+        VPRCHK(dev_alloc(h, &h->d_fp_table, 4));
+        HIPCHK(h, hipMemcpyAsync(h->d_fp_table, h->d_fp, sizeof(h->d_fp), hipMemcpyHostToDevice, h->stream));
+        h->jobs_cap = int32_t(std::min<int64_t>(jobs_total + 1, 0x7fffffff));
+        VPRCHK(dev_alloc(h, &h->d_jobs, size_t(h->jobs_cap)));
+        VPRCHK(dev_alloc(h, &h->d_njobs, 1));
+        // device-side result columns
+        DevResults &R = h->dR;
+        memset(&R, 0, sizeof(R));
+        for (int s = 0; s < 4; s++) {
+            const float *vq = nullptr;
+            VPRCHK(dev_upload(h, &vq, b->var_qual[s], size_t(h->n_var[s])));
+            R.var_qual[s] = vq;
+        }
+        // every column vpr_download returns lives in ONE device region (256-byte aligned pieces), so that a caller whose
+        // result block mirrors it (vpr_results_alloc) gets everything with a single copy
+        {
+            uint8_t *base = nullptr;
+            size_t off = 0;
+            auto place = [&](auto *&p, size_t cnt) {
+                using T = std::remove_reference_t<decltype(*p)>;
+                if (base) p = reinterpret_cast<T *>(base + off);
+                off += (std::max<size_t>(cnt, 1) * sizeof(T) + 255) & ~size_t(255);
+            };
+            for (int pass = 0; pass < 2; pass++) {
+                off = 0;
+                for (int s = 0; s < 4; s++)
+                    for (int w = 0; w < 2; w++) {
+                        const size_t nv = size_t(h->n_var[s]);
+                        place(R.v[s][w].errtype, nv); place(R.v[s][w].sync_group, nv); place(R.v[s][w].credit, nv);
+                        place(R.v[s][w].ref_ed, nv); place(R.v[s][w].query_ed, nv); place(R.v[s][w].callq, nv);
+                    }
+                place(R.aln_dist, na); place(R.aln_end_plane, na); place(R.aln_beg_plane, na); place(R.aln_status, na);
+                place(R.sc_phase, size_t(n)); place(R.orig_phase_dist, size_t(n)); place(R.swap_phase_dist, size_t(n));
+                if (pass == 0) {
+                    VPRCHK(dev_alloc(h, &base, off));
+                    h->res_dev = base; h->res_bytes = off;
+                }
+            }
+        }
+        VPRCHK(dev_alloc(h, &R.tally, 6));
+        R.max_qual = h->cfg.max_qual;
+        R.credit_threshold = h->cfg.credit_threshold;
+        R.phase_threshold = h->cfg.phase_threshold;
+        h->tie_list_cap = int32_t(std::min<size_t>(std::max<size_t>(na, 4096), size_t(1) << 20));
+        VPRCHK(dev_alloc(h, &h->d_tie_list, size_t(h->tie_list_cap)));
+        VPRCHK(dev_alloc(h, &h->d_tie_cnt, 8));
+        VPRCHK(dev_alloc(h, &h->d_tie_ndec, TIE_DEC_SLOTS));
+        // fail lists: round 0 in [0, na + na/16 + 256) (a list that feeds a kernel directly is padded), the retry rounds of
+        // the two ladders behind, the tie rounds' (which reject nothing) last
+        const size_t n_fail = 4 * na + na / 16 + 1024, n_slots = 2 + 4 * LadderCtx::N_SLOTS;
+        VPRCHK(dev_alloc(h, &h->d_fail, n_fail));
+        VPRCHK(dev_alloc(h, &h->d_cnt, n_slots));
+        VPRCHK(pin_array(h, &h->hp_fail, n_fail));
+        VPRCHK(pin_array(h, &h->hp_cnt, n_slots));
+        VPRCHK(pin_array(h, &h->hp_tie_list, size_t(h->tie_list_cap)));
+        VPRCHK(pin_array(h, &h->hp_tie_cnt, 32));
+        h->hp_flag = h->hp_tie_cnt + 8;     // [0..1] fail lists of round 0, [2..3] tie lists, [4..7] ladders idle, [8] speculative list
+        memset(h->hp_cnt, 0, n_slots * sizeof(int32_t));
+        memset(h->hp_tie_cnt, 0, 32 * sizeof(int32_t));
+        return VPR_OK;
+    }
+
+    // ---- what the memory plan (M) says, into the handle; round 0's workspace and the four ladders' first workspaces
+    int workspaces() {
+        h->mem_reserve = M.reserve;
+        h->arena_bytes = M.budget;
+        VPRCHK(dev_alloc(h, &h->d_arena, size_t(M.budget) + 256));
+        h->lad_budget = M.lad_half; h->tie_budget = M.tie_half;
+        h->lad_bytes = 0; h->tie_bytes = M.kept_scratch;
+        h->want0 = M.want;
+        if (h->debug) M.print();
+        for (int k = (h->cfg.band_mode != 0 ? 0 : 2); k < 4; k++) {   // (dense mode: only the tie rounds need one)
+            h->lad[k].arena_bytes = M.lad_arena[k];
+            h->lad_bytes += M.lad_arena[k];
+            VPRCHK(dev_alloc(h, &h->lad[k].arena, size_t(M.lad_arena[k]) + 256));
+        }
+        return VPR_OK;
+    }
+
+    // ---- the work list: every alignment, or with VPR_CFG_HAP_DEDUP those that are no copy of another one (k_hap_alias)
+    int work_list() {
+        all.resize(na);
+        h->alias.assign(size_t(n), 0);
+        h->n_aliased = 0;
+        VPRCHK(dev_alloc(h, &h->d_alias, size_t(std::max(n, 1))));
+        HIPCHK(h, hipMemsetAsync(h->d_alias, 0, size_t(std::max(n, 1)), h->stream));
+        if (n && (h->cfg.flags & VPR_CFG_HAP_DEDUP)) {
+            hipLaunchKernelGGL(k_hap_alias, blocks(int64_t(n)), dim3(256), 0, h->stream, D, h->d_alias);
+            HIPCHK(h, hipMemcpyAsync(h->alias.data(), h->d_alias, size_t(n), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, x_sync(h, h->stream, SITE));
+            size_t kept = 0;
+            for (size_t a = 0; a < na; a++)
+                if (alias_source(h->alias[a >> 2], int(a & 3)) < 0) all[kept++] = int32_t(a);
+            h->n_aliased = int64_t(na - kept);
+            all.resize(kept);
+        } else {
+            par_for(na, [&](size_t b0, size_t e0, int) { for (size_t k = b0; k < e0; k++) all[k] = int32_t(k); });
+        }
+        np = all.size();
+        return VPR_OK;
+    }
+
+    // ---- round 0's plan over the work list, cached (descriptors + work list live on the device): on the device where that
+    // applies (plan0_device), else make_plan; the second copy of the long part's forward flags; the alignments' places in the plan
+    int plan_round0() {
+        if (!h->p0.valid) h->level.assign(na, uint8_t(LV_DENSE));      // (else: set by the upload's pass over the superclusters)
+        if (np == na && lv0 <= LV_Q16 && !getenv("VPR_HOST_PLAN")) VPRCHK(plan0_device(h, lv0, h->ev_offsets, &dev_plan));
+        if (!dev_plan) VPRCHK(make_plan(h, all, lv0, h->plan0, h->d_arena, h->arena_bytes, 0, true));
+        lap(dev_plan ? "plan on the device" : "make_plan");
+        // the long part's forward flags are kept a second time (tie rounds copy them back instead of repeating the sweep:
+        // k_fwd_stripe_save / k_restore_stripe): a region as large as the part's share of the workspace -- the front of every
+        // chunk -- unless that is more than 1 GB (a batch of tens of thousands of long alignments is a throughput problem, not a
+        // latency chain)
+        h->d_save = nullptr; h->save_bytes = 0;
+        if (lv0 <= LV_Q16 && LONG_LV == LV_C1 && !h->no_flag_save && !h->plan0.off128.empty()) {
+            int64_t need = 0;
+            for (const Chunk &ch : h->plan0.chunks)
+                if (ch.n_long > 0)
+                    need = std::max<int64_t>(need, ch.n_long < ch.count ? int64_t(h->plan0.off128[size_t(ch.work_off + ch.n_long)]) * 128 : h->plan0.arena_used);
+            if (need > 0 && need <= (int64_t(1) << 30)) {
+                // (optional: without the copy the tie rounds of the long part repeat the forward sweep, as with VPR_NO_FLAG_SAVE)
+                h->soft_alloc = true;
+                const int rc_save = dev_alloc(h, &h->d_save, size_t(need) + 256);
+                h->soft_alloc = false;
+                if (rc_save == VPR_OK) h->save_bytes = need;
+                else { h->d_save = nullptr; h->err.clear(); (void)hipGetLastError(); }
+            }
+        }
+        h->level0 = h->level;
+        if (!dev_plan) {
+            h->plan0_pos.assign(na, -1);
+            par_for(np, [&](size_t b0, size_t e0, int) { for (size_t k = b0; k < e0; k++) h->plan0_pos[size_t(h->plan0.work[k])] = int32_t(k); });
+            VPRCHK(dev_alloc(h, &h->plan0.d_descs, np));
+            VPRCHK(dev_alloc(h, &h->plan0.d_work, np));
+        }
+        return VPR_OK;
+    }
+
+    // ---- round 0's descriptors on the device, in plan order and by alignment, and the zero level's waves
+    int round0_descs() {
+        Plan &P0 = h->plan0;
+        if (h->n_aliased)
+            hipLaunchKernelGGL(k_alias_descs, blocks(int64_t(na)), dim3(256), 0, h->stream, batch_offsets(D), h->d_alias, n, h->d_descs);
+        if (dev_plan) {
+            // (descriptors, wave headers and position words are already enqueued: plan0_device)
+        } else if (np && P0.lazy) {
+            // the plan crosses the link as (alignment, workspace offset) pairs; the device builds both descriptor tables
+            int32_t *hw = nullptr;
+            VPRCHK(pin_array(h, &hw, np * 2));
+            uint32_t *ho = reinterpret_cast<uint32_t *>(hw + np);
+            par_for(np, [&](size_t b0, size_t e0, int) {
+                memcpy(hw + b0, P0.work.data() + b0, (e0 - b0) * 4);
+                memcpy(ho + b0, P0.off128.data() + b0, (e0 - b0) * 4);
+            });
+            uint32_t *d_off = nullptr;
+            VPRCHK(dev_alloc(h, &d_off, np));
+            HIPCHK(h, hipMemcpyAsync(P0.d_work, hw, np * 4, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(d_off, ho, np * 4, hipMemcpyHostToDevice, h->stream));
+            hipLaunchKernelGGL(k_build_plan, blocks(int64_t(np)), dim3(256), 0, h->stream, batch_offsets(D), P0.d_work, d_off, int(np), P0.lv,
+                               P0.long_lt, P0.tag_or, P0.d_descs, h->d_descs);
+        } else if (np) {
+            HIPCHK(h, hipMemcpyAsync(P0.d_descs, P0.descs.data(), np * sizeof(AlnDesc), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(P0.d_work, P0.work.data(), np * 4, hipMemcpyHostToDevice, h->stream));
+            hipLaunchKernelGGL(k_scatter_descs, blocks(int64_t(np)), dim3(256), 0, h->stream, P0.d_descs, int(np), h->d_descs);
+        }
+        if (lv0 == LV_Z && !dev_plan) VPRCHK(prep_zero_lane(h));
+        return VPR_OK;
+    }
+
+    // ---- the wait; what K0 reported and how long it took
+    int finish() {
+        HIPCHK(h, x_sync(h, h->stream, SITE));
+        HIPCHK(h, hipGetLastError());
+        lap("plan + upload");
+        uint32_t err = 0;
+        HIPCHK(h, hipMemcpy(&err, h->d_err, 4, hipMemcpyDeviceToHost));
+        // (err: some supercluster has more than eight swap sources on one position -- DevBatch::sc_limit says which; its four
+        // alignments come back with VPR_ST_ERR_LIMIT, everything else is evaluated)
+        h->n_limit_sc = err ? 1 : 0;
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ev_prep[0], ev_prep[1]);
+        h->timing.ms_prep = ms;
+        h->uploaded = true;
+        return VPR_OK;
+    }
+};
 }  // namespace
 
 
@@ -1196,525 +1785,9 @@ int vpr_upload(vpr_handle *h, const vpr_batch *b) {
     if (!h || !b) return VPR_ERR_ARG;
     if (b->n_sc < 0) return fail(h, VPR_ERR_ARG, "negative n_sc");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const bool dbg = h->debug;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double T0 = now();
-    const bool tim = getenv("VPR_TIMING") != nullptr;       // host-side laps without device synchronisation
-    auto lap = [&](const char *what) {
-        if (dbg) { (void)hipDeviceSynchronize(); fprintf(stderr, "[vpr] upload %-28s %.3f s\n", what, now() - T0); }
-        else if (tim) fprintf(stderr, "[vpr] upload (host) %-28s %.3f s\n", what, now() - T0);
-    };
+    Upload u(h, b);         // (its clock starts here: the first lap is the release)
     free_batch(h);
-    lap("previous batch released");
-    const int n = b->n_sc;
-    h->n_sc = n;
-    DevBatch &D = h->dB;
-    memset(&D, 0, sizeof(D));
-    D.n_sc = n;
-    int rc;
-    int64_t hap_len[4], ref_len = b->ref_off[n];
-    for (int s = 0; s < 4; s++) {
-        hap_len[s] = b->hap_off[s][n];
-        h->n_var[s] = b->var_off[s][n];
-        if ((rc = dev_upload(h, &D.hap_off[s], b->hap_off[s], n + 1))) return rc;
-        if ((rc = dev_upload(h, &D.hap_seq[s], b->hap_seq[s], hap_len[s]))) return rc;
-        if ((rc = dev_upload(h, &D.hap_ptr[s], b->hap_ptr[s], hap_len[s]))) return rc;
-        if ((rc = dev_upload(h, &D.hap_flag[s], b->hap_flag[s], hap_len[s]))) return rc;
-        if ((rc = dev_upload(h, &D.var_off[s], b->var_off[s], n + 1))) return rc;
-        if ((rc = dev_upload(h, &D.var_pos[s], b->var_pos[s], h->n_var[s]))) return rc;
-        h->var_off[s].assign(b->var_off[s], b->var_off[s] + n + 1);
-        h->var_qual[s].assign(b->var_qual[s], b->var_qual[s] + h->n_var[s]);
-        if ((rc = dev_alloc(h, &D.has_ins[s], ref_len))) return rc;
-        if ((rc = dev_alloc(h, &D.vs_hap[s], hap_len[s]))) return rc;
-        if ((rc = dev_alloc(h, &D.dspan[s], size_t(n)))) return rc;
-        if ((rc = dev_alloc(h, &D.sc_hap[s], hap_len[s]))) return rc;
-        HIPCHK(h, hipMemsetAsync(D.has_ins[s], 0, std::max<int64_t>(ref_len, 1), h->stream));
-        if (s == 0) {
-            if ((rc = dev_alloc(h, &D.sc_limit, size_t(std::max(b->n_sc, 1))))) return rc;
-            HIPCHK(h, hipMemsetAsync(D.sc_limit, 0, size_t(std::max(b->n_sc, 1)), h->stream));
-        }
-    }
-    lap("  inputs: haplotype arrays");
-    if ((rc = dev_upload(h, &D.ref_off, b->ref_off, n + 1))) return rc;
-    if ((rc = dev_upload(h, &D.ref_seq, b->ref_seq, ref_len))) return rc;
-    if ((rc = dev_alloc(h, &D.sc_ref, ref_len))) return rc;
-    for (int q = 0; q < 2; q++) {
-        if ((rc = dev_upload(h, &D.ref_ptr[q], b->ref_ptr[q], ref_len))) return rc;
-        if ((rc = dev_upload(h, &D.ref_flag[q], b->ref_flag[q], ref_len))) return rc;
-        if ((rc = dev_alloc(h, &D.cand_q[q], hap_len[q]))) return rc;
-        if ((rc = dev_alloc(h, &D.cand_r[q], ref_len))) return rc;
-        if ((rc = dev_alloc(h, &D.cand2_q[q], hap_len[q]))) return rc;
-        if ((rc = dev_alloc(h, &D.cand2_r[q], ref_len))) return rc;
-        if ((rc = dev_alloc(h, &D.fk_q[q], hap_len[q]))) return rc;
-        if ((rc = dev_alloc(h, &D.fk_r[q], ref_len))) return rc;
-        if ((rc = dev_alloc(h, &D.bk_q[q], hap_len[q]))) return rc;
-        if ((rc = dev_alloc(h, &D.bk_r[q], ref_len))) return rc;
-        if ((rc = dev_alloc(h, &D.vs_ref[q], ref_len))) return rc;
-        if ((rc = dev_alloc(h, &D.fk4_q[q], hap_len[q]))) return rc;
-        if ((rc = dev_alloc(h, &D.fk4_r[q], ref_len))) return rc;
-        if ((rc = dev_alloc(h, &D.tk[q], hap_len[2 + q]))) return rc;
-        if ((rc = dev_alloc(h, &D.tj[q], hap_len[2 + q] + 8))) return rc;
-        if ((rc = dev_alloc(h, &D.wk_q[q], hap_len[q]))) return rc;
-        if ((rc = dev_alloc(h, &D.wk_r[q], ref_len))) return rc;
-        if ((rc = dev_alloc(h, &D.wk_t[q], hap_len[2 + q]))) return rc;
-        if ((rc = dev_alloc(h, &D.xb_q[q], hap_len[q]))) return rc;
-        if ((rc = dev_alloc(h, &D.xb_r[q], ref_len))) return rc;
-        HIPCHK(h, hipMemsetAsync(D.cand_q[q], 0xff, std::max<int64_t>(hap_len[q], 1) * sizeof(int4), h->stream));
-        HIPCHK(h, hipMemsetAsync(D.cand_r[q], 0xff, std::max<int64_t>(ref_len, 1) * sizeof(int4), h->stream));
-        HIPCHK(h, hipMemsetAsync(D.cand2_q[q], 0xff, std::max<int64_t>(hap_len[q], 1) * sizeof(int4), h->stream));
-        HIPCHK(h, hipMemsetAsync(D.cand2_r[q], 0xff, std::max<int64_t>(ref_len, 1) * sizeof(int4), h->stream));
-    }
-    lap("  inputs: reference arrays, constants' blocks");
-    if ((rc = dev_alloc(h, &h->d_err, 1))) return rc;
-    HIPCHK(h, hipMemsetAsync(h->d_err, 0, 4, h->stream));
-    if (!h->ev_offsets) HIPCHK(h, hipEventCreateWithFlags(&h->ev_offsets, hipEventDisableTiming));
-    HIPCHK(h, hipEventRecord(h->ev_offsets, h->stream));       // the batch's offsets are on the device: what the device planner reads
-    if (h->gen_src) {       // the strings, pointers and flags are written on the device from the variant tables (pr_gen.hip)
-        const vpr_variants *v = h->gen_src;
-        GenTables G;
-        GenOut O;
-        memset(&G, 0, sizeof(G));
-        const int64_t ctg_total = v->ctg_off[v->n_ctg];
-        if (ctg_total > h->ctg_bytes) {
-            if (h->d_ctg_seq) (void)x_free(h, h->d_ctg_seq, SITE);
-            h->d_ctg_seq = nullptr; h->ctg_bytes = 0;
-            void *q = nullptr;
-            if (x_malloc(h, &q, size_t(ctg_total) + 256, SITE) != hipSuccess) return fail(h, VPR_ERR_NOMEM, "contig sequence (%lld bytes)", (long long)ctg_total);
-            h->d_ctg_seq = static_cast<uint8_t *>(q);
-            h->ctg_bytes = ctg_total;
-        }
-        if (ctg_total) HIPCHK(h, hipMemcpyAsync(h->d_ctg_seq, v->ctg_seq, size_t(ctg_total), hipMemcpyHostToDevice, h->stream));
-        G.ctg_seq = h->d_ctg_seq;
-        if ((rc = dev_upload(h, &G.ctg_off, v->ctg_off, size_t(v->n_ctg) + 1))) return rc;
-        if ((rc = dev_upload(h, &G.sc_ctg, v->sc_ctg, size_t(n)))) return rc;
-        if ((rc = dev_upload(h, &G.sc_beg, v->sc_beg, size_t(n)))) return rc;
-        if ((rc = dev_upload(h, &G.sc_end, v->sc_end, size_t(n)))) return rc;
-        for (int s = 0; s < 4; s++) {
-            const size_t nv = size_t(h->n_var[s]);
-            std::vector<int64_t> pl(PAR_MAX, 1);
-            par_for(nv, [&](size_t b0, size_t e0, int tid) {
-                int64_t m = 1;
-                for (size_t k = b0; k < e0; k++)
-                    m = std::max(m, std::max(v->var_ref_off[s][k] + v->var_ref_len[s][k], v->var_alt_off[s][k] + v->var_alt_len[s][k]));
-                pl[size_t(tid)] = m;
-            });
-            int64_t pool_len = 1;
-            for (int64_t m : pl) pool_len = std::max(pool_len, m);
-            G.var_pos_rel[s] = D.var_pos[s];
-            if ((rc = dev_upload(h, &G.var_type[s], v->var_type[s], nv))) return rc;
-            if ((rc = dev_upload(h, &G.ref_off[s], v->var_ref_off[s], nv))) return rc;
-            if ((rc = dev_upload(h, &G.alt_off[s], v->var_alt_off[s], nv))) return rc;
-            if ((rc = dev_upload(h, &G.ref_len[s], v->var_ref_len[s], nv))) return rc;
-            if ((rc = dev_upload(h, &G.alt_len[s], v->var_alt_len[s], nv))) return rc;
-            if ((rc = dev_upload(h, &G.pool[s], v->allele_pool[s], size_t(pool_len)))) return rc;
-            O.hap_seq[s] = const_cast<uint8_t *>(D.hap_seq[s]); O.hap_ptr[s] = const_cast<int32_t *>(D.hap_ptr[s]);
-            O.hap_flag[s] = const_cast<uint8_t *>(D.hap_flag[s]);
-        }
-        O.ref_seq = const_cast<uint8_t *>(D.ref_seq);
-        for (int q = 0; q < 2; q++) { O.ref_ptr[q] = const_cast<int32_t *>(D.ref_ptr[q]); O.ref_flag[q] = const_cast<uint8_t *>(D.ref_flag[q]); }
-        if (n > 0) hipLaunchKernelGGL(k_generate, dim3(unsigned((n + 4 * GEN_SC_PER_WAVE - 1) / (4 * GEN_SC_PER_WAVE)), 4), dim3(256), 0, h->stream, D, G, O);
-        HIPCHK(h, hipGetLastError());
-    }
-    lap("inputs copied");
-
-    // ---- K0: position attributes
-    hipEvent_t e0, e1;
-    HIPCHK(h, hipEventCreate(&e0));
-    HIPCHK(h, hipEventCreate(&e1));
-    HIPCHK(h, hipEventRecord(e0, h->stream));
-    auto blocks = [](int64_t n_) { return dim3(unsigned((n_ + 255) / 256)); };
-    if (n > 0) hipLaunchKernelGGL(k_prep_scof, dim3(unsigned((n + 255) / 256), 5), dim3(256), 0, h->stream, D);
-    for (int q = 0; q < 2; q++) {
-        if (hap_len[q] > 0)
-            hipLaunchKernelGGL(k_prep_cand, blocks(hap_len[q]), dim3(256), 0, h->stream, D, q, 0, hap_len[q], h->d_err);
-        if (ref_len > 0)
-            hipLaunchKernelGGL(k_prep_cand, blocks(ref_len), dim3(256), 0, h->stream, D, q, 1, ref_len, h->d_err);
-    }
-    for (int q = 0; q < 2; q++) {
-        if (hap_len[q] > 0) hipLaunchKernelGGL(k_prep_pack, blocks(hap_len[q]), dim3(256), 0, h->stream, D, q, 0, hap_len[q]);
-        if (ref_len > 0) hipLaunchKernelGGL(k_prep_pack, blocks(ref_len), dim3(256), 0, h->stream, D, q, 1, ref_len);
-    }
-    lap("  prep: scof, cand, pack");
-    for (int s = 0; s < 4; s++)
-        if (hap_len[s] > 0)
-            hipLaunchKernelGGL(k_prep_ins, blocks(hap_len[s]), dim3(256), 0, h->stream, D, s, hap_len[s]);
-    if (n > 0) hipLaunchKernelGGL(k_prep_suffix, dim3((n + 4 * SUFFIX_SC_PER_WAVE - 1) / (4 * SUFFIX_SC_PER_WAVE), 6), dim3(256), 0, h->stream, D);
-    {
-        void *pd = nullptr;
-        { int rc_pin = pin_alloc(h, &pd, size_t(std::max(n, 1)) * 4 * sizeof(int2)); if (rc_pin) return rc_pin; }
-        for (int s = 0; s < 4; s++) {
-            h->hp_dspan[s] = static_cast<int2 *>(pd) + size_t(s) * size_t(n);
-            if (n > 0) HIPCHK(h, hipMemcpyAsync(h->hp_dspan[s], D.dspan[s], size_t(n) * sizeof(int2), hipMemcpyDeviceToHost, h->stream));
-        }
-    }
-    lap("  prep: ins, suffix, spans");
-    for (int q = 0; q < 2; q++) {
-        if (hap_len[q] > 0) hipLaunchKernelGGL(k_prep_xb, blocks(hap_len[q]), dim3(256), 0, h->stream, D, q, 0, hap_len[q]);
-        if (ref_len > 0) hipLaunchKernelGGL(k_prep_xb, blocks(ref_len), dim3(256), 0, h->stream, D, q, 1, ref_len);
-    }
-    for (int s = 0; s < 2; s++)
-        if (hap_len[2 + s] > 0) hipLaunchKernelGGL(k_prep_tj, blocks(hap_len[2 + s]), dim3(256), 0, h->stream, D, s, hap_len[2 + s]);
-    for (int w = 0; w < 6; w++) {
-        const int64_t np = w < 2 ? hap_len[w] : (w < 4 ? ref_len : hap_len[w - 2]);
-        if (np > 0) hipLaunchKernelGGL(k_prep_q16, blocks(np), dim3(256), 0, h->stream, D, w, np);
-        if (np > 0) hipLaunchKernelGGL(k_prep_wk, blocks(np), dim3(256), 0, h->stream, D, w, np);
-    }
-    HIPCHK(h, hipEventRecord(e1, h->stream));
-
-    lap("prep kernels");
-    // ---- base descriptors: a function of the offsets (BaseDescs); here only the sums and the checks
-    h->descs.set(b, h->var_off);
-    h->ed_max_len = -1;
-    int64_t sec_total = 0, jobs_total = 0;
-    int64_t cells = 0, bytes_alg = 0;
-    {
-        for (int s = 0; s < 4; s++) sec_total += 2 * b->var_off[s][n];
-        sec_total += 16 * int64_t(n);
-        // ONE pass over the superclusters: the checks and sums of the batch and -- for a windowed round 0 over all alignments, the
-        // usual case -- everything the host contributes to round 0's plan (plan0_device): the level of every alignment, the
-        // parts' sums, the total workspace need (which is also what the arena has to hold), the long alignments.  (Three
-        // passes over four million alignments until round 4, two of them through the full descriptors.)
-        const int lv0_ = h->cfg.band_mode == 0 ? LV_DENSE : h->cfg.band_mode == 2 ? LV_C1 : h->cfg.band_mode == 3 ? LV_Q16 : LV_Z;
-        const bool plan_pass = lv0_ <= LV_Q16 && !(h->cfg.flags & VPR_CFG_HAP_DEDUP) && n > 0;
-        const int LLT = h->long_lt;
-        h->p0 = vpr_handle::Plan0Pass();
-        if (plan_pass) h->level.resize(size_t(n) * 4);
-        struct Acc { int64_t jobs = 0, cells = 0, bytes = 0; int bad = -1; vpr_handle::Plan0Pass P; };
-        std::vector<Acc> acc(PAR_MAX);
-        par_for(size_t(n), [&](size_t b0, size_t e0, int tid) {
-            Acc &A = acc[size_t(tid)];
-            AlnDesc d{};
-            for (size_t scu = b0; scu < e0; scu++) {
-                const int sc = int(scu);
-                const int64_t Lr = b->ref_off[sc + 1] - b->ref_off[sc];
-                int64_t Lh[4];
-                for (int s = 0; s < 4; s++) Lh[s] = b->hap_off[s][sc + 1] - b->hap_off[s][sc];
-                int64_t nv = 0;
-                for (int s = 0; s < 4; s++) nv += b->var_off[s][sc + 1] - b->var_off[s][sc];
-                A.bytes += 6 * (Lh[0] + Lh[1] + Lh[2] + Lh[3]) + 11 * Lr + 26 * nv;
-                if ((Lh[0] < 1 || Lh[1] < 1 || Lh[2] < 1 || Lh[3] < 1 || Lr < 1) && A.bad < 0) A.bad = sc;
-                for (int i = 0; i < 4; i++) {
-                    const int64_t Lq = Lh[i >> 1], Lt = Lh[2 + (i & 1)];
-                    // (deferred sections: both segments longer than 32, or one longer than ED_INLINE_LONG -- segments are disjoint)
-                    A.jobs += std::min(Lr, Lt) / 33 + Lr / (ED_INLINE_LONG + 1) + Lt / (ED_INLINE_LONG + 1);
-                    A.cells += (Lq + Lr) * Lt;
-                    if (!plan_pass) continue;
-                    d.Lq = int32_t(Lq); d.Lr = int32_t(Lr); d.Lt = int32_t(Lt);
-                    d.path_cap = d.Lq + d.Lr + d.Lt + 4;
-                    const int dl = plan_level_of(lv0_, LLT, d.Lt);
-                    const int W = LV_WINDOW[dl], part = d.Lt >= LLT ? 0 : 1;
-                    A.P.part_cells[part] += int64_t(std::min(W, d.Lq) + std::min(W, d.Lr)) * d.Lt;
-                    A.P.part_in[part] += 6 * int64_t(d.Lq) + 6 * int64_t(d.Lt) + 6 * int64_t(d.Lr);
-                    A.P.part_dense[part] += int64_t(d.Lq + d.Lr) * d.Lt;
-                    A.P.part_rows[part] += d.Lt;
-                    h->level[size_t(sc) * 4 + size_t(i)] = uint8_t(dl);
-                    if (d.Lt >= LLT)
-                        A.P.big.emplace_back(-(int64_t(round_up(std::min(W, d.Lq), 16) + round_up(std::min(W, d.Lr), 16)) * d.Lt), int32_t(sc * 4 + i));
-                    const int64_t need = window_layout(d, dl, 0, 0);
-                    A.P.need128 += need / 128;
-                    A.P.need_max = std::max(A.P.need_max, need);
-                    if ((d.Lt < LLT && d.Lt > 0xfffe) || d.Lq < 1 || d.Lr < 1 || d.Lt < 1) A.P.bad = true;
-                }
-            }
-        });
-        int bad = -1;
-        for (const Acc &A : acc) {
-            jobs_total += A.jobs; cells += A.cells; bytes_alg += A.bytes;
-            if (A.bad >= 0 && (bad < 0 || A.bad < bad)) bad = A.bad;
-            for (int q = 0; q < 2; q++) {
-                h->p0.part_cells[q] += A.P.part_cells[q]; h->p0.part_in[q] += A.P.part_in[q];
-                h->p0.part_dense[q] += A.P.part_dense[q]; h->p0.part_rows[q] += A.P.part_rows[q];
-            }
-            h->p0.need128 += A.P.need128; h->p0.need_max = std::max(h->p0.need_max, A.P.need_max);
-            h->p0.bad = h->p0.bad || A.P.bad;
-            h->p0.big.insert(h->p0.big.end(), A.P.big.begin(), A.P.big.end());
-        }
-        h->p0.valid = plan_pass;
-        if (bad >= 0) return fail(h, VPR_ERR_ARG, "supercluster %d has an empty string", bad);
-    }
-    bytes_alg += 2 * cells;
-    h->timing.cells_dense = cells;
-    h->timing.bytes_algorithmic = bytes_alg;
-
-    lap("descriptors");
-    const size_t na = h->descs.size();
-    if ((rc = dev_alloc(h, &h->d_descs, na))) return rc;
-    if ((rc = dev_alloc(h, &h->d_outs, na))) return rc;
-    h->n_secs_cap = sec_total;
-    if ((rc = dev_alloc(h, &h->d_secs, size_t(sec_total)))) return rc;
-    for (int q = 0; q < 4; q++)
-        if ((rc = dev_alloc(h, &h->d_fp[q], size_t(h->n_var[q >> 1])))) return rc;
-    if ((rc = dev_alloc(h, &h->d_fp_table, 4))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_fp_table, h->d_fp, sizeof(h->d_fp), hipMemcpyHostToDevice, h->stream));
-    h->jobs_cap = int32_t(std::min<int64_t>(jobs_total + 1, 0x7fffffff));
-    if ((rc = dev_alloc(h, &h->d_jobs, size_t(h->jobs_cap)))) return rc;
-    if ((rc = dev_alloc(h, &h->d_njobs, 1))) return rc;
-    // device-side result columns
-    DevResults &R = h->dR;
-    memset(&R, 0, sizeof(R));
-    for (int s = 0; s < 4; s++) {
-        const float *vq = nullptr;
-        if ((rc = dev_upload(h, &vq, b->var_qual[s], size_t(h->n_var[s])))) return rc;
-        R.var_qual[s] = vq;
-    }
-    // every column vpr_download returns lives in ONE device region (256-byte aligned pieces), so that a caller whose
-    // result block mirrors it (vpr_results_alloc) gets everything with a single copy
-    {
-        uint8_t *base = nullptr;
-        size_t off = 0;
-        auto place = [&](auto *&p, size_t cnt) {
-            using T = std::remove_reference_t<decltype(*p)>;
-            if (base) p = reinterpret_cast<T *>(base + off);
-            off += (std::max<size_t>(cnt, 1) * sizeof(T) + 255) & ~size_t(255);
-        };
-        for (int pass = 0; pass < 2; pass++) {
-            off = 0;
-            for (int s = 0; s < 4; s++)
-                for (int w = 0; w < 2; w++) {
-                    const size_t nv = size_t(h->n_var[s]);
-                    place(R.v[s][w].errtype, nv); place(R.v[s][w].sync_group, nv); place(R.v[s][w].credit, nv);
-                    place(R.v[s][w].ref_ed, nv); place(R.v[s][w].query_ed, nv); place(R.v[s][w].callq, nv);
-                }
-            place(R.aln_dist, na); place(R.aln_end_plane, na); place(R.aln_beg_plane, na); place(R.aln_status, na);
-            place(R.sc_phase, size_t(n)); place(R.orig_phase_dist, size_t(n)); place(R.swap_phase_dist, size_t(n));
-            if (pass == 0) {
-                if ((rc = dev_alloc(h, &base, off))) return rc;
-                h->res_dev = base; h->res_bytes = off;
-            }
-        }
-    }
-    if ((rc = dev_alloc(h, &R.tally, 6))) return rc;
-    R.max_qual = h->cfg.max_qual;
-    R.credit_threshold = h->cfg.credit_threshold;
-    R.phase_threshold = h->cfg.phase_threshold;
-    h->tie_list_cap = int32_t(std::min<size_t>(std::max<size_t>(na, 4096), size_t(1) << 20));
-    if ((rc = dev_alloc(h, &h->d_tie_list, size_t(h->tie_list_cap)))) return rc;
-    if ((rc = dev_alloc(h, &h->d_tie_cnt, 8))) return rc;
-    if ((rc = dev_alloc(h, &h->d_tie_ndec, TIE_DEC_SLOTS))) return rc;
-    // fail lists: round 0 in [0, na + na/16 + 256) (a list that feeds a kernel directly is padded), the retry rounds of
-    // the two ladders behind, the tie rounds' (which reject nothing) last
-    const size_t n_fail = 4 * na + na / 16 + 1024, n_slots = 2 + 4 * LadderCtx::N_SLOTS;
-    if ((rc = dev_alloc(h, &h->d_fail, n_fail))) return rc;
-    if ((rc = dev_alloc(h, &h->d_cnt, n_slots))) return rc;
-    {
-        void *pf = nullptr, *pc = nullptr, *pl = nullptr, *pt = nullptr;
-        { int rc_pin = pin_alloc(h, &pf, n_fail * sizeof(int32_t)); if (rc_pin) return rc_pin; }
-        { int rc_pin = pin_alloc(h, &pc, n_slots * sizeof(int32_t)); if (rc_pin) return rc_pin; }
-        { int rc_pin = pin_alloc(h, &pl, size_t(h->tie_list_cap) * sizeof(int4)); if (rc_pin) return rc_pin; }
-        { int rc_pin = pin_alloc(h, &pt, 32 * sizeof(int32_t)); if (rc_pin) return rc_pin; }
-        h->hp_fail = static_cast<int32_t *>(pf);
-        h->hp_cnt = static_cast<int32_t *>(pc);
-        h->hp_tie_list = static_cast<int4 *>(pl);
-        h->hp_tie_cnt = static_cast<int32_t *>(pt);
-        h->hp_flag = h->hp_tie_cnt + 8;     // [0..1] fail lists of round 0, [2..3] tie lists, [4..7] ladders idle, [8] speculative list
-        memset(h->hp_cnt, 0, n_slots * sizeof(int32_t));
-        memset(h->hp_tie_cnt, 0, 32 * sizeof(int32_t));
-    }
-
-    lap("result/aux allocations");
-    // ---- arena for flag matrices, band origins and walks
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
-    {   // (the driver's figure lags behind this process's own large frees: dev_books)
-        const int64_t fb = books_free(int64_t(free_b), int64_t(total_b));
-        if (h->debug && fb != int64_t(free_b)) fprintf(stderr, "[vpr] memory plan: the driver reports %.1f GB free, the books %.1f\n", double(free_b) / 1e9, double(fb) / 1e9);
-        free_b = size_t(fb);
-    }
-    // what the batch may take: the free memory (the blocks kept from the previous batch count: the allocations below take
-    // them first) less the tenth of the device the library leaves alone; on a device mostly taken by others, half of what is free
-    int64_t avail = int64_t(free_b), avail_cache = 0;
-    for (const auto &c : h->dev_cache) avail_cache += int64_t(c.bytes);
-    avail += avail_cache;
-    int64_t scratch_kept = 0;            // (the replay scratches have the handle's lifetime: part of the plan, and taken already)
-    for (int k = 0; k < 4; k++) for (int e = 0; e < 2; e++) scratch_kept += h->lad[k].tie_scratch_bytes[e];
-    avail += scratch_kept;
-    h->mem_reserve = int64_t(double(total_b) * free_share());
-    avail = std::max<int64_t>(avail - h->mem_reserve, avail / 2);
-    // What the upload allocates BEHIND this plan comes off first (ADVICE r5: the ladders' and replays' halves were promised memory
-    // the lane levels then took): the lane levels' interleaved position words (4 B per position of the short part) and logs
-    // (20 B per truth row), padded to the waves' longest alignments (measured: < 15 %), the distance-1 level's blocks (0.8 of
-    // both, zl_finish), the device planner's temporaries (28 B per alignment) and the saved forward flags of the long part.
-    int64_t lane_est = 0;
-    if (h->p0.valid && h->cfg.band_mode != 0 && h->cfg.band_mode != 2) {
-        const double zl = 1.15 * (double(h->p0.part_in[1]) / 6.0 * 4.0 + 20.0 * double(h->p0.part_rows[1]));
-        lane_est = int64_t(zl * (getenv("VPR_NO_D1") ? 1.0 : 1.8)) + 28 * int64_t(h->descs.size());
-        avail = std::max<int64_t>(avail - lane_est, avail / 2);
-    }
-    int64_t budget = h->cfg.workspace_bytes > 0 ? h->cfg.workspace_bytes : int64_t(double(avail) * arena_share());
-    if (budget < (8 << 20)) budget = 8 << 20;
-    // do not allocate more than round 0 can use (its layout per alignment: make_plan)
-    int64_t want = 0;
-    {
-        const int bm = h->cfg.band_mode;
-        const bool q16ok = (bm == 1 || bm == 3);
-        std::vector<int64_t> wants(PAR_MAX, 0);
-        if (h->p0.valid) wants[0] = h->p0.need128 * 128 + 4096;       // (exactly what round 0's plan will ask for)
-        else
-        par_for(h->descs.size(), [&](size_t b0, size_t e0, int tid) {
-          int64_t want = 0;
-          for (size_t k = b0; k < e0; k++) {
-            const AlnDesc &d = h->descs[k];
-            int64_t flags;
-            if (bm != 0 && q16ok && d.Lt < h->long_lt) {
-                const int64_t nstr = (int64_t(d.Lt) + 3) / 4;
-                flags = nstr * 128 + round_up(nstr * 8, 64);
-            } else if (bm != 0) {
-                const int W = (q16ok && bm != 2) ? LV_WINDOW[LONG_LV] : 64;
-                flags = round_up(round_up(std::min(W, d.Lq), 16) * int64_t(d.Lt), 64) +
-                        round_up(round_up(std::min(W, d.Lr), 16) * int64_t(d.Lt), 64) + round_up(8 * int64_t(d.Lt), 64);
-            } else {
-                flags = round_up(round_up(d.Lq, 32) * int64_t(d.Lt), 64) + round_up(round_up(d.Lr, 32) * int64_t(d.Lt), 64);
-            }
-            want += flags + round_up(int64_t(d.path_cap) * int64_t(sizeof(PathEnt)) + 128, 128) + 256;
-          }
-          wants[size_t(tid)] = want;
-        });
-        for (int64_t w : wants) want += w;
-        if (h->cfg.workspace_bytes <= 0) budget = std::min(budget, std::max<int64_t>(want, 256 << 20));
-    }
-    h->arena_bytes = budget;
-    if ((rc = dev_alloc(h, &h->d_arena, size_t(budget) + 256))) return rc;
-    // What round 0 left is split between the ladders' workspaces and the replay scratches.  The ladders (two retry ladders
-    // beside round 0, two for the tie rounds) start with a sixteenth of round 0's need each -- the short part's with at most
-    // 2 GB -- and grow on demand inside their half (lad_grow); the replay scratches are allocated by the first tie round
-    // (cfg.workspace_bytes bounds each workspace instead).
-    {
-        const int64_t rest = std::max<int64_t>(avail - budget, 0);
-        h->lad_budget = rest / 2; h->tie_budget = rest - rest / 2;
-        h->lad_bytes = 0; h->tie_bytes = scratch_kept;
-        h->want0 = want;
-        // (a handle that has released a batch knows what its ladders grew to: the same fraction of this batch's round-0 need,
-        // all four scaled down together if that is more than the ladders' half)
-        int64_t first[4] = {0, 0, 0, 0}, first_sum = 0;
-        for (int k = 0; k < 4; k++) {
-            int64_t b2 = std::min<int64_t>(h->lad_budget / 4, int64_t(ladder_share() * double(std::max<int64_t>(want / 16, int64_t(1) << 30))));
-            if (k & 1) b2 = std::min<int64_t>(b2, int64_t(2) << 30);
-            first[k] = std::max<int64_t>(b2, std::min<int64_t>(int64_t(h->lad_hw[k] * double(want)), h->lad_arena_max));
-            first_sum += first[k];
-        }
-        const double shrink = first_sum > h->lad_budget && first_sum > 0 ? double(h->lad_budget) / double(first_sum) : 1.0;
-        if (h->debug)
-            fprintf(stderr, "[vpr] memory plan: free %.1f GB + kept blocks %.1f + scratches %.1f, reserve %.1f, lane levels %.1f -> %.1f to plan; round 0 wants %.1f, gets %.1f; "
-                            "ladders' half %.1f (first workspaces %.1f %.1f %.1f %.1f), replays' half %.1f\n",
-                    double(free_b) / 1e9, double(avail_cache) / 1e9, double(scratch_kept) / 1e9, double(h->mem_reserve) / 1e9, double(lane_est) / 1e9, double(avail) / 1e9,
-                    double(want) / 1e9, double(budget) / 1e9, double(h->lad_budget) / 1e9, double(first[0]) * shrink / 1e9, double(first[1]) * shrink / 1e9,
-                    double(first[2]) * shrink / 1e9, double(first[3]) * shrink / 1e9, double(h->tie_budget) / 1e9);
-        for (int k = (h->cfg.band_mode != 0 ? 0 : 2); k < 4; k++) {   // (dense mode: only the tie rounds need one)
-            int64_t b2 = h->cfg.workspace_bytes;
-            if (b2 <= 0) b2 = int64_t(double(first[k]) * shrink);
-            if (b2 < (8 << 20)) b2 = 8 << 20;
-            h->lad[k].arena_bytes = b2;
-            h->lad_bytes += b2;
-            if ((rc = dev_alloc(h, &h->lad[k].arena, size_t(b2) + 256))) return rc;
-        }
-    }
-
-    lap("arena allocation");
-    // ---- round-0 plan over all alignments, cached (descriptors + work list live on the device)
-    std::vector<int32_t> &all = h->scratch_i32[1];
-    all.resize(na);
-    h->alias.assign(size_t(b->n_sc), 0);
-    h->n_aliased = 0;
-    if ((rc = dev_alloc(h, &h->d_alias, size_t(std::max(b->n_sc, 1))))) return rc;
-    HIPCHK(h, hipMemsetAsync(h->d_alias, 0, size_t(std::max(b->n_sc, 1)), h->stream));
-    if (b->n_sc && (h->cfg.flags & VPR_CFG_HAP_DEDUP)) {
-        hipLaunchKernelGGL(k_hap_alias, blocks(int64_t(b->n_sc)), dim3(256), 0, h->stream, D, h->d_alias);
-        HIPCHK(h, hipMemcpyAsync(h->alias.data(), h->d_alias, size_t(b->n_sc), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, x_sync(h, h->stream, SITE));
-        size_t np = 0;
-        for (size_t a = 0; a < na; a++)
-            if (alias_source(h->alias[a >> 2], int(a & 3)) < 0) all[np++] = int32_t(a);
-        h->n_aliased = int64_t(na - np);
-        all.resize(np);
-    } else {
-        par_for(na, [&](size_t b0, size_t e0, int) { for (size_t k = b0; k < e0; k++) all[k] = int32_t(k); });
-    }
-    const size_t np = all.size();      // alignments that are computed
-    if (!h->p0.valid) h->level.assign(na, uint8_t(LV_DENSE));      // (else: set by the upload's pass over the superclusters)
-    const int lv0 = h->cfg.band_mode == 0 ? LV_DENSE
-                    : h->cfg.band_mode == 2 ? LV_C1
-                    : h->cfg.band_mode == 3 ? LV_Q16 : LV_Z;
-    bool dev_plan = false;
-    if (np == na && lv0 <= LV_Q16 && !getenv("VPR_HOST_PLAN") && (rc = plan0_device(h, lv0, h->ev_offsets, &dev_plan))) return rc;
-    if (!dev_plan && (rc = make_plan(h, all, lv0, h->plan0, h->d_arena, h->arena_bytes, 0, true))) return rc;
-    lap(dev_plan ? "plan on the device" : "make_plan");
-    // the long part's forward flags are kept a second time (tie rounds copy them back instead of repeating the sweep:
-    // k_fwd_stripe_save / k_restore_stripe): a region as large as the part's share of the workspace -- the front of every
-    // chunk -- unless that is more than 1 GB (a batch of tens of thousands of long alignments is a throughput problem, not a
-    // latency chain)
-    h->d_save = nullptr; h->save_bytes = 0;
-    if (lv0 <= LV_Q16 && LONG_LV == LV_C1 && !h->no_flag_save && !h->plan0.off128.empty()) {
-        int64_t need = 0;
-        for (const Chunk &ch : h->plan0.chunks)
-            if (ch.n_long > 0)
-                need = std::max<int64_t>(need, ch.n_long < ch.count ? int64_t(h->plan0.off128[size_t(ch.work_off + ch.n_long)]) * 128 : h->plan0.arena_used);
-        if (need > 0 && need <= (int64_t(1) << 30)) {
-            // (optional: without the copy the tie rounds of the long part repeat the forward sweep, as with VPR_NO_FLAG_SAVE)
-            h->soft_alloc = true;
-            const int rc_save = dev_alloc(h, &h->d_save, size_t(need) + 256);
-            h->soft_alloc = false;
-            if (rc_save == VPR_OK) h->save_bytes = need;
-            else { h->d_save = nullptr; h->err.clear(); (void)hipGetLastError(); }
-        }
-    }
-    h->level0 = h->level;
-    if (!dev_plan) {
-        h->plan0_pos.assign(na, -1);
-        par_for(np, [&](size_t b0, size_t e0, int) { for (size_t k = b0; k < e0; k++) h->plan0_pos[size_t(h->plan0.work[k])] = int32_t(k); });
-        if ((rc = dev_alloc(h, &h->plan0.d_descs, np))) return rc;
-        if ((rc = dev_alloc(h, &h->plan0.d_work, np))) return rc;
-    }
-    lap("plan0_pos");
-    if (h->n_aliased) {
-        BatchOffsets DO;
-        for (int s = 0; s < 4; s++) { DO.hap_off[s] = D.hap_off[s]; DO.var_off[s] = D.var_off[s]; }
-        DO.ref_off = D.ref_off;
-        hipLaunchKernelGGL(k_alias_descs, blocks(int64_t(na)), dim3(256), 0, h->stream, DO, h->d_alias, b->n_sc, h->d_descs);
-    }
-    if (dev_plan) {
-        // (descriptors, wave headers and position words are already enqueued: plan0_device)
-    } else if (np && h->plan0.lazy) {
-        // the plan crosses the link as (alignment, workspace offset) pairs; the device builds both descriptor tables
-        void *pw = nullptr;
-        { int rc_pin = pin_alloc(h, &pw, np * 8); if (rc_pin) return rc_pin; }
-        int32_t *hw = static_cast<int32_t *>(pw);
-        uint32_t *ho = reinterpret_cast<uint32_t *>(hw + np);
-        const Plan &P0 = h->plan0;
-        par_for(np, [&](size_t b0, size_t e0, int) {
-            memcpy(hw + b0, P0.work.data() + b0, (e0 - b0) * 4);
-            memcpy(ho + b0, P0.off128.data() + b0, (e0 - b0) * 4);
-        });
-        uint32_t *d_off = nullptr;
-        if ((rc = dev_alloc(h, &d_off, np))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->plan0.d_work, hw, np * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(d_off, ho, np * 4, hipMemcpyHostToDevice, h->stream));
-        BatchOffsets DO;
-        for (int s = 0; s < 4; s++) { DO.hap_off[s] = D.hap_off[s]; DO.var_off[s] = D.var_off[s]; }
-        DO.ref_off = D.ref_off;
-        hipLaunchKernelGGL(k_build_plan, blocks(int64_t(np)), dim3(256), 0, h->stream, DO, h->plan0.d_work, d_off, int(np), P0.lv,
-                           P0.long_lt, P0.tag_or, h->plan0.d_descs, h->d_descs);
-    } else if (np) {
-        HIPCHK(h, hipMemcpyAsync(h->plan0.d_descs, h->plan0.descs.data(), np * sizeof(AlnDesc), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->plan0.d_work, h->plan0.work.data(), np * 4, hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(k_scatter_descs, blocks(int64_t(np)), dim3(256), 0, h->stream, h->plan0.d_descs, int(np), h->d_descs);
-    }
-    if (lv0 == LV_Z && !dev_plan && (rc = prep_zero_lane(h))) return rc;
-
-    HIPCHK(h, x_sync(h, h->stream, SITE));
-    HIPCHK(h, hipGetLastError());
-    lap("plan + upload");
-    uint32_t err = 0;
-    HIPCHK(h, hipMemcpy(&err, h->d_err, 4, hipMemcpyDeviceToHost));
-    // (err: some supercluster has more than eight swap sources on one position -- DevBatch::sc_limit says which; its four
-    // alignments come back with VPR_ST_ERR_LIMIT, everything else is evaluated)
-    h->n_limit_sc = err ? 1 : 0;
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    h->timing.ms_prep = ms;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    h->uploaded = true;
-    return VPR_OK;
+    return u.run();
 }
 
 int vpr_upload_variants(vpr_handle *h, const vpr_variants *v) {
@@ -1827,8 +1900,6 @@ struct Exec {
         for (const Chunk &ch : P0.chunks) n_long_all += ch.n_long;
         if (n_long_all >= LONG_BULK) std::swap(s_long, s_short);
     }
-
-    static dim3 blocks(int64_t n_) { return dim3(unsigned((n_ + 255) / 256)); }
 
     // HIP events bracket each launch on the stream the kernel is launched on
     bool need_err_check = false;    // a dense round holds an alignment only the strips can take: did the planner cut it?

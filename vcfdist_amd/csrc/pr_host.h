@@ -1,6 +1,6 @@
 // pr_host.h -- host-side types of the library shared by its translation units: the planning structures, the handle, and the
 // helpers every unit calls (error reporting, the counted allocator calls, device and page-locked blocks of the batch / the execute).
-//   pr_api.hip      planner, vpr_create / vpr_upload (memory plan) / vpr_execute (Exec), all device kernels of the path
+//   pr_api.hip      planner, vpr_create / vpr_upload (Upload: its stages; MemPlan: the memory plan) / vpr_execute (Exec), all device kernels of the path
 //   pr_mem.hip      allocator wrappers, the process-wide books of device memory, block caches (dev_alloc, pin_alloc, exec_alloc)
 //   pr_results.hip  vpr_download, vpr_results_alloc, tallies, timing and launch statistics
 //   pr_collect.hip  the counters histogram, vpr_pr_counts, and the RCCL collectives (vpr_allreduce_counts, vpr_allgather_phase);
@@ -454,6 +454,12 @@ const char *vpr_create_error();                                      // the mess
         if (e_ != hipSuccess)                                                                   \
             return fail(h, VPR_ERR_DEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
+// the same for a call of the library's own that returns a VPR_ code (its message is already in the handle)
+#define VPRCHK(call)                                                                            \
+    do {                                                                                        \
+        const int rc_ = (call);                                                                 \
+        if (rc_) return rc_;                                                                    \
+    } while (0)
 #define SITE_STR2(x) #x
 #define SITE_STR(x) SITE_STR2(x)
 #define SITE __FILE__ ":" SITE_STR(__LINE__)
@@ -509,6 +515,14 @@ template <typename T>
 int dev_alloc(vpr_handle *h, T **p, size_t n) {
     void *q = nullptr;
     const int rc = dev_alloc_bytes(h, &q, (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~size_t(255));
+    *p = static_cast<T *>(q);
+    return rc;
+}
+// n elements of page-locked host memory of the batch's lifetime (pin_alloc)
+template <typename T>
+int pin_array(vpr_handle *h, T **p, size_t n) {
+    void *q = nullptr;
+    const int rc = pin_alloc(h, &q, n * sizeof(T));
     *p = static_cast<T *>(q);
     return rc;
 }
