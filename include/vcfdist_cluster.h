@@ -91,10 +91,17 @@ typedef struct vcl_wfa_stats {
 } vcl_wfa_stats;
 
 /* Clusters of one (callset, hap) on one contig.  sub/open/extend: g.sub, g.open, g.extend (defaults 5, 6, 2);
-   max_cluster_itrs: g.max_cluster_itrs (4); reach_min_gap: g.reach_min_gap (10).  device: HIP device ordinal. */
+   max_cluster_itrs: g.max_cluster_itrs (4); reach_min_gap: g.reach_min_gap (10).  device: HIP device ordinal.
+   VCL_ERR_ARG for a variant at position 0 (a cluster's region starts one base in front of its first variant; the reference
+   exits there) or one that passes the contig's end. */
 int vcl_wfa_cluster(const vcl_hap_seq *hap, const uint8_t *ctg_seq, int32_t ctg_len, int32_t sub, int32_t open,
                     int32_t extend, int32_t max_cluster_itrs, int32_t reach_min_gap, int32_t device,
                     vcl_clusters **out, vcl_wfa_stats *stats);
+
+/* Which kernel variant the calling thread's last vcl_wfa_cluster call ran (read-only, reset when that call is entered): jobs
+   and kernel launches per size class.  Classes 0..3: strings and ring in 8 / 16 / 32 / 64 KiB of LDS; class 4: the
+   global-scratch variant.  Align and reach jobs of every iteration and doubling round are counted together. */
+int vcl_wfa_last_classes(int64_t jobs[5], int64_t launches[5]);
 
 /* max_query_len * max_truth_len of supercluster k (the factor in front of the 20 B/cell of cluster.cpp:99) */
 int64_t vcl_supercluster_cells(const vcl_hap haps[4], const vcl_superclusters *s, int32_t k);

@@ -219,6 +219,9 @@ int vco_wfa_cluster(const vcl_hap_seq *hs, const uint8_t *ctg_seq, int32_t ctg_l
         vars.alts.emplace_back(reinterpret_cast<const char *>(hs->pool + hs->alt_off[v]), size_t(h->alt_len[v]));
     }
     const std::string fasta(reinterpret_cast<const char *>(ctg_seq), size_t(ctg_len));
+    // a variant at position 0 (the region starts one base in front of it) or past the contig's end: the reference exits
+    for (int v = 0; v < vars.n; v++)
+        if (vars.poss[v] < 1 || vars.poss[v] + vars.rlens[v] > ctg_len) return VCL_ERR_ARG;
     vcl_wfa_stats st;
     memset(&st, 0, sizeof(st));
     std::vector<int> left_reach, right_reach, prev_clusters;

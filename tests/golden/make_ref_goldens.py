@@ -1,7 +1,7 @@
 """Regenerates tests/golden/ref/: cases and what the REFERENCE's own functions answer for them (oracle/_ref/ref_harness, built by
 `make -C oracle ref` where the reference's sources are at hand).  Seeded and deterministic; refuses to run without the
 harness.  tests/ref_pins.py describes the files; tests/golden/README.md the case sets.  Run from the repository's root:
-    python tests/golden/make_ref_goldens.py [set ...]          (sets: swg ed cluster chain demo realign window_edges; default: all)"""
+    python tests/golden/make_ref_goldens.py [set ...]          (sets: swg ed cluster chain demo realign window_edges cluster_edges; default: all)"""
 import os
 import sys
 import time
@@ -317,6 +317,32 @@ def make_cluster():
         save(name, "cluster", variants_to_case(v, args + base), 600)
 
 
+def cluster_edge_case(cases, pen, itrs):
+    """cases of tests/wfa_cluster_cases.py as one cluster case: a contig per case, its variants as query hap 1"""
+    sites = [(ci, p, t, r, a, 30.0) for ci, c in enumerate(cases) for p, t, r, a in c.variants]
+    args = ["-c", "biwfa", "-x", str(pen[0]), "-o", str(pen[1]), "-e", str(pen[2]), "-i", str(itrs), "-t", "4", "-v", "0", "-n"]
+    return R.chain_case([(c.name, c.ctg.encode()) for c in cases], [R.slot_from_sites(sites)] + [R.empty_slot()] * 3, args)
+
+
+def make_cluster_edges():
+    """tests/wfa_cluster_cases.py: the biWFA clustering at its size classes, lane chunks, ring length, doubling rounds, contig ends
+    and merge passes.  One fixture per penalty set and iteration limit (the arguments are per fixture); a case of undefined input
+    is a fixture of its own, `_refused` where the reference refuses it"""
+    import wfa_cluster_cases as WC
+    names = lambda cases: dict(case_names=np.frombuffer("\n".join(c.name for c in cases).encode(), np.uint8))
+    for (pen, itrs), cases in sorted(WC.fixture_sets().items()):
+        out = save(WC.fixture_name(pen, itrs), "cluster", cluster_edge_case(cases, pen, itrs), 300, extra=names(cases))
+        assert not isinstance(out, str), out
+    for c in WC.UNDEFINED:
+        case = cluster_edge_case([c], c.pen, c.itrs[0])
+        try:
+            R.run_harness("cluster", case, timeout=60)
+            tail = ""
+        except R.Refused:
+            tail = "_refused"
+        save("cluster_biwfa_edges_" + c.name[len("edge_"):] + tail, "cluster", case, 60, extra=names([c]))
+
+
 def demo_case(args):
     import demo_pipeline as DP
     from vcfdist_amd import io as IO
@@ -387,7 +413,7 @@ def make_realign():
 
 
 SETS = {"swg": make_swg, "ed": make_ed, "cluster": make_cluster, "chain": make_chain, "demo": make_demo, "realign": make_realign,
-        "window_edges": make_window_edges}          # (chain_window_edges: a set of its own, it computes needed_level for the whole table)
+        "window_edges": make_window_edges, "cluster_edges": make_cluster_edges}          # (chain_window_edges: a set of its own, it computes needed_level for the whole table)
 
 
 def main(argv):

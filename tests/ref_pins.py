@@ -23,7 +23,9 @@ Cases
              p<s>_<w>_{errtype, sync_group, callq, ref_ed, query_ed, credit} per variant (rows as the input's) and phasing w;
              with -d ed_{ctg, pos, hap, type, len, sc, min_qual, max_qual}; realign: r<s>_* the realigned tables.
   chain_window_edges also stores x_case_names: the names of its cases in tests/window_edge_cases.py's table, one per line, in the
-             order of its contigs (a contig and, with `-c gap 2000`, a supercluster per case)."""
+             order of its contigs (a contig and, with `-c gap 2000`, a supercluster per case).
+  cluster_biwfa_edges_* store x_case_names likewise: the names of their cases in tests/wfa_cluster_cases.py's table, a contig per
+             case, the case's variants in slot 0."""
 import os
 import re
 import subprocess

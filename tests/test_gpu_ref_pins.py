@@ -21,7 +21,7 @@ ERR_LIMIT = 128          # VPR_ST_ERR_LIMIT
 
 CHAIN = [n for n in R.fixture_names("chain_") + R.fixture_names("demo_") if R.Fixture(n).refused is None]
 REALIGN = R.fixture_names("realign_")
-BIWFA = [n for n in CHAIN + R.fixture_names("cluster_") if R.case_args(R.Fixture(n).case)["cluster"][0] == "biwfa" and not n.endswith("_d")]
+BIWFA = [n for n in CHAIN + [n for n in R.fixture_names("cluster_") if not n.endswith("_refused")] if R.case_args(R.Fixture(n).case)["cluster"][0] == "biwfa" and not n.endswith("_d")]
 # _limit_batch's run of k directly adjacent one-base deletion records (it starts at position 200).  A position keeps up to eight
 # allowed swap sources (pr_device.h); behind a run of k records there are k + 1, so k = 7 is the most the library evaluates and
 # k = 8, 9, 12 come back with VPR_ST_ERR_LIMIT: that refusal is what is asserted here, the fixture's answer for those superclusters

@@ -27,11 +27,13 @@ SWG = R.fixture_names("swg_")
 ED = R.fixture_names("ed_")
 CHAIN = R.fixture_names("chain_") + R.fixture_names("demo_")
 REALIGN = R.fixture_names("realign_")
+# (a refused cluster case, cluster_biwfa_edges_pos0_refused, is held by tests/test_wfa_cluster_cases.py)
+CLUSTER = [n for n in R.fixture_names("cluster_") if not n.endswith("_refused")]
 
 
 def test_the_fixture_sets_are_there():
     """every set of tests/golden/README.md: a missing directory must not turn the parametrised pins below into nothing"""
-    assert len(SWG) >= 6 + 8 + 2 and len(ED) >= 4 and len(REALIGN) >= 3 + 5 and len(R.fixture_names("cluster_")) >= 7
+    assert len(SWG) >= 6 + 8 + 2 and len(ED) >= 4 and len(REALIGN) >= 3 + 5 and len(CLUSTER) >= 7 + 11
     assert len([n for n in CHAIN if n.startswith("chain_")]) >= 6 + 1 + 6 + 4 + 2 + 6 and len([n for n in CHAIN if n.startswith("demo_")]) == 6
     for pen in ("562", "321", "432", "111", "921", "132"):
         assert f"swg_hand_{pen}" in SWG
@@ -159,9 +161,10 @@ def oracle_pr(v):
     return O.run(O.generate(v))
 
 
-@pytest.mark.parametrize("name", R.fixture_names("cluster_"))
+@pytest.mark.parametrize("name", CLUSTER)
 def test_cluster_oracles_equal_the_reference_clusters(name):
-    """simple_cluster (gap and size) and wf_swg_cluster on whole synthetic contigs, other penalties and iteration limits"""
+    """simple_cluster (gap and size) and wf_swg_cluster on whole synthetic contigs, other penalties and iteration limits, and on the
+    edge cases of tests/wfa_cluster_cases.py (cluster_biwfa_edges_*)"""
     from vcfdist_amd import api
     fx = R.Fixture(name)
     assert fx.refused is None, fx.refused

@@ -33,7 +33,7 @@ class VclWfaStats(C.Structure):
 
 
 EXPORTED = ["vcl_simple_cluster", "vcl_clusters_free", "vcl_supercluster", "vcl_superclusters_free",
-            "vcl_supercluster_cells", "vcl_supercluster_cells_all", "vcl_wfa_cluster"]
+            "vcl_supercluster_cells", "vcl_supercluster_cells_all", "vcl_wfa_cluster", "vcl_wfa_last_classes"]
 
 
 class Hap:
@@ -209,3 +209,15 @@ def wfa_cluster(hap: HapSeq, ctg, sub=5, open=6, extend=2, max_cluster_itrs=4, r
         L.vcl_clusters_free.argtypes = [C.POINTER(VclClusters)]
         L.vcl_clusters_free(out)
     return res, dict(iterations=st.iterations, align_calls=st.align_calls, reach_calls=st.reach_calls, ms_device=st.ms_device)
+
+
+def wfa_last_classes(L=None):
+    """jobs and launches per size class (8 / 16 / 32 / 64 KiB of LDS, global scratch) of this thread's last wfa_cluster call on
+    the library -> (jobs[5], launches[5])"""
+    L = L or api.lib()
+    jobs, launches = np.zeros(5, np.int64), np.zeros(5, np.int64)
+    L.vcl_wfa_last_classes.argtypes = [A.P_i64, A.P_i64]
+    rc = L.vcl_wfa_last_classes(A._ptr(jobs, C.c_int64), A._ptr(launches, C.c_int64))
+    if rc:
+        raise ValueError(f"vcl_wfa_last_classes failed: {rc}")
+    return jobs.tolist(), launches.tolist()

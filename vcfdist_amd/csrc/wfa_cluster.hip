@@ -100,7 +100,7 @@ __device__ int gen_str(const DevHap &H, int beg_idx, int end_idx, int beg_pos, i
         } else {
             const int ref_end = (var_idx < end_idx) ? min(end_pos, H.pos[var_idx]) : end_pos;
             if (ref_end < ref_pos) break;   // overlapping variants: the reference ERRORs
-            const int n = ref_end - ref_pos;
+            const int n = max(min(ref_end, H.ctg_len) - ref_pos, 0);   // std::string::substr stops at the contig's end
             for (int k = lane; k < n; k += 64) S.setq(len + k, H.ctg[ref_pos + k]);
             len += n;
             ref_pos = ref_end;
@@ -293,7 +293,8 @@ __global__ void __launch_bounds__(64) k_wfa_reach(DevHap H, const WfaJob *__rest
             }
             if (reverse && s - o >= 0) {
                 for (int m = M_INS; m < MATS; m++) {
-                    const int p = S.ld(m * z + row(o) * y + d);
+                    // open == 0: row(o) is this row, whose INS / DEL values so far are still in registers
+                    const int p = o == 0 ? (m == M_INS ? vins : vdel) : S.ld(m * z + row(o) * y + d);
                     if (p >= 0 && p < query_len && diag + p >= 0 && diag + p < truth_len && p > vsub) vsub = p;
                 }
             }
@@ -326,7 +327,7 @@ __global__ void __launch_bounds__(64) k_wfa_reach(DevHap H, const WfaJob *__rest
 }
 
 // host mirror of generate_str's length arithmetic
-int gen_len(const vcl_hap &h, int beg_idx, int end_idx, int beg_pos, int end_pos) {
+int gen_len(const vcl_hap &h, int ctg_len, int beg_idx, int end_idx, int beg_pos, int end_pos) {
     int var_idx = beg_idx, len = 0;
     while (var_idx < h.n_var && h.pos[var_idx] < beg_pos) var_idx++;
     for (int ref_pos = beg_pos; ref_pos < end_pos;) {
@@ -339,7 +340,7 @@ int gen_len(const vcl_hap &h, int beg_idx, int end_idx, int beg_pos, int end_pos
         } else {
             const int ref_end = (var_idx < end_idx) ? std::min(end_pos, h.pos[var_idx]) : end_pos;
             if (ref_end < ref_pos) break;
-            len += ref_end - ref_pos;
+            len += std::max(std::min(ref_end, ctg_len) - ref_pos, 0);
             ref_pos = ref_end;
         }
     }
@@ -355,11 +356,21 @@ T *dev_copy(const T *src, size_t n, std::vector<void *> &allocs) {
     return static_cast<T *>(p);
 }
 
+// size classes of the calling thread's last vcl_wfa_cluster call: jobs and launches per class (vcl_wfa_last_classes)
+thread_local int64_t t_class_jobs[5], t_class_launches[5];
+
 }  // namespace
+
+extern "C" int vcl_wfa_last_classes(int64_t jobs[5], int64_t launches[5]) {
+    if (!jobs || !launches) return VCL_ERR_ARG;
+    for (int b = 0; b < 5; b++) { jobs[b] = t_class_jobs[b]; launches[b] = t_class_launches[b]; }
+    return VCL_OK;
+}
 
 extern "C" int vcl_wfa_cluster(const vcl_hap_seq *hs, const uint8_t *ctg_seq, int32_t ctg_len, int32_t sub, int32_t open,
                                int32_t extend, int32_t max_cluster_itrs, int32_t reach_min_gap, int32_t device,
                                vcl_clusters **out, vcl_wfa_stats *stats) {
+    for (int b = 0; b < 5; b++) t_class_jobs[b] = t_class_launches[b] = 0;
     if (!hs || !out || !ctg_seq || ctg_len <= 0 || sub <= 0 || open < 0 || extend <= 0) return VCL_ERR_ARG;
     *out = nullptr;
     const vcl_hap &h = hs->cols;
@@ -367,6 +378,8 @@ extern "C" int vcl_wfa_cluster(const vcl_hap_seq *hs, const uint8_t *ctg_seq, in
     for (int v = 0; v < n; v++) {
         if (h.type[v] < 1 || h.type[v] > 3) return VCL_ERR_TYPE;
         if (v && h.pos[v] < h.pos[v - 1]) return VCL_ERR_ARG;
+        // a region starts one base in front of its first variant: position 0 has none (the reference's generate_str exits)
+        if (h.pos[v] < 1 || int64_t(h.pos[v]) + h.rlen[v] > ctg_len) return VCL_ERR_ARG;
     }
     vcl_wfa_stats st;
     memset(&st, 0, sizeof(st));
@@ -443,6 +456,7 @@ extern "C" int vcl_wfa_cluster(const vcl_hap_seq *hs, const uint8_t *ctg_seq, in
                 size_t hi = lo;
                 while (hi < jobs.size() && bucket_of(jobs[hi]) == b) hi++;
                 const unsigned cnt = unsigned(hi - lo);
+                t_class_jobs[b] += cnt; t_class_launches[b]++;
                 const size_t shm = b < 4 ? size_t(LIM[b]) : 0;
                 if (align) {
                     if (b < 4) hipLaunchKernelGGL(k_wfa_align<true>, dim3(cnt), dim3(64), shm, nullptr, H, d_jobs + lo, int(cnt), d_scratch, d_res, sub, open, extend);
@@ -489,7 +503,7 @@ extern "C" int vcl_wfa_cluster(const vcl_hap_seq *hs, const uint8_t *ctg_seq, in
                 j.q_beg = std::max(0, h.pos[bi] - 1);
                 j.q_end = std::min(ctg_len, h.pos[ei - 1] + h.rlen[ei - 1] + 1);
                 j.r_beg = j.q_beg; j.r_len = j.q_end - j.q_beg;
-                j.q_len = gen_len(h, bi, ei, j.q_beg, j.q_end);
+                j.q_len = gen_len(h, ctg_len, bi, ei, j.q_beg, j.q_end);
                 j.out = int32_t(k);
                 jobs.push_back(j);
             }
@@ -528,7 +542,7 @@ extern "C" int vcl_wfa_cluster(const vcl_hap_seq *hs, const uint8_t *ctg_seq, in
                         j.r_len = std::min(std::min(S.ref_len, S.end_pos - S.beg_pos), ctg_len - j.r_beg);
                     }
                     j.q_beg = S.beg_pos; j.q_end = S.end_pos;
-                    j.q_len = gen_len(h, bi, ei, j.q_beg, j.q_end);
+                    j.q_len = gen_len(h, ctg_len, bi, ei, j.q_beg, j.q_end);
                     j.main_diag = S.main_diag; j.main_diag_start = S.main_diag_start; j.max_score = sc;
                     j.reverse = S.reverse;
                     j.out = int32_t(jobs.size());
