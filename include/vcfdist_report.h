@@ -8,6 +8,7 @@
  *   vrp_write_context_bed        (none: the intervals of the sequence-context strata, include/vcfdist_context.h)
  *   vrp_write_repeat_bed         (none: the intervals of the repeat strata, include/vcfdist_repeats.h)
  *   vrp_write_long_repeat_bed    (none: the intervals of the long repeat strata, include/vcfdist_longrepeats.h)
+ *   vrp_write_near_repeat_bed    (none: the intervals of the near-repeat strata, include/vcfdist_nearrepeats.h)
  *   vrp_write_phase_blocks       write_results, phase-blocks.tsv                  src/print.cpp:585-609
  *   vrp_write_superclusters      write_results, superclusters.tsv                  src/print.cpp:611-671
  *   vrp_write_variants           write_results, query.tsv / truth.tsv              src/print.cpp:673-876
@@ -101,6 +102,9 @@ int vrp_write_repeat_bed(const char *prefix, const char *const *contigs, int32_t
                          const int64_t *iv_off, const int32_t *start, const int32_t *stop);
 /* <prefix>long-repeat-strata.bed: the same for the long repeat strata (include/vcfdist_longrepeats.h). */
 int vrp_write_long_repeat_bed(const char *prefix, const char *const *contigs, int32_t n_ctg, const char *const *names, int32_t n_strata,
+                              const int64_t *iv_off, const int32_t *start, const int32_t *stop);
+/* <prefix>near-repeat-strata.bed: the same for the near-repeat strata (include/vcfdist_nearrepeats.h). */
+int vrp_write_near_repeat_bed(const char *prefix, const char *const *contigs, int32_t n_ctg, const char *const *names, int32_t n_strata,
                               const int64_t *iv_off, const int32_t *start, const int32_t *stop);
 
 int vrp_write_phase_blocks(const char *path, const vrp_contig *ctgs, int32_t n_ctg);

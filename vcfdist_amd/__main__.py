@@ -16,6 +16,8 @@ alone, and context-strata.bed holds their intervals.  With --stratify-repeats th
 where the FASTA is not unique, found genome-wide on the GPU before the contig loop) follow the list's strata, in front of the context
 strata, and repeat-strata.bed holds their intervals.  With --stratify-long-repeats the default long repeat strata (repeated 64-, 100-
 and 250-mers, include/vcfdist_longrepeats.h: one more genome-wide pass) follow those, and long-repeat-strata.bed holds their intervals.
+With --stratify-near-repeats K:M[,K:M...] the near-repeat strata the user names (k-mers that occur again within M substitutions,
+include/vcfdist_nearrepeats.h: one more genome-wide pass) follow those, and near-repeat-strata.bed holds their intervals.
 With --stratify-variants the default variant strata
 (include/vcfdist_varstrata.h: transitions / transversions, indel size bins, hom / het, isolated / crowded -- bits made on the GPU from
 the variant tables) follow those, or stand alone, and variant-strata.tsv lists them with their numbers of members.  With --bootstrap N
@@ -35,6 +37,7 @@ comparison finds --, shifted, regrouped, partial), from the resident sync groups
 match-kinds-summary.tsv; works under several ranks in both --shard modes."""
 import argparse
 import os
+import re
 import sys
 from dataclasses import dataclass, field
 
@@ -160,8 +163,33 @@ def option_on(args, option):
     return getattr(args, option[2:].replace("-", "_"))
 
 
+# The near-repeat family (include/vcfdist_nearrepeats.h) has no defaults: its strata are the user's, parsed from the option's value
+NEAR_OPTION = "--stratify-near-repeats"
+NEAR_FAMILY = dict(option=NEAR_OPTION, word="near repeat", defaults=None, intervals="nearrepeat_intervals",
+                   download="download_nearrepeat_intervals", stats_call="nearrepeat_stats", stats_kw=dict(cost=True), timing="nearrepeat_timing",
+                   write="write_near_repeat_bed")
+
+
+def near_strata(text):
+    """the value of --stratify-near-repeats, K:M[,K:M...] -> [A.VprNearStratum]; the messages are main.cpp's"""
+    specs = []
+    for entry in text.split(","):
+        m = re.fullmatch(r"([0-9]{1,9}):([0-9]{1,9})", entry)
+        if m is None:
+            raise SystemExit(f"ERROR: {NEAR_OPTION}: entry '{entry}' is not K:M")
+        k, mm = int(m.group(1)), int(m.group(2))
+        if mm > A.NREP_MAX_M or k < 8 * (mm + 1) or k > A.NREP_MAX_K:
+            raise SystemExit(f"ERROR: {NEAR_OPTION}: entry '{entry}': M must be 0 to {A.NREP_MAX_M} and K 8 (M + 1) to {A.NREP_MAX_K}")
+        if any((sp.k, sp.m) == (k, mm) for sp in specs):
+            raise SystemExit(f"ERROR: {NEAR_OPTION}: duplicate entry '{entry}'")
+        if len(specs) == A.NREP_MAX_SPEC:
+            raise SystemExit(f"ERROR: {NEAR_OPTION}: more than {A.NREP_MAX_SPEC} entries")
+        specs.append(A.near_kmer(k, mm))
+    return specs
+
+
 def stratifying(args):
-    return bool(args.stratify) or any(option_on(args, row["option"]) for row in FAMILIES)
+    return bool(args.stratify) or bool(args.stratify_near_repeats) or any(option_on(args, row["option"]) for row in FAMILIES)
 
 
 @dataclass
@@ -169,10 +197,11 @@ class Family:
     """a row of FAMILIES in a StrataPlan, and what the run makes of it"""
     option: str; word: str; defaults: object
     intervals: str = None; download: str = None; stats_call: str = None; timing: str = None; write: str = None
+    stats_kw: dict = field(default_factory=dict)    # the near-repeat family: its statistics with the cost
     specs: object = None                            # the strata's parameters; None: the option is off
     names: list = field(default_factory=list)
     rows: dict = field(default_factory=dict)        # k-mer families, context: per contig, every stratum's intervals
-    stats: object = None                            # k-mer families: the valid and the repeated starts of every stratum
+    stats: object = None                            # k-mer families: the valid and the repeated starts of every stratum (near: and the cost)
     ms: float = 0.0                                 # on the device
 
 
@@ -182,7 +211,9 @@ class StrataPlan:
     names: list = field(default_factory=list)
     beds: list = field(default_factory=list)
     families: list = field(default_factory=lambda: [Family(**row) for row in FAMILIES])
-    kmer = property(lambda self: [fam for fam in self.families[:2] if fam.specs])       # the genome-wide families that are on
+    near: Family = field(default_factory=lambda: Family(**NEAR_FAMILY))     # the user's near-repeat strata, behind the long repeat family's
+    kmer = property(lambda self: [fam for fam in self.families[:2] + [self.near] if fam.specs])       # the genome-wide families that are on
+    ordered = property(lambda self: self.families[:2] + [self.near] + self.families[2:])            # in table order
     ctx = property(lambda self: self.families[2])
     vs = property(lambda self: self.families[3])
 
@@ -297,7 +328,7 @@ def keep_context_intervals(pr, ctx, name):
 
 
 def kmer_strata(fam, fasta, args, device=0):
-    """--stratify-repeats, --stratify-long-repeats: the family's genome-wide pass over all contigs of the FASTA, those without a
+    """--stratify-repeats, --stratify-long-repeats, --stratify-near-repeats: the family's genome-wide pass over all contigs of the FASTA, those without a
     variant included, on a handle of its own that is gone before the evaluation starts.  Every rank computes the same arrays."""
     cfg = A.default_config(device=device)
     cfg.max_qual = float(args.max_qual)
@@ -306,7 +337,7 @@ def kmer_strata(fam, fasta, args, device=0):
     getattr(pr, fam.intervals)([fasta[c] for c in names], fam.specs)
     rows = getattr(pr, fam.download)()
     fam.rows = {c: [rows[k][j] for k in range(len(fam.specs))] for j, c in enumerate(names)}
-    fam.stats = getattr(pr, fam.stats_call)()
+    fam.stats = getattr(pr, fam.stats_call)(**fam.stats_kw)
     fam.ms = sum(getattr(pr, fam.timing)())
     pr.close()
 
@@ -596,6 +627,10 @@ def argument_parser():
                     help="the default long repeat strata (bases covered by a 64-, 100- or 250-mer that occurs more than once in the FASTA, on "
                          "either strand), built on the GPU in one more genome-wide pass, behind the strata of --stratify and "
                          "--stratify-repeats; also writes long-repeat-strata.bed")
+    ap.add_argument(NEAR_OPTION, metavar="K:M[,K:M...]",
+                    help="near-repeat strata (bases covered by a K-mer that occurs again in the FASTA, on either strand, with at most M "
+                         "substitutions; M 0 to 3, K 8 (M + 1) to 32, up to 4 entries), built on the GPU in one more genome-wide pass, "
+                         "named near_k<K>_m<M>, behind the strata of --stratify-long-repeats; also writes near-repeat-strata.bed")
     ap.add_argument("--stratify-context", action="store_true",
                     help="the default sequence-context strata (homopolymers, short tandem repeats, GC bands), built on the GPU from the "
                          "FASTA, behind those of --stratify or alone; their intervals are written to context-strata.bed")
@@ -633,6 +668,7 @@ def parse(argv=None):
     if args.cluster[0] in ("gap", "size") and len(args.cluster) > 1:
         args.cluster_gap = int(args.cluster[1])
     args.cluster = args.cluster[0]
+    args.near = near_strata(args.stratify_near_repeats) if args.stratify_near_repeats is not None else []
     if args.max_size + 2 > args.max_supercluster_size:          # globals.cpp:478-481
         raise SystemExit("ERROR: Max supercluster size (-s) must be at least two larger than max variant size (-l).")
     if args.error_window is not None and not args.classify_errors:
@@ -690,10 +726,15 @@ def plan_strata(args):
         except IOError as e:
             raise SystemExit(f"ERROR: {e}")
         plan.names = list(names)
-    for fam in plan.families:
-        if not option_on(args, fam.option):
+    for fam in plan.ordered:
+        if fam is plan.near:
+            if not args.near:
+                continue
+            fam.names, fam.specs = [api.nearrepeat_name(sp) for sp in args.near], args.near
+        elif not option_on(args, fam.option):
             continue
-        fam.names, fam.specs = fam.defaults()
+        else:
+            fam.names, fam.specs = fam.defaults()
         for n in fam.names:
             if n in plan.names:
                 raise SystemExit(f"ERROR: strata list '{args.stratify}': duplicate stratum name '{n}' (a {fam.word} stratum of {fam.option})")
@@ -856,7 +897,11 @@ def report(args, plan, tot, rows):
         say(f"stratified: {len(plan.names)} strata, {int(tot.seen_none[1])} of {int(tot.seen_none[0])} hap-variants in none of them")
         for fam in plan.kmer:
             n_iv = sum(len(a) for per in fam.rows.values() for a, _ in per)
-            starts = ", ".join(f"{int(v)} valid and {int(r)} repeated starts (k={sp.k})" for sp, v, r in zip(fam.specs, *fam.stats))
+            if fam is plan.near:
+                starts = ", ".join(f"{int(v)} valid and {int(r)} near-repeated starts (k={sp.k}, m={sp.m})" for sp, v, r in zip(fam.specs, *fam.stats[:2]))
+                starts += f", {int(fam.stats[2].sum())} compares, longest run {int(fam.stats[3].max())}"
+            else:
+                starts = ", ".join(f"{int(v)} valid and {int(r)} repeated starts (k={sp.k})" for sp, v, r in zip(fam.specs, *fam.stats))
             say(f"{fam.word} strata: {n_iv} intervals of {len(fam.specs)} strata, {starts}, {fam.ms:.3f} ms on the device")
         if plan.ctx.specs:
             n_iv = sum(len(a) for per in plan.ctx.rows.values() for a, _ in per)

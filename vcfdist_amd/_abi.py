@@ -564,6 +564,23 @@ def rep_kmer(k, slop=0):
     return VprRepeatStratum(k, slop)
 
 
+# ---- include/vcfdist_nearrepeats.h
+NREP_MAX_M, NREP_MAX_K, NREP_MAX_SPEC = 3, 32, 4
+
+
+class VprNearStratum(C.Structure):
+    _fields_ = [("k", C.c_int32), ("m", C.c_int32), ("slop", C.c_int32)]
+
+    def __repr__(self):
+        return f"near_repeat(k={self.k}, m={self.m}, slop={self.slop})"
+
+
+def near_kmer(k, m, slop=0):
+    """a near-repeat stratum: the bases covered by a k-mer that occurs again in the genome (either strand) with at most m
+    substitutions, padded by slop; 0 <= m <= 3, 8 (m + 1) <= k <= 32"""
+    return VprNearStratum(k, m, slop)
+
+
 # ---- include/vcfdist_varstrata.h
 VS_SIZE, VS_TI, VS_TV, VS_HOM, VS_HET, VS_NEAR = range(6)
 VS_MAX_SPEC = 64

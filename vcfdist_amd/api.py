@@ -110,6 +110,12 @@ def lib():
     L.vpr_longrepeat_download_intervals.argtypes = [H, A.P_i32, A.P_i32]
     L.vpr_longrepeat_stats.argtypes = [H, A.P_i64, A.P_i64, A.P_i64, A.P_i64]
     L.vpr_longrepeat_timing.argtypes = [H] + [C.POINTER(C.c_double)] * 4
+    L.vpr_nearrepeat_intervals.argtypes = [H, C.c_int32, A.P_i64, A.P_u8, C.POINTER(A.VprNearStratum), C.c_int32]
+    L.vpr_nearrepeat_interval_counts.argtypes = [H, A.P_i64]
+    L.vpr_nearrepeat_download_intervals.argtypes = [H, A.P_i32, A.P_i32]
+    L.vpr_nearrepeat_stats.argtypes = [H, A.P_i64, A.P_i64, A.P_i64, A.P_i64]
+    L.vpr_nearrepeat_timing.argtypes = [H] + [C.POINTER(C.c_double)] * 4
+    L.vpr_nearrepeat_name.argtypes = [C.POINTER(A.VprNearStratum), C.c_char_p, C.c_size_t]
     L.vpr_varstrata_default.argtypes = [C.POINTER(C.POINTER(A.VprVariantStratum)), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.c_int32)]
     L.vpr_varstrata_masks.argtypes = [H, C.POINTER(A.VprVariants), C.POINTER(A.VprVariantStratum), C.c_int32, C.c_int32]
     L.vpr_varstrata_timing.argtypes = [H, C.POINTER(C.c_double)]
@@ -170,6 +176,9 @@ REPEATS_EXPORTED = ["vpr_repeats_default", "vpr_repeat_intervals", "vpr_repeat_i
 # include/vcfdist_longrepeats.h
 LONGREPEATS_EXPORTED = ["vpr_longrepeats_default", "vpr_longrepeat_intervals", "vpr_longrepeat_interval_counts",
                         "vpr_longrepeat_download_intervals", "vpr_longrepeat_stats", "vpr_longrepeat_timing", "vrp_write_long_repeat_bed"]
+# include/vcfdist_nearrepeats.h
+NEARREPEATS_EXPORTED = ["vpr_nearrepeat_intervals", "vpr_nearrepeat_interval_counts", "vpr_nearrepeat_download_intervals",
+                        "vpr_nearrepeat_stats", "vpr_nearrepeat_timing", "vpr_nearrepeat_name", "vrp_write_near_repeat_bed"]
 # include/vcfdist_varstrata.h
 VARSTRATA_EXPORTED = ["vpr_varstrata_default", "vpr_varstrata_masks", "vpr_varstrata_timing", "vrp_write_variant_strata"]
 # include/vcfdist_errclass.h
@@ -251,6 +260,15 @@ def repeats_default():
     if rc:
         raise VprError(f"vpr_repeats_default failed ({rc})")
     return [names[k].decode() for k in range(n.value)], [A.VprRepeatStratum.from_buffer_copy(spec[k]) for k in range(n.value)]
+
+
+def nearrepeat_name(spec):
+    """the name of a near-repeat stratum in the tables (vpr_nearrepeat_name): near_k<K>_m<M>"""
+    buf = C.create_string_buffer(64)
+    rc = lib().vpr_nearrepeat_name(C.byref(spec), buf, len(buf))
+    if rc != 0:
+        raise VprError(f"vpr_nearrepeat_name failed ({rc})")
+    return buf.value.decode()
 
 
 def longrepeats_default():
@@ -565,9 +583,9 @@ class PrecisionRecall:
                 seq = np.zeros(1, np.uint8)
         return off, seq
 
-    def _repeat_call(self, entry, attr, contigs, spec):
+    def _repeat_call(self, entry, attr, contigs, spec, stratum=A.VprRepeatStratum):
         off, seq = self._genome(contigs)
-        arr = (A.VprRepeatStratum * max(len(spec), 1))(*spec) if spec is not None else None
+        arr = (stratum * max(len(spec), 1))(*spec) if spec is not None else None
         setattr(self, attr, None)
         self._chk(getattr(lib(), entry)(self._h, len(off) - 1, A._ptr(off, C.c_int64), A._ptr(seq, C.c_uint8) if seq is not None else None,
                                         arr, len(spec) if spec is not None else 1), entry)
@@ -604,6 +622,29 @@ class PrecisionRecall:
         """(ms_base, ms_levels, ms_last, ms_intervals) of the last longrepeat_intervals, from HIP events on the handle's stream"""
         t = [C.c_double() for _ in range(4)]
         self._chk(lib().vpr_longrepeat_timing(self._h, *[C.byref(x) for x in t]), "vpr_longrepeat_timing")
+        return tuple(x.value for x in t)
+
+    def nearrepeat_intervals(self, contigs, spec):
+        """The near-repeat strata (include/vcfdist_nearrepeats.h): the intervals of every entry of `spec` (A.near_kmer) for the whole
+        genome, built on the device in one call.  contigs: as for repeat_intervals.  The handle needs no batch."""
+        self._repeat_call("vpr_nearrepeat_intervals", "_nearrepeats", contigs, spec, A.VprNearStratum)
+
+    def download_nearrepeat_intervals(self):
+        """the intervals of the last nearrepeat_intervals: rows[spec][contig] = (starts, stops), int32 arrays, 0-based half-open"""
+        return self._repeat_rows("vpr_nearrepeat", "_nearrepeats")
+
+    def nearrepeat_stats(self, cost=False):
+        """(valid starts, near-repeated starts) per entry of the last nearrepeat_intervals: two int64 arrays; with `cost` also the
+        compares made and the longest run of equal block keys"""
+        n_spec = (getattr(self, "_nearrepeats", None) or (1, 1))[0]
+        a, b, c, d = (np.zeros(n_spec, np.int64) for _ in range(4))
+        self._chk(lib().vpr_nearrepeat_stats(self._h, *[A._ptr(x, C.c_int64) for x in (a, b, c, d)]), "vpr_nearrepeat_stats")
+        return (a, b, c, d) if cost else (a, b)
+
+    def nearrepeat_timing(self):
+        """(ms_pack, ms_sort, ms_probe, ms_intervals) of the last nearrepeat_intervals, from HIP events on the handle's stream"""
+        t = [C.c_double() for _ in range(4)]
+        self._chk(lib().vpr_nearrepeat_timing(self._h, *[C.byref(x) for x in t]), "vpr_nearrepeat_timing")
         return tuple(x.value for x in t)
 
     def repeat_intervals(self, contigs, spec):

@@ -13,7 +13,7 @@
 //   vcfdist_gpu <query.vcf[.gz]> <truth.vcf[.gz]> <ref.fasta[.gz]> [-b regions.bed] [-p prefix] [-n] [-c biwfa | gap N | size N] [-l max variant size]
 //               [-s max supercluster size] [-mn / -mx qual] [-f filters] [-i iterations] [-x -o -e penalties] [-ct credit threshold] [-pt phasing threshold]
 //               [-sv threshold] [--reach-min-gap N] [--strict] [--device N] [-d] [-ex -eo -ee evaluation penalties] [-rq] [-rt] [-ro] [--stratify strata.tsv]
-//               [--stratify-repeats] [--stratify-long-repeats] [--stratify-context] [--stratify-variants] [--bootstrap N] [--bootstrap-seed S]
+//               [--stratify-repeats] [--stratify-long-repeats] [--stratify-near-repeats K:M[,K:M...]] [--stratify-context] [--stratify-variants] [--bootstrap N] [--bootstrap-seed S]
 //               [--classify-errors] [--error-window N] [--classify-matches] [--cut-classes]
 // What an option adds (its header under include/ says how) and the files it writes:
 //   -d                       vcfdist_distance.h: the distance metrics (edits_wrapper, dist.cpp:1908-2077) behind each contig's path (main.cpp:223-238)
@@ -22,6 +22,8 @@
 //   --stratify FILE          vcfdist_strata.h: the counters also cut by the BEDs of a GIAB list (name<TAB>path): stratified-precision-recall[-summary].tsv
 //   --stratify-repeats       vcfdist_repeats.h: default strata where the FASTA is not unique, one genome-wide pass before the contigs: repeat-strata.bed
 //   --stratify-long-repeats  vcfdist_longrepeats.h: repeated 64-, 100- and 250-mers, one more genome-wide pass: long-repeat-strata.bed
+//   --stratify-near-repeats  vcfdist_nearrepeats.h: K-mers that occur again within M substitutions (the user's entries, near_k<K>_m<M>), one
+//                            more genome-wide pass: near-repeat-strata.bed
 //   --stratify-context       vcfdist_context.h: homopolymers, short tandem repeats, GC bands, intervals built from the FASTA: context-strata.bed
 //   --stratify-variants      vcfdist_varstrata.h: transitions / transversions, indel size bins, hom / het, isolated / crowded: variant-strata.tsv
 //                            (the strata stand in this order in every table; each default set also stands alone)
@@ -55,6 +57,7 @@
 #include "../../include/vcfdist_context.h"
 #include "../../include/vcfdist_repeats.h"
 #include "../../include/vcfdist_longrepeats.h"
+#include "../../include/vcfdist_nearrepeats.h"
 #include "../../include/vcfdist_strata.h"
 #include "../../include/vcfdist_varstrata.h"
 #include "../../include/vcfdist_errclass.h"
@@ -65,6 +68,7 @@ namespace {
 struct Args {
     std::string query, truth, fasta, bed, filter, prefix = "./", cluster = "biwfa", stratify;
     bool stratify_context = false, stratify_variants = false, stratify_repeats = false, stratify_long_repeats = false;
+    std::vector<vpr_near_stratum> near;    // --stratify-near-repeats: the entries (empty: not given)
     int max_size = 5000, min_qual = 0, max_qual = 60, cluster_gap = 50, max_iterations = 4, max_supercluster_size = 10000;
     int sub = 5, open = 6, extend = 2, sv_threshold = 50, reach_min_gap = 10, device = 0;
     int eval_sub = 3, eval_open = 2, eval_extend = 1;      // globals.h:52-55
@@ -120,6 +124,34 @@ int error_window(const char *v) {
     if (n < 0 || n > INT32_MAX) die("ERROR: Must provide an error window of 0 to %d bases", INT32_MAX);
     return int(n);
 }
+// --stratify-near-repeats K:M[,K:M...]: numbers within the limits of include/vcfdist_nearrepeats.h, no entry twice, at most four
+std::vector<vpr_near_stratum> near_strata(const std::string &text) {
+    static const char *O = "--stratify-near-repeats";
+    std::vector<vpr_near_stratum> specs;
+    auto number = [](const std::string &t, int &x) {
+        if (t.empty() || t.size() > 9 || t.find_first_not_of("0123456789") != std::string::npos) return false;
+        x = atoi(t.c_str());
+        return true;
+    };
+    size_t at = 0;
+    while (true) {
+        const size_t comma = text.find(',', at);
+        const std::string entry = text.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
+        const size_t colon = entry.find(':');
+        int k = 0, m = 0;
+        if (colon == std::string::npos || !number(entry.substr(0, colon), k) || !number(entry.substr(colon + 1), m))
+            die("ERROR: %s: entry '%s' is not K:M", O, entry.c_str());
+        if (m > VPR_NREP_MAX_M || k < 8 * (m + 1) || k > VPR_NREP_MAX_K)
+            die("ERROR: %s: entry '%s': M must be 0 to %d and K 8 (M + 1) to %d", O, entry.c_str(), VPR_NREP_MAX_M, VPR_NREP_MAX_K);
+        for (const vpr_near_stratum &sp : specs)
+            if (sp.k == k && sp.m == m) die("ERROR: %s: duplicate entry '%s'", O, entry.c_str());
+        if (specs.size() == VPR_NREP_MAX_SPEC) die("ERROR: %s: more than %d entries", O, VPR_NREP_MAX_SPEC);
+        specs.push_back(vpr_near_stratum{k, m, 0});
+        if (comma == std::string::npos) break;
+        at = comma + 1;
+    }
+    return specs;
+}
 void warn(const std::string &m) { fprintf(stderr, "[WARN  vcfdist] %s\n", m.c_str()); }
 
 Args parse(int argc, char **argv) {
@@ -156,6 +188,7 @@ Args parse(int argc, char **argv) {
         else if (o == "--stratify-context") a.stratify_context = true;
         else if (o == "--stratify-repeats") a.stratify_repeats = true;
         else if (o == "--stratify-long-repeats") a.stratify_long_repeats = true;
+        else if (o == "--stratify-near-repeats") a.near = near_strata(need(i));
         else if (o == "--stratify-variants") a.stratify_variants = true;
         else if (o == "--bootstrap") a.bootstrap = bootstrap_replicates(need(i));
         else if (o == "--bootstrap-seed") a.bootstrap_seed = bootstrap_seed(need(i));
@@ -179,7 +212,7 @@ Args parse(int argc, char **argv) {
     if (a.error_window >= 0 && !a.classify_errors) die("ERROR: --error-window needs --classify-errors");
     if (a.error_window < 0) a.error_window = VPR_EC_DEFAULT_WINDOW;
     if (a.cut_classes && !a.classify_errors && !a.classify_matches) die("ERROR: --cut-classes needs --classify-errors or --classify-matches");
-    if (a.cut_classes && a.stratify.empty() && !a.stratify_repeats && !a.stratify_long_repeats && !a.stratify_context && !a.stratify_variants && !a.bootstrap)
+    if (a.cut_classes && a.stratify.empty() && !a.stratify_repeats && !a.stratify_long_repeats && a.near.empty() && !a.stratify_context && !a.stratify_variants && !a.bootstrap)
         die("ERROR: --cut-classes needs --stratify, --stratify-context, --stratify-variants or --bootstrap");
     if ((a.realign_query || a.realign_truth) && (a.sub < 1 || a.extend < 1))
         die("ERROR: realignment needs a mismatch penalty (-x) and a gap-extension penalty (-e) of at least 1");
@@ -261,7 +294,9 @@ void read_inputs(const Args &A, Inputs &in) {
 
 // ---- which strata, in which order: the list's, the repeat and long repeat families', the context and the variant defaults
 // A family of genome-wide k-mer strata (--stratify-repeats: include/vcfdist_repeats.h, --stratify-long-repeats:
-// include/vcfdist_longrepeats.h): its option and its word in the messages, its entries and writer, and what its pass gave.
+// include/vcfdist_longrepeats.h): its option and its word in the messages, its entries and writer, and what its pass gave.  The
+// near-repeat family (--stratify-near-repeats: include/vcfdist_nearrepeats.h) has no defaults and a spec type of its own: its
+// entries are the parsed argument's (near_spec, with the names made of them), and its statistics carry the cost.
 struct KmerFamily {
     bool Args::*on;
     const char *option, *word, *defaults_name;
@@ -279,6 +314,10 @@ struct KmerFamily {
     std::vector<int32_t> start = {}, stop = {};
     std::vector<int64_t> valid = {}, repeated = {};      // [n] starts
     double ms = 0;                                       // device ms of the pass
+    std::vector<vpr_near_stratum> near_spec = {};        // the near-repeat family alone: its entries, its names, its compares and longest runs
+    std::vector<std::string> near_names = {};
+    std::vector<const char *> near_name_ptrs = {};
+    std::vector<int64_t> compares = {}, max_run = {};
 };
 int long_repeat_stats(vpr_handle *h, int64_t *n_valid, int64_t *n_repeated) {
     int64_t n_last[VPR_LREP_MAX_SPEC];
@@ -288,11 +327,13 @@ struct StrataPlan : Pinned {
     std::vector<std::string> names;                      // every stratum in table order
     std::vector<vio_bed *> beds;                         // the list's BEDs
     int n_list = 0, n_bed = 0, n_pre = 0, n_strata = 0;  // strata up to the list's, the k-mer families', the context, the variant ones
-    KmerFamily kmer[2] = {
+    KmerFamily kmer[3] = {
         {&Args::stratify_repeats, "--stratify-repeats", "repeat", "vpr_repeats_default", vpr_repeats_default, vpr_repeat_intervals, vpr_repeat_interval_counts,
          vpr_repeat_download_intervals, vpr_repeat_stats, vpr_repeat_timing, vrp_write_repeat_bed},
         {&Args::stratify_long_repeats, "--stratify-long-repeats", "long repeat", "vpr_longrepeats_default", vpr_longrepeats_default, vpr_longrepeat_intervals,
-         vpr_longrepeat_interval_counts, vpr_longrepeat_download_intervals, long_repeat_stats, vpr_longrepeat_timing, vrp_write_long_repeat_bed}};
+         vpr_longrepeat_interval_counts, vpr_longrepeat_download_intervals, long_repeat_stats, vpr_longrepeat_timing, vrp_write_long_repeat_bed},
+        {nullptr, "--stratify-near-repeats", "near repeat", nullptr, nullptr, nullptr, vpr_nearrepeat_interval_counts, vpr_nearrepeat_download_intervals,
+         nullptr, vpr_nearrepeat_timing, vrp_write_near_repeat_bed}};
     const vpr_context_stratum *ctx_spec = nullptr; const vpr_variant_stratum *vs_spec = nullptr;
     const char *const *ctx_names = nullptr, *const *vs_names = nullptr;
     int32_t n_ctx = 0, n_vs = 0;
@@ -335,14 +376,26 @@ void append_default_strata(std::vector<std::string> &names, const char *const *d
         names.push_back(defaults[k]);
     }
 }
-// the table order: the list's strata, the two k-mer families' (their intervals come from a genome-wide pass each in front of the
+// the table order: the list's strata, the three k-mer families' (their intervals come from a genome-wide pass each in front of the
 // contig loop and then travel with the list's rows), the default sequence-context strata, the default variant strata
 void plan_strata(const Args &A, StrataPlan &S) {
     if (!A.stratify.empty()) read_strata(A.stratify, S);
     S.n_list = int(S.names.size());
     for (KmerFamily &F : S.kmer) {
-        if (!(A.*F.on)) continue;
-        if (F.defaults(&F.spec, &F.names, &F.n)) die("ERROR: %s failed", F.defaults_name);
+        if (!F.on) {             // the near-repeat family: the user's entries
+            if (A.near.empty()) continue;
+            F.near_spec = A.near;
+            for (const vpr_near_stratum &sp : F.near_spec) {
+                char buf[64];
+                if (vpr_nearrepeat_name(&sp, buf, sizeof(buf))) die("ERROR: vpr_nearrepeat_name failed");
+                F.near_names.push_back(buf);
+            }
+            F.near_name_ptrs = c_strs(F.near_names);
+            F.names = F.near_name_ptrs.data(); F.n = int32_t(F.near_spec.size());
+        } else {
+            if (!(A.*F.on)) continue;
+            if (F.defaults(&F.spec, &F.names, &F.n)) die("ERROR: %s failed", F.defaults_name);
+        }
         append_default_strata(S.names, F.names, F.n, F.word, F.option, A.stratify);
     }
     S.n_bed = int(S.names.size());
@@ -363,11 +416,17 @@ void kmer_pass(KmerFamily &F, const vpr_config &cfg, const vio_fasta *fa) {
     vpr_handle *hr = nullptr;
     if (vpr_create(&cfg, &hr)) { fprintf(stderr, "vpr_create: %s\n", vpr_last_error(nullptr)); exit(2); }
     F.off.assign(size_t(F.n) * size_t(fa->n_ctg) + 1, 0);
-    if (F.intervals(hr, fa->n_ctg, fa->ctg_off, fa->seq, F.spec, F.n) || F.counts(hr, F.off.data())) die("ERROR: %s", vpr_last_error(hr));
+    const bool near = !F.near_spec.empty();
+    if ((near ? vpr_nearrepeat_intervals(hr, fa->n_ctg, fa->ctg_off, fa->seq, F.near_spec.data(), F.n)
+              : F.intervals(hr, fa->n_ctg, fa->ctg_off, fa->seq, F.spec, F.n)) || F.counts(hr, F.off.data()))
+        die("ERROR: %s", vpr_last_error(hr));
     F.start.assign(size_t(F.off.back()) + 1, 0); F.stop.assign(size_t(F.off.back()) + 1, 0);
     F.valid.assign(size_t(F.n), 0); F.repeated.assign(size_t(F.n), 0);
     double ms[4] = {0, 0, 0, 0};
-    if (F.download(hr, F.start.data(), F.stop.data()) || F.stats(hr, F.valid.data(), F.repeated.data()) || F.timing(hr, &ms[0], &ms[1], &ms[2], &ms[3]))
+    F.compares.assign(size_t(F.n), 0); F.max_run.assign(size_t(F.n), 0);
+    if (F.download(hr, F.start.data(), F.stop.data()) ||
+        (near ? vpr_nearrepeat_stats(hr, F.valid.data(), F.repeated.data(), F.compares.data(), F.max_run.data()) : F.stats(hr, F.valid.data(), F.repeated.data())) ||
+        F.timing(hr, &ms[0], &ms[1], &ms[2], &ms[3]))
         die("ERROR: %s", vpr_last_error(hr));
     F.ms = ms[0] + ms[1] + ms[2] + ms[3];
     vpr_destroy(hr);
@@ -386,7 +445,18 @@ void kmer_report(const KmerFamily &F) {
     std::string starts;
     for (int k = 0; k < F.n; k++) {
         char buf[128];
-        snprintf(buf, sizeof(buf), "%lld valid and %lld repeated starts (k=%d), ", (long long)F.valid[size_t(k)], (long long)F.repeated[size_t(k)], F.spec[k].k);
+        if (F.near_spec.empty())
+            snprintf(buf, sizeof(buf), "%lld valid and %lld repeated starts (k=%d), ", (long long)F.valid[size_t(k)], (long long)F.repeated[size_t(k)], F.spec[k].k);
+        else
+            snprintf(buf, sizeof(buf), "%lld valid and %lld near-repeated starts (k=%d, m=%d), ", (long long)F.valid[size_t(k)], (long long)F.repeated[size_t(k)],
+                     F.near_spec[size_t(k)].k, F.near_spec[size_t(k)].m);
+        starts += buf;
+    }
+    if (!F.near_spec.empty()) {
+        long long compares = 0, longest = 0;
+        for (int k = 0; k < F.n; k++) { compares += F.compares[size_t(k)]; longest = std::max<long long>(longest, F.max_run[size_t(k)]); }
+        char buf[128];
+        snprintf(buf, sizeof(buf), "%lld compares, longest run %lld, ", compares, longest);
         starts += buf;
     }
     fprintf(stderr, "[vcfdist_amd] %s strata: %lld intervals of %d strata, %s%.3f ms on the device\n", F.word, (long long)F.off.back(), F.n, starts.c_str(), F.ms);
@@ -921,7 +991,7 @@ void write_outputs(const Run &R, const std::string &cmd, const std::vector<std::
         if (A.bootstrap)
             wrote(vrp_write_bootstrap_stratified(pre, names.data(), S.n_strata, T.strat_total.data(), T.boot_strat.data(), A.bootstrap, A.bootstrap_seed,
                                                  A.min_qual, A.max_qual));
-        for (const KmerFamily &F : S.kmer) {           // repeat-strata.bed, long-repeat-strata.bed
+        for (const KmerFamily &F : S.kmer) {           // repeat-strata.bed, long-repeat-strata.bed, near-repeat-strata.bed
             if (!F.n) continue;
             std::vector<int64_t> off(1, 0);
             std::vector<int32_t> st, sp;

@@ -1753,6 +1753,7 @@ void vpr_destroy(vpr_handle *h) {
     context_free(h);
     repeats_free(h);
     longrepeats_free(h);
+    nearrepeats_free(h);
     free_batch(h);
     for (auto &b : h->dev_cache) (void)x_free(h, b.p, SITE);
     for (int k = 0; k < 4; k++)

@@ -9,6 +9,7 @@
 //   pr_context.hip  the sequence-context strata (include/vcfdist_context.h): interval lists built from the contig sequences
 //   pr_repeats.hip  the repeat strata (include/vcfdist_repeats.h): genome-wide repeated k-mers, in front of pr_context.hip's run passes;
 //                   the host scaffold of a genome-wide k-mer call and the rows' state that pr_longrepeats.hip shares (pr_kmer.h)
+//   pr_nearrepeats.hip the near-repeat strata (include/vcfdist_nearrepeats.h): k-mers repeated within m mismatches, by block sorts and a probe
 //   pr_longrepeats.hip the long repeat strata (include/vcfdist_longrepeats.h): repeated k-mers of 33..256 bases by rank doubling
 //   pr_varstrata.hip the variant strata (include/vcfdist_varstrata.h): bits made from the variant tables themselves
 //   pr_errclass.hip the error classes (include/vcfdist_errclass.h): why each FP and FN is wrong
@@ -279,6 +280,7 @@ struct StrataState;                      // the membership words and the stratif
 struct ContextState;                     // the sequence-context intervals (pr_context.hip)
 struct KmerState;                        // the rows of a genome-wide k-mer call (pr_kmer.h): the repeat intervals (pr_repeats.hip)
 struct LongRepeatState;                  // the same with the levels' counts: the long repeat intervals (pr_longrepeats.hip)
+struct NearRepeatState;                  // the same with the compares and the longest run: the near-repeat intervals (pr_nearrepeats.hip)
 struct LabelState;                       // the label bytes and the label histogram of a label pass (pr_label.h)
 enum { LABEL_ERRCLASS, LABEL_MATCHKIND, LABEL_PASSES };     // the label passes: pr_errclass.hip, pr_matchkind.hip
 struct CutState;                         // the histogram, keys and device time of a count cut (pr_cut.h)
@@ -438,6 +440,7 @@ struct vpr_handle {
     ContextState *context = nullptr;     // vpr_context_masks (pr_context.hip), released by the next one or vpr_destroy
     KmerState *repeats = nullptr;        // vpr_repeat_intervals (pr_repeats.hip), released by the next one or vpr_destroy
     LongRepeatState *longrepeats = nullptr;   // vpr_longrepeat_intervals (pr_longrepeats.hip), released by the next one or vpr_destroy
+    NearRepeatState *nearrepeats = nullptr;   // vpr_nearrepeat_intervals (pr_nearrepeats.hip), released by the next one or vpr_destroy
     CutState *boot = nullptr;            // vpr_pr_counts_boot (pr_cut.hip), created by its first call, released with the batch
     LabelState *label[LABEL_PASSES] = {nullptr, nullptr};   // vpr_errclass / vpr_matchkind (pr_label.hip), created by a pass's first call, released with the batch
     double varstrata_ms = 0;             // device time of the last vpr_varstrata_masks' kernel launches (pr_varstrata.hip)
@@ -501,6 +504,7 @@ void strata_commit(vpr_handle *h);
 void context_free(vpr_handle *h);                                    // pr_context.hip: the resident context intervals
 void repeats_free(vpr_handle *h);                                    // pr_repeats.hip: the repeat intervals (host memory: pr_kmer.h)
 void longrepeats_free(vpr_handle *h);                              // pr_longrepeats.hip: the long repeat intervals (the same)
+void nearrepeats_free(vpr_handle *h);                              // pr_nearrepeats.hip: the near-repeat intervals (the same)
 void label_free(vpr_handle *h);                                    // pr_label.hip: the label bytes and histograms of both label passes
 void boot_free(vpr_handle *h);                                       // pr_cut.hip: the replicate histogram and the keys
 // pr_collect.hip, shared by the three counters entries (vpr_pr_counts; _strata, _boot: pr_cut.hip; `entry`: the entry's name, for the

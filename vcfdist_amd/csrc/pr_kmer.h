@@ -6,7 +6,9 @@
 // call) + N / 8 (the flag bits) + 1/8 byte per base of the largest piece (its masked copy) + per pair sorted 2 x 12 bytes (key and
 // value, double-buffered for the sort) + the tiles' counts + rocPRIM's temporary + what the run passes take (pr_context.hip).  All
 // of it goes with the call: the rows are downloaded at its end and live in host memory until the next call or vpr_destroy.  At
-// most 2^32 - 1 bases: values are 32-bit.
+// most 2^32 - 1 bases: values are 32-bit.  The near-repeat strata (pr_nearrepeats.hip) keep a forward and a reverse-complement
+// record per valid start, the strand in the value's lowest bit: per valid start 12 bytes (the packed forward pairs, kept over the
+// entry's blocks) + 2 x 2 x 12 bytes (both records, double-buffered for the sort), 60 in all, and at most 2^31 - 1 bases.
 #ifndef PR_KMER_H_
 #define PR_KMER_H_
 #include "pr_host.h"
@@ -106,8 +108,8 @@ struct KmerWork {
         *n_out = n;
         return VPR_OK;
     }
-    // (canon, start) of the valid starts of length k <= 32 (k_rep_pack), by compact
-    int pack(int k, uint32_t *n);
+    // (canon, start) of the valid starts of length k <= 32 (k_rep_pack), by compact; forward: (fwd, start), the strands kept apart
+    int pack(int k, uint32_t *n, bool forward = false);
     // the flags cleared; with n > 0 the repeated ones of the n sorted pairs flagged at their last base and counted (k_rep_mark)
     int mark(uint32_t n, int k, unsigned long long *n_rep);
     // the rows of an entry from the flags, piece by piece (k_rep_piece_words, ctx_intervals_from_flags), into row `slot` of d_off

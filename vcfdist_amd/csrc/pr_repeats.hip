@@ -37,9 +37,10 @@ const char *const DEFAULT_NAMES[] = {"rep_k16", "rep_k24", "rep_k32"};
 const char *const ENTRY = "vpr_repeat_intervals";
 
 // The starts G .. G + 15 of one lane, whose bytes [G, G + 48) are in w: returns how many are valid and, with EMIT, writes their
-// (canon, start) from keys[at] / vals[at] on in start order.  Base G + jj is consumed at step jj; the k-mer that ends there starts
+// (canon, start) -- with FWD (fwd, start), the forward code, for a caller that tells the strands apart (pr_nearrepeats.hip) -- from
+// keys[at] / vals[at] on in start order.  Base G + jj is consumed at step jj; the k-mer that ends there starts
 // at G + jj - (k - 1) and is valid iff the last k bases consumed were called and no contig began behind the first of them.
-template <bool EMIT>
+template <bool EMIT, bool FWD = false>
 __device__ inline uint32_t rep_roll(const uint32_t (&w)[REP_WORDS], int64_t G, const int64_t *__restrict__ ctg_off, int n_ctg, int k,
                                     uint64_t *__restrict__ keys, uint32_t *__restrict__ vals, uint32_t at) {
     int c = ctg_of(ctg_off, n_ctg, G);
@@ -65,7 +66,7 @@ __device__ inline uint32_t rep_roll(const uint32_t (&w)[REP_WORDS], int64_t G, c
             rc = (rc >> 2) | (uint64_t(3u - code) << top);
         }
         if (jj >= k - 1 && run >= k) {
-            if (EMIT) { keys[at + n] = fwd < rc ? fwd : rc; vals[at + n] = uint32_t(Gp - (k - 1)); }
+            if (EMIT) { keys[at + n] = FWD || fwd < rc ? fwd : rc; vals[at + n] = uint32_t(Gp - (k - 1)); }
             n++;
         }
     }
@@ -78,7 +79,7 @@ __device__ inline uint32_t rep_roll(const uint32_t (&w)[REP_WORDS], int64_t G, c
 // counts; every lane puts its valid starts behind those of the lanes before it into LDS, and the workgroup copies the tile's
 // pairs out behind its offset with consecutive lanes on consecutive elements (a lane storing its own 16 directly would put the
 // 64 lanes of a store on 64 different lines).
-template <bool WRITE>
+template <bool WRITE, bool FWD>
 __global__ void __launch_bounds__(256) k_rep_pack(const uint8_t *__restrict__ seq, const int64_t *__restrict__ ctg_off, int n_ctg, int64_t N, int k,
                                                   uint32_t *__restrict__ out, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals) {
     __shared__ uint32_t lds[4];
@@ -101,7 +102,7 @@ __global__ void __launch_bounds__(256) k_rep_pack(const uint8_t *__restrict__ se
     } else {
         __shared__ uint64_t tile_keys[REP_TILE];
         __shared__ uint32_t tile_vals[REP_TILE];
-        if (n) (void)rep_roll<true>(w, G, ctg_off, n_ctg, k, tile_keys, tile_vals, before);      // (before + n <= total <= REP_TILE)
+        if (n) (void)rep_roll<true, FWD>(w, G, ctg_off, n_ctg, k, tile_keys, tile_vals, before);      // (before + n <= total <= REP_TILE)
         __syncthreads();
         const uint32_t at = out[blockIdx.x];
         for (uint32_t i = threadIdx.x; i < total; i += REP_WG) { keys[at + i] = tile_keys[i]; vals[at + i] = tile_vals[i]; }
@@ -248,9 +249,9 @@ int KmerWork::sort(size_t n, unsigned bits) {
     return VPR_OK;
 }
 
-int KmerWork::pack(int k, uint32_t *n) {
+int KmerWork::pack(int k, uint32_t *n, bool forward) {
     return compact(n_tiles, [&](bool write, uint32_t *out, uint64_t *ks, uint32_t *vs) {
-        const auto kernel = write ? k_rep_pack<true> : k_rep_pack<false>;
+        const auto kernel = !write ? k_rep_pack<false, false> : forward ? k_rep_pack<true, true> : k_rep_pack<true, false>;
         hipLaunchKernelGGL(kernel, dim3(unsigned(n_tiles)), dim3(REP_WG), 0, h->stream, d_seq, d_ctg, n_ctg, N, k, out, ks, vs);
     }, n);
 }

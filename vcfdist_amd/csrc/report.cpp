@@ -201,7 +201,7 @@ extern "C" int vrp_write_stratified(const char *prefix, const char *const *names
     return VRP_OK;
 }
 
-// context-strata.bed, repeat-strata.bed and long-repeat-strata.bed: one body
+// context-strata.bed, repeat-strata.bed, long-repeat-strata.bed and near-repeat-strata.bed: one body
 static int write_strata_bed(const char *entry, const char *file, const char *prefix, const char *const *contigs, int32_t n_ctg,
                             const char *const *names, int32_t n_strata, const int64_t *iv_off, const int32_t *start, const int32_t *stop) {
     const std::string who = entry;
@@ -233,6 +233,11 @@ extern "C" int vrp_write_repeat_bed(const char *prefix, const char *const *conti
 extern "C" int vrp_write_long_repeat_bed(const char *prefix, const char *const *contigs, int32_t n_ctg, const char *const *names, int32_t n_strata,
                                          const int64_t *iv_off, const int32_t *start, const int32_t *stop) {
     return write_strata_bed("vrp_write_long_repeat_bed", "long-repeat-strata.bed", prefix, contigs, n_ctg, names, n_strata, iv_off, start, stop);
+}
+
+extern "C" int vrp_write_near_repeat_bed(const char *prefix, const char *const *contigs, int32_t n_ctg, const char *const *names, int32_t n_strata,
+                                         const int64_t *iv_off, const int32_t *start, const int32_t *stop) {
+    return write_strata_bed("vrp_write_near_repeat_bed", "near-repeat-strata.bed", prefix, contigs, n_ctg, names, n_strata, iv_off, start, stop);
 }
 
 extern "C" int vrp_write_variant_strata(const char *prefix, const char *const *names, const vpr_variant_stratum *spec, int32_t n_spec,

@@ -25,7 +25,7 @@ class VrpContig(C.Structure):
                 ("n_flips", C.c_int32), ("switches", A.P_i32), ("flips", A.P_i32)]
 
 
-EXPORTED = ["vrp_phase_blocks", "vrp_write_precision_recall", "vrp_write_stratified", "vrp_write_context_bed", "vrp_write_repeat_bed", "vrp_write_long_repeat_bed", "vrp_write_bootstrap", "vrp_write_bootstrap_stratified", "vrp_write_phase_blocks", "vrp_write_superclusters",
+EXPORTED = ["vrp_phase_blocks", "vrp_write_precision_recall", "vrp_write_stratified", "vrp_write_context_bed", "vrp_write_repeat_bed", "vrp_write_long_repeat_bed", "vrp_write_near_repeat_bed", "vrp_write_bootstrap", "vrp_write_bootstrap_stratified", "vrp_write_phase_blocks", "vrp_write_superclusters",
             "vrp_write_switchflips", "vrp_write_phasing_summary", "vrp_ng50",
             "vrp_write_variants", "vrp_write_summary_vcf", "vrp_write_distance", "vrp_write_edits", "vrp_write_vcf", "vrp_last_error"]
 
@@ -172,6 +172,11 @@ def write_repeat_bed(prefix, contigs, names, intervals):
 def write_long_repeat_bed(prefix, contigs, names, intervals):
     """long-repeat-strata.bed (include/vcfdist_longrepeats.h): the same for the long repeat strata"""
     _write_strata_bed("vrp_write_long_repeat_bed", prefix, contigs, names, intervals)
+
+
+def write_near_repeat_bed(prefix, contigs, names, intervals):
+    """near-repeat-strata.bed (include/vcfdist_nearrepeats.h): the same for the near-repeat strata"""
+    _write_strata_bed("vrp_write_near_repeat_bed", prefix, contigs, names, intervals)
 
 
 def write_variant_strata(prefix, names, spec, n_query, n_truth):
