@@ -134,6 +134,11 @@ def test_tie_round_of_the_long_part_copies_the_saved_forward_flags():
 # the walk at every window level
 # ----------------------------------------------------------------------------------------------------------------------
 def _check_paths(batch, cfg, pairs):
+    """the walks of `pairs` (supercluster, alignment) against the oracle's path.  A random batch finishes its alignments in different
+    rounds, and vpr_download_path serves only the round that finished last in its ladder (an earlier round's workspace has been
+    reused): an alignment whose path cannot be downloaded is passed over, and half of the pairs must have been checked.  That
+    allowance belongs to random batches alone: tests/test_gpu_walk_edges.py runs one homozygous case per batch, whose four
+    alignments finish in the same round, skips nothing and treats a failed download as a failure."""
     cfg.flags |= A.CFG_KEEP_PATHS       # (the zero-distance lane kernel writes 16-byte path entries on request only)
     pr = api.PrecisionRecall(cfg)
     pr.run(batch)

@@ -745,6 +745,9 @@ __global__ void __launch_bounds__(64) k_bwd_stripe(DevBatch B, const AlnDesc *__
     lo[0] = __builtin_amdgcn_readlane(cbQ, (n_stripes - 1) & 63);
     lo[1] = __builtin_amdgcn_readlane(cbR, (n_stripes - 1) & 63);
     int bkc[2], bkn[2];
+    // the constants of the column just behind the window (uniform): a stripe's last row steps diagonally out of the window's last
+    // column into the window of the stripe above, and tp of that successor is no lane's own
+    int bec[2] = {0, 0}, ben[2];
 #pragma unroll
     for (int p = 0; p < 2; p++) {
         hi[p] = min(Lp[p] - 1, lo[p] + FS_W - 1);
@@ -769,8 +772,10 @@ __global__ void __launch_bounds__(64) k_bwd_stripe(DevBatch B, const AlnDesc *__
 #pragma unroll
         for (int p = 0; p < 2; p++) {
             bkn[p] = int(FK_NONE24);
+            ben[p] = 0;
             const int xn = nlo[p] + col;
             if (s > 0 && xn <= min(Lp[p] - 1, nlo[p] + FS_W - 1)) bkn[p] = bk[p][xn];
+            if (s > 0 && nlo[p] + FS_W <= Lp[p] - 1) ben[p] = bk[p][nlo[p] + FS_W];
         }
         // ---- per-lane constants of this stripe
         bool valid[2];
@@ -780,7 +785,7 @@ __global__ void __launch_bounds__(64) k_bwd_stripe(DevBatch B, const AlnDesc *__
         for (int p = 0; p < 2; p++) {
             valid[p] = lo[p] + col <= hi[p];
             tp_own[p] = (bkc[p] >> 24) & 1;
-            tp_right[p] = wave_shr1(tp_own[p], 0);
+            tp_right[p] = wave_shr1(tp_own[p], (bec[p] >> 24) & 1);     // (lane 0: the column behind the window; used in the stripe's last row only)
             zl[p] = bkc[p] & 0xffffff;   // swap target (absolute index in the other plane) or FK_NONE24
             zkey[p] = f_swp_key(rank_of(uint32_t(bkc[p]) >> 24));
         }
@@ -884,7 +889,7 @@ __global__ void __launch_bounds__(64) k_bwd_stripe(DevBatch B, const AlnDesc *__
         // record across the loop's back edge of which loads are done: with a store or a load still in its books there it put a
         // `s_waitcnt vmcnt(0)` in front of the first use of bkc -- right behind the NEXT stripe's loads: a full round trip per
         // stripe of eight rows, and another one per store in front of the next store's data)
-        asm volatile("" ::"v"(bkn[0]), "v"(bkn[1]) : "memory");
+        asm volatile("" ::"v"(bkn[0]), "v"(bkn[1]), "v"(ben[0]), "v"(ben[1]) : "memory");
         // ---- flush this stripe's path_ptr rows (in place of the forward flags), 16 bytes per lane (lds_to_global16: issued
         // without the compiler's knowledge; the rows are next read by the walk, another kernel)
 #pragma unroll
@@ -898,6 +903,7 @@ __global__ void __launch_bounds__(64) k_bwd_stripe(DevBatch B, const AlnDesc *__
         lo[0] = nlo[0]; lo[1] = nlo[1];
         hi[0] = min(Lq - 1, lo[0] + FS_W - 1); hi[1] = min(Lr - 1, lo[1] + FS_W - 1);
         bkc[0] = bkn[0]; bkc[1] = bkn[1];
+        bec[0] = ben[0]; bec[1] = ben[1];
         if ((s & 63) == 0 && s > 0) {
             cbQ = lbQ; cbR = lbR;
             load_chunk(((s - 1) & ~63) - 64, lbQ, lbR);

@@ -406,7 +406,9 @@ __global__ void __launch_bounds__(NW * 64) k_bwd_wide(DevBatch B, const AlnDesc 
             bkn[p] = int(FK_NONE24); bkrn[p] = 0;
             const int xn = nlo[p] + col, nh = min(Lp[p] - 1, nlo[p] + W - 1);
             if (s > 0 && xn <= nh) bkn[p] = bk[p][xn];
-            if (s > 0 && xn + 1 <= nh) bkrn[p] = bk[p][xn + 1];
+            // (column + 1 of the window's last column lies behind the window: a stripe's last row steps diagonally into it, in the
+            // window of the stripe above)
+            if (s > 0 && xn <= nh && xn + 1 <= Lp[p] - 1) bkrn[p] = bk[p][xn + 1];
         }
         bool valid[2];
         int tp_right[2], zl[2];
@@ -414,7 +416,7 @@ __global__ void __launch_bounds__(NW * 64) k_bwd_wide(DevBatch B, const AlnDesc 
 #pragma unroll
         for (int p = 0; p < 2; p++) {
             valid[p] = lo[p] + col <= hi[p];
-            tp_right[p] = (lo[p] + col + 1 <= hi[p]) ? ((bkrc[p] >> 24) & 1) : 0;
+            tp_right[p] = (bkrc[p] >> 24) & 1;
             zl[p] = bkc[p] & 0xffffff;   // swap target (absolute index in the other plane) or FK_NONE24
             zkey[p] = f_swp_key(rank_of(uint32_t(bkc[p]) >> 24));
         }
