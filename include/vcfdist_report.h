@@ -9,6 +9,7 @@
  *   vrp_write_repeat_bed         (none: the intervals of the repeat strata, include/vcfdist_repeats.h)
  *   vrp_write_long_repeat_bed    (none: the intervals of the long repeat strata, include/vcfdist_longrepeats.h)
  *   vrp_write_near_repeat_bed    (none: the intervals of the near-repeat strata, include/vcfdist_nearrepeats.h)
+ *   vrp_write_derived_strata     (none: derived-strata.tsv, declared in include/vcfdist_derive.h)
  *   vrp_write_phase_blocks       write_results, phase-blocks.tsv                  src/print.cpp:585-609
  *   vrp_write_superclusters      write_results, superclusters.tsv                  src/print.cpp:611-671
  *   vrp_write_variants           write_results, query.tsv / truth.tsv              src/print.cpp:673-876

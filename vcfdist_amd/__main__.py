@@ -20,7 +20,11 @@ With --stratify-near-repeats K:M[,K:M...] the near-repeat strata the user names 
 include/vcfdist_nearrepeats.h: one more genome-wide pass) follow those, and near-repeat-strata.bed holds their intervals.
 With --stratify-variants the default variant strata
 (include/vcfdist_varstrata.h: transitions / transversions, indel size bins, hom / het, isolated / crowded -- bits made on the GPU from
-the variant tables) follow those, or stand alone, and variant-strata.tsv lists them with their numbers of members.  With --bootstrap N
+the variant tables) follow those, or stand alone, and variant-strata.tsv lists them with their numbers of members.  With
+--stratify-derive NAME=EXPR (repeatable) a stratum is made on the GPU from the membership bits of the strata in front of it
+(include/vcfdist_derive.h: & | ! and parentheses over stratum names, '*' globs standing for the union of what they match), and with
+--stratify-cross LIST:LIST (repeatable) every pair a&b of the two lists of globs; they follow every other stratum, the derived ones
+first, need another --stratify* option, and derived-strata.tsv lists them with their numbers of members.  With --bootstrap N
 the counters are
 resampled N times on the GPU (include/vcfdist_bootstrap.h: a Poisson bootstrap over superclusters, conditional on the phasing, the
 BEST threshold kept at the point estimate's): bootstrap-precision-recall-summary.tsv with 95 % percentile intervals for precision,
@@ -206,12 +210,30 @@ class Family:
 
 
 @dataclass
+class Derived:
+    """the derived and the crossed strata of a StrataPlan (--stratify-derive, --stratify-cross; include/vcfdist_derive.h), behind every
+    other stratum: their names, kinds (A.DV_KIND_*) and expressions as derived-strata.tsv lists them, and the one call's programs"""
+    names: list = field(default_factory=list)
+    kinds: list = field(default_factory=list)
+    expressions: list = field(default_factory=list)
+    code_off: list = field(default_factory=lambda: [0])
+    code: list = field(default_factory=list)
+    ms: float = 0.0                                 # on the device
+
+    def add(self, name, kind, expression, code):
+        self.names.append(name); self.kinds.append(kind); self.expressions.append(expression)
+        self.code += [int(c) for c in code]
+        self.code_off.append(len(self.code))
+
+
+@dataclass
 class StrataPlan:
     """which strata, in which order (StrataPlan in main.cpp): every stratum's name in table order, the list's BEDs, the families"""
     names: list = field(default_factory=list)
     beds: list = field(default_factory=list)
     families: list = field(default_factory=lambda: [Family(**row) for row in FAMILIES])
     near: Family = field(default_factory=lambda: Family(**NEAR_FAMILY))     # the user's near-repeat strata, behind the long repeat family's
+    derived: Derived = field(default_factory=Derived)                       # behind everything else
     kmer = property(lambda self: [fam for fam in self.families[:2] + [self.near] if fam.specs])       # the genome-wide families that are on
     ordered = property(lambda self: self.families[:2] + [self.near] + self.families[2:])            # in table order
     ctx = property(lambda self: self.families[2])
@@ -242,7 +264,8 @@ def matchkind_line(p):
 
 class Totals:
     """the sums over the contigs (Totals in main.cpp): counts[2][4][3][nq], with strata the stratified ones, the hap-variants seen
-    and in no stratum and the variant strata's members per callset, with --bootstrap the replicates' (and per stratum), the label
+    and in no stratum and the variant strata's members per callset (behind everything else the derived strata's, when there are
+    such), with --bootstrap the replicates' (and per stratum), the label
     passes with their cuts.  tally lists the int64 arrays that are summed over the ranks, in the order of the vector (pack, unpack):
     every sum is added in place, so the list made here stays the owners'."""
     def __init__(self, args, plan):
@@ -272,7 +295,8 @@ class Totals:
                 p.strata = zeros(n_strata, 2, 4, p.labels, nq) if plan else None
                 p.boot = zeros(n_rep, 2, 4, p.labels, nq) if n_rep else None
         tally = [self.total, self.strat, self.seen_none, self.vs_members, self.boot, self.boot_strat] + [p.counts for p in self.passes]
-        self.tally = [a for a in tally + [cut for p in self.passes for cut in (p.strata, p.boot)] if a is not None]
+        self.dv_members = zeros(2, len(plan.derived.names)) if plan and plan.derived.names else None
+        self.tally = [a for a in tally + [cut for p in self.passes for cut in (p.strata, p.boot)] + [self.dv_members] if a is not None]
 
 
 def pack(arrays):
@@ -305,10 +329,15 @@ def stratify_contig(pr, prep, plan, tot, args, pb, part_idx=None):
         keep_context_intervals(pr, plan.ctx, name)
     elif table is not None:
         pr.strata_masks(prep["variants"], table)
-    n_pre = n_strata - len(plan.vs.specs or ())
+    dv = plan.derived
+    n_vs = len(plan.vs.specs or ())
+    n_pre = n_strata - len(dv.names) - n_vs
     if plan.vs.specs:       # --stratify-variants: the bits made from the variant tables follow in the same words
         pr.varstrata_masks(prep["variants"], plan.vs.specs, append=n_pre > 0)
         plan.vs.ms += pr.varstrata_timing()
+    if dv.names:            # --stratify-derive, --stratify-cross: one call on the bits that are there, per variant (a shard's edge cannot matter)
+        pr.derive_masks(dv.code_off, dv.code)
+        dv.ms += pr.derive_timing()
     words = pr.download_strata_masks()
     if part_idx is not None:
         words = [np.stack([shard.subset_per_variant(w, whole.var_off[s], part_idx) for w in words[s]]) for s in range(4)]
@@ -316,9 +345,11 @@ def stratify_contig(pr, prep, plan, tot, args, pb, part_idx=None):
     tot.strat += S.pr_counts_strata(pr, None, pb, args.min_qual, args.max_qual)     # (the classes are resident: pr_counts)
     for w in words:
         tot.seen_none += (w.shape[1], int((np.bitwise_or.reduce(w, axis=0) == 0).sum()))
-    for k in range(n_pre, n_strata):      # variant-strata.tsv: the members of every variant stratum, per callset
-        for s, w in enumerate(words):
-            tot.vs_members[s >> 1, k - n_pre] += int(((w[k >> 6] >> np.uint64(k & 63)) & np.uint64(1)).sum())
+    # variant-strata.tsv, derived-strata.tsv: the members of every variant stratum and of every derived one, per callset
+    for members, first, n in ((tot.vs_members, n_pre, n_vs), (tot.dv_members, n_pre + n_vs, len(dv.names))):
+        for k in range(first, first + n):
+            for s, w in enumerate(words):
+                members[s >> 1, k - first] += int(((w[k >> 6] >> np.uint64(k & 63)) & np.uint64(1)).sum())
 
 
 def keep_context_intervals(pr, ctx, name):
@@ -638,6 +669,14 @@ def argument_parser():
                     help="the default variant strata (transitions / transversions, indel size bins, hom / het, isolated / crowded), made "
                          "on the GPU from the variant tables, behind those of --stratify and --stratify-context or alone; "
                          "variant-strata.tsv lists them with their numbers of members")
+    ap.add_argument("--stratify-derive", metavar="NAME=EXPR", action="append", default=[],
+                    help="a stratum derived on the GPU from the membership bits of the strata in front of it (repeatable): operands are "
+                         "stratum names, or globs with '*' that stand for the union of what they match; operators | & ! and parentheses; "
+                         "!x is every hap-variant that is not a member of x.  Needs another --stratify* option; the derived strata follow "
+                         "every other stratum in command-line order and are listed in derived-strata.tsv")
+    ap.add_argument("--stratify-cross", metavar="LIST:LIST", action="append", default=[],
+                    help="the strata a&b of every pair of two lists of globs (glob[,glob...]; repeatable), behind the derived strata, which "
+                         "the lists may name; at most 512 derived plus crossed strata in all")
     ap.add_argument("--bootstrap", metavar="N", type=bootstrap_replicates, default=0,
                     help="resample the counters N times (1 to 100000) over superclusters on the GPU: 95 %% percentile intervals for "
                          "precision, recall and F1 (bootstrap-precision-recall-summary.tsv, bootstrap-replicates.tsv)")
@@ -718,6 +757,9 @@ def plan_strata(args):
     """--stratify*: the strata list and every BED it names, read and checked before any input is opened, and behind the list's strata
     the defaults of every family that is on.  -> StrataPlan, or None without such an option"""
     if not stratifying(args):
+        for option in (DERIVE_OPTION, CROSS_OPTION):
+            if option_on(args, option):
+                raise SystemExit(f"ERROR: {option} needs another --stratify* option")
         return None
     plan = StrataPlan()
     if args.stratify:
@@ -739,7 +781,35 @@ def plan_strata(args):
             if n in plan.names:
                 raise SystemExit(f"ERROR: strata list '{args.stratify}': duplicate stratum name '{n}' (a {fam.word} stratum of {fam.option})")
         plan.names += fam.names
+    derive_strata(args, plan)
     return plan
+
+
+DERIVE_OPTION, CROSS_OPTION = "--stratify-derive", "--stratify-cross"
+
+
+def derive_strata(args, plan):
+    """--stratify-derive, --stratify-cross: every entry compiled by the library (one compiler for both command lines: its messages)
+    against the names in front of it -- the derived entries in command-line order, then the crossed pairs, option by option"""
+    dv = plan.derived
+
+    def add(option, name, kind, expression, code):
+        if len(dv.names) == A.DV_MAX_CLI:
+            raise SystemExit(f"ERROR: {option}: more than {A.DV_MAX_CLI} derived and crossed strata")
+        dv.add(name, kind, expression, code)
+        plan.names.append(name)
+    try:
+        for entry in args.stratify_derive:
+            option = DERIVE_OPTION
+            name, code = api.derive_compile(entry, plan.names)
+            add(option, name, A.DV_KIND_DERIVE, entry.split("=", 1)[1], code)
+        for entry in args.stratify_cross:
+            option = CROSS_OPTION
+            for a, b in api.derive_cross(entry, plan.names):
+                name = plan.names[a] + "&" + plan.names[b]
+                add(option, name, A.DV_KIND_CROSS, name, (a, b, A.DV_AND))
+    except api.VprError as e:
+        raise SystemExit(f"ERROR: {option}: {e}")
 
 
 EMPTY_SLOT = dict(pos=np.zeros(0, np.int32), rlen=np.zeros(0, np.int32), type=np.zeros(0, np.uint8), var_qual=np.zeros(0, np.float32),
@@ -851,6 +921,7 @@ def reduce_ranks(args, ranks, plan, tot, reports):
         plan.ctx.rows = {k: v for part in gathered for k, v in part.items()}
     # the device times that are summed over the ranks, as (owner, attribute): one list, gathered once
     times = [(fam, "ms") for fam in ((plan.ctx, plan.vs) if plan is not None else ()) if fam.specs]
+    times += [(plan.derived, "ms")] if plan is not None and plan.derived.names else []
     times += [(p, "ms") for p in tot.passes] + [(p, "cut_ms") for p in tot.passes if args.cut_classes]
     dist.all_gather_object(gathered, tuple(getattr(owner, name) for owner, name in times))
     for i, (owner, name) in enumerate(times):
@@ -871,6 +942,9 @@ def write_outputs(args, inp, plan, tot, reports):
             RP.write_context_bed(prefix, inp.contigs, plan.ctx.names, plan.ctx.rows)
         if plan.vs.specs:
             RP.write_variant_strata(prefix, plan.vs.names, plan.vs.specs, tot.vs_members[0], tot.vs_members[1])
+        if plan.derived.names:
+            dv = plan.derived
+            RP.write_derived_strata(prefix, dv.names, dv.kinds, dv.expressions, tot.dv_members[0], tot.dv_members[1])
     for p in tot.passes:
         getattr(RP, p.write)(prefix, p.counts, tot.total, mn, mx)
     if tot.boot is not None:
@@ -908,6 +982,10 @@ def report(args, plan, tot, rows):
             say(f"context strata: {n_iv} intervals of {len(plan.ctx.specs)} strata, {plan.ctx.ms:.3f} ms on the device")
         if plan.vs.specs:
             say(f"variant strata: {len(plan.vs.specs)} strata, {plan.vs.ms:.3f} ms on the device")
+        if plan.derived.names:
+            n_cross = sum(k == A.DV_KIND_CROSS for k in plan.derived.kinds)
+            say(f"derived strata: {len(plan.derived.names)} strata ({len(plan.derived.names) - n_cross} derived, {n_cross} crossed), "
+                f"{plan.derived.ms:.3f} ms on the device")
     for p in tot.passes:
         print(p.line(p), file=sys.stderr)
     if args.cut_classes:

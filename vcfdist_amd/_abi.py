@@ -612,6 +612,12 @@ def vs_near(window, min_n, max_n=-1):
     return VprVariantStratum(VS_NEAR, 0, 0, 0, window, min_n, max_n)
 
 
+# ---- include/vcfdist_derive.h
+DV_AND, DV_OR, DV_NOT = -1, -2, -3
+DV_MAX_DEPTH, DV_MAX_SPEC, DV_MAX_CODE, DV_MAX_CLI = 32, 1024, 65536, 512
+DV_KIND_DERIVE, DV_KIND_CROSS = 0, 1
+
+
 # ---- include/vcfdist_errclass.h
 EC_GT, EC_SYNC, EC_PHASE, EC_SITE, EC_NEAR, EC_ALONE, EC_LOWQ = range(7)
 EC_CLASSES = 7

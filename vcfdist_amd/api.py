@@ -119,6 +119,12 @@ def lib():
     L.vpr_varstrata_default.argtypes = [C.POINTER(C.POINTER(A.VprVariantStratum)), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.c_int32)]
     L.vpr_varstrata_masks.argtypes = [H, C.POINTER(A.VprVariants), C.POINTER(A.VprVariantStratum), C.c_int32, C.c_int32]
     L.vpr_varstrata_timing.argtypes = [H, C.POINTER(C.c_double)]
+    L.vpr_derive_masks.argtypes = [H, A.P_i32, A.P_i32, C.c_int32]
+    L.vpr_derive_timing.argtypes = [H, C.POINTER(C.c_double)]
+    L.vpr_derive_compile.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.c_char_p, C.c_size_t, A.P_i32, C.c_int32, C.POINTER(C.c_int32)]
+    L.vpr_derive_cross.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, A.P_i32, C.c_int32, C.POINTER(C.c_int32)]
+    L.vpr_derive_last_error.restype = C.c_char_p
+    L.vpr_derive_last_error.argtypes = []
     for name, own in (("errclass", [C.c_int32]), ("matchkind", [])):      # the label passes; own: errclass' window
         args = [C.POINTER(A.VprVariants), C.c_void_p, A.P_i32] + own + [C.c_int32, C.c_int32, A.P_i64]
         getattr(L, f"vpr_{name}").argtypes = [H] + args
@@ -181,6 +187,9 @@ NEARREPEATS_EXPORTED = ["vpr_nearrepeat_intervals", "vpr_nearrepeat_interval_cou
                         "vpr_nearrepeat_stats", "vpr_nearrepeat_timing", "vpr_nearrepeat_name", "vrp_write_near_repeat_bed"]
 # include/vcfdist_varstrata.h
 VARSTRATA_EXPORTED = ["vpr_varstrata_default", "vpr_varstrata_masks", "vpr_varstrata_timing", "vrp_write_variant_strata"]
+# include/vcfdist_derive.h
+DERIVE_EXPORTED = ["vpr_derive_masks", "vpr_derive_timing", "vpr_derive_compile", "vpr_derive_cross", "vpr_derive_last_error",
+                   "vrp_write_derived_strata"]
 # include/vcfdist_errclass.h
 ERRCLASS_EXPORTED = ["vpr_errclass", "vpr_allreduce_errclass", "vpr_errclass_download", "vpr_errclass_timing", "vpr_errclass_names",
                      "vrp_write_error_classes"]
@@ -287,6 +296,28 @@ def varstrata_default():
     if rc:
         raise VprError(f"vpr_varstrata_default failed ({rc})")
     return [names[k].decode() for k in range(n.value)], [A.VprVariantStratum.from_buffer_copy(spec[k]) for k in range(n.value)]
+
+
+def _c_names(names):
+    return (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+
+
+def derive_compile(entry, names, code_cap=A.DV_MAX_CODE):
+    """one NAME=EXPR of --stratify-derive against `names`, the strata in front of it in table order (vpr_derive_compile,
+    include/vcfdist_derive.h) -> (NAME, the postfix program as int32).  A malformed entry raises VprError with the library's text."""
+    name, code, n = C.create_string_buffer(len(entry.encode()) + 1), np.zeros(max(code_cap, 1), np.int32), C.c_int32()
+    if lib().vpr_derive_compile(entry.encode(), _c_names(names), len(names), name, len(name), A._ptr(code, C.c_int32), code_cap, C.byref(n)):
+        raise VprError(lib().vpr_derive_last_error().decode())
+    return name.value.decode(), code[:n.value].copy()
+
+
+def derive_cross(entry, names, pairs_cap=A.DV_MAX_CLI):
+    """one LIST:LIST of --stratify-cross against `names` (vpr_derive_cross) -> [(a, b)], indices into names, left-major; the crossed
+    stratum is a & b, named names[a] + "&" + names[b].  A malformed entry raises VprError with the library's text."""
+    pairs, n = np.zeros(2 * max(pairs_cap, 1), np.int32), C.c_int32()
+    if lib().vpr_derive_cross(entry.encode(), _c_names(names), len(names), A._ptr(pairs, C.c_int32), pairs_cap, C.byref(n)):
+        raise VprError(lib().vpr_derive_last_error().decode())
+    return [(int(pairs[2 * i]), int(pairs[2 * i + 1])) for i in range(n.value)]
 
 
 def _label_names(entry, n):
@@ -686,6 +717,21 @@ class PrecisionRecall:
         self._chk(lib().vpr_varstrata_masks(self._h, C.byref(vs), arr, len(spec), 1 if append else 0), "vpr_varstrata_masks")
         n_old = self._strata[0] if append else 0
         self._strata = (n_old + len(spec), [int(vs.var_off[h][n_sc]) for h in range(A.HAPS)])
+
+    def derive_masks(self, code_off, code):
+        """The derived strata (include/vcfdist_derive.h): entry j's postfix program code[code_off[j]:code_off[j + 1]] (operands >= 0,
+        A.DV_AND / A.DV_OR / A.DV_NOT) runs on the device over every hap-variant's resident membership bits and becomes stratum
+        n_prev + j behind the resident ones.  Reads no variant tables."""
+        off, code = np.ascontiguousarray(code_off, np.int32), np.ascontiguousarray(code, np.int32)
+        n = len(off) - 1
+        if code.size == 0:
+            code = np.zeros(1, np.int32)
+        self._chk(lib().vpr_derive_masks(self._h, A._ptr(off, C.c_int32), A._ptr(code, C.c_int32), n), "vpr_derive_masks")
+        self._strata = (self._strata[0] + n, self._strata[1])
+
+    def derive_timing(self):
+        """ms of the last derive_masks' kernel launches, from HIP events on the handle's stream"""
+        return self._timing("vpr_derive_timing")
 
     def _timing(self, entry):
         """the one device time (ms) that `entry` returns"""

@@ -13,7 +13,7 @@
 //   vcfdist_gpu <query.vcf[.gz]> <truth.vcf[.gz]> <ref.fasta[.gz]> [-b regions.bed] [-p prefix] [-n] [-c biwfa | gap N | size N] [-l max variant size]
 //               [-s max supercluster size] [-mn / -mx qual] [-f filters] [-i iterations] [-x -o -e penalties] [-ct credit threshold] [-pt phasing threshold]
 //               [-sv threshold] [--reach-min-gap N] [--strict] [--device N] [-d] [-ex -eo -ee evaluation penalties] [-rq] [-rt] [-ro] [--stratify strata.tsv]
-//               [--stratify-repeats] [--stratify-long-repeats] [--stratify-near-repeats K:M[,K:M...]] [--stratify-context] [--stratify-variants] [--bootstrap N] [--bootstrap-seed S]
+//               [--stratify-repeats] [--stratify-long-repeats] [--stratify-near-repeats K:M[,K:M...]] [--stratify-context] [--stratify-variants] [--stratify-derive NAME=EXPR]... [--stratify-cross LIST:LIST]... [--bootstrap N] [--bootstrap-seed S]
 //               [--classify-errors] [--error-window N] [--classify-matches] [--cut-classes]
 // What an option adds (its header under include/ says how) and the files it writes:
 //   -d                       vcfdist_distance.h: the distance metrics (edits_wrapper, dist.cpp:1908-2077) behind each contig's path (main.cpp:223-238)
@@ -27,6 +27,10 @@
 //   --stratify-context       vcfdist_context.h: homopolymers, short tandem repeats, GC bands, intervals built from the FASTA: context-strata.bed
 //   --stratify-variants      vcfdist_varstrata.h: transitions / transversions, indel size bins, hom / het, isolated / crowded: variant-strata.tsv
 //                            (the strata stand in this order in every table; each default set also stands alone)
+//   --stratify-derive        vcfdist_derive.h: NAME=EXPR, a stratum made from the membership bits of the strata in front of it (& | ! and parentheses
+//                            over names, '*' globs for the union of what they match), repeatable, behind every other stratum: derived-strata.tsv
+//   --stratify-cross         vcfdist_derive.h: LIST:LIST, the strata a&b of every pair of two lists of globs, repeatable, behind the derived ones
+//                            (both need another --stratify* option; at most VPR_DV_MAX_CLI of them in all)
 //   --classify-errors        vcfdist_errclass.h: the first error class that applies to every query FP and truth FN, something within --error-window N
 //                            bases (default 50) among them: error-classes[-summary].tsv
 //   --classify-matches       vcfdist_matchkind.h: exact, shifted, regrouped or partial for every TP of either callset: match-kinds[-summary].tsv
@@ -60,6 +64,7 @@
 #include "../../include/vcfdist_nearrepeats.h"
 #include "../../include/vcfdist_strata.h"
 #include "../../include/vcfdist_varstrata.h"
+#include "../../include/vcfdist_derive.h"
 #include "../../include/vcfdist_errclass.h"
 #include "../../include/vcfdist_matchkind.h"
 
@@ -69,6 +74,7 @@ struct Args {
     std::string query, truth, fasta, bed, filter, prefix = "./", cluster = "biwfa", stratify;
     bool stratify_context = false, stratify_variants = false, stratify_repeats = false, stratify_long_repeats = false;
     std::vector<vpr_near_stratum> near;    // --stratify-near-repeats: the entries (empty: not given)
+    std::vector<std::string> derive, cross;     // --stratify-derive, --stratify-cross: the entries as given, in command-line order
     int max_size = 5000, min_qual = 0, max_qual = 60, cluster_gap = 50, max_iterations = 4, max_supercluster_size = 10000;
     int sub = 5, open = 6, extend = 2, sv_threshold = 50, reach_min_gap = 10, device = 0;
     int eval_sub = 3, eval_open = 2, eval_extend = 1;      // globals.h:52-55
@@ -190,6 +196,8 @@ Args parse(int argc, char **argv) {
         else if (o == "--stratify-long-repeats") a.stratify_long_repeats = true;
         else if (o == "--stratify-near-repeats") a.near = near_strata(need(i));
         else if (o == "--stratify-variants") a.stratify_variants = true;
+        else if (o == "--stratify-derive") a.derive.push_back(need(i));
+        else if (o == "--stratify-cross") a.cross.push_back(need(i));
         else if (o == "--bootstrap") a.bootstrap = bootstrap_replicates(need(i));
         else if (o == "--bootstrap-seed") a.bootstrap_seed = bootstrap_seed(need(i));
         else if (o == "--classify-errors") a.classify_errors = true;
@@ -326,7 +334,7 @@ int long_repeat_stats(vpr_handle *h, int64_t *n_valid, int64_t *n_repeated) {
 struct StrataPlan : Pinned {
     std::vector<std::string> names;                      // every stratum in table order
     std::vector<vio_bed *> beds;                         // the list's BEDs
-    int n_list = 0, n_bed = 0, n_pre = 0, n_strata = 0;  // strata up to the list's, the k-mer families', the context, the variant ones
+    int n_list = 0, n_bed = 0, n_pre = 0, n_strata = 0;  // strata up to the list's, the k-mer families', the context; all of them
     KmerFamily kmer[3] = {
         {&Args::stratify_repeats, "--stratify-repeats", "repeat", "vpr_repeats_default", vpr_repeats_default, vpr_repeat_intervals, vpr_repeat_interval_counts,
          vpr_repeat_download_intervals, vpr_repeat_stats, vpr_repeat_timing, vrp_write_repeat_bed},
@@ -337,6 +345,14 @@ struct StrataPlan : Pinned {
     const vpr_context_stratum *ctx_spec = nullptr; const vpr_variant_stratum *vs_spec = nullptr;
     const char *const *ctx_names = nullptr, *const *vs_names = nullptr;
     int32_t n_ctx = 0, n_vs = 0;
+    // --stratify-derive, --stratify-cross (include/vcfdist_derive.h), behind every other stratum: their names, kinds and expressions
+    // as derived-strata.tsv lists them, and the one call's programs
+    struct Derived {
+        std::vector<std::string> names, expressions;
+        std::vector<int32_t> kinds, code_off = {0}, code;
+        int n_cross = 0;
+    } dv;
+    int32_t n_dv = 0;
     ~StrataPlan() { for (vio_bed *b : beds) vio_bed_free(b); }
 };
 // --stratify: the strata list (GIAB format: name<TAB>path per line, blank and '#' lines skipped, a relative path is taken from
@@ -376,8 +392,47 @@ void append_default_strata(std::vector<std::string> &names, const char *const *d
         names.push_back(defaults[k]);
     }
 }
+// --stratify-derive, --stratify-cross: every entry compiled by the library (one compiler for both command lines: its messages) against
+// the names in front of it -- the derived entries in command-line order, then the crossed pairs, option by option
+void derive_strata(const Args &A, StrataPlan &S) {
+    if (S.names.empty()) {
+        if (!A.derive.empty()) die("ERROR: --stratify-derive needs another --stratify* option");
+        if (!A.cross.empty()) die("ERROR: --stratify-cross needs another --stratify* option");
+        return;
+    }
+    StrataPlan::Derived &D = S.dv;
+    auto add = [&](const char *option, const std::string &name, int32_t kind, const std::string &expression, const int32_t *code, int32_t n_code) {
+        if (S.n_dv == VPR_DV_MAX_CLI) die("ERROR: %s: more than %d derived and crossed strata", option, VPR_DV_MAX_CLI);
+        D.names.push_back(name); D.kinds.push_back(kind); D.expressions.push_back(expression);
+        D.code.insert(D.code.end(), code, code + n_code);
+        D.code_off.push_back(int32_t(D.code.size()));
+        S.names.push_back(name); S.n_dv++;
+    };
+    std::vector<int32_t> code(VPR_DV_MAX_CODE), pairs(2 * VPR_DV_MAX_CLI);
+    for (const std::string &entry : A.derive) {
+        const std::vector<const char *> names = c_strs(S.names);
+        std::vector<char> name(entry.size() + 1);
+        int32_t n_code = 0;
+        if (vpr_derive_compile(entry.c_str(), names.data(), int32_t(names.size()), name.data(), name.size(), code.data(), int32_t(code.size()), &n_code))
+            die("ERROR: --stratify-derive: %s", vpr_derive_last_error());
+        add("--stratify-derive", name.data(), VPR_DV_KIND_DERIVE, entry.substr(entry.find('=') + 1), code.data(), n_code);
+    }
+    for (const std::string &entry : A.cross) {
+        const std::vector<const char *> names = c_strs(S.names);
+        int32_t n_pairs = 0;
+        if (vpr_derive_cross(entry.c_str(), names.data(), int32_t(names.size()), pairs.data(), VPR_DV_MAX_CLI, &n_pairs))
+            die("ERROR: --stratify-cross: %s", vpr_derive_last_error());
+        for (int32_t i = 0; i < n_pairs; i++) {
+            const int32_t a = pairs[size_t(2 * i)], b = pairs[size_t(2 * i + 1)], and_ab[3] = {a, b, VPR_DV_AND};
+            const std::string name = S.names[size_t(a)] + "&" + S.names[size_t(b)];
+            add("--stratify-cross", name, VPR_DV_KIND_CROSS, name, and_ab, 3);
+            D.n_cross++;
+        }
+    }
+}
 // the table order: the list's strata, the three k-mer families' (their intervals come from a genome-wide pass each in front of the
-// contig loop and then travel with the list's rows), the default sequence-context strata, the default variant strata
+// contig loop and then travel with the list's rows), the default sequence-context strata, the default variant strata, the derived
+// and the crossed strata
 void plan_strata(const Args &A, StrataPlan &S) {
     if (!A.stratify.empty()) read_strata(A.stratify, S);
     S.n_list = int(S.names.size());
@@ -408,6 +463,7 @@ void plan_strata(const Args &A, StrataPlan &S) {
         if (vpr_varstrata_default(&S.vs_spec, &S.vs_names, &S.n_vs)) die("ERROR: vpr_varstrata_default failed");
         append_default_strata(S.names, S.vs_names, S.n_vs, "variant", "--stratify-variants", A.stratify);
     }
+    derive_strata(A, S);
     S.n_strata = int(S.names.size());
 }
 // the genome-wide pass over all contigs of the FASTA, on a handle of its own: the evaluation has the memory back
@@ -661,11 +717,12 @@ struct Totals {
     std::vector<int64_t> total, strat_total;             // counts[2][4][3][nq]; --stratify*: counts[n_strata][2][4][3][nq]
     int64_t strat_vars = 0, strat_none = 0;              // hap-variants seen / in no stratum
     std::vector<int64_t> vs_query, vs_truth;             // variant-strata.tsv: members per callset
+    std::vector<int64_t> dv_query, dv_truth;             // derived-strata.tsv: the same
     std::vector<std::string> ctx_contigs;                // context-strata.bed: contigs, rows contig-major
     std::vector<int64_t> ctx_off = {0};
     std::vector<int32_t> ctx_start, ctx_stop;
     std::vector<int64_t> boot_total, boot_strat;         // --bootstrap: counts[n_rep][2][4][3][nq], with strata also [n_strata][n_rep][...]
-    double vs_ms = 0, ctx_ms = 0, boot_ms = 0;           // device ms of the launches
+    double vs_ms = 0, dv_ms = 0, ctx_ms = 0, boot_ms = 0;    // device ms of the launches
     LabelPass pass[2] = {
         {"error classes", &Args::classify_errors, VPR_EC_CLASSES, label_errors, vpr_errclass_timing, vrp_write_error_classes, vpr_errclass_strata,
          vpr_errclass_boot, vpr_errclass_cut_timing, vrp_write_error_classes_stratified, vrp_write_error_classes_bootstrap},
@@ -677,6 +734,7 @@ struct Totals {
         total.assign(size_t(2) * VPR_VARTYPES * 3 * size_t(A.max_qual - A.min_qual + 1), 0);
         strat_total.assign(total.size() * size_t(S.n_strata), 0);
         vs_query.assign(size_t(S.n_vs), 0); vs_truth.assign(size_t(S.n_vs), 0);
+        dv_query.assign(size_t(S.n_dv), 0); dv_truth.assign(size_t(S.n_dv), 0);
         boot_total.assign(total.size() * size_t(A.bootstrap), 0); boot_strat.assign(boot_total.size() * size_t(S.n_strata), 0);
         for (LabelPass &P : pass) {
             const bool on = A.*P.option;
@@ -800,6 +858,12 @@ void stratify_contig(const Run &R, Contig &c) {
         check(R, c, vpr_varstrata_masks(R.h, &c.V, S.vs_spec, S.n_vs, S.n_pre ? 1 : 0) || vpr_varstrata_timing(R.h, &ms));
         T.vs_ms += ms;
     }
+    // (with --stratify-derive / --stratify-cross one call on the bits that are there appends theirs)
+    if (S.n_dv) {
+        double ms = 0;
+        check(R, c, vpr_derive_masks(R.h, S.dv.code_off.data(), S.dv.code.data(), S.n_dv) || vpr_derive_timing(R.h, &ms));
+        T.dv_ms += ms;
+    }
     std::vector<int64_t> counts(T.strat_total.size(), 0);
     check(R, c, vpr_pr_counts_strata(R.h, nullptr, c.pb.data(), A.min_qual, A.max_qual, counts.data()));
     add_into(T.strat_total.data(), counts.data(), counts.size());
@@ -816,6 +880,8 @@ void stratify_contig(const Run &R, Contig &c) {
             T.strat_none += any == 0;
             for (int k = 0; k < S.n_vs; k++)
                 (i < 2 ? T.vs_query : T.vs_truth)[size_t(k)] += int64_t(words[i][size_t((S.n_pre + k) >> 6) * nv + v] >> ((S.n_pre + k) & 63) & 1);
+            for (int k = 0, at = S.n_pre + S.n_vs; k < S.n_dv; k++, at++)
+                (i < 2 ? T.dv_query : T.dv_truth)[size_t(k)] += int64_t(words[i][size_t(at >> 6) * nv + v] >> (at & 63) & 1);
         }
         T.strat_vars += int64_t(nv);
     }
@@ -891,7 +957,7 @@ void context_only(const Run &R, Contig &c) {
 //   1. vpr_upload_variants -> vpr_execute -> vpr_results_alloc / vpr_download;  2. -d: vpr_distance* (distance_contig)
 //   3. status masking -> vpr_phase -> vpr_pr_counts (this makes the variant classes resident)
 //   4. vpr_errclass / vpr_matchkind (label_contig: the label bytes become resident)
-//   5. the masks: vpr_context_masks or vpr_strata_masks, then vpr_varstrata_masks appended behind them (stratify_contig)
+//   5. the masks: vpr_context_masks or vpr_strata_masks, then vpr_varstrata_masks and vpr_derive_masks appended behind them (stratify_contig)
 //   6. vpr_pr_counts_strata -> vpr_strata_download_masks -> the context intervals (stratify_contig, keep_context_intervals)
 //   7. vpr_pr_counts_boot for the whole contig and every stratum (bootstrap_contig);  8. the label cuts (cut_contig)
 //   9. the warnings (print_warnings)
@@ -1002,6 +1068,9 @@ void write_outputs(const Run &R, const std::string &cmd, const std::vector<std::
         if (S.n_ctx)
             wrote(vrp_write_context_bed(pre, ctx_cn.data(), int32_t(ctx_cn.size()), S.ctx_names, S.n_ctx, T.ctx_off.data(), T.ctx_start.data(), T.ctx_stop.data()));
         if (S.n_vs) wrote(vrp_write_variant_strata(pre, S.vs_names, S.vs_spec, S.n_vs, T.vs_query.data(), T.vs_truth.data()));
+        if (S.n_dv)
+            wrote(vrp_write_derived_strata(pre, c_strs(S.dv.names).data(), S.dv.kinds.data(), c_strs(S.dv.expressions).data(), S.n_dv, T.dv_query.data(),
+                                           T.dv_truth.data()));
     }
     for (const LabelPass &P : T.pass)
         if (!P.total.empty()) wrote(P.write(pre, P.total.data(), T.total.data(), A.min_qual, A.max_qual));
@@ -1031,6 +1100,9 @@ void report(const Run &R) {
     if (S.n_ctx)
         fprintf(stderr, "[vcfdist_amd] context strata: %lld intervals of %d strata, %.3f ms on the device\n", (long long)T.ctx_start.size(), S.n_ctx, T.ctx_ms);
     if (S.n_vs) fprintf(stderr, "[vcfdist_amd] variant strata: %d strata, %.3f ms on the device\n", S.n_vs, T.vs_ms);
+    if (S.n_dv)
+        fprintf(stderr, "[vcfdist_amd] derived strata: %d strata (%d derived, %d crossed), %.3f ms on the device\n", S.n_dv, S.n_dv - S.dv.n_cross, S.dv.n_cross,
+                T.dv_ms);
     if (A.classify_errors) {      // the classified errors at threshold NONE: the ALL rows' classes of both callsets
         long long n_fp = 0, n_fn = 0;
         for (int c = 0; c < VPR_EC_CLASSES; c++) {

@@ -12,6 +12,7 @@
 //   pr_nearrepeats.hip the near-repeat strata (include/vcfdist_nearrepeats.h): k-mers repeated within m mismatches, by block sorts and a probe
 //   pr_longrepeats.hip the long repeat strata (include/vcfdist_longrepeats.h): repeated k-mers of 33..256 bases by rank doubling
 //   pr_varstrata.hip the variant strata (include/vcfdist_varstrata.h): bits made from the variant tables themselves
+//   pr_derive.hip   the derived strata (include/vcfdist_derive.h): boolean programs over the resident membership bits
 //   pr_errclass.hip the error classes (include/vcfdist_errclass.h): why each FP and FN is wrong
 //   pr_matchkind.hip the match kinds (include/vcfdist_matchkind.h): how each TP was matched
 //   pr_vartab.hip   the host check and the one-block upload of the variant tables those two share (pr_vartab.h)
@@ -444,6 +445,7 @@ struct vpr_handle {
     CutState *boot = nullptr;            // vpr_pr_counts_boot (pr_cut.hip), created by its first call, released with the batch
     LabelState *label[LABEL_PASSES] = {nullptr, nullptr};   // vpr_errclass / vpr_matchkind (pr_label.hip), created by a pass's first call, released with the batch
     double varstrata_ms = 0;             // device time of the last vpr_varstrata_masks' kernel launches (pr_varstrata.hip)
+    double derive_ms = 0;                // device time of the last vpr_derive_masks' kernel launches (pr_derive.hip)
     vpr_timing timing;
     bool uploaded = false, executed = false;
 };
@@ -501,6 +503,8 @@ int strata_masks_device(vpr_handle *h, const vpr_variants *v, int32_t n_strata, 
 int strata_extend(vpr_handle *h, const char *entry, int32_t n_add, const int64_t n_var[VPR_HAPS], bool append, int32_t *n_prev,
                   uint64_t *words[VPR_HAPS], int32_t *n_words);
 void strata_commit(vpr_handle *h);
+// pr_strata.hip, for pr_derive.hip: the number of strata and the per-slot variant counts of the resident words; false without valid words
+bool strata_resident(const vpr_handle *h, int32_t *n_strata, int64_t n_var[VPR_HAPS]);
 void context_free(vpr_handle *h);                                    // pr_context.hip: the resident context intervals
 void repeats_free(vpr_handle *h);                                    // pr_repeats.hip: the repeat intervals (host memory: pr_kmer.h)
 void longrepeats_free(vpr_handle *h);                              // pr_longrepeats.hip: the long repeat intervals (the same)

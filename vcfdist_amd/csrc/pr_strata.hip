@@ -224,6 +224,14 @@ int strata_extend(vpr_handle *h, const char *entry, int32_t n_add, const int64_t
 
 void strata_commit(vpr_handle *h) { h->strata->valid = true; }
 
+bool strata_resident(const vpr_handle *h, int32_t *n_strata, int64_t n_var[VPR_HAPS]) {
+    const StrataState *S = h->strata;
+    if (!S || !S->valid) return false;
+    *n_strata = S->n_strata;
+    for (int s = 0; s < VPR_HAPS; s++) n_var[s] = S->n_var[s];
+    return true;
+}
+
 CutState &strata_cut(vpr_handle *h) { return h->strata->cut; }
 
 int strata_view(vpr_handle *h, const char *entry, int32_t *n_strata, const uint64_t *words[VPR_HAPS]) {

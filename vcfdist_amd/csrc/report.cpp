@@ -16,6 +16,7 @@
 #include "../../include/vcfdist_report.h"
 #include "../../include/vcfdist_bootstrap.h"
 #include "../../include/vcfdist_varstrata.h"
+#include "../../include/vcfdist_derive.h"
 #include "../../include/vcfdist_errclass.h"
 #include "../../include/vcfdist_matchkind.h"
 
@@ -260,6 +261,24 @@ extern "C" int vrp_write_variant_strata(const char *prefix, const char *const *n
                 num(size, s.min_len).c_str(), num(size && s.max_len != 0, s.max_len).c_str(), num(near, s.window).c_str(), num(near, s.min_n).c_str(),
                 num(near && s.max_n >= 0, s.max_n).c_str(), (long long)n_query[k], (long long)n_truth[k]);
     }
+    if (!out.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn);
+    return VRP_OK;
+}
+
+extern "C" int vrp_write_derived_strata(const char *prefix, const char *const *names, const int32_t *kind, const char *const *expression, int32_t n,
+                                        const int64_t *n_query, const int64_t *n_truth) {
+    if (!prefix || !names || !kind || !expression || n < 0 || !n_query || !n_truth) return fail(VRP_ERR_ARG, "vrp_write_derived_strata: bad argument");
+    for (int32_t k = 0; k < n; k++) {
+        if (!names[k] || !expression[k]) return fail(VRP_ERR_ARG, "vrp_write_derived_strata: null stratum name or expression");
+        if (kind[k] != VPR_DV_KIND_DERIVE && kind[k] != VPR_DV_KIND_CROSS) return fail(VRP_ERR_ARG, "vrp_write_derived_strata: unknown kind");
+    }
+    const std::string fn = std::string(prefix) + "derived-strata.tsv";
+    File out(fn.c_str());
+    if (!out) return fail(VRP_ERR_OPEN, "cannot create " + fn);
+    fputs("NAME\tKIND\tEXPRESSION\tQUERY_MEMBERS\tTRUTH_MEMBERS\n", out);
+    for (int32_t k = 0; k < n; k++)
+        fprintf(out, "%s\t%s\t%s\t%lld\t%lld\n", names[k], kind[k] == VPR_DV_KIND_CROSS ? "cross" : "derive", expression[k], (long long)n_query[k],
+                (long long)n_truth[k]);
     if (!out.finish()) return fail(VRP_ERR_OPEN, "write error on " + fn);
     return VRP_OK;
 }

@@ -25,7 +25,7 @@ class VrpContig(C.Structure):
                 ("n_flips", C.c_int32), ("switches", A.P_i32), ("flips", A.P_i32)]
 
 
-EXPORTED = ["vrp_phase_blocks", "vrp_write_precision_recall", "vrp_write_stratified", "vrp_write_context_bed", "vrp_write_repeat_bed", "vrp_write_long_repeat_bed", "vrp_write_near_repeat_bed", "vrp_write_bootstrap", "vrp_write_bootstrap_stratified", "vrp_write_phase_blocks", "vrp_write_superclusters",
+EXPORTED = ["vrp_phase_blocks", "vrp_write_precision_recall", "vrp_write_stratified", "vrp_write_context_bed", "vrp_write_repeat_bed", "vrp_write_long_repeat_bed", "vrp_write_near_repeat_bed", "vrp_write_derived_strata", "vrp_write_bootstrap", "vrp_write_bootstrap_stratified", "vrp_write_phase_blocks", "vrp_write_superclusters",
             "vrp_write_switchflips", "vrp_write_phasing_summary", "vrp_ng50",
             "vrp_write_variants", "vrp_write_summary_vcf", "vrp_write_distance", "vrp_write_edits", "vrp_write_vcf", "vrp_last_error"]
 
@@ -193,6 +193,23 @@ def write_variant_strata(prefix, names, spec, n_query, n_truth):
     L.vrp_write_variant_strata.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(A.VprVariantStratum), C.c_int32, A.P_i64, A.P_i64]
     _check(L.vrp_write_variant_strata(prefix.encode(), narr, sarr, len(names), A._ptr(nq, C.c_int64), A._ptr(nt, C.c_int64)),
            "vrp_write_variant_strata")
+
+
+def write_derived_strata(prefix, names, kinds, expressions, n_query, n_truth):
+    """derived-strata.tsv (include/vcfdist_derive.h): one row per derived or crossed stratum -- name, kind (A.DV_KIND_*), the
+    expression as given (a&b for a cross), and the numbers of query and of truth hap-variants that are members"""
+    if not len(names) == len(kinds) == len(expressions) == len(n_query) == len(n_truth):
+        raise ReportError(f"{len(names)} names, {len(kinds)} kinds, {len(expressions)} expressions, {len(n_query)} / {len(n_truth)} member counts")
+    nq, nt, kd = np.ascontiguousarray(n_query, np.int64), np.ascontiguousarray(n_truth, np.int64), np.ascontiguousarray(kinds, np.int32)
+    if nq.size == 0:
+        nq = nt = np.zeros(1, np.int64)
+        kd = np.zeros(1, np.int32)
+    L = api.lib()
+    narr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+    earr = (C.c_char_p * max(len(names), 1))(*[e.encode() for e in expressions])
+    L.vrp_write_derived_strata.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), A.P_i32, C.POINTER(C.c_char_p), C.c_int32, A.P_i64, A.P_i64]
+    _check(L.vrp_write_derived_strata(prefix.encode(), narr, A._ptr(kd, C.c_int32), earr, len(names), A._ptr(nq, C.c_int64), A._ptr(nt, C.c_int64)),
+           "vrp_write_derived_strata")
 
 
 def _write_label_counts(entry, prefix, label_counts, n_labels, counts, min_qual, max_qual):
